@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path on MI355X: frames x views / s, heat-map -> triangulated 3-D.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps, writes the last timed step's outputs if --dump-outputs is
+given and prints the line.  Everything else the benchmark measures (roofline, exact_modes, companions, cpu_baseline, the
+exposed all-reduce of N > 1 training, the detail record) runs only with --full, after the headline's timed region.
+
+--dump-outputs DIR: what the timed path returned in its last timed step (heat-maps + triangulation results; a training step's
+loss, parameters and gradients), as DIR/<name>.npy in float32 / float64, at most 64 MB in all -- an array that does not fit its
+share is replaced by a fixed seeded sample of its flattened elements.  The inputs depend on the arguments only.
 
 N > 1 without torchrun's RANK in the environment: this process starts the N ranks itself (as CHILD processes,
 ``python -m torch.distributed.run --nproc-per-node N bench.py ...``, before anything here touches the GPU) and relays
@@ -16,7 +24,7 @@ One step = one pass of the hot path over one batch.  Frames are independent, so 
 frames with NO data-path collective (weak scaling: per-GPU work is fixed).
 
 Prints ONE JSON line on rank 0 -- at most 4 096 characters (compact_line; round 5's 21.9 KB line fell out of the driver's stdout tail) -- with the
-driver's contract fields plus
+driver's contract fields plus, with --full,
   roofline     the dominant kernel family by time: {kernel (a label), bound, achieved, peak, unit, frac, traffic, seconds_in_kernel_per_step}.
                For C2 the fused 3x3 stride-1 convs on the fp16 matrix cores: algorithmic conv FLOPs of its launches in one step / the time
                spent in them (hipEvents around every launch on the launch stream, mval_net_forward_timed) against the peak of the split
@@ -30,7 +38,7 @@ driver's contract fields plus
                the same workload; "parity_sample" compares the HIP path with the oracle on that sample's first frames (heat-map max error,
                2-D key-point equality, MPJPE and worst-joint delta in mm) -- outside every timed region.
 Everything else the run measured -- the other kernel families each against its own bound, pass counts, notes, per-rank attribution, the
-companions' own records -- goes to the detail record (--detail-out, default bench_detail.json beside this script).
+companions' own records -- goes to the detail record (--detail-out; with --full its default is bench_detail.json beside this script).
 """
 from __future__ import annotations
 
@@ -582,6 +590,38 @@ def path_kernels(dev, frames, v, j, hh, wh):
     return out
 
 
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all .npy payloads together
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes {name: array} as out_dir/<name>.npy: floating arrays as float32 / float64 (narrower floats widened to float32), integer and
+    bool arrays as float64 (exact).  Smallest arrays first, each gets an equal share of what the budget has left; an array larger than
+    its share is replaced by the elements at a fixed seeded sample of its flattened indices (sorted), so that two runs pick the same."""
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.dtype.kind == "f":
+            a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        else:
+            a = a.astype(np.float64)
+        conv[name] = a
+    left = DUMP_LIMIT_BYTES
+    written = {}
+    for i, name in enumerate(sorted(conv, key=lambda k: conv[k].nbytes)):
+        a = conv[name]
+        share = left // (len(conv) - i) - 128  # (the .npy header)
+        if a.nbytes > share:
+            n = max(share // a.itemsize, 0)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=n, replace=False, shuffle=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes + 128
+        written[name] = list(a.shape)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -611,18 +651,26 @@ def main():
     ap.add_argument("--no-rooflines", action="store_true",
                     help="profiling passes (tools/collect_profiles.sh): skip the per-kernel measurement runs after the timed region, so that a "
                          "rocprofv3 trace of this command holds the workload's steps only")
-    ap.add_argument("--min-timed-seconds", type=float, default=2.0,
-                    help="the K-step region is repeated until it is at least this long (counter passes use 0: K steps exactly)")
+    ap.add_argument("--min-timed-seconds", type=float, default=0.0,
+                    help="the K-step region is repeated until it is at least this long (default 0: K timed steps exactly)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures: roofline, exact_modes, companions, cpu_baseline, the "
+                         "exposed all-reduce of N > 1 training, and the detail record (--detail-out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--no-companions", action="store_true",
                     help="default c2 run: skip the C3 / C4 companion lines (child processes after the headline)")
     ap.add_argument("--shared-device", action="store_true",
                     help="TEST ONLY (tests/test_gpu_distributed.py): the N ranks all use cuda:0 and talk over gloo -- the rehearsal of this "
                          "script's N > 1 code (self-launch, barriers, rank reductions, attribution, DDP) on a one-GPU box.  RCCL refuses two "
                          "ranks on one device; the collectives' payloads are the same device tensors.  Not a measurement: the line says so")
-    ap.add_argument("--detail-out", default=os.path.join(ROOT, "bench_detail.json"),
+    ap.add_argument("--detail-out", default=None,
                     help="file for the run's full record (every kernel family, notes, pass counts, per-rank attribution, the companions' own "
-                         "records); stdout carries only the compact line (<= 4 KB).  '' = do not write it")
+                         "records); stdout carries only the compact line (<= 4 KB).  Default: bench_detail.json beside this script with --full, "
+                         "none without.  '' = do not write it")
     args = ap.parse_args()
+    if args.detail_out is None:
+        args.detail_out = os.path.join(ROOT, "bench_detail.json") if args.full else ""
     pool_pass = args.pool is not None or WORKLOADS[args.workload].get("pool") is not None
     if args.steps is None:
         args.steps = 1 if (args.pool or 0) > 4096 else 3 if pool_pass else 150 if args.workload == "c2" else 40
@@ -708,7 +756,7 @@ def main():
         else:
             opt = torch.optim.Adam([{"params": model.parameters(), "lr": 1e-3}], **({"fused": True} if adam_kind == "fused" else {}))
         loss_fn = Pose2DMeanSquaredError()
-        gt = torch.rand(frames * v, j, h // 4, w // 4, device=dev)
+        gt = torch.rand(frames * v, j, h // 4, w // 4, device=dev, generator=torch.Generator(device=dev).manual_seed(11))
         pv = torch.ones(frames * v, j, 1, 1, dtype=torch.uint8, device=dev)
 
     def coreset_pass():
@@ -857,8 +905,11 @@ def main():
                 sc = score_decode_heatmaps_batch(wl["score"], "AVG", hm, valid, 4)
                 r = triangulate_batch(hm, proj, 4, valid, keypoints_2d=sc[4])
                 r["al_metric"] = sc[0]
-                return r
-            return triangulate_batch(hm, proj, 4, valid)
+            else:
+                r = triangulate_batch(hm, proj, 4, valid)
+            if args.dump_outputs:  # (kept only when they are written: otherwise a step's maps are released at its end, as before)
+                r["heatmaps"] = hm
+            return r
 
     def sync():
         torch.cuda.synchronize()
@@ -866,8 +917,8 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # The timed region is K steps, repeated until it is at least ~2 s long (the driver's --steps 20 is 0.25 s of this
-    # workload: clocks and caches have not settled); every repeat runs exactly K steps, all of them are timed.
+    # The timed region is exactly K steps; with --min-timed-seconds S > 0 it is repeated until it is at least S long (one untimed
+    # step estimates the count); every repeat runs exactly K steps, all of them are timed.
     repeats = 1
     with torch.set_grad_enabled(train):
         if args.warmup == 0 and wl.get("pool"):  # (--warmup 0 on a pool pass: build the plan on one batch instead of a whole pass)
@@ -876,7 +927,7 @@ def main():
         for _ in range(args.warmup if wl.get("pool") else max(args.warmup, 1)):
             r = step()
         sync()
-        if not wl.get("pool"):
+        if not wl.get("pool") and args.min_timed_seconds > 0:
             t0 = time.perf_counter()
             r = step()
             sync()
@@ -922,7 +973,17 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
-    if train and (world > 1 or args.rccl_world_1) and isinstance(net, torch.nn.parallel.DistributedDataParallel):
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before anything below runs another step
+        if train:  # (a training step returns its loss and leaves the updated parameters and this step's gradients)
+            ps = [p.detach() for p in model.parameters()]
+            gs = [p.grad.detach() if p.grad is not None else torch.zeros_like(p) for p in model.parameters()]
+            dumped = {"loss": r["keypoints_3d"], "parameters": torch.cat([p.reshape(-1) for p in ps]),
+                      "gradients": torch.cat([g.reshape(-1) for g in gs])}
+        else:
+            dumped = dict(r)
+        dump_outputs(args.dump_outputs, dumped)
+    if args.full and train and (world > 1 or args.rccl_world_1) and isinstance(net, torch.nn.parallel.DistributedDataParallel):
         # exposed all-reduce: the same step with the gradient synchronisation switched off (no_sync) against the normal one
         def timed_steps(k, ctx):
             sync()
@@ -946,7 +1007,7 @@ def main():
 
     # ---- roofline of the dominant kernel family (outside the timed region) ------------------------
     roof = None
-    rank_roof = -1 if args.no_rooflines else 0
+    rank_roof = 0 if args.full and not args.no_rooflines else -1
     if rank == rank_roof and train:
         with torch.enable_grad():
             roof = train_rooflines(model, step, frames, v, _conv_mode())
@@ -1087,7 +1148,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(el / args.steps * 1e3, 3),
-            "timed_repeats": repeats,  # the K-step region was timed this many times back to back (>= 2 s in all); value is per K
+            "timed_repeats": repeats,  # the K-step region was timed this many times back to back (1 unless --min-timed-seconds); value is per K
             "higher_is_better": True,
             "scaling": "strong" if wl.get("pool") else "weak",
             "vs_baseline": None,
@@ -1147,7 +1208,7 @@ def main():
             out["metric"] += " [input-inclusive: --with-input]"
         if attribution is not None:
             out["attribution"] = attribution
-        if not train and not wl.get("pool") and world == 1 and not args.no_exact_modes:
+        if args.full and not train and not wl.get("pool") and world == 1 and not args.no_exact_modes:
             # the same step with the other conv kernel families (plans are cached per mode), outside the timed region
             exact = {}
             headline_mode = _conv_mode()
@@ -1181,7 +1242,7 @@ def main():
             exact["note"] = ("ms per step; h2 = round 2's kernels (fp32 NHWC activations, split while staging), bf3 = exact 3-way "
                              "bf16 split (six MFMA products), fp32 = exact-fp32 MFMA (v_mfma_f32_16x16x4_f32) everywhere")
             out["exact_modes"] = exact
-        if not args.no_cpu_baseline and train and world == 1:
+        if args.full and not args.no_cpu_baseline and train and world == 1:
             cpu = cpu_baseline_train(wl, sd_np, args.cpu_seconds)
             # the training step's parity sample: the HIP path (a fresh model from the same synthetic weights, train mode) on the oracle's
             # sample -- loss, heat-maps and three gradients against the CPU oracle's autograd (outside every timed region)
@@ -1204,7 +1265,7 @@ def main():
             }
             del m2
             out["cpu_baseline"] = cpu
-        if not args.no_cpu_baseline and not train and world == 1:  # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and not train and world == 1:  # rank 0 at N = 1 only
             cpu = cpu_baseline(wl, sd_np, args.cpu_seconds)
             # BASELINE.json's "MPJPE vs ref": the HIP path on the oracle's first sample (outside every timed region)
             chk = cpu.pop("_check")
@@ -1221,7 +1282,7 @@ def main():
                 "max_joint_delta_mm": float(delta.max()),
             }
             out["cpu_baseline"] = cpu
-        if args.workload == "c2" and world == 1 and not args.no_companions and not args.rccl_world_1:
+        if args.full and args.workload == "c2" and world == 1 and not args.no_companions and not args.rccl_world_1:
             # BASELINE configs[2] / [3] under the same (driver) clock: child processes of this command, run after the headline's
             # timed region and measurements; each times >= 2 s of its own step.  A failure is recorded, not raised.
             import subprocess
@@ -1237,8 +1298,8 @@ def main():
                                 ("c2_with_input", ["--steps", "100", "--warmup", "5", "--no-cpu-baseline", "--with-input", "--no-rooflines"])):
                 fd, child_detail = tempfile.mkstemp(prefix=f"mval_bench_{name}_", suffix=".json")
                 os.close(fd)
-                cmd = [sys.executable, os.path.abspath(__file__), "--workload", name.split("_")[0], "--no-companions", "--no-exact-modes",
-                       "--detail-out", child_detail] + extra
+                cmd = [sys.executable, os.path.abspath(__file__), "--workload", name.split("_")[0], "--full", "--no-companions", "--no-exact-modes",
+                       "--min-timed-seconds", "2", "--detail-out", child_detail] + extra
                 if args.no_cpu_baseline and "--no-cpu-baseline" not in cmd:
                     cmd.append("--no-cpu-baseline")
                 t0 = time.perf_counter()

@@ -1,8 +1,11 @@
 """bench.py's launch contract, checked without a GPU: `--gpus N` on a node with fewer than N devices must fail loudly
-(not report n_gpus = 1), and under torchrun a WORLD_SIZE that disagrees with --gpus is an error too."""
+(not report n_gpus = 1), and under torchrun a WORLD_SIZE that disagrees with --gpus is an error too; the line, --full and
+--dump-outputs (one test marked gpu runs a plain benchmark)."""
 import os
 import subprocess
 import sys
+
+import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -99,3 +102,68 @@ def test_compact_line_survives_non_finite_and_oversized_input():
     assert len(line) <= 4096
     d = json.loads(line)
     assert d["value"] is None and d["ms_per_step"] is None and len(d["roofline"]["kernel"]) <= 60 and "all" not in d["attribution"]["per_rank_s"]
+
+
+def test_full_and_dump_outputs_are_options():
+    r = _run(["--help"])
+    assert r.returncode == 0
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout and "--steps" in r.stdout
+
+
+def test_dump_outputs_types_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files only, at most 64 MB in all; an array larger than its share is replaced by the
+    same seeded sample of its elements on every call."""
+    import numpy as np
+    import torch
+
+    m = _bench_mod()
+    rng = np.random.default_rng(3)
+    arrays = {"big": rng.standard_normal(20_000_000).astype(np.float32),  # 80 MB: sampled
+              "kp": torch.from_numpy(rng.standard_normal((4, 19, 3))),
+              "idx": torch.arange(10, dtype=torch.int64), "mask": np.array([True, False]), "half": torch.ones(3, dtype=torch.float16)}
+    for d in ("a", "b"):
+        m.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in arrays)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in files)
+    assert total <= 64_000_000 and total > 60_000_000
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(a, b)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "kp.npy"), arrays["kp"].numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "idx.npy"), np.arange(10, dtype=np.float64))
+    assert np.load(tmp_path / "a" / "half.npy").dtype == np.float32
+    big = np.load(tmp_path / "a" / "big.npy")
+    assert big.ndim == 1 and 10_000_000 < big.size < arrays["big"].size and np.isin(big[:100], arrays["big"]).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_k_steps_and_dumps_outputs(tmp_path):
+    """A plain run: the contract fields, exactly --steps timed steps, none of the --full measurements, and --dump-outputs writes the last
+    step's heat-maps and triangulation results -- the same values on a second run with the same arguments."""
+    import json
+
+    import numpy as np
+
+    lines = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        ls = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(ls) == 1
+        lines.append(json.loads(ls[0]))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert d[k] is not None, k
+    assert d["steps"] == 3 and d["timed_repeats"] == 1 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["roofline"] is None and not ({"cpu_baseline", "exact_modes", "companions", "detail"} & set(d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert {"heatmaps.npy", "keypoints_3d.npy", "keypoints_2d.npy"} <= set(files)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    hm = np.load(tmp_path / "a" / "heatmaps.npy")
+    assert hm.dtype == np.float32 and hm.shape == (32, 4, 19, 64, 64) and np.isfinite(hm).all()
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-6, err_msg=f)

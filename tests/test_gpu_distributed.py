@@ -160,7 +160,7 @@ def test_rccl_world_1_training_step_under_ddp():
     torch.cuda.empty_cache()  # (the child needs ~60 GB: give back what earlier tests of THIS process left in torch's caching allocator)
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29643")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--workload", "c3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--rccl-world-1"], capture_output=True, text=True, env=env, timeout=900)
+                        "--rccl-world-1", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["ms_per_step"] < 200
@@ -293,14 +293,15 @@ def test_bench_two_rank_rehearsal_pool_passes(tmp_path, workload):
 
 
 def test_bench_two_rank_rehearsal_training_step(tmp_path):
-    """The C3 line at two ranks on one GPU: DistributedDataParallel over gloo, `repeats` agreed by all_reduce, the exposed
-    all-reduce measurement (step vs the same step under no_sync) in the line."""
+    """The C3 line at two ranks on one GPU: DistributedDataParallel over gloo, `repeats` agreed by all_reduce (any --min-timed-seconds
+    above 0 runs that agreement; this one keeps it at one repeat), the exposed all-reduce measurement (step vs the same step under
+    no_sync, a --full measurement) in the line."""
     import gc
 
     gc.collect()
     torch.cuda.empty_cache()
     d = _bench_line(["--gpus", "2", "--workload", "c3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-rooflines", "--shared-device",
-                     "--min-timed-seconds", "0", "--detail-out", str(tmp_path / "d.json")])
+                     "--min-timed-seconds", "0.001", "--full", "--detail-out", str(tmp_path / "d.json")])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["images_per_step_per_gpu"] == 128
     at = d["attribution"]

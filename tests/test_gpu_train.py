@@ -957,7 +957,8 @@ def test_train_p2_wide_gamma_spread_vs_float64(dev, monkeypatch):
     the bound.  One HRNet-W32 step with gammas spread over 2^-8 .. 1 on the default plan and on the h2 plan (MVAL_TRAIN_P2=0: the SAME
     fp16-split arithmetic with scales from the tensors' exact maxima), each against float64 torch-CPU autograd: the P2 plan's per-tensor
     gradient errors are no worse than the h2 plan's (what the a-priori bound could cost), the loss agrees with float64 to 1e-5, and both
-    stay within an order of magnitude of torch-CPU fp32's own distance from float64.  (Why not "within 2x of torch-CPU fp32" as
+    stay within an order of magnitude of fp32's own distance from float64 (the worse of two exact-fp32 evaluations, torch-CPU's and the
+    exact-fp32 MFMA plan's, as test_all_gradients_vs_cpu_oracle takes it).  (Why not "within 2x of the fp32 floor" as
     test_all_gradients_vs_cpu_oracle: with small gammas many pre-activations sit near zero, and ONE ReLU-mask flip anywhere early moves
     the median of every run that has it -- tools/gamma_diag.py: at this spread the two fp16-split plans share a flip the bf16x3 and
     exact-fp32 plans do not have, at 2^-4 torch-CPU fp32 itself is the outlier.)"""
@@ -993,16 +994,27 @@ def test_train_p2_wide_gamma_spread_vs_float64(dev, monkeypatch):
         l.backward()
         return l.item(), sdc
 
+    # a second EXACT-fp32 evaluation in another summation order, as test_all_gradients_vs_cpu_oracle has it: the exact-fp32 MFMA plan
+    monkeypatch.delenv("MVAL_TRAIN_P2")
+    monkeypatch.setenv("MVAL_CONV", "fp32")
+    l_x, g_x, plan_x, _ = hip()
+    assert not plan_x.uses_p2
+
     l64, sd64 = cpu(torch.float64)
     l32, sd32 = cpu(torch.float32)
-    assert abs(l_p2 - l64) <= 1e-5 * abs(l64) and abs(l_h2 - l64) <= 1e-5 * abs(l64)
+    assert abs(l_p2 - l64) <= 1e-5 * abs(l64) and abs(l_h2 - l64) <= 1e-5 * abs(l64) and abs(l_x - l64) <= 1e-5 * abs(l64)
     e_p2 = np.asarray([_rel(g_p2[k], sd64[k].grad.numpy()) for k in g_p2])
     e_h2 = np.asarray([_rel(g_h2[k], sd64[k].grad.numpy()) for k in g_p2])
     ec = np.asarray([_rel(sd32[k].grad.numpy(), sd64[k].grad.numpy()) for k in g_p2])
+    ex = np.asarray([_rel(g_x[k], sd64[k].grad.numpy()) for k in g_p2])
     st = lambda e: f"median {np.median(e):.2e} p90 {np.percentile(e, 90):.2e} max {e.max():.2e}"
-    print(f"\nwide gamma spread: slack {plan.p2_slack}; gradient error vs float64: P2 {st(e_p2)}; h2 {st(e_h2)}; torch-CPU fp32 {st(ec)}")
+    print(f"\nwide gamma spread: slack {plan.p2_slack}; gradient error vs float64: P2 {st(e_p2)}; h2 {st(e_h2)}; torch-CPU fp32 {st(ec)}; "
+          f"exact-fp32 MFMA {st(ex)}")
     assert np.median(e_p2) <= 1.5 * np.median(e_h2) + 1e-3 and np.percentile(e_p2, 90) <= 1.5 * np.percentile(e_h2, 90) + 2e-3 and e_p2.max() <= 1.5 * e_h2.max() + 1e-2
-    assert np.median(e_p2) <= 10.0 * np.median(ec) + 1e-3 and e_p2.max() <= 10.0 * ec.max() + 1e-2
+    # torch-CPU's summation order follows the host's thread count and CPU (this fixture's fp32 median: 6.7e-4 at 1 or 32 threads on one
+    # host, 2.2e-4 at 16, 1.8e-4 single-threaded on another): the floor is the WORSE of the two exact-fp32 evaluations
+    floor = lambda f: max(f(ec), f(ex))
+    assert np.median(e_p2) <= 10.0 * floor(np.median) + 1e-3 and e_p2.max() <= 10.0 * floor(np.max) + 1e-2
 
 
 def test_train_p2_slack_guard_hands_over_to_h2(dev):

@@ -168,6 +168,23 @@ int mval_coreset_features(const double* pose, double* feat, int64_t n, int J, in
  * cluster centres [K,D] f64 for every feature row feat [n,D] f64 (first minimum, as KMeans.predict). */
 int mval_nearest_center(const double* feat, const double* centers, int64_t n, int D, int K, int* label, void* stream);
 
+/* Workspace bytes of one mval_kmeans_fit call (0 for non-positive sizes). */
+size_t mval_kmeans_workspace_bytes(int64_t n, int D, int K, int L);
+
+/* strategy.py:38-52 KMeans(SAL.NUM_CLUSTERS, random_state=RANDOM_SEED).fit(kp_values): ONE initialisation of
+ * sklearn 1.7.2's KMeans (Lloyd, unit weights) on X [n,D] f64, float64 throughout, fixed reduction order
+ * (bit-reproducible).  Fits on X - mean(X) and adds the mean back; tol_abs = tol * mean(var(X, axis=0)).
+ *   init_centers [K,D] f64, or NULL for greedy k-means++ seeding with the host's draws: first_idx (the first
+ *   centre) and rand_u [(K-1)*L] f64 (L = n_local_trials uniforms per further centre, in sklearn's order);
+ *   centers [K,D] f64 ; labels [n] i32 ; inertia [1] f64 ; n_iter [1] i32 (sklearn's n_iter_) ;
+ *   init_idx [K] i64 = the seeding picks (-1 with init_centers) ; ws >= mval_kmeans_workspace_bytes.
+ * Empty clusters are relocated to the farthest rows, largest distance first (lower index on equal distances).
+ * Limits: K <= n, K <= 256, D <= 512, K*D <= 3840, L <= 16.  Unlike the other entry points this one
+ * synchronises `stream` every 16 Lloyd iterations to stop once converged (not graph-capturable). */
+int mval_kmeans_fit(const double* X, int64_t n, int D, int K, const double* init_centers, int64_t first_idx,
+                    const double* rand_u, int L, int max_iter, double tol, double* centers, int* labels,
+                    double* inertia, int* n_iter, int64_t* init_idx, void* ws, void* stream);
+
 size_t mval_kcenter_workspace_bytes(int64_t n_obs, int D);
 
 /* utils/coreset.py:49-95 greedy k-center on feat [n_obs,D] f64 with sklearn's expanded

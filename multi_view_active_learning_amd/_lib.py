@@ -42,6 +42,7 @@ def lib() -> C.CDLL:
                 l = C.CDLL(LIB_PATH)
                 l.mval_last_error.restype = C.c_char_p
                 l.mval_kcenter_workspace_bytes.restype = C.c_size_t
+                l.mval_kmeans_workspace_bytes.restype = C.c_size_t
                 l.mval_net_create.restype = C.c_void_p
                 l.mval_packed_weight_floats.restype = C.c_size_t
                 l.mval_op_flops.restype = C.c_double
@@ -353,6 +354,35 @@ def nearest_center(feat, centers):
         "mval_nearest_center",
     )
     return out
+
+
+def kmeans_workspace_bytes(n: int, d: int, k: int, n_trials: int) -> int:
+    return int(lib().mval_kmeans_workspace_bytes(C.c_longlong(n), C.c_int(d), C.c_int(k), C.c_int(n_trials)))
+
+
+def kmeans_fit(x, k, init_centers, first_idx, rand_u, n_trials, max_iter, tol):
+    """One KMeans initialisation + Lloyd run on x (n, D) f64 (device).  init_centers (K, D) f64 or None (k-means++
+    with first_idx and rand_u ((K-1)*n_trials,) f64).  Returns device tensors (centers (K, D) f64, labels (n,) int32,
+    inertia (1,) f64, n_iter (1,) int32, init_idx (K,) int64)."""
+    n, d = x.shape
+    dev = x.device
+    centers = torch.empty((k, d), dtype=torch.float64, device=dev)
+    labels = torch.empty((n,), dtype=torch.int32, device=dev)
+    inertia = torch.empty((1,), dtype=torch.float64, device=dev)
+    n_iter = torch.empty((1,), dtype=torch.int32, device=dev)
+    init_idx = torch.empty((k,), dtype=torch.int64, device=dev)
+    ws = torch.empty((kmeans_workspace_bytes(n, d, k, n_trials) // 8 + 1,), dtype=torch.float64, device=dev)
+    _check(
+        lib().mval_kmeans_fit(
+            _p(_req(x, torch.float64, "X")), C.c_longlong(n), C.c_int(d), C.c_int(k),
+            _p(None if init_centers is None else _req(init_centers, torch.float64, "init")), C.c_longlong(first_idx),
+            _p(None if rand_u is None else _req(rand_u, torch.float64, "rand_u")), C.c_int(n_trials),
+            C.c_int(max_iter), C.c_double(tol), _p(centers), _p(labels), _p(inertia), _p(n_iter), _p(init_idx),
+            _p(ws), _stream(),
+        ),
+        "mval_kmeans_fit",
+    )
+    return centers, labels, inertia, n_iter, init_idx
 
 
 def coreset_features(pose, root_idx, n, j, rows):

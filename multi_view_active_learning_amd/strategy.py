@@ -127,6 +127,24 @@ class ActiveLearningStrategy:
         self.joint_root_index = 2 if al_cfg.DATA.TYPE == "panoptic" else 21  # strategy.py:34-37
         self.loss = Pose2DMeanSquaredError()
 
+    @property
+    def kmeans(self):
+        """The SAL pose clusters (strategy.py:38-52), fitted on the device on first access: for
+        ``EXPR_TYPE == "SAL"`` with a ``SAL.CLUSTER_FILE_PATH``, ``KMeans(SAL.NUM_CLUSTERS,
+        random_state=RANDOM_SEED)`` on the file's root-relative poses; otherwise None.  Hand it to
+        ``select_sal_guids(..., kmeans_centers=st.kmeans)``."""
+        if "_kmeans" not in self.__dict__:
+            cfg = self.al_cfg
+            km = None
+            if cfg.EXPR_TYPE == "SAL" and cfg.SAL.CLUSTER_FILE_PATH != "":
+                from .utils.experiment_io import read_cluster_features
+                from .utils.kmeans import KMeans
+
+                feats = read_cluster_features(cfg.SAL.CLUSTER_FILE_PATH, self.joint_root_index)
+                km = KMeans(cfg.SAL.NUM_CLUSTERS, random_state=cfg.RANDOM_SEED).fit(feats)
+            self._kmeans = km
+        return self._kmeans
+
     # ---- model glue ---------------------------------------------------------------
     @staticmethod
     def _compute_batch_heatmap(pose_estimator, data):
@@ -319,7 +337,7 @@ class ActiveLearningStrategy:
         sampled by AL, are not pseudo-labelled yet, have a finite sal_metric and MORE than SAL.INLIER_THRESHOLD
         inliers; sort ascending by sal_metric (stable); then either fill SAL.NUM_CLUSTERS pose clusters with
         pseudo_num_frames // NUM_CLUSTERS frames each (cluster of a frame = nearest of ``kmeans_centers``,
-        (K, 3J) float64, to its root-relative pose -- ONE device launch for all candidates instead of a
+        (K, 3J) float64 or a fitted ``utils.kmeans.KMeans`` such as ``self.kmeans``, to its root-relative pose -- ONE device launch for all candidates instead of a
         ``kmeans.predict`` per frame) or, without clusters, ``random.sample`` of the best 2 N (python's
         global RNG, exactly like the reference)."""
         import random
@@ -342,6 +360,8 @@ class ActiveLearningStrategy:
         pose = torch.as_tensor(np.asarray([sal_dict["pred_3d_keypoints"][g] for g in sal_guids], dtype=np.float64)).to(device)
         n, j, rows = pose.shape
         feat = _lib.coreset_features(pose.contiguous(), self.joint_root_index, n, j, rows)
+        if hasattr(kmeans_centers, "cluster_centers_"):  # a fitted KMeans (utils/kmeans.py, e.g. ``self.kmeans``)
+            kmeans_centers = kmeans_centers.cluster_centers_
         centers = torch.as_tensor(np.asarray(kmeans_centers, dtype=np.float64)).to(device).contiguous()
         labels = _lib.nearest_center(feat, centers).cpu().tolist()
         counter = [0] * k

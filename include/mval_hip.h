@@ -269,7 +269,7 @@ typedef struct mval_op {
    * t_in_amax_off[j], 1x1 weights packed MVAL_PACK_MFMA16_H2 at t_w_off[j], folded BN at t_scale_off[j] / t_shift_off[j], bound
    * [A, B] at t_bound_off[j]; relu: the activation of the sum. */
   int32_t n_terms, t_cin[3], t_up[3];
-  int32_t reserved0; /* (round 4's multi-conv launch marker; must be 0) */
+  int32_t no_stem;   /* 1: a 3-channel NCHW stem conv runs on the generic direct kernel, not the stem kernel (the all-direct plan) */
   int64_t t_in_off[3], t_in_amax_off[3], t_w_off[3], t_scale_off[3], t_shift_off[3], t_bound_off[3];
 } mval_op;
 
@@ -333,8 +333,8 @@ int mval_op_launch(const mval_op* op, int n_images, float* workspace, const floa
 
 void* mval_net_create(const mval_op* ops, int n_ops);
 void mval_net_destroy(void* net);
-/* Branch concurrency of mval_net_forward: -1 = decided by the MVAL_STREAMS environment variable (default:
- * on), 0 = every op on the caller's stream, 1 = fork / join over private streams.  Both forms can be
+/* Branch concurrency of mval_net_forward: 1 or -1 = fork / join over private streams (a new net's default),
+ * 0 = every op on the caller's stream.  Both forms can be
  * captured into a hipGraph (the fork / join uses events recorded on the capturing stream).  The side streams and
  * events are per device and shared by all nets: ONE forward (or training pass) in flight per device at a time. */
 int mval_net_set_multi_stream(void* net, int mode);
@@ -521,7 +521,7 @@ typedef struct mval_train_op {
                      * apply writes ONLY the P2 planes (every consumer of its output reads those: no fp32 NHWC copy);
                      * bit 6: this op's BatchNorm backward is round 3's pair (masked copy + in-place dz; reads `out`: not with bits 1 - 3);
                      * bit 7: this op's batch statistics come from the separate pass over z, not from its conv's epilogue partials
-                     * (bits 6 / 7 are the caller's A/B switches: the library reads no environment variable for them) */
+                     * (bits 6 / 7 / 13 are the caller's decisions: the library reads no environment variable) */
   int64_t in_p2_off, in_p2_rows_off, out_p2_off, out_p2_rows_off, res1_amax_off, res2_amax_off;
   /* p2_flags bit 3: with bit 2 -- the weight gradient reads dz from the planes as well, so the BatchNorm backward writes no fp32 dz.
    * p2_flags bit 2: the op's data gradient runs on the P2 kernels (stride 1): its BatchNorm backward ALSO writes dz as P2 planes into the
@@ -541,10 +541,8 @@ typedef struct mval_train_op {
                             * producer's backward skips that pass */
 } mval_train_op;
 #define MVAL_TRAIN_BSUM 4096
-/* p2_flags bit 13 on every op of a backward call (the library looks at the call's last op): the weight gradients' slab reductions of the call run
- * as ONE launch per 64 ops when its lanes have joined; wsf is then one arena of n_lanes * wsf_floats_per_lane floats that must hold the sum of
- * mval_conv_wgrad_workspace_floats (rounded up to 64) over the call's ops. */
-#define MVAL_TRAIN_WGRAD_DEFER 8192
+/* p2_flags bit 13: this op's weight gradient runs on the exact-fp32 kernels even where the split kernel covers it (the exact-fp32 plan). */
+#define MVAL_TRAIN_WGRAD_FP32 8192
 
 /* ones_off / zeros_off: params offsets of >= max(cout) floats of 1.0 / 0.0.
  * ws: ws_doubles >= 512*maxC*2 doubles.  With room for cout * (conv workgroups) * 2 doubles of an op (about
@@ -556,8 +554,6 @@ int mval_train_forward(const mval_train_op* ops, int n_ops, int n_images, float*
 /* gz: scratch >= max over ops of N*hout*wout*cout floats; wsf: >= max wgrad workspace;
  * sums: >= 2*maxC floats.  The gradient w.r.t. the network output must already be in garena at
  * the last op's gout_off (NHWC). */
-/* Measurement only (profiles/r06 item 2b): wsf of the next backward calls holds k regions of region_floats per lane, walked op by op. */
-int mval_train_slab_rotation(int k, int64_t region_floats);
 int mval_train_backward(const mval_train_op* ops, int n_ops, int n_images, float* arena, float* garena,
                         const float* params, int64_t ones_off, int64_t zeros_off, const float* input_nchw,
                         float* gz, float* wsf, double* ws, float* sums, void* stream);

@@ -10,7 +10,7 @@ void mval_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* mval_last_error(void) { return g_err; }
-extern "C" int mval_version(void) { return 100; }
+extern "C" int mval_version(void) { return 101; }
 
 // Compute units of the current device, cached per device (the persistent launchers size their grids with it).
 #include <atomic>

@@ -23,8 +23,6 @@
 //   * split-K over workgroups, per-split slabs and the float64 slab reduction exactly as in
 //     conv_wgrad.hip (same slab layout, same reduce kernel); the next tile's operands travel
 //     global -> registers during the MFMA loop.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "conv_common.h"
@@ -381,24 +379,10 @@ static void wb_launch(const WgradBf3Args& a, dim3 grid, hipStream_t s) {
     hipLaunchKernelGGL((conv_wgrad_bf3_kernel<3, KS, S, TH, TW, NT, MI>), grid, dim3(256), 3 * plane, s, a);
 }
 
-// Launches the split-bf16 weight gradient of a conv (3x3 stride 1 / 2, pad 1; 1x1 stride 1 with >= 64
-// channels on both sides) into `slabs` ([PS][k*k][Cin][Cout]); returns the number of slabs written, or
-// 0 when the shape is not covered (the caller then uses the exact-fp32 kernel).  max_slabs bounds PS
-// (workspace size).  x is (N, Hin, Win, Cin), dz (N, Hout, Wout, Cout).
-// x_amax / dz_amax: both non-null = the fp16x2 split with those magnitude rows, else bf16x3.
-int mval_launch_wgrad_bf3_p2(const float* x, const void* x_p2, const unsigned* x_p2_rows, const float* dz, float* slabs, int N, int Hin,
-                             int Win, int Cin, int Hout, int Wout, int Cout, int k, int stride, int max_slabs, const unsigned* x_amax,
-                             const unsigned* dz_amax, hipStream_t s, const void* dz_p2 = nullptr, const unsigned* dz_p2_rows = nullptr);
+// The shapes the split-bf16 weight gradient covers: 3x3 stride 1 / 2, pad 1; 1x1 stride 1 with >= 64 channels on both sides
 int mval_wgrad_bf3_covers(int Cin, int Cout, int k, int stride) {
-  const char* e = getenv("MVAL_CONV");
-  if ((e && e[0] == 'f') || (Cin & 3) || (Cout & 3) || Cin < 16 || Cout < 16) return 0;
+  if ((Cin & 3) || (Cout & 3) || Cin < 16 || Cout < 16) return 0;
   return (k == 3 && (stride == 1 || stride == 2)) || (k == 1 && stride == 1 && Cin >= 64 && Cout >= 64);
-}
-
-int mval_launch_wgrad_bf3(const float* x, const float* dz, float* slabs, int N, int Hin, int Win, int Cin, int Hout,
-                          int Wout, int Cout, int k, int stride, int max_slabs, const unsigned* x_amax,
-                          const unsigned* dz_amax, hipStream_t s) {
-  return mval_launch_wgrad_bf3_p2(x, nullptr, nullptr, dz, slabs, N, Hin, Win, Cin, Hout, Wout, Cout, k, stride, max_slabs, x_amax, dz_amax, s);
 }
 
 static thread_local const float* g_wb_xz[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -409,23 +393,20 @@ void mval_conv_wgrad_set_z_x(const float* mean, const float* invstd, const float
   g_wb_xz_sqrt_m1 = sqrt_m1;
 }
 
+// Launches the split-bf16 weight gradient of a conv the kernel covers (mval_wgrad_bf3_covers) into `slabs`
+// ([PS][k*k][Cin][Cout]); returns the number of slabs written, or 0 when the shape is not covered or `split` is
+// false (the caller then uses the exact-fp32 kernel).  max_slabs bounds PS (workspace size).  x is (N, Hin, Win, Cin),
+// dz (N, Hout, Wout, Cout).  x_amax / dz_amax: both non-null = the fp16x2 split with those magnitude rows, else bf16x3.
 // x_p2 != nullptr: x as P2 planes (+ rows) instead of fp32 NHWC (needs dz_amax: the fp16 split; Cin % 8 == 0)
 int mval_launch_wgrad_bf3_p2(const float* x, const void* x_p2, const unsigned* x_p2_rows, const float* dz, float* slabs, int N, int Hin,
                              int Win, int Cin, int Hout, int Wout, int Cout, int k, int stride, int max_slabs, const unsigned* x_amax,
-                             const unsigned* dz_amax, hipStream_t s, const void* dz_p2, const unsigned* dz_p2_rows) {
+                             const unsigned* dz_amax, hipStream_t s, const void* dz_p2, const unsigned* dz_p2_rows, bool split) {
   // (XZ: mval_conv_wgrad_set_z_x before the call -- x is then the producer's raw z; consumed by THIS call whatever it returns)
   const float* xz[4] = {g_wb_xz[0], g_wb_xz[1], g_wb_xz[2], g_wb_xz[3]};
   g_wb_xz[0] = g_wb_xz[1] = g_wb_xz[2] = g_wb_xz[3] = nullptr;
   const int refuse = xz[0] ? -1 : 0;  // (no other kernel can stand in: x is not the activation)
-  static int enabled = -1;
-  if (enabled < 0) {
-    const char* e = getenv("MVAL_CONV");
-    enabled = (e && e[0] == 'f') ? 0 : 1;  // MVAL_CONV=fp32: exact-fp32 MFMA kernels everywhere
-  }
-  if (!enabled || (Cin & 3) || (Cout & 3) || Cin < 16 || Cout < 16) return refuse;
-  const bool k3 = k == 3 && (stride == 1 || stride == 2);
-  const bool k1 = k == 1 && stride == 1 && Cin >= 64 && Cout >= 64;
-  if (!k3 && !k1) return refuse;
+  if (!split || !mval_wgrad_bf3_covers(Cin, Cout, k, stride)) return refuse;
+  const bool k1 = k == 1;
   WgradBf3Args a;
   a.x = x; a.dz = dz; a.slabs = slabs;
   a.N = N; a.Hin = Hin; a.Win = Win; a.H = Hout; a.W = Wout; a.Cin = Cin; a.Cout = Cout;

@@ -3,7 +3,7 @@
 //
 // The direct kernels cover the operators that are not GEMM-shaped enough for the matrix
 // cores (3-channel stems, max-pool) or not yet ported to them (transposed conv); they are
-// also the on-device cross-check for the MFMA kernels (MVAL_FORCE_DIRECT=1).
+// also the on-device cross-check for the MFMA kernels (the all-direct plan).
 #include <stdlib.h>
 
 #include <mutex>
@@ -282,15 +282,6 @@ int mval_launch_conv_direct(const ConvArgs& a, int kind, hipStream_t s) {
 }
 
 // ---- op executor ------------------------------------------------------------------------
-static int force_direct() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MVAL_FORCE_DIRECT");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v;
-}
-
 static void fill_geometry(ConvArgs& a, const mval_op* op, int n_images) {
   a.N = n_images;
   a.Hin = op->hin; a.Win = op->win; a.Cin = op->cin;
@@ -379,7 +370,7 @@ extern "C" int mval_op_algo_supported(const mval_op* op, int n_images, int algo)
 static int op_keeps_argmax_keys(const mval_op* op) {
   if (!op || op->kind != MVAL_OP_CONV || !op->out_nchw || op->up || op->out_off >= 0 || op->k != 1 || op->stride != 1) return 0;
   if (op->algo == MVAL_ALGO_MFMA_P2) return 1;
-  return op->algo == MVAL_ALGO_MFMA && !force_direct();  // (conv_mfma.hip's 1x1 kernels: the heat-map layer of the h2 / bf3 / fp32 plans)
+  return op->algo == MVAL_ALGO_MFMA;  // (conv_mfma.hip's 1x1 kernels: the heat-map layer of the h2 / bf3 / fp32 plans)
 }
 
 static int op_launch(const mval_op* op, int n_images, float* workspace, const float* params, const float* net_input,
@@ -582,7 +573,6 @@ static int op_launch(const mval_op* op, int n_images, float* workspace, const fl
     MVAL_REQUIRE(rc == 0, "mval_op_launch: no split MFMA kernel for conv k%d s%d cin%d cout%d", op->k, op->stride, op->cin,
                  op->cout);
   } else if ((op->kind == MVAL_OP_CONV || op->kind == MVAL_OP_DECONV) && op->algo == MVAL_ALGO_MFMA) {
-    MVAL_REQUIRE(!force_direct(), "MVAL_FORCE_DIRECT=1 but the plan was packed for the MFMA kernels");
     if (op->kind == MVAL_OP_DECONV) deconv_as_conv(a, op);
     int rc = mval_launch_conv_mfma(a, s);
     MVAL_REQUIRE(rc == 0, "mval_op_launch: no MFMA kernel for conv k%d s%d cin%d cout%d", op->k, op->stride, op->cin,
@@ -591,7 +581,7 @@ static int op_launch(const mval_op* op, int n_images, float* workspace, const fl
   } else {
     MVAL_REQUIRE(op->kind == MVAL_OP_MAXPOOL || (a.w && a.scale && a.shift), "mval_op_launch: missing parameters");
     // 3-channel NCHW stems have their own store-shaped kernel; everything else is generic
-    if (op->kind != MVAL_OP_CONV || force_direct() || mval_launch_conv_stem(a, s))
+    if (op->kind != MVAL_OP_CONV || op->no_stem || mval_launch_conv_stem(a, s))
       mval_launch_conv_direct(a, op->kind, s);
     else
       amax_kept = true;  // the stem kernel keeps it
@@ -608,17 +598,8 @@ static MvalLanes g_lanes[MVAL_MAX_DEVICES];
 struct MvalNet {
   std::vector<mval_op> ops;
   int n_lanes = 1;
-  int lanes_override = -1;  // -1: MVAL_STREAMS decides; 0 / 1: forced off / on (mval_net_set_multi_stream)
+  bool multi_stream = true;  // (mval_net_set_multi_stream)
 };
-
-static int multi_stream_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MVAL_STREAMS");
-    v = (e && e[0] == '1' && e[1] == 0) ? 0 : 1;  // MVAL_STREAMS=1 forces single-stream execution
-  }
-  return v;
-}
 
 extern "C" void* mval_net_create(const mval_op* ops, int n_ops) {
   if (!ops || n_ops <= 0) {
@@ -635,7 +616,7 @@ extern "C" void* mval_net_create(const mval_op* ops, int n_ops) {
 
 extern "C" int mval_net_set_multi_stream(void* net, int mode) {
   MVAL_REQUIRE(net && mode >= -1 && mode <= 1, "mval_net_set_multi_stream: bad arguments");
-  reinterpret_cast<MvalNet*>(net)->lanes_override = mode;
+  reinterpret_cast<MvalNet*>(net)->multi_stream = mode != 0;
   return 0;
 }
 
@@ -704,7 +685,7 @@ static int net_forward(void* net, int n_images, float* workspace, const float* p
   MVAL_REQUIRE(net, "mval_net_forward: null net");
   MvalNet* n = reinterpret_cast<MvalNet*>(net);
   hipStream_t main_s = mval_stream(stream);
-  const bool multi = n->n_lanes > 1 && (n->lanes_override < 0 ? multi_stream_enabled() : n->lanes_override != 0);
+  const bool multi = n->n_lanes > 1 && n->multi_stream;
   MvalLanes* L = multi ? mval_device_lanes() : nullptr;
   if (multi) MVAL_REQUIRE(L != nullptr, "mval_net_forward: could not create the side streams");
   MvalLaneWalk walk(L, main_s);

@@ -44,18 +44,11 @@ extern "C" int mval_bn_bwd_fused(const float*, const float*, const float*, const
 // (MVAL_TRAIN_BWD_FUSED=0).  (Round 4 read the environment here on every call as well: a switch flipped between plan build and a later
 // step sent ops whose fp32 output was never written down the path that reads it -- ADVICE round 4.)
 int mval_conv_wgrad_on(const float* x, const float* dz, float* dw, float* ws, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout,
-                       int k, int stride, int pad, int x_nchw, const uint32_t* x_amax_row, const uint32_t* dz_amax_row, hipStream_t s);
+                       int k, int stride, int pad, int x_nchw, bool split, const uint32_t* x_amax_row, const uint32_t* dz_amax_row,
+                       hipStream_t s);
 void mval_conv_wgrad_set_p2_x(const void* planes, const unsigned* rows);  // conv_wgrad.hip: x as P2 planes for the next weight gradient
 void mval_conv_wgrad_set_p2_dz(const void* planes, const unsigned* rows);  // ... and dz
 void mval_conv_wgrad_set_z_x(const float* mean, const float* invstd, const float* gamma, const float* beta, float sqrt_m1);  // conv_wgrad_bf3.hip: x = relu(BatchNorm(z))
-struct WgradReduceJob {  // (conv_wgrad.hip)
-  const float* slabs;
-  float* dw;
-  int PS, T, Cin, Cout, parts;
-};
-void mval_conv_wgrad_defer(WgradReduceJob* out);  // the next mval_conv_wgrad_on records its slab reduction instead of launching it
-int mval_wgrad_reduce_jobs(const WgradReduceJob* jobs, int n, hipStream_t s);
-extern "C" size_t mval_conv_wgrad_workspace_floats(int cin, int cout, int k);
 void mval_bn_bwd_set_presummed(const double* part, const float* gmaxc, int nslots);  // train_ops.hip: the next fused BatchNorm backward finds its reduction done
 // ---- measurement mode (bench.py, the c3 line's per-kernel roofline): hipEvents around every launch group of a
 // training step, summed per kernel family.  Off unless mval_train_timing() armed it; the events are resolved (one
@@ -274,11 +267,6 @@ static int lane_of(const mval_train_op& t, int bit, int n_lanes) {
   return (n_lanes > 1 && (t.p2_flags & bit) && t.op.lane > 0 && t.op.lane < n_lanes) ? t.op.lane : 0;
 }
 
-#ifdef MVAL_TRAIN_ABLATE
-#include <stdio.h>
-extern int g_train_ablate;
-static int g_train_fwd_calls = 0, g_train_ablated = 0;
-#endif
 static int train_forward(const mval_train_op* ops, int n_ops, int n_images, float* arena, const float* params,
                          int64_t ones_off, int64_t zeros_off, const float* input_nchw, float* output_nchw,
                          double* ws0, int64_t ws_doubles, int n_lanes, float momentum, float eps, void* stream0) {
@@ -289,15 +277,6 @@ static int train_forward(const mval_train_op* ops, int n_ops, int n_images, floa
   // (A forward without joins at the phase changes -- every op behind the events of its producers, as the backward's MVAL_TRAIN_LANE_FREE --
   // measured the same or slower: C3 61.3-61.6 ms against 61.0-61.3 with the joins, profiles/r05/train_lanes_free2.log.)
   MvalLaneWalk walk(L, mval_stream(stream0));
-#ifdef MVAL_TRAIN_ABLATE
-  {
-    const char* e = getenv("MVAL_TRAIN_ABL");
-    g_train_ablate = e ? atoi(e) : 0;
-    g_train_fwd_calls++;
-    if (g_train_fwd_calls == 4 && g_train_ablate) fprintf(stderr, "[ablate %d] forward applies skipped per step: %d\n", g_train_ablate, g_train_ablated);
-    g_train_ablated = 0;
-  }
-#endif
   for (int i = 0; i < n_ops; i++) {
     g_tt_op = i;
     const mval_train_op& t = ops[i];
@@ -398,14 +377,6 @@ static int train_forward(const mval_train_op* ops, int n_ops, int n_images, floa
       // probe steps (first step, then every 1 024th): the planes are written then so that the probe measures this tensor like every other
       if (t.z_out && !(g_probe && i < g_probe_n)) continue;
       TtScope tt(TT_BN_APPLY, s);
-#ifdef MVAL_TRAIN_ABLATE
-      // measurement build only (profiles/r06: the step-level UPPER BOUND of BatchNorm-apply-in-the-consumer's-staging): from the third
-      // forward on, the apply of every residual-free ReLU op whose output exists as planes only is skipped -- its consumers read stale planes
-      if ((g_train_ablate & 1) && g_train_fwd_calls > 2 && t.out_p2_off > 0 && (t.p2_flags & 2) && op.res1_off < 0 && op.res2_off < 0 && op.relu && op.up == 0) {
-        g_train_ablated++;
-        continue;
-      }
-#endif
       if (t.out_p2_off > 0) {
         // (p2_flags bit 4 / 5) a residual that exists as planes only is read from those
         const bool r1p = (t.p2_flags & 16) && op.res1_off >= 0 && t.res1_p2_off > 0, r2p = (t.p2_flags & 32) && op.res2_off >= 0 && t.res2_p2_off > 0;
@@ -460,22 +431,12 @@ extern "C" int mval_train_forward_lanes(const mval_train_op* ops, int n_ops, int
                        eps, stream);
 }
 
-// (measurement only: MVAL_WGRAD_SLAB_ROT, engine_train.py -- the weight gradients' slab workspace of a lane as K regions walked op by op)
-static int g_slab_rot = 1;
-static int64_t g_slab_region = 0;
-extern "C" int mval_train_slab_rotation(int k, int64_t region_floats) {
-  g_slab_rot = k > 1 ? k : 1;
-  g_slab_region = region_floats;
-  return 0;
-}
-
 static int train_backward(const mval_train_op* ops, int n_ops, int n_images, float* arena, float* garena,
                           const float* params, int64_t ones_off, int64_t zeros_off, const float* input_nchw,
                           float* gz0, float* wsf0, double* ws0, float* sums0, int n_lanes, int64_t gz_stride, int64_t wsf_stride,
                           int64_t ws_stride, int64_t sums_stride, void* stream0) {
   MVAL_REQUIRE(ops && n_ops > 0 && n_images > 0 && garena && gz0 && wsf0 && ws0 && sums0 && n_lanes >= 1 && n_lanes <= MVAL_MAX_LANES,
                "mval_train_backward: bad arguments");
-  const int n_lanes_arg = n_lanes;  // (the workspace holds this many slices whatever the measurement mode does to n_lanes)
   if (g_tt_out) n_lanes = 1;
   MvalLanes* L = n_lanes > 1 ? mval_device_lanes() : nullptr;
   if (n_lanes > 1) MVAL_REQUIRE(L != nullptr, "mval_train_backward: could not create the side streams");
@@ -486,14 +447,6 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
   order.keep = free_run;
   // (round 6, MVAL_TRAIN_BSUM) per lane: the slots of reduction partials the last data gradient on that lane left in the lane's `ws` for
   // the op `presum_for` -- the very next op of the list (zin_rel == -1), so nothing else touches that scratch in between
-  // (round 6, MVAL_TRAIN_WGRAD_DEFER on the call's last op) every op's weight-gradient slabs go to a region of their own inside the whole
-  // workspace (all lanes' slices as ONE arena, walked in list order) and the reductions run as one launch per 64 ops when the call's lanes
-  // have joined -- 293 seven-microsecond launches per step become one per backward segment
-  const bool defer_reduce = !g_tt_out && wsf_stride > 0 && (ops[n_ops - 1].p2_flags & MVAL_TRAIN_WGRAD_DEFER);
-  std::vector<WgradReduceJob> rjobs;
-  if (defer_reduce) rjobs.reserve(n_ops);
-  int64_t slab_off = 0;
-  const int64_t slab_cap = wsf_stride * (int64_t)n_lanes_arg;
   int presum_slots[MVAL_MAX_LANES] = {0, 0, 0, 0};
   const mval_train_op* presum_for[MVAL_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
   for (int i = n_ops - 1; i >= 0; i--) {
@@ -507,7 +460,7 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
     if (free_run) order.before(t.gout_off, s);  // (the op reads its output's gradient: behind the slot's last writer)
     void* stream = reinterpret_cast<void*>(s);
     float* gz = gz0 + (int64_t)lane * gz_stride;
-    float* wsf = wsf0 + (int64_t)lane * wsf_stride + (g_slab_rot > 1 ? (int64_t)((g_tt_base + i) % g_slab_rot) * g_slab_region : 0);
+    float* wsf = wsf0 + (int64_t)lane * wsf_stride;
     double* ws = ws0 + (int64_t)lane * ws_stride;
     float* sums = sums0 + (int64_t)lane * sums_stride;
     const bool bwd_fused = !(t.p2_flags & 64);  // (bit 6: round 3's backward pair -- the plan's decision, MVAL_TRAIN_BWD_FUSED=0; it reads `out`)
@@ -571,16 +524,7 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
       // is the conv  x' = conv(y', W as [cout' = cin][cin' = cout], stride s, pad p), so
       //   dW = weight gradient of that conv with input dz (at the output resolution) and "dz" = x;
       //   dx = that conv applied to dz (plain stride-2 conv on the matrix cores).
-      float* wsd = wsf;
-      if (defer_reduce) {
-        const int64_t need = ((int64_t)mval_conv_wgrad_workspace_floats(op.cout, op.cin, op.k) + 63) & ~(int64_t)63;
-        MVAL_REQUIRE(slab_off + need <= slab_cap, "mval_train_backward: op %d: the slab workspace does not hold this call's deferred reductions", i);
-        wsd = wsf0 + slab_off;
-        slab_off += need;
-        rjobs.emplace_back();
-        mval_conv_wgrad_defer(&rjobs.back());
-      }
-      rc = mval_conv_wgrad(gz, x, t.dweight, wsd, n_images, op.hout, op.wout, op.cout, op.hin, op.win, op.cin, op.k,
+      rc = mval_conv_wgrad(gz, x, t.dweight, wsf, n_images, op.hout, op.wout, op.cout, op.hin, op.win, op.cin, op.k,
                            op.stride, op.pad, 0, stream);
       if (rc) return rc;
       if (t.gin_off >= 0) {
@@ -624,18 +568,9 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
       xw = arena + pr.z_off;
     } else if (t.fwd_p2 && (t.p2_flags & 1))  // (wgrad_p2: this op's input exists as P2 planes and its weight gradient reads those)
       mval_conv_wgrad_set_p2_x(arena + t.in_p2_off, reinterpret_cast<const unsigned*>(arena + t.in_p2_rows_off));
-    float* wsl = wsf;
-    if (defer_reduce) {
-      const int64_t need = ((int64_t)mval_conv_wgrad_workspace_floats(op.cin, op.cout, op.k) + 63) & ~(int64_t)63;
-      MVAL_REQUIRE(slab_off + need <= slab_cap, "mval_train_backward: op %d: the slab workspace (%lld floats) does not hold this call's deferred reductions", i,
-                   (long long)slab_cap);
-      wsl = wsf0 + slab_off;
-      slab_off += need;
-      rjobs.emplace_back();
-      mval_conv_wgrad_defer(&rjobs.back());
-    }
-    rc = mval_conv_wgrad_on(xw, gz, t.dweight, wsl, n_images, op.hin, op.win, op.cin, op.hout, op.wout, op.cout, op.k, op.stride, op.pad,
-                            op.in_nchw, (x_row && !t.zin_rel) ? x_row : nullptr, (x_row && !t.zin_rel) ? gz_row : nullptr, s);
+    rc = mval_conv_wgrad_on(xw, gz, t.dweight, wsf, n_images, op.hin, op.win, op.cin, op.hout, op.wout, op.cout, op.k, op.stride, op.pad,
+                            op.in_nchw, !(t.p2_flags & MVAL_TRAIN_WGRAD_FP32), (x_row && !t.zin_rel) ? x_row : nullptr,
+                            (x_row && !t.zin_rel) ? gz_row : nullptr, s);
     }
     if (rc) return rc;
     if (t.gin_off >= 0) {
@@ -698,10 +633,6 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
   }
   walk.finish();
   lanes_free.finish();
-  if (!rjobs.empty()) {  // (every lane has joined the caller's stream: the slabs are complete)
-    int rc = mval_wgrad_reduce_jobs(rjobs.data(), (int)rjobs.size(), mval_stream(stream0));
-    if (rc) return rc;
-  }
   tt_flush();
   return 0;
 }

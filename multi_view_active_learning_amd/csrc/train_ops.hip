@@ -392,9 +392,6 @@ __global__ __launch_bounds__(TR_APPLY_THREADS) __attribute__((amdgpu_waves_per_e
   if (amax_row) tr_amax_store(amax_row, amax);
 }
 
-#ifdef MVAL_TRAIN_ABLATE
-int g_train_ablate = 0;  // bit 0: skip the forward apply of residual-free P2-only ops (net_train.hip); bit 1: skip the backward reduction of residual-free ops
-#endif
 extern "C" int mval_bn_apply_fwd_p2_res(const float* z, const float* mean, const float* invstd, const float* gamma, const float* beta,
                                         const float* res1, const float* res2, float* out, void* p2_planes, uint32_t* p2_rows, int N, int H,
                                         int W, int C, int up, int relu, uint32_t* amax_row, uint8_t* relu_mask, const uint32_t* res1_row,
@@ -1082,9 +1079,6 @@ extern "C" int mval_bn_bwd_fused_p2(const float* gout, const float* out, const u
                        1.0f / (float)M, (float)sqrt(M > 1 ? (double)M - 1.0 : 1.0), bound_slot);
     MVAL_CHECK_LAUNCH("mval_bn_bwd_fused/finalize (pre-summed)");
   } else {
-#ifdef MVAL_TRAIN_ABLATE  // (measurement build only: the upper bound of "the backward reduction in the producer dgrad's epilogue" -- the sums stay stale)
-  if (!(g_train_ablate & 2) || gres1 || gres2)
-#endif
   hipLaunchKernelGGL(bn_bwd_reduce2_kernel, dim3(nb), dim3(256), sh, s, gout, out, z, mean, invstd, gamma, beta, gres1, gres2, ws,
                      (int)M, C, mask_mode, overwrite, relu_mask, p2 ? gmax_ws : nullptr, p2 ? bound_slot : nullptr);
   MVAL_CHECK_LAUNCH("mval_bn_bwd_fused/reduce");

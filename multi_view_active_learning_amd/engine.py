@@ -50,7 +50,7 @@ class MvalOp(C.Structure):
         ("w2_off", C.c_int64), ("scale2_off", C.c_int64), ("shift2_off", C.c_int64),
         ("bound_off", C.c_int64), ("bound2_off", C.c_int64), ("res1_amax_off", C.c_int64), ("res2_amax_off", C.c_int64),
         ("w3_off", C.c_int64), ("scale3_off", C.c_int64), ("shift3_off", C.c_int64), ("bound3_off", C.c_int64),
-        ("n_terms", C.c_int32), ("t_cin", C.c_int32 * 3), ("t_up", C.c_int32 * 3), ("reserved0", C.c_int32),
+        ("n_terms", C.c_int32), ("t_cin", C.c_int32 * 3), ("t_up", C.c_int32 * 3), ("no_stem", C.c_int32),
         ("t_in_off", C.c_int64 * 3), ("t_in_amax_off", C.c_int64 * 3), ("t_w_off", C.c_int64 * 3), ("t_scale_off", C.c_int64 * 3),
         ("t_shift_off", C.c_int64 * 3), ("t_bound_off", C.c_int64 * 3),
     ]
@@ -61,6 +61,20 @@ _KIND = {"conv": OP_CONV, "maxpool": OP_MAXPOOL, "deconv": OP_DECONV}
 
 def _align(n, a=64):
     return (n + a - 1) // a * a
+
+
+# switch -> the value an unset variable stands for: what an inference plan is built under (_plan_for reads them once per plan; the values
+# are the plan-cache key, and a plan never changes its kernels after it is built)
+_SWITCHES = {"MVAL_CONV": "p2", "MVAL_FORCE_DIRECT": "0", "MVAL_P2": "1", "MVAL_P2_W48": "1", "MVAL_FUSE_BLOCKS": "1", "MVAL_P2_BNECK": "1",
+             "MVAL_P2_STEM": "1", "MVAL_P2_FUSE_UP": "1", "MVAL_EPILOGUE_DECODE": "1", "MVAL_STREAMS": "multi"}
+
+
+def _switches(table=_SWITCHES):
+    """The switches of ``table`` (this module's, or engine_train's) as the environment sets them now: {name: value}."""
+    sw = {k: os.environ.get(k, d) for k, d in table.items()}
+    if sw["MVAL_CONV"] not in ("p2", "h2", "bf3", "fp32"):
+        raise ValueError("MVAL_CONV must be p2, h2, bf3 or fp32")
+    return sw
 
 
 def _conv_mode():
@@ -74,15 +88,10 @@ def _conv_mode():
                     producers keep; measured as accurate as the fp32-MFMA chain);
     bf3          -- exact three-way bf16 splits (6 MFMA products; what training plans always use);
     fp32         -- exact fp32-input MFMA (v_mfma_f32_16x16x4_f32) everywhere."""
-    mode = os.environ.get("MVAL_CONV", "p2")
-    if mode not in ("p2", "h2", "bf3", "fp32"):
-        raise ValueError("MVAL_CONV must be p2, h2, bf3 or fp32")
-    return mode
+    return _switches()["MVAL_CONV"]
 
 
 def _mfma_ok(op, in_nchw):
-    if os.environ.get("MVAL_FORCE_DIRECT") == "1":
-        return False
     if op.kind == "deconv":  # ConvTranspose2d(k4, s2, p1): stride-1 conv over the zero-dilated input
         return op.cin % 16 == 0 and (op.k, op.stride, op.pad) == (4, 2, 1)
     return (op.kind == "conv" and not in_nchw and op.cin % 16 == 0 and op.k in (1, 3)
@@ -101,8 +110,11 @@ def _pack_mode(op, pack):
 
 
 class InferencePlan:
-    def __init__(self, model, n, h, w, device):
+    def __init__(self, model, n, h, w, device, sw=None):
+        """sw: the switches the plan is built under (_switches(); default: as the environment sets them now)."""
         self.model, self.n, self.h, self.w, self.device = model, n, h, w, device
+        sw = self.sw = sw or _switches()
+        direct = sw["MVAL_FORCE_DIRECT"] == "1"  # the all-direct (VALU) plan: the on-device cross-check of the MFMA kernels
         g = model._graph
         self.graph = g
         # ---- activation geometry, op by op ------------------------------------------------
@@ -174,8 +186,8 @@ class InferencePlan:
         self.param_jobs = []  # (op index, packing, w_off, scale_off, shift_off)
         ptop = 0
         # P2 plan (csrc/conv_p2.h): every op but the image stem reads and writes fp16-pair planes; all or nothing
-        self.p2 = _conv_mode() == "p2" and os.environ.get("MVAL_FORCE_DIRECT") != "1" and self._p2_covers(lib, g, geo, n)
-        mode = "h2" if _conv_mode() == "p2" else _conv_mode()
+        self.p2 = sw["MVAL_CONV"] == "p2" and not direct and self._p2_covers(lib, g, geo, n, sw)
+        mode = "h2" if sw["MVAL_CONV"] == "p2" else sw["MVAL_CONV"]
         row_of = {}  # P2: activation id -> float offset of its n rows
         if self.p2:
             for a in g.acts:
@@ -191,8 +203,8 @@ class InferencePlan:
             m.k, m.stride, m.pad, m.cin, m.cout = op.k, op.stride, op.pad, op.cin, op.cout
             m.hin, m.win, m.hout, m.wout = hin, win, hout, wout
             m.up, m.relu, m.in_nchw, m.out_nchw = op.up, int(op.relu), int(in_nchw), int(out_nchw)
-            m.algo = ALGO_DIRECT
-            if _mfma_ok(op, in_nchw) and lib.mval_op_mfma_supported(C.byref(m), C.c_int(n)):
+            m.algo, m.no_stem = ALGO_DIRECT, int(direct)
+            if not direct and _mfma_ok(op, in_nchw) and lib.mval_op_mfma_supported(C.byref(m), C.c_int(n)):
                 m.algo = ALGO_MFMA
                 # fp32-accurate 16-bit splits on the matrix cores (fp16x2: 5.3x, bf16x3: 2.67x the fp32-MFMA rate)
                 # (the fp16 split wants one image per tile; maps under 8 rows fall back to bf16x3)
@@ -252,11 +264,12 @@ class InferencePlan:
         self.net = lib.mval_net_create(self.ops, C.c_int(len(self.ops)))
         if not self.net:
             raise _lib.MvalError("mval_net_create failed: " + lib.mval_last_error().decode())
+        _lib._check(lib.mval_net_set_multi_stream(C.c_void_p(self.net), C.c_int(0 if sw["MVAL_STREAMS"] == "1" else 1)), "mval_net_set_multi_stream")
 
     @staticmethod
-    def _p2_covers(lib, g, geo, n):
+    def _p2_covers(lib, g, geo, n, sw):
         """Every op after the image stem has a P2 kernel (HRNet: yes; PoseResNet's max-pool / transposed convs: no)."""
-        if os.environ.get("MVAL_P2", "1") == "0":
+        if sw["MVAL_P2"] == "0":
             return False
         stems = 0
         stem_dst = None
@@ -277,12 +290,12 @@ class InferencePlan:
                 return False
             # a transposed conv is four parity launches of persistent workgroups: on a few images (BASELINE configs[0]: 8) the h2 plan's
             # one launch with small tiles is ahead (1.55 vs 1.68 ms), from ~32 images on the P2 plan (C1 x 16: 7.2 vs 7.8 ms)
-            if op.kind == "deconv" and n < 32 and os.environ.get("MVAL_P2") != "force":
+            if op.kind == "deconv" and n < 32 and sw["MVAL_P2"] != "force":
                 return False
             # HRNet-W48 (48- / 96-channel branches: half-empty second K chunk; 24 x 18 and 12 x 9 maps) ran SLOWER on P2 than on
             # the h2 kernels through round 3 (C4 24.8 vs 22.4 ms); with round 4's full-width odd tiles (conv_p2.hip OW) and the
             # 48- / 96-channel fused up-paths it is ahead (21.8 vs 22.1 ms).  MVAL_P2_W48=0 keeps such plans on h2.
-            if op.cin % 32 and os.environ.get("MVAL_P2_W48", "1") == "0" and os.environ.get("MVAL_P2") != "force":
+            if op.cin % 32 and sw["MVAL_P2_W48"] == "0" and sw["MVAL_P2"] != "force":
                 return False
             m = MvalOp()
             m.kind, m.algo = _KIND[op.kind], ALGO_MFMA_P2
@@ -301,13 +314,13 @@ class InferencePlan:
         residuals and output; BasicBlocks of the 32- / 64-channel branches (hrnet.py:36-52) become ONE MVAL_OP_BLOCK
         launch (csrc/conv_block_p2.hip; MVAL_FUSE_BLOCKS=0 keeps the pair: the on-device cross-check)."""
         lib = _lib.lib()
-        fuse = os.environ.get("MVAL_FUSE_BLOCKS", "1") != "0"
+        fuse = self.sw["MVAL_FUSE_BLOCKS"] != "0"
         # measured (128 images): 32 channels on 64x64 maps 81 us fused vs 2 x 44 us; 64 channels on 32x32 maps 77 us
         # fused vs 2 x 33 us -- the two 64-channel convs are no longer HBM-bound one by one, so only the 32-channel
         # blocks are fused (round 3 measured the fused 64-channel block at 77 us against 2 x 33 for its two P2 convs; 10.38 vs 10.37 ms as a step)
         fuse_c = {32}
-        fuse_bneck = fuse and os.environ.get("MVAL_P2_BNECK", "1") != "0"
-        fuse_up = fuse and os.environ.get("MVAL_P2_FUSE_UP", "1") != "0"
+        fuse_bneck = fuse and self.sw["MVAL_P2_BNECK"] != "0"
+        fuse_up = fuse and self.sw["MVAL_P2_FUSE_UP"] != "0"
         uses = {}
         for op in g.ops:
             for a in (op.src, op.res1, op.res2):
@@ -320,7 +333,7 @@ class InferencePlan:
             C.memmove(C.byref(m), C.byref(self.graph_ops[i]), C.sizeof(MvalOp))
             if op.src == g.input:
                 b = g.ops[i + 1] if i + 1 < len(g.ops) else None
-                if (fuse and os.environ.get("MVAL_P2_STEM", "1") != "0" and b is not None and op.kind == b.kind == "conv" and op.k == b.k == 3
+                if (fuse and self.sw["MVAL_P2_STEM"] != "0" and b is not None and op.kind == b.kind == "conv" and op.k == b.k == 3
                         and op.stride == b.stride == 2 and op.pad == b.pad == 1 and op.cin == 3 and op.cout == b.cin == b.cout == 64 and op.bn and b.bn
                         and op.relu and b.relu and b.src == op.dst and uses.get(op.dst, 0) == 1 and b.res1 is None and b.res2 is None
                         and op.up == b.up == 0 and b.dst != g.output and (op.phase, op.lane) == (b.phase, b.lane)):
@@ -501,7 +514,7 @@ class InferencePlan:
         hrnet.py:36-52) whose two convs run on the fp16-split kernels becomes ONE MVAL_OP_BLOCK launch
         (csrc/conv_block.hip); everything else is launched op by op.  MVAL_FUSE_BLOCKS=0 keeps the unfused pair (the
         on-device cross-check of the fused kernel, tests/test_gpu_models.py)."""
-        fuse = os.environ.get("MVAL_FUSE_BLOCKS", "1") != "0"
+        fuse = self.sw["MVAL_FUSE_BLOCKS"] != "0"
         uses = {}
         for op in g.ops:
             for a in (op.src, op.res1, op.res2):
@@ -619,14 +632,14 @@ class InferencePlan:
     def _check_p2_slack(self):
         self._slack_pending = False
         self.p2_slack = self.p2_slack_log2()
-        if self.p2_slack > P2_MAX_SLACK_LOG2 and os.environ.get("MVAL_P2", "1") != "force":
+        if self.p2_slack > P2_MAX_SLACK_LOG2 and self.sw["MVAL_P2"] != "force":
             raise P2SlackError(self.p2_slack)
 
     # ---- run ---------------------------------------------------------------------------------
     def _keys_wanted(self):
         """Decode from the heat-map layer's epilogue: the plan's last kernel also keeps arg-max keys of every
         map it stores (mval_net_forward_keys), unless it runs on a generic kernel or MVAL_EPILOGUE_DECODE=0."""
-        return _lib.epilogue_decode_enabled() and bool(_lib.lib().mval_net_keeps_argmax_keys(C.c_void_p(self.net)))
+        return self.sw["MVAL_EPILOGUE_DECODE"] != "0" and bool(_lib.lib().mval_net_keeps_argmax_keys(C.c_void_p(self.net)))
 
     def _launch(self, x, out, keys=None):
         if keys is not None:
@@ -788,36 +801,19 @@ class P2SlackError(_lib.MvalError):
         self.slack = slack
 
 
-class _conv_mode_as:
-    """Temporarily select a conv kernel family (the plan cache is keyed by it).  Not thread-safe: os.environ."""
-
-    def __init__(self, mode):
-        self.mode = mode
-
-    def __enter__(self):
-        self.old = os.environ.get("MVAL_CONV")
-        os.environ["MVAL_CONV"] = self.mode
-
-    def __exit__(self, *exc):
-        if self.old is None:
-            os.environ.pop("MVAL_CONV", None)
-        else:
-            os.environ["MVAL_CONV"] = self.old
-
-
-def _plan_for(model, x):
+def _plan_for(model, x, sw=None):
+    """The model's plan for the shape of x under the switches sw (default: _switches())."""
     n, c, h, w = x.shape
     if c != 3:
         raise ValueError("expected (N, 3, H, W) images")
+    sw = sw or _switches()
     cache = model.__dict__.setdefault("_plans", {})
-    key = (n, h, w, x.device.index, os.environ.get("MVAL_FORCE_DIRECT") == "1", _conv_mode(), os.environ.get("MVAL_FUSE_BLOCKS", "1"),
-           os.environ.get("MVAL_P2", "1"), os.environ.get("MVAL_P2_W48", "1"), os.environ.get("MVAL_P2_BNECK", "1"), os.environ.get("MVAL_P2_STEM", "1"), os.environ.get("MVAL_P2_FUSE_UP", "1"),
-           os.environ.get("MVAL_EPILOGUE_DECODE", "1"))
+    key = (n, h, w, x.device.index) + tuple(sw.values())
     plan = cache.get(key)
     if plan is None:
         if len(cache) >= 4:  # keep the arena footprint bounded
             cache.pop(next(iter(cache)))
-        plan = cache[key] = InferencePlan(model, n, h, w, x.device)
+        plan = cache[key] = InferencePlan(model, n, h, w, x.device, sw)
     return plan
 
 
@@ -852,28 +848,27 @@ def run_network(model, x):
         from .engine_train import run_network_train
 
         return run_network_train(model, x)
+    sw = _switches()
     cap = _max_images_per_launch(model, x.shape[2], x.shape[3])
 
-    def run():
+    def run(sw):
         if x.shape[0] > cap:  # very large batches run as equal slices of one plan size (plus a remainder plan)
-            return torch.cat([_plan_for(model, xs).forward(xs) for xs in x.split(cap)])
-        return _plan_for(model, x).forward(x)
+            return torch.cat([_plan_for(model, xs, sw).forward(xs) for xs in x.split(cap)])
+        return _plan_for(model, x, sw).forward(x)
 
     # P2 plans whose a-priori bounds sit too far above the activations of the CURRENT parameters (checked on the first
     # forward after every parameter change) hand over to the h2 plan until the parameters change again
     fb = model.__dict__.get("_p2_fallback_sig")
-    if fb is not None and _conv_mode() == "p2":
+    if fb is not None and sw["MVAL_CONV"] == "p2":
         if _param_signature(model) == fb:
-            with _conv_mode_as("h2"):
-                return run()
+            return run(dict(sw, MVAL_CONV="h2"))
         model.__dict__["_p2_fallback_sig"] = None
     try:
-        return run()
+        return run(sw)
     except P2SlackError as e:
         import warnings
 
         warnings.warn(f"{e}; using the h2 kernels (fp32 activations, exact per-image scales) for these parameters. "
                       "MVAL_P2=force keeps the P2 plan, MVAL_P2_SLACK_CHECK=0 skips the check.", RuntimeWarning, stacklevel=3)
         model.__dict__["_p2_fallback_sig"] = _param_signature(model)
-        with _conv_mode_as("h2"):
-            return run()
+        return run(dict(sw, MVAL_CONV="h2"))

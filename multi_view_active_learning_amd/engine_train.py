@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from .engine import (ALGO_DIRECT, ALGO_MFMA, ALGO_MFMA_BF3, ALGO_MFMA_H2, PACK_HWIO, PACK_MFMA16, PACK_MFMA16_BF3,
-                     PACK_MFMA16_H2, _KIND, _PACK_OF, MvalOp, _align, _conv_mode, _mfma_ok)
+                     PACK_MFMA16_H2, _KIND, _PACK_OF, MvalOp, _align, _mfma_ok, _switches)
 
 TRAIN_AMAX_ROW = 576  # dwords per magnitude row in training: [count, <= 512 partial maxima], one row per tensor
 
@@ -68,22 +68,18 @@ TRAIN_P2_MAX_SLACK_LOG2 = 15.0
 # Gaussian tensor crosses 0.5 at a slack of ~2^14; the BASELINE plan measures < 0.02 (tests/test_gpu_train.py).
 TRAIN_P2_MAX_SMALL_FRAC = 0.5
 SLACK_EVERY = int(os.environ.get("MVAL_TRAIN_SLACK_EVERY", "1024"))
-# switch -> the value an unset variable stands for (the key must tell "unset" from every other setting: MVAL_TRAIN_LANES defaults to mode 3)
-_SWITCHES = {"MVAL_TRAIN_P2": "1", "MVAL_TRAIN_P2_WGRAD": "1", "MVAL_TRAIN_P2_DGRAD": "1", "MVAL_TRAIN_P2_RES": "1", "MVAL_TRAIN_EPI_STATS": "1",
-             "MVAL_TRAIN_BWD_FUSED": "1", "MVAL_TRAIN_RELU_MASK": "1", "MVAL_TRAIN_DGRAD_PARITY": "1", "MVAL_TRAIN_LANES": "3",
-             "MVAL_TRAIN_BN_IN_CONV": "1", "MVAL_TRAIN_BN_BWD_IN_DGRAD": "1", "MVAL_WGRAD_SLAB_ROT": "1",
-             "MVAL_TRAIN_WGRAD_BATCH": "0"}
+# switch -> the value an unset variable stands for: what a training plan is built under (run_network_train reads them once per step into
+# the plan-cache key; a plan never changes its paths after it is built.  The key must tell "unset" from every other setting: MVAL_TRAIN_LANES
+# defaults to mode 3)
+_SWITCHES = {"MVAL_CONV": "p2", "MVAL_FORCE_DIRECT": "0", "MVAL_TRAIN_P2": "1", "MVAL_TRAIN_P2_WGRAD": "1", "MVAL_TRAIN_P2_DGRAD": "1",
+             "MVAL_TRAIN_P2_RES": "1", "MVAL_TRAIN_EPI_STATS": "1", "MVAL_TRAIN_BWD_FUSED": "1", "MVAL_TRAIN_RELU_MASK": "1",
+             "MVAL_TRAIN_DGRAD_PARITY": "1", "MVAL_TRAIN_LANES": "3", "MVAL_TRAIN_BN_IN_CONV": "1", "MVAL_TRAIN_BN_BWD_IN_DGRAD": "1"}
 MAX_LANES = 4            # (csrc/conv_common.h MVAL_MAX_LANES)
 TRAIN_LANE_FWD, TRAIN_LANE_BWD, TRAIN_LANE_ORD, TRAIN_LANE_FREE = 256, 512, 1024, 2048  # (include/mval_hip.h MVAL_TRAIN_LANE_*)
 TRAIN_BSUM = 4096  # (MVAL_TRAIN_BSUM)
-TRAIN_WGRAD_DEFER = 8192  # (MVAL_TRAIN_WGRAD_DEFER)
+TRAIN_WGRAD_FP32 = 8192  # (MVAL_TRAIN_WGRAD_FP32)
 
 _ARMED = None  # weakref to the plan whose probe rows the library currently points at (one slot per process: csrc/net_train.hip g_probe)
-
-
-def _switches():
-    """The A/B switches a training plan is built under (part of the plan-cache key: a plan never changes its paths after it is built)."""
-    return tuple(os.environ.get(k, d) for k, d in _SWITCHES.items())
 
 
 def lane_flags(g, nl, mode):
@@ -114,7 +110,12 @@ def lane_flags(g, nl, mode):
 
 
 class TrainPlan:
-    def __init__(self, model, n, h, w, device, p2=True):
+    def __init__(self, model, n, h, w, device, p2=True, sw=None):
+        """sw: the switches the plan is built under (_switches(_SWITCHES); default: as the environment sets them now)."""
+        sw = self.sw = sw or _switches(_SWITCHES)
+        direct = sw["MVAL_FORCE_DIRECT"] == "1"
+        bf3 = sw["MVAL_CONV"] in ("bf3", "h2", "p2")  # (p2 is an inference activation format: training runs its h2 arithmetic)
+        h2 = sw["MVAL_CONV"] in ("h2", "p2")  # fp16x2 split (3 products) where it applies, else bf16x3 (6)
         g = model._graph
         self.model, self.graph, self.n, self.device = model, g, n, device
         self.steps, self.forwards, self.p2_slack, self._probe = 0, 0, None, None
@@ -182,9 +183,7 @@ class TrainPlan:
             m.up, m.relu, m.in_nchw, m.out_nchw = op.up, int(op.relu), int(in_nchw), int(out_nchw)
             m.phase, m.lane = op.phase, op.lane
             m.algo = ALGO_DIRECT
-            bf3 = _conv_mode() in ("bf3", "h2", "p2")  # (p2 is an inference activation format: training runs its h2 arithmetic)
-            h2 = _conv_mode() in ("h2", "p2")  # fp16x2 split (3 products) where it applies, else bf16x3 (6)
-            if _mfma_ok(op, in_nchw) and lib.mval_op_mfma_supported(C.byref(m), C.c_int(n)):
+            if not direct and _mfma_ok(op, in_nchw) and lib.mval_op_mfma_supported(C.byref(m), C.c_int(n)):
                 m.algo = ALGO_MFMA
                 if bf3 and op.kind == "conv" and op.k in (1, 3) and (op.cin % 32 == 0 or op.cin == 48):
                     for cand in ((ALGO_MFMA_H2, ALGO_MFMA_BF3) if (h2 and op.src != g.input and op.src in keeps_row) else (ALGO_MFMA_BF3,)):
@@ -256,7 +255,7 @@ class TrainPlan:
                             t.gz_amax_off = self.gz_amax_off
                 # stride-2 3x3 on even sizes: four 2x2 parity convs over dz instead of a 3x3 conv over the zero-dilated dz
                 # (2.25x fewer tap-pixels, and the fp16 split applies); weights packed with mode 4 as k = 4
-                if bf3 and op.k == 3 and op.stride == 2 and op.pad == 1 and os.environ.get("MVAL_TRAIN_DGRAD_PARITY", "1") != "0":
+                if bf3 and op.k == 3 and op.stride == 2 and op.pad == 1 and sw["MVAL_TRAIN_DGRAD_PARITY"] != "0":
                     for cand in ((ALGO_MFMA_H2, ALGO_MFMA_BF3) if (h2 and op.bn) else (ALGO_MFMA_BF3,)):
                         if lib.mval_conv_dgrad_parity_supported(C.c_int(n), C.c_int(hin), C.c_int(win), C.c_int(op.cin), C.c_int(hout),
                                                                 C.c_int(wout), C.c_int(op.cout), C.c_int(cand)):
@@ -282,7 +281,7 @@ class TrainPlan:
         p2_act = {}
         self.n_bn_in_conv = 0  # (round 6: ops whose BatchNorm apply runs inside their reader's staging; set below for P2 plans)
         self.p2_rows = []
-        if h2 and p2 and os.environ.get("MVAL_TRAIN_P2", "1") != "0":
+        if h2 and p2 and sw["MVAL_TRAIN_P2"] != "0":
             for i, op in enumerate(g.ops):
                 t = self.ops[i]
                 k = producer.get(op.src)
@@ -316,8 +315,8 @@ class TrainPlan:
                         setattr(pt, name, amax_row[r_])
             # weight gradients read x from the planes where the split kernel covers the conv; an activation whose EVERY consumer reads the
             # planes (P2 forward conv + P2 weight gradient, no residual use, not the network output) is not written as fp32 at all
-            p2w = os.environ.get("MVAL_TRAIN_P2_WGRAD", "1") != "0"
-            fused_bwd = os.environ.get("MVAL_TRAIN_BWD_FUSED", "1") != "0"  # (round 3's BatchNorm backward reads `out` and writes fp32 dz only)
+            p2w = sw["MVAL_TRAIN_P2_WGRAD"] != "0"
+            fused_bwd = sw["MVAL_TRAIN_BWD_FUSED"] != "0"  # (round 3's BatchNorm backward reads `out` and writes fp32 dz only)
             consumers = {}
             for i, op in enumerate(g.ops):
                 consumers.setdefault(op.src, []).append(i)
@@ -327,7 +326,7 @@ class TrainPlan:
             # a residual can be read from the planes as well (mval_bn_apply_fwd_p2_res) when the op that adds it runs the P2 apply: then
             # a block output whose every reader takes the planes -- the next block's first conv, its weight gradient, the residual add at
             # that block's end -- is P2-only too (MVAL_TRAIN_P2_RES=0: residuals stay fp32 NHWC)
-            p2res = os.environ.get("MVAL_TRAIN_P2_RES", "1") != "0"
+            p2res = sw["MVAL_TRAIN_P2_RES"] != "0"
             res_users = {}
             for i, op in enumerate(g.ops):
                 for r_, bit in ((op.res1, 16), (op.res2, 32)):
@@ -337,7 +336,7 @@ class TrainPlan:
                 cons = consumers.get(a_, [])
                 po = g.ops[producer[a_]]
                 # (its own backward must not need `out` either: a ReLU behind residual adds takes its mask from the mask bytes)
-                own_ok = not (po.relu and (po.res1 is not None or po.res2 is not None)) or (os.environ.get("MVAL_TRAIN_RELU_MASK", "1") != "0" and po.up == 0)
+                own_ok = not (po.relu and (po.res1 is not None or po.res2 is not None)) or (sw["MVAL_TRAIN_RELU_MASK"] != "0" and po.up == 0)
                 users = res_users.get(a_, [])
                 users_ok = all(self.ops[i].out_p2_off > 0 and g.ops[i].bn for i, _ in users) and (p2res or not users)
                 if p2w and fused_bwd and own_ok and users_ok and a_ != g.output and cons and all(self.ops[i].fwd_p2 and (self.ops[i].p2_flags & 1) for i in cons):
@@ -353,7 +352,7 @@ class TrainPlan:
             # (planes of the largest dz, rows, reduction scratch); MVAL_TRAIN_P2_DGRAD=0: the h2 data gradients.  (Round 5 also ran the
             # four parity convs of the stride-2 data gradients on conv_p2_kernel<2, ...> from the dz planes: 65.47 vs 65.2 ms per C3 step --
             # four persistent launches against the h2 kernel's one: not kept.)
-            if os.environ.get("MVAL_TRAIN_P2_DGRAD", "1") != "0" and fused_bwd:
+            if sw["MVAL_TRAIN_P2_DGRAD"] != "0" and fused_bwd:
                 want = []
                 for i, op in enumerate(g.ops):
                     t = self.ops[i]
@@ -377,7 +376,7 @@ class TrainPlan:
                         self.ops[i].gz_p2_off, self.ops[i].gz_p2_rows_off = planes, rows
                         op = g.ops[i]
                         # the weight gradient reads dz from the planes too where the split kernel covers the conv: no fp32 copy of dz
-                        if (os.environ.get("MVAL_TRAIN_P2_WGRAD", "1") != "0" and op.cout % 8 == 0
+                        if (p2w and op.cout % 8 == 0
                                 and lib.mval_conv_wgrad_split_covers(C.c_int(op.cin), C.c_int(op.cout), C.c_int(op.k), C.c_int(op.stride))
                                 and ((self.ops[i].p2_flags & 1) or self.ops[i].op.in_amax_off > 0)):
                             self.ops[i].p2_flags |= 8
@@ -386,7 +385,7 @@ class TrainPlan:
             # 3x3 stride-1 P2 conv on the same lane, with the P2 weight gradient reading dz from planes, is never written: that conv's staging
             # and its weight gradient's staging apply the BatchNorm from the producer's raw z.  MVAL_TRAIN_BN_IN_CONV=0: the separate apply pass.
             self.n_bn_in_conv = 0
-            if os.environ.get("MVAL_TRAIN_BN_IN_CONV", "1") != "0":
+            if sw["MVAL_TRAIN_BN_IN_CONV"] != "0":
                 lib.mval_conv_p2_inz_supported.restype = C.c_int
                 for a_ in p2_act:
                     k = producer[a_]
@@ -407,16 +406,17 @@ class TrainPlan:
                     ct.zin_rel = k - j
                     self.n_bn_in_conv += 1
 
-        # the two BatchNorm A/B switches are the PLAN's decision and travel in p2_flags (bit 6: round 3's backward pair, bit 7: statistics by
-        # the separate pass): net_train.hip does not read the environment
-        bits = (0 if os.environ.get("MVAL_TRAIN_BWD_FUSED", "1") != "0" else 64) | (0 if os.environ.get("MVAL_TRAIN_EPI_STATS", "1") != "0" else 128)
+        # the two BatchNorm A/B switches and the exact-fp32 weight gradients of MVAL_CONV=fp32 are the PLAN's decision and travel in p2_flags
+        # (bit 6: round 3's backward pair, bit 7: statistics by the separate pass, bit 13): net_train.hip does not read the environment
+        bits = ((0 if sw["MVAL_TRAIN_BWD_FUSED"] != "0" else 64) | (0 if sw["MVAL_TRAIN_EPI_STATS"] != "0" else 128)
+                | (0 if bf3 else TRAIN_WGRAD_FP32))
         for i, op in enumerate(g.ops):  # producers leave max |out| where a split conv will look for it
             self.ops[i].out_amax_off = amax_row.get(op.dst, 0)
             self.ops[i].p2_flags |= bits
         self.uses_p2 = any(t.out_p2_off > 0 or (t.p2_flags & 4) for t in self.ops)
         # ReLU behind residual adds (BasicBlock / Bottleneck outputs, fuse sums at the conv resolution): the forward apply keeps
         # (out > 0) as one byte per float4, the backward reads that instead of `out` (a sixteenth of the bytes)
-        if os.environ.get("MVAL_TRAIN_RELU_MASK", "1") != "0":
+        if sw["MVAL_TRAIN_RELU_MASK"] != "0":
             for i, op in enumerate(g.ops):
                 if op.bn and op.relu and op.up == 0 and (op.res1 is not None or op.res2 is not None) and op.cout % 4 == 0:
                     self.ops[i].mask_off = self._row_top
@@ -428,7 +428,7 @@ class TrainPlan:
         # BasicBlock) and with residuals (mask from the kept bits: conv2 of a block followed by another block; the apply pass then also
         # scatters the residual gradients).  The library checks the rest at launch (same lane, room for the partials).
         self.n_bn_bwd_in_dgrad = 0
-        if self.uses_p2 and os.environ.get("MVAL_TRAIN_BN_BWD_IN_DGRAD", "1") != "0" and os.environ.get("MVAL_TRAIN_BWD_FUSED", "1") != "0":
+        if self.uses_p2 and sw["MVAL_TRAIN_BN_BWD_IN_DGRAD"] != "0" and sw["MVAL_TRAIN_BWD_FUSED"] != "0":
             lib.mval_conv_p2_bsum_supported.restype = C.c_int
             for j in range(1, len(g.ops)):
                 co, ct, po, pt = g.ops[j], self.ops[j], g.ops[j - 1], self.ops[j - 1]
@@ -477,11 +477,6 @@ class TrainPlan:
         self.stats = torch.zeros(max(stat_top, 64), **f32)
         # (lanes: one slice of every scratch buffer per lane, mval_train_*_lanes)
         self.gz_lane, self.wsf_lane = _align(max(gz_max, 64)), _align(max(wsf_max, 64))
-        # (measurement only, profiles/r06 item 2b: MVAL_WGRAD_SLAB_ROT=K gives every lane K slab regions and the library walks them op by op, so an op's
-        # slab reduction reads from HBM instead of the Infinity Cache -- what a reduction deferred to the end of a backward segment would do)
-        self.slab_rot = max(1, int(os.environ.get("MVAL_WGRAD_SLAB_ROT", "1")))
-        self.wsf_region = self.wsf_lane
-        self.wsf_lane *= self.slab_rot
         self.gz = torch.empty(self.gz_lane * self.n_lanes, **f32)
         self.wsf = torch.empty(self.wsf_lane * self.n_lanes, **f32)
         # float64 scratch of the BatchNorm reductions; sized so that the forward conv epilogues' per-workgroup statistics
@@ -532,22 +527,6 @@ class TrainPlan:
                 bounds.append(i)
         bounds.append(len(g.ops))
         self.segments = [(a, b) for a, b in zip(bounds, bounds[1:]) if b > a]
-        # Round 6 (MVAL_TRAIN_WGRAD_DEFER; opt-in: MVAL_TRAIN_WGRAD_BATCH=1): the weight gradients' slab reductions of a backward segment as ONE
-        # launch per 64 ops at its end, every op's slabs in a region of its own (the workspace becomes one arena that holds the largest segment's
-        # regions).  Bit-identical and MEASURED SLOWER -- C3 57.7-58.3 -> 60.8 ms (profiles/r06/wgrad_reduce_batched_ab.log): the per-op reduction
-        # reads its 28-56 MB of slabs back from the Infinity Cache right after they were written, into a buffer the next op overwrites there; deferred,
-        # ~5 GB of slabs per step go out to HBM and come back (the 293 launches it saves are worth at most 1.5 ms: wgrad_reduce_bounds...log).
-        self.wgrad_batch = os.environ.get("MVAL_TRAIN_WGRAD_BATCH", "0") == "1" and self.slab_rot == 1
-        if self.wgrad_batch:
-            lib.mval_conv_wgrad_workspace_floats.restype = C.c_size_t
-            need = [0 if op.kind == "maxpool" else (int(lib.mval_conv_wgrad_workspace_floats(C.c_int(op.cin), C.c_int(op.cout), C.c_int(op.k))) + 63) // 64 * 64
-                    for op in g.ops]
-            total = max(sum(need[a:b]) for a, b in self.segments)
-            if total > self.wsf_lane * self.n_lanes:
-                self.wsf_lane = _align((total + self.n_lanes - 1) // self.n_lanes)
-                self.wsf = torch.empty(self.wsf_lane * self.n_lanes, dtype=torch.float32, device=device)
-            for t in self.ops:
-                t.p2_flags |= TRAIN_WGRAD_DEFER
         self.seg_params = []
         for lo, hi in self.segments:
             ps = []
@@ -576,7 +555,7 @@ class TrainPlan:
         self.n_lanes = 1
         # 0: one stream; 1: lanes in the phases without shared gradient slots only; 2: in all phases; 3 (default): and the backward without
         # joins at the phase changes -- every dependency through the slot events
-        mode = os.environ.get("MVAL_TRAIN_LANES", _SWITCHES["MVAL_TRAIN_LANES"])
+        mode = self.sw["MVAL_TRAIN_LANES"]
         if mode == "0" or not g.ops:
             return
         nl = min(MAX_LANES, max(op.lane for op in g.ops) + 1)
@@ -753,7 +732,7 @@ class TrainPlan:
         # (activations only: a dz tensor is mostly tiny values by construction -- the mean terms at masked positions -- whose ABSOLUTE error,
         # <= 2^-25 scaled, is what enters the gradient sums; its fraction is reported, not judged)
         small = res["act"]["max_small_frac"] if res["act"] else 0.0
-        if (worst > TRAIN_P2_MAX_SLACK_LOG2 or small > TRAIN_P2_MAX_SMALL_FRAC) and os.environ.get("MVAL_TRAIN_P2", "1") != "force":
+        if (worst > TRAIN_P2_MAX_SLACK_LOG2 or small > TRAIN_P2_MAX_SMALL_FRAC) and self.sw["MVAL_TRAIN_P2"] != "force":
             import warnings
 
             warnings.warn(f"P2 training plan: a-priori bound 2^{worst:.1f} above a tensor's maximum (limit 2^{TRAIN_P2_MAX_SLACK_LOG2:.0f}), {small:.2f} of a "
@@ -818,8 +797,6 @@ class TrainPlan:
         lo, hi = self.segments[k]
         grads = self._grads
         sub = (MvalTrainOp * (hi - lo)).from_address(C.addressof(self.ops) + lo * C.sizeof(MvalTrainOp))
-        if self.slab_rot > 1:
-            _lib.lib().mval_train_slab_rotation(C.c_int(self.slab_rot), C.c_int64(self.wsf_region))
         _lib.lib().mval_train_timing_base(C.c_int(lo))  # (measurement mode's per-operator breakdown)
         _lib._check(
             _lib.lib().mval_train_backward_lanes(
@@ -893,11 +870,12 @@ def run_network_train(model, x):
     n, c, h, w = x.shape
     cache = model.__dict__.setdefault("_train_plans", {})
     p2 = not model.__dict__.get("_train_p2_off", False)  # (the slack probe's verdict on this model's parameters, TrainPlan._probe_read)
-    key = (n, h, w, x.device.index, _conv_mode(), p2) + _switches()  # (the mode and the switches select the plan's kernels and packings)
+    sw = _switches(_SWITCHES)
+    key = (n, h, w, x.device.index, p2) + tuple(sw.values())  # (the switches select the plan's kernels and packings)
     plan = cache.get(key)
     if plan is None:
         cache.clear()  # one training geometry at a time: the arenas are large
-        plan = cache[key] = TrainPlan(model, n, h, w, x.device, p2=p2)
+        plan = cache[key] = TrainPlan(model, n, h, w, x.device, p2=p2, sw=sw)
     carry = x
     for k in range(len(plan.segments)):
         carry = _SegFn.apply(carry, plan, k, *plan.seg_params[k])

@@ -418,7 +418,7 @@ def test_argmax_keys_serve_only_the_plans_factorisation(monkeypatch):
     assert _lib.argmax_keys_of(out) is None
 
 
-def test_python_constants_match_the_header():
+def test_ctypes_mirror_constants_match_the_header():
     """The ctypes mirror restates a few #defines / enum values of include/mval_hip.h: they must agree."""
     import os
     import re
@@ -438,7 +438,8 @@ def test_python_constants_match_the_header():
     from multi_view_active_learning_amd import engine_train
 
     assert define("MVAL_TRAIN_LANE_FWD") == engine_train.TRAIN_LANE_FWD and define("MVAL_TRAIN_LANE_BWD") == engine_train.TRAIN_LANE_BWD
-    assert define("MVAL_TRAIN_LANE_ORD") == engine_train.TRAIN_LANE_ORD and define("MVAL_TRAIN_BSUM") == engine_train.TRAIN_BSUM and define("MVAL_TRAIN_WGRAD_DEFER") == engine_train.TRAIN_WGRAD_DEFER
+    assert define("MVAL_TRAIN_LANE_ORD") == engine_train.TRAIN_LANE_ORD and define("MVAL_TRAIN_BSUM") == engine_train.TRAIN_BSUM
+    assert define("MVAL_TRAIN_WGRAD_FP32") == engine_train.TRAIN_WGRAD_FP32
     # the ctypes mirror of mval_train_op ends with the round-6 fields and has the header's size (8-byte aligned, two int32 at the end)
     assert [f[0] for f in engine_train.MvalTrainOp._fields_][-2:] == ["zin_rel", "z_out"]
     csrc = open(os.path.join(os.path.dirname(__file__), "..", "multi_view_active_learning_amd", "csrc", "conv_common.h")).read()

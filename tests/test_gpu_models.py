@@ -316,8 +316,12 @@ def test_network_fused_blocks_vs_unfused(dev, mode, monkeypatch):
     assert float((y1 - y2).abs().max()) <= tol
 
 
-def test_network_mfma_vs_direct_kernels(dev, monkeypatch):
-    """On-device cross-check: the MFMA plan and the all-direct (VALU) plan agree."""
+def test_network_mfma_vs_direct_kernels(dev, monkeypatch, tmp_path):
+    """On-device cross-check: the MFMA plan and the all-direct (VALU) plan agree.  The all-direct plan built after a default forward in
+    the same process runs the kernels a fresh process runs under MVAL_FORCE_DIRECT=1: the same bits."""
+    import subprocess
+    import sys
+
     c = cases.model_cases()["w32_small"]
     m, sd = _load(c, dev)
     x = torch.from_numpy(cases.model_input(c)).to(dev)
@@ -328,6 +332,14 @@ def test_network_mfma_vs_direct_kernels(dev, monkeypatch):
         want = models.hrnet_forward(sd, x.cpu(), models.HRNET_W32)
     assert (y1 - want).abs().max() < 2e-4 * want.abs().max()
     assert (y2 - want).abs().max() < 2e-4 * want.abs().max()
+    here, out = os.path.dirname(os.path.abspath(__file__)), str(tmp_path / "direct.npy")
+    subprocess.run([sys.executable, "-c", f"import sys; sys.path[:0] = {[os.path.dirname(here), G, here]!r}\n"
+                    "import numpy as np, torch, cases, test_gpu_models as t\n"
+                    "c = cases.model_cases()['w32_small']\n"
+                    "m, _ = t._load(c, torch.device('cuda:0'))\n"
+                    "with torch.no_grad():\n"
+                    f"    np.save({out!r}, m(torch.from_numpy(cases.model_input(c)).cuda()).cpu().numpy())\n"], check=True, timeout=900)
+    np.testing.assert_array_equal(y2.numpy(), np.load(out))
 
 
 def test_state_dict_reload_repacks(dev):

@@ -351,6 +351,35 @@ def test_all_gradients_vs_cpu_oracle(dev, c, monkeypatch):
             np.testing.assert_allclose(v.cpu().numpy(), sd32[k].detach().numpy(), rtol=2e-4, atol=2e-5, err_msg=k)
 
 
+def _in_fresh_process(code, out):
+    """Runs `code` in a new Python process (the environment of this one; the repository, tests/golden and tests/ on its path) and loads
+    the file `out` it saved."""
+    import subprocess
+    import sys
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    subprocess.run([sys.executable, "-c", f"import sys; sys.path[:0] = {[os.path.dirname(here), G, here]!r}\n" + code], check=True, timeout=900)
+    return np.load(out)
+
+
+def test_fp32_plan_after_a_default_step_equals_a_fresh_process(dev, monkeypatch, tmp_path):
+    """A training plan built under MVAL_CONV=fp32 after a default-mode step in the same process runs its own mode's kernels (the weight
+    gradients on the exact-fp32 kernel included: the library keeps no switch of its own): its gradients equal, bit for bit, those of a
+    fresh process that ran only the fp32 step."""
+    c = cases.train_cases()["w32_train"]
+    _train_once(c, dev)
+    monkeypatch.setenv("MVAL_CONV", "fp32")
+    m = _train_once(c, dev)[0]
+    out = str(tmp_path / "grads.npz")
+    want = _in_fresh_process("import numpy as np, torch, cases, test_gpu_train as t\n"
+                             "m = t._train_once(cases.train_cases()['w32_train'], torch.device('cuda:0'))[0]\n"
+                             f"np.savez({out!r}, *[p.grad.cpu().numpy() for p in m.parameters()])\n", out)
+    got = [p.grad.cpu().numpy() for p in m.parameters()]
+    assert len(want.files) == len(got)
+    bad = [k for i, ((k, _), g) in enumerate(zip(m.named_parameters(), got)) if not np.array_equal(g, want[f"arr_{i}"])]
+    assert not bad, (len(bad), bad[:5])
+
+
 def test_train_step_guard_and_eval_after_train(dev):
     from multi_view_active_learning_amd.config import get_default_configs
     from multi_view_active_learning_amd.strategy import ActiveLearningStrategy
@@ -626,27 +655,6 @@ def test_bn_in_conv_is_bit_identical_to_the_separate_apply(dev, case, monkeypatc
     print(f"[bn bwd in dgrad] gradient rel-L2 vs the reduction pass: median {errs[len(errs) // 2]:.2e} worst {errs[-1]:.2e}")
     assert errs[-1] < 5e-2 and errs[len(errs) // 2] < 5e-3, (errs[-1], errs[len(errs) // 2])
     assert all(torch.equal(b, rf[k]) for k, b in m1.named_buffers() if "running" in k)
-
-
-@pytest.mark.parametrize("case", [cases.train_cases()["w32_train"], cases.train_cases()["r50_train"]], ids=["w32_train", "r50_train"])
-def test_batched_slab_reductions_are_bit_identical_to_the_per_op_launches(dev, case, monkeypatch):
-    """Round 6 (MVAL_TRAIN_WGRAD_DEFER, opt-in MVAL_TRAIN_WGRAD_BATCH=1: measured slower, profiles/r06): the weight gradients' split-K slab
-    reductions of a backward segment as ONE launch per 64 ops at the segment's end (every op's slabs in a region of their own) instead of one
-    7 us launch per op.  Every output is still summed by the same number of lanes in the same order, so the gradients equal the per-op form
-    (the default) bit for bit -- HRNet-W32 and PoseResNet-50 (transposed convs: the roles-swapped weight gradient)."""
-    from multi_view_active_learning_amd import engine_train
-
-    monkeypatch.setenv("MVAL_TRAIN_WGRAD_BATCH", "1")
-    m1, _, hm1, l1, _ = _train_once(case, dev)
-    plan = next(iter(m1._train_plans.values()))
-    assert plan.wgrad_batch and all(t.p2_flags & engine_train.TRAIN_WGRAD_DEFER for t in plan.ops)
-    g1 = {k: p.grad.detach().clone() for k, p in m1.named_parameters()}
-    monkeypatch.setenv("MVAL_TRAIN_WGRAD_BATCH", "0")
-    m0, _, hm0, l0, _ = _train_once(case, dev)
-    assert not next(iter(m0._train_plans.values())).wgrad_batch
-    assert torch.equal(hm1, hm0) and torch.equal(l1, l0)
-    bad = [k for k, p in m0.named_parameters() if not torch.equal(p.grad, g1[k])]
-    assert not bad, (len(bad), bad[:5])
 
 
 @pytest.mark.parametrize("wd", [0.0, 0.01], ids=["plain", "weight_decay"])

@@ -535,11 +535,22 @@ typedef struct mval_train_op {
    * upsample, planes only) has exactly one reader, the 3x3 stride-1 P2 conv `zin_rel` ops away, whose forward staging and whose weight
    * gradient's staging compute relu(BatchNorm(z)) from this op's raw z, batch statistics and affine parameters on the way into LDS
    * (csrc/conv_p2.h P2Args::in_z, conv_wgrad_bf3.hip XZ: the same arithmetic, scale and split as the apply pass -- bit-identical operands).
-   * zin_rel != 0 (the reader): ops[i + zin_rel] is that producer (zin_rel < 0: it precedes the reader in the list). */
+   * zin_rel != 0 (the reader): ops[i + zin_rel] is that producer (zin_rel < 0: it precedes the reader in the list).  mval_train_backward*
+   * may be called on a sub-range of the list: `ops` must then point INTO the full op list whenever an op of the range has zin_rel != 0,
+   * because the producer may lie before ops[0] and is dereferenced there. */
   int32_t zin_rel, z_out;  /* p2_flags bit 12 (MVAL_TRAIN_BSUM, with zin_rel == -1): this op's data gradient -- the ONLY writer of its
                             * producer's output gradient -- also keeps the BatchNorm backward reduction of what it writes (P2Args::bs_z), and the
                             * producer's backward skips that pass */
 } mval_train_op;
+/* p2_flags bits 0 - 7 (the prose at the fields above says when each applies): */
+#define MVAL_TRAIN_WGRAD_X_P2 1     /* the weight gradient reads the op's input from the P2 planes */
+#define MVAL_TRAIN_OUT_P2_ONLY 2    /* the apply writes ONLY the P2 planes of the op's output: no fp32 NHWC copy */
+#define MVAL_TRAIN_DGRAD_P2 4       /* the data gradient runs on the P2 kernels: the BatchNorm backward also writes dz as P2 planes */
+#define MVAL_TRAIN_WGRAD_DZ_P2 8    /* with MVAL_TRAIN_DGRAD_P2: the weight gradient reads dz from the planes too, no fp32 dz is written */
+#define MVAL_TRAIN_RES1_P2 16       /* the forward apply reads res1 from that activation's P2 planes (res1_p2_off) */
+#define MVAL_TRAIN_RES2_P2 32       /* the forward apply reads res2 from that activation's P2 planes (res2_p2_off) */
+#define MVAL_TRAIN_BN_BWD_PAIR 64   /* the BatchNorm backward is round 3's pair (reads `out`): not with bits 1 - 3 */
+#define MVAL_TRAIN_STATS_PASS 128   /* batch statistics by the separate pass over z, not from the conv's epilogue partials */
 #define MVAL_TRAIN_BSUM 4096
 /* p2_flags bit 13: this op's weight gradient runs on the exact-fp32 kernels even where the split kernel covers it (the exact-fp32 plan). */
 #define MVAL_TRAIN_WGRAD_FP32 8192

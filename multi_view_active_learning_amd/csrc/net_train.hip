@@ -285,7 +285,7 @@ static int train_forward(const mval_train_op* ops, int n_ops, int n_images, floa
     hipStream_t s = walk.stream_for(op.phase, lane);
     void* stream = reinterpret_cast<void*>(s);
     double* ws = ws0 + (int64_t)lane * ws_doubles;
-    const bool epi_stats = !(t.p2_flags & 128);  // (bit 7: batch statistics by the separate pass over z -- the plan's decision, MVAL_TRAIN_EPI_STATS=0)
+    const bool epi_stats = !(t.p2_flags & MVAL_TRAIN_STATS_PASS);  // (bit 7: batch statistics by the separate pass over z -- the plan's decision, MVAL_TRAIN_EPI_STATS=0)
     ConvArgs a = {};
     geometry(a, op, n_images);
     a.in = op.in_off >= 0 ? arena + op.in_off : input_nchw;
@@ -379,9 +379,9 @@ static int train_forward(const mval_train_op* ops, int n_ops, int n_images, floa
       TtScope tt(TT_BN_APPLY, s);
       if (t.out_p2_off > 0) {
         // (p2_flags bit 4 / 5) a residual that exists as planes only is read from those
-        const bool r1p = (t.p2_flags & 16) && op.res1_off >= 0 && t.res1_p2_off > 0, r2p = (t.p2_flags & 32) && op.res2_off >= 0 && t.res2_p2_off > 0;
+        const bool r1p = (t.p2_flags & MVAL_TRAIN_RES1_P2) && op.res1_off >= 0 && t.res1_p2_off > 0, r2p = (t.p2_flags & MVAL_TRAIN_RES2_P2) && op.res2_off >= 0 && t.res2_p2_off > 0;
         rc = mval_bn_apply_fwd_p2_res(a.out, t.mean, t.invstd, t.gamma, t.beta, (op.res1_off >= 0 && !r1p) ? arena + op.res1_off : nullptr,
-                                  (op.res2_off >= 0 && !r2p) ? arena + op.res2_off : nullptr, (t.p2_flags & 2) ? nullptr : out, arena + t.out_p2_off,
+                                  (op.res2_off >= 0 && !r2p) ? arena + op.res2_off : nullptr, (t.p2_flags & MVAL_TRAIN_OUT_P2_ONLY) ? nullptr : out, arena + t.out_p2_off,
                                   reinterpret_cast<uint32_t*>(arena + t.out_p2_rows_off), n_images, op.hout, op.wout, op.cout, op.up, op.relu,
                                   t.out_amax_off > 0 ? reinterpret_cast<uint32_t*>(arena + t.out_amax_off) : nullptr,
                                   t.mask_off > 0 ? reinterpret_cast<uint8_t*>(arena + t.mask_off) : nullptr,
@@ -463,8 +463,8 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
     float* wsf = wsf0 + (int64_t)lane * wsf_stride;
     double* ws = ws0 + (int64_t)lane * ws_stride;
     float* sums = sums0 + (int64_t)lane * sums_stride;
-    const bool bwd_fused = !(t.p2_flags & 64);  // (bit 6: round 3's backward pair -- the plan's decision, MVAL_TRAIN_BWD_FUSED=0; it reads `out`)
-    MVAL_REQUIRE(bwd_fused || !(t.p2_flags & (2 | 4 | 8)), "mval_train_backward: op %d: the round-3 BatchNorm backward with a P2-only output / P2 dz", i);
+    const bool bwd_fused = !(t.p2_flags & MVAL_TRAIN_BN_BWD_PAIR);  // (bit 6: round 3's backward pair -- the plan's decision, MVAL_TRAIN_BWD_FUSED=0; it reads `out`)
+    MVAL_REQUIRE(bwd_fused || !(t.p2_flags & (MVAL_TRAIN_OUT_P2_ONLY | MVAL_TRAIN_DGRAD_P2 | MVAL_TRAIN_WGRAD_DZ_P2)), "mval_train_backward: op %d: the round-3 BatchNorm backward with a P2-only output / P2 dz", i);
     MVAL_REQUIRE(t.gout_off >= 0, "mval_train_backward: op %d has no output gradient slot", i);
     if (op.kind == MVAL_OP_MAXPOOL) {
       if (t.gin_off >= 0) {
@@ -482,7 +482,7 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
     uint32_t* gz_row = (t.has_bn && t.gz_amax_off > 0) ? reinterpret_cast<uint32_t*>(arena + t.gz_amax_off) : nullptr;
     int rc;
     // (p2_flags bit 2) the data gradient on the P2 kernels: the BatchNorm backward also leaves dz as P2 planes
-    const bool dz_p2 = (t.p2_flags & 4) && t.gz_p2_off > 0 && t.gin_off >= 0 && bwd_fused && t.has_bn && op.up == 0;
+    const bool dz_p2 = (t.p2_flags & MVAL_TRAIN_DGRAD_P2) && t.gz_p2_off > 0 && t.gin_off >= 0 && bwd_fused && t.has_bn && op.up == 0;
     if (ord) {  // (the BatchNorm backward scatters the residual gradients)
       order.before(t.gres1_off, s);
       order.before(t.gres2_off, s);
@@ -497,7 +497,7 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
       rc = mval_bn_bwd_fused_p2(garena + t.gout_off, outp, t.mask_off > 0 ? reinterpret_cast<const uint8_t*>(arena + t.mask_off) : nullptr,
                              arena + t.z_off, t.mean, t.invstd, t.gamma, t.beta,
                              t.gres1_off >= 0 ? garena + t.gres1_off : nullptr, t.gres2_off >= 0 ? garena + t.gres2_off : nullptr,
-                             (dz_p2 && (t.p2_flags & 8)) ? nullptr : gz,  // (bit 3: the weight gradient reads the planes too: no fp32 dz)
+                             (dz_p2 && (t.p2_flags & MVAL_TRAIN_WGRAD_DZ_P2)) ? nullptr : gz,  // (bit 3: the weight gradient reads the planes too: no fp32 dz)
                              t.dgamma, t.dbeta, ws, sums, n_images, op.hout, op.wout, op.cout, op.relu, t.first_touch >> 1, gz_row,
                              dz_p2 ? arena + t.gz_p2_off : nullptr, dz_p2 ? reinterpret_cast<uint32_t*>(arena + t.gz_p2_rows_off) : nullptr,
                              dz_p2 ? arena + t.gz_p2_rows_off + (int64_t)n_images * P2_ROW : nullptr,
@@ -557,16 +557,16 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
     const uint32_t* x_row = (gz_row && op.in_amax_off > 0) ? reinterpret_cast<const uint32_t*>(arena + op.in_amax_off) : nullptr;
     {
     TtScope tt(TT_WGRAD, s);
-    if (dz_p2 && (t.p2_flags & 8))
+    if (dz_p2 && (t.p2_flags & MVAL_TRAIN_WGRAD_DZ_P2))
       mval_conv_wgrad_set_p2_dz(arena + t.gz_p2_off, reinterpret_cast<const unsigned*>(arena + t.gz_p2_rows_off));
     const float* xw = x;
     if (t.zin_rel) {  // (round 6) x = relu(BatchNorm(z)) of the producer, applied by the weight gradient's staging
       const mval_train_op& pr = (&t)[t.zin_rel];
-      MVAL_REQUIRE(dz_p2 && (t.p2_flags & 8), "mval_train_backward: op %d: zin_rel needs the weight gradient that reads dz from planes", i);
+      MVAL_REQUIRE(dz_p2 && (t.p2_flags & MVAL_TRAIN_WGRAD_DZ_P2), "mval_train_backward: op %d: zin_rel needs the weight gradient that reads dz from planes", i);
       const double Mp = (double)n_images * pr.op.hout * pr.op.wout;
       mval_conv_wgrad_set_z_x(pr.mean, pr.invstd, pr.gamma, pr.beta, (float)sqrt(Mp > 1 ? Mp - 1.0 : 1.0));
       xw = arena + pr.z_off;
-    } else if (t.fwd_p2 && (t.p2_flags & 1))  // (wgrad_p2: this op's input exists as P2 planes and its weight gradient reads those)
+    } else if (t.fwd_p2 && (t.p2_flags & MVAL_TRAIN_WGRAD_X_P2))  // (wgrad_p2: this op's input exists as P2 planes and its weight gradient reads those)
       mval_conv_wgrad_set_p2_x(arena + t.in_p2_off, reinterpret_cast<const unsigned*>(arena + t.in_p2_rows_off));
     rc = mval_conv_wgrad_on(xw, gz, t.dweight, wsf, n_images, op.hin, op.win, op.cin, op.hout, op.wout, op.cout, op.k, op.stride, op.pad,
                             op.in_nchw, !(t.p2_flags & MVAL_TRAIN_WGRAD_FP32), (x_row && !t.zin_rel) ? x_row : nullptr,
@@ -598,7 +598,7 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
           const mval_train_op& pr = ops[i - 1];
           const bool has_res = pr.op.res1_off >= 0 || pr.op.res2_off >= 0;
           if (pr.has_bn && pr.op.relu && (!has_res || pr.mask_off > 0) && pr.op.up == 0 && pr.gout_off == t.gin_off && pr.gz_p2_rows_off > 0 &&
-              !(pr.p2_flags & 64) && (pr.p2_flags & 4) && pr.gz_p2_off > 0 && pr.gin_off >= 0 && (pr.op.cout & 3) == 0 &&
+              !(pr.p2_flags & MVAL_TRAIN_BN_BWD_PAIR) && (pr.p2_flags & MVAL_TRAIN_DGRAD_P2) && pr.gz_p2_off > 0 && pr.gin_off >= 0 && (pr.op.cout & 3) == 0 &&
               lane_of(pr, MVAL_TRAIN_LANE_BWD, n_lanes) == lane) {
             p.bs_z = arena + pr.z_off;
             p.bs_mask = has_res ? reinterpret_cast<const unsigned char*>(arena + pr.mask_off) : nullptr;

@@ -109,6 +109,51 @@ def _pack_mode(op, pack):
     return {PACK_HWIO: 1, PACK_MFMA16: 2, PACK_MFMA16_BF3: 3, PACK_MFMA16_H2: 3}[pack]
 
 
+def _geometry(g, h, w):
+    """Activation geometry of graph ``g`` on an h x w input, op by op -> (dims: activation id -> (H, W), geo: per op (hin, win, hout, wout)
+    at the conv's own resolution, before its upsample)."""
+    dims = {g.input: (h, w)}
+    geo = []
+    for op in g.ops:
+        hin, win = dims[op.src]
+        if op.kind == "deconv":
+            hout, wout = (hin - 1) * op.stride - 2 * op.pad + op.k, (win - 1) * op.stride - 2 * op.pad + op.k
+        else:
+            hout, wout = (hin + 2 * op.pad - op.k) // op.stride + 1, (win + 2 * op.pad - op.k) // op.stride + 1
+        full = (hout << op.up, wout << op.up)
+        for r in (op.res1, op.res2):
+            if r is not None and dims[r] != full:
+                raise ValueError(f"input {h}x{w}: branch resolutions do not line up at {op.conv}")
+        dims[op.dst] = full
+        geo.append((hin, win, hout, wout))
+    return dims, geo
+
+
+def _fill_op(m, g, op, geo_i, offset):
+    """What graph op ``op`` IS, into the MvalOp ``m`` of a plan: kind, geometry, epilogue, layouts, phase / lane and the arena offsets of its
+    tensors (``offset``: activation id -> float offset; network input / output: -1).  No algorithm, no parameters (w / scale / shift: -1)."""
+    m.kind = _KIND[op.kind]
+    m.k, m.stride, m.pad, m.cin, m.cout = op.k, op.stride, op.pad, op.cin, op.cout
+    m.hin, m.win, m.hout, m.wout = geo_i
+    m.up, m.relu = op.up, int(op.relu)
+    m.in_nchw, m.out_nchw = int(g.acts[op.src].layout == "nchw"), int(g.acts[op.dst].layout == "nchw")
+    m.phase, m.lane = op.phase, op.lane
+    m.in_off, m.out_off = -1 if op.src == g.input else offset[op.src], -1 if op.dst == g.output else offset[op.dst]
+    m.res1_off, m.res2_off = (-1 if r is None else offset[r] for r in (op.res1, op.res2))
+    m.w_off = m.scale_off = m.shift_off = -1
+
+
+def _query_op(kind, k, stride, pad, cin, cout, hin, win, hout, wout, **fields):
+    """A scratch MvalOp for a support query (mval_op_algo_supported): the conv's geometry plus the ``fields`` the caller names; every other
+    field stays zero -- the predicates read more fields than any one query sets, so a caller passes exactly what its question depends on."""
+    m = MvalOp()
+    m.kind, m.k, m.stride, m.pad, m.cin, m.cout = kind, k, stride, pad, cin, cout
+    m.hin, m.win, m.hout, m.wout = hin, win, hout, wout
+    for name, v in fields.items():
+        setattr(m, name, v)
+    return m
+
+
 class InferencePlan:
     def __init__(self, model, n, h, w, device, sw=None):
         """sw: the switches the plan is built under (_switches(); default: as the environment sets them now)."""
@@ -117,21 +162,7 @@ class InferencePlan:
         direct = sw["MVAL_FORCE_DIRECT"] == "1"  # the all-direct (VALU) plan: the on-device cross-check of the MFMA kernels
         g = model._graph
         self.graph = g
-        # ---- activation geometry, op by op ------------------------------------------------
-        dims = {g.input: (h, w)}
-        geo = []
-        for op in g.ops:
-            hin, win = dims[op.src]
-            if op.kind == "deconv":
-                hout, wout = (hin - 1) * op.stride - 2 * op.pad + op.k, (win - 1) * op.stride - 2 * op.pad + op.k
-            else:
-                hout, wout = (hin + 2 * op.pad - op.k) // op.stride + 1, (win + 2 * op.pad - op.k) // op.stride + 1
-            full = (hout << op.up, wout << op.up)
-            for r in (op.res1, op.res2):
-                if r is not None and dims[r] != full:
-                    raise ValueError(f"input {h}x{w}: branch resolutions do not line up at {op.conv}")
-            dims[op.dst] = full
-            geo.append((hin, win, hout, wout))
+        dims, geo = _geometry(g, h, w)
         self.out_hw = dims[g.output]
         self.out_channels = g.acts[g.output].channels
         # ---- arena: liveness-based slot reuse --------------------------------------------------
@@ -195,16 +226,10 @@ class InferencePlan:
                     row_of[a.id] = self._amax_top
                     self._amax_top += n * P2_ROW
         for i, op in enumerate(g.ops):
-            hin, win, hout, wout = geo[i]
-            in_nchw = g.acts[op.src].layout == "nchw"
-            out_nchw = g.acts[op.dst].layout == "nchw"
             m = self.ops[i]
-            m.kind = _KIND[op.kind]
-            m.k, m.stride, m.pad, m.cin, m.cout = op.k, op.stride, op.pad, op.cin, op.cout
-            m.hin, m.win, m.hout, m.wout = hin, win, hout, wout
-            m.up, m.relu, m.in_nchw, m.out_nchw = op.up, int(op.relu), int(in_nchw), int(out_nchw)
+            _fill_op(m, g, op, geo[i], offset)
             m.algo, m.no_stem = ALGO_DIRECT, int(direct)
-            if not direct and _mfma_ok(op, in_nchw) and lib.mval_op_mfma_supported(C.byref(m), C.c_int(n)):
+            if not direct and _mfma_ok(op, m.in_nchw) and lib.mval_op_mfma_supported(C.byref(m), C.c_int(n)):
                 m.algo = ALGO_MFMA
                 # fp32-accurate 16-bit splits on the matrix cores (fp16x2: 5.3x, bf16x3: 2.67x the fp32-MFMA rate)
                 # (the fp16 split wants one image per tile; maps under 8 rows fall back to bf16x3)
@@ -215,12 +240,6 @@ class InferencePlan:
                             break
             if self.p2 and op.src != g.input and op.kind != "maxpool":
                 m.algo = ALGO_MFMA_P2
-            m.in_off = -1 if op.src == g.input else offset[op.src]
-            m.out_off = -1 if op.dst == g.output else offset[op.dst]
-            m.res1_off = -1 if op.res1 is None else offset[op.res1]
-            m.res2_off = -1 if op.res2 is None else offset[op.res2]
-            m.w_off = m.scale_off = m.shift_off = -1
-            m.phase, m.lane = op.phase, op.lane
             if m.algo == ALGO_MFMA_H2:
                 if op.src not in amax_slot:
                     amax_slot[op.src] = self._amax_top
@@ -297,13 +316,9 @@ class InferencePlan:
             # 48- / 96-channel fused up-paths it is ahead (21.8 vs 22.1 ms).  MVAL_P2_W48=0 keeps such plans on h2.
             if op.cin % 32 and sw["MVAL_P2_W48"] == "0" and sw["MVAL_P2"] != "force":
                 return False
-            m = MvalOp()
-            m.kind, m.algo = _KIND[op.kind], ALGO_MFMA_P2
-            m.res1_off = -1 if op.res1 is None else 0
-            m.res2_off = -1 if op.res2 is None else 0
-            m.k, m.stride, m.pad, m.cin, m.cout = op.k, op.stride, op.pad, op.cin, op.cout
-            m.hin, m.win, m.hout, m.wout = hin, win, hout, wout
-            m.up, m.relu, m.out_nchw = op.up, int(op.relu), int(g.acts[op.dst].layout == "nchw")
+            m = _query_op(_KIND[op.kind], op.k, op.stride, op.pad, op.cin, op.cout, hin, win, hout, wout, algo=ALGO_MFMA_P2,
+                          res1_off=-1 if op.res1 is None else 0, res2_off=-1 if op.res2 is None else 0,
+                          up=op.up, relu=int(op.relu), out_nchw=int(g.acts[op.dst].layout == "nchw"))
             if not lib.mval_op_algo_supported(C.byref(m), C.c_int(n), C.c_int(ALGO_MFMA_P2)):
                 return False
         return stems == 1

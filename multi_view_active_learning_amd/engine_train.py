@@ -24,14 +24,13 @@ import weakref
 import torch
 
 from . import _lib
-from .engine import (ALGO_DIRECT, ALGO_MFMA, ALGO_MFMA_BF3, ALGO_MFMA_H2, PACK_HWIO, PACK_MFMA16, PACK_MFMA16_BF3,
-                     PACK_MFMA16_H2, _KIND, _PACK_OF, MvalOp, _align, _mfma_ok, _switches)
+from .engine import (ALGO_DIRECT, ALGO_MFMA, ALGO_MFMA_BF3, ALGO_MFMA_H2, ALGO_MFMA_P2, P2_ROW, PACK_MFMA16_BF3, PACK_MFMA16_H2, _PACK_OF,
+                     MvalOp, _align, _fill_op, _geometry, _mfma_ok, _query_op, _switches)
 
 TRAIN_AMAX_ROW = 576  # dwords per magnitude row in training: [count, <= 512 partial maxima], one row per tensor
 
 BN_MOMENTUM = 0.1
 BN_EPS = 1e-5
-_F = C.POINTER(C.c_float)
 
 
 class MvalTrainOp(C.Structure):
@@ -75,6 +74,9 @@ _SWITCHES = {"MVAL_CONV": "p2", "MVAL_FORCE_DIRECT": "0", "MVAL_TRAIN_P2": "1", 
              "MVAL_TRAIN_P2_RES": "1", "MVAL_TRAIN_EPI_STATS": "1", "MVAL_TRAIN_BWD_FUSED": "1", "MVAL_TRAIN_RELU_MASK": "1",
              "MVAL_TRAIN_DGRAD_PARITY": "1", "MVAL_TRAIN_LANES": "3", "MVAL_TRAIN_BN_IN_CONV": "1", "MVAL_TRAIN_BN_BWD_IN_DGRAD": "1"}
 MAX_LANES = 4            # (csrc/conv_common.h MVAL_MAX_LANES)
+# mval_train_op.p2_flags (include/mval_hip.h MVAL_TRAIN_*, same names)
+TRAIN_WGRAD_X_P2, TRAIN_OUT_P2_ONLY, TRAIN_DGRAD_P2, TRAIN_WGRAD_DZ_P2, TRAIN_RES1_P2, TRAIN_RES2_P2 = 1, 2, 4, 8, 16, 32
+TRAIN_BN_BWD_PAIR, TRAIN_STATS_PASS = 64, 128
 TRAIN_LANE_FWD, TRAIN_LANE_BWD, TRAIN_LANE_ORD, TRAIN_LANE_FREE = 256, 512, 1024, 2048  # (include/mval_hip.h MVAL_TRAIN_LANE_*)
 TRAIN_BSUM = 4096  # (MVAL_TRAIN_BSUM)
 TRAIN_WGRAD_FP32 = 8192  # (MVAL_TRAIN_WGRAD_FP32)
@@ -111,79 +113,92 @@ def lane_flags(g, nl, mode):
 
 class TrainPlan:
     def __init__(self, model, n, h, w, device, p2=True, sw=None):
-        """sw: the switches the plan is built under (_switches(_SWITCHES); default: as the environment sets them now)."""
+        """sw: the switches the plan is built under (_switches(_SWITCHES); default: as the environment sets them now).
+
+        The plan is decided by the passes below, one decision each.  THEIR ORDER IS PART OF THE PLAN: arena rows, parameter floats and
+        statistics slots are handed out from running counters (self._row_top, self._ptop, self._stat_top), so moving a pass, or the order in
+        which one pass hands out rows, moves every later offset.  The passes talk through the ops' fields and these plan attributes:
+        dims / geo (_geometry), _act_off, _amax_row (activation -> magnitude row), _producer / _consumers / _res_users (graph lookups),
+        _p2_act (activation -> (planes, rows))."""
         sw = self.sw = sw or _switches(_SWITCHES)
-        direct = sw["MVAL_FORCE_DIRECT"] == "1"
-        bf3 = sw["MVAL_CONV"] in ("bf3", "h2", "p2")  # (p2 is an inference activation format: training runs its h2 arithmetic)
-        h2 = sw["MVAL_CONV"] in ("h2", "p2")  # fp16x2 split (3 products) where it applies, else bf16x3 (6)
+        self._bf3 = sw["MVAL_CONV"] in ("bf3", "h2", "p2")  # (p2 is an inference activation format: training runs its h2 arithmetic)
+        self._h2 = sw["MVAL_CONV"] in ("h2", "p2")  # fp16x2 split (3 products) where it applies, else bf16x3 (6)
         g = model._graph
         self.model, self.graph, self.n, self.device = model, g, n, device
         self.steps, self.forwards, self.p2_slack, self._probe = 0, 0, None, None
-        lib = _lib.lib()
-        dims = {g.input: (h, w)}
-        geo = []
-        for op in g.ops:
-            hin, win = dims[op.src]
-            if op.kind == "deconv":
-                hout, wout = (hin - 1) * op.stride - 2 * op.pad + op.k, (win - 1) * op.stride - 2 * op.pad + op.k
-            else:
-                hout, wout = (hin + 2 * op.pad - op.k) // op.stride + 1, (win + 2 * op.pad - op.k) // op.stride + 1
-            full = (hout << op.up, wout << op.up)
-            for r in (op.res1, op.res2):
-                if r is not None and dims[r] != full:
-                    raise ValueError(f"input {h}x{w}: branch resolutions do not line up at {op.conv}")
-            dims[op.dst] = full
-            geo.append((hin, win, hout, wout))
-        self.out_hw = dims[g.output]
-        self.out_channels = g.acts[g.output].channels
-        # ---- arenas: every activation and every raw conv output is kept --------------------------
+        self.dims, self.geo = _geometry(g, h, w)
+        self.out_hw, self.out_channels = self.dims[g.output], g.acts[g.output].channels
+        self.maxc = max(op.cout for op in g.ops)
+        self._producer = {op.dst: k for k, op in enumerate(g.ops)}
+        self._consumers, self._res_users = {}, {}  # activation -> ops that read it as input / [(op, its TRAIN_RES*_P2 bit)] that add it
+        for i, op in enumerate(g.ops):
+            self._consumers.setdefault(op.src, []).append(i)
+            for r_, bit in ((op.res1, TRAIN_RES1_P2), (op.res2, TRAIN_RES2_P2)):
+                if r_ is not None:
+                    self._res_users.setdefault(r_, []).append((i, bit))
+        self._p2_act, self.p2_rows = {}, []
+        self.n_bn_in_conv = self.n_bn_bwd_in_dgrad = 0  # (round 6: BatchNorm applies / backward sums that run inside the reader; P2 plans only)
+        self._layout_arena()
+        self._choose_algorithms()
+        if self._h2 and p2 and sw["MVAL_TRAIN_P2"] != "0":
+            self._p2_forward_convs()
+            self._p2_wgrads_and_planes_only()
+            self._p2_dgrads()
+            self._bn_apply_in_reader()
+        self._plan_wide_flags()
+        self._relu_masks()
+        self._bn_backward_sums_in_reader()
+        if g.input in self._amax_row:
+            raise _lib.MvalError("the network input cannot feed an fp16-split conv")
+        self._assign_lanes()
+        self.arena_floats = _align(self._row_top)
+        self._first_touch()
+        self._allocate()
+        self._autograd_order()
+
+    def _layout_arena(self):
+        """Arena layout: every activation and every raw conv output is kept.  Reads dims / geo; sets _act_off, _act_top, the ops' z_off,
+        gz_amax_off (the dz magnitude row) and starts _row_top behind it."""
+        g, n = self.graph, self.n
         top = 0
-        act_off = {}
+        act_off = self._act_off = {}
         for a in g.acts:
-            if a.id in (g.input,) or a.id not in dims:
+            if a.id in (g.input,) or a.id not in self.dims:
                 continue
             # the graph output also gets a slot: its NHWC gradient lives at the same offset of garena
             act_off[a.id] = top
-            top += _align(n * dims[a.id][0] * dims[a.id][1] * a.channels)
+            top += _align(n * self.dims[a.id][0] * self.dims[a.id][1] * a.channels)
         self._act_top = top  # (the gradient arena mirrors the activation slots only)
-        z_off = []
+        self.ops = (MvalTrainOp * len(g.ops))()
         for i, op in enumerate(g.ops):
+            self.ops[i].z_off = -1
             if op.bn:
-                z_off.append(top)
-                top += _align(n * geo[i][2] * geo[i][3] * op.cout)
-            else:
-                z_off.append(-1)
+                self.ops[i].z_off = top
+                top += _align(n * self.geo[i][2] * self.geo[i][3] * op.cout)
         # magnitude rows of the fp16-split convs (MVAL_CONV=h2, the default): one per activation a split conv reads,
         # one for the dz scratch
-        amax_row = {}
+        self._amax_row = {}
         self.gz_amax_off = top
         top += TRAIN_AMAX_ROW
-        self._row_top = top  # rows are handed out below, the arena is sized after the op loop
-        # ---- parameters: forward packing, dgrad packing, ones / zeros ---------------------------
-        maxc = max(op.cout for op in g.ops)
-        self.maxc = maxc
-        ptop = 0
-        self.ops = (MvalTrainOp * len(g.ops))()
-        self.jobs = []
-        stat_top = 0
-        self.stat_off = []
-        gz_max, wsf_max = 0, 0
+        self._row_top = top  # rows are handed out by the later passes, the arena is sized after the last of them
+
+    def _choose_algorithms(self):
+        """Per op: forward algo, data-gradient algo and form, and the parameter layout (forward packing, dgrad packing).  Reads geo, _act_off,
+        the switches; sets the ops' descriptive fields, algo / dgrad_algo / dgrad_form, in_amax_off (rows from _row_top), w_off / shift_off /
+        wd_off (from _ptop), jobs, stat_off (from _stat_top), _gz_max / _wsf_max."""
+        g, n, sw, lib, act_off, amax_row = self.graph, self.n, self.sw, _lib.lib(), self._act_off, self._amax_row
+        direct, bf3, h2 = sw["MVAL_FORCE_DIRECT"] == "1", self._bf3, self._h2
+        ptop = stat_top = gz_max = wsf_max = 0
+        self.jobs, self.stat_off = [], []
         # a tensor's magnitude row is written by its producer's BatchNorm apply (or max-pool) only: a conv WITHOUT BatchNorm
         # leaves none, so its consumers may not use the fp16 split (ADVICE round 2: latent today, only final_layer lacks BN)
         keeps_row = {op.dst for op in g.ops if op.bn or op.kind == "maxpool"}
         for i, op in enumerate(g.ops):
-            hin, win, hout, wout = geo[i]
-            in_nchw = g.acts[op.src].layout == "nchw"
-            out_nchw = g.acts[op.dst].layout == "nchw"
-            t = self.ops[i]
-            m = t.op
-            m.kind = _KIND[op.kind]
-            m.k, m.stride, m.pad, m.cin, m.cout = op.k, op.stride, op.pad, op.cin, op.cout
-            m.hin, m.win, m.hout, m.wout = hin, win, hout, wout
-            m.up, m.relu, m.in_nchw, m.out_nchw = op.up, int(op.relu), int(in_nchw), int(out_nchw)
-            m.phase, m.lane = op.phase, op.lane
+            hin, win, hout, wout = self.geo[i]
+            t, m = self.ops[i], self.ops[i].op
+            _fill_op(m, g, op, self.geo[i], act_off)
             m.algo = ALGO_DIRECT
-            if not direct and _mfma_ok(op, in_nchw) and lib.mval_op_mfma_supported(C.byref(m), C.c_int(n)):
+            if not direct and _mfma_ok(op, m.in_nchw) and lib.mval_op_mfma_supported(C.byref(m), C.c_int(n)):
                 m.algo = ALGO_MFMA
                 if bf3 and op.kind == "conv" and op.k in (1, 3) and (op.cin % 32 == 0 or op.cin == 48):
                     for cand in ((ALGO_MFMA_H2, ALGO_MFMA_BF3) if (h2 and op.src != g.input and op.src in keeps_row) else (ALGO_MFMA_BF3,)):
@@ -195,24 +210,15 @@ class TrainPlan:
                     amax_row[op.src] = self._row_top
                     self._row_top += TRAIN_AMAX_ROW
                 m.in_amax_off = amax_row[op.src]
-            m.in_off = -1 if op.src == g.input else act_off[op.src]
-            m.out_off = -1 if op.dst == g.output else act_off[op.dst]
-            m.res1_off = -1 if op.res1 is None else act_off[op.res1]
-            m.res2_off = -1 if op.res2 is None else act_off[op.res2]
-            m.w_off = m.scale_off = m.shift_off = -1
-            t.z_off = z_off[i]
             t.has_bn = int(bool(op.bn))
             t.gout_off = act_off[op.dst]
-            t.gin_off = -1 if op.src == g.input else act_off[op.src]
-            t.gres1_off = -1 if op.res1 is None else act_off[op.res1]
-            t.gres2_off = -1 if op.res2 is None else act_off[op.res2]
-            t.wd_off = -1
-            t.dgrad_algo = ALGO_DIRECT
-            if h2 and op.bn:  # dz's magnitude row: the fp16-split data / weight gradients read it
+            t.gin_off, t.gres1_off, t.gres2_off = m.in_off, m.res1_off, m.res2_off  # (the gradient arena mirrors the activation slots)
+            t.wd_off, t.dgrad_algo = -1, ALGO_DIRECT
+            if h2 and op.bn:  # dz's magnitude row: the fp16-split data / weight gradients (only BatchNorm'd ops get them) read it
                 t.gz_amax_off = self.gz_amax_off
+            self.stat_off.append(stat_top)
             if op.kind == "maxpool":  # no parameters; backward routes the gradient to the window arg-max
                 self.jobs.append((i, None, None))
-                self.stat_off.append(stat_top)
                 continue
             if op.kind == "deconv" and (m.algo != ALGO_MFMA or not op.bn):
                 raise NotImplementedError(f"training a transposed conv needs the MFMA form (k4 s2 p1, cin % 16 == 0) + BN: {op.conv}")
@@ -229,17 +235,7 @@ class TrainPlan:
                 # (cin, cout, k, k) weights read as Conv2d weights (cout' = cin, cin' = cout)
                 if t.gin_off >= 0:
                     t.dgrad_algo = ALGO_MFMA
-                    dpack = _PACK_OF[ALGO_MFMA]
-                    nd = int(lib.mval_packed_weight_floats(C.c_int(dpack), C.c_int(op.cin), C.c_int(op.cout), C.c_int(op.k)))
-                    t.wd_off = ptop
-                    ptop += _align(nd)
-                self.jobs.append((i, fpack, dpack))
-                self.stat_off.append(stat_top)
-                stat_top += 2 * _align(op.cout)
-                gz_max = max(gz_max, n * hout * wout * op.cout)
-                wsf_max = max(wsf_max, int(lib.mval_conv_wgrad_workspace_floats(C.c_int(op.cout), C.c_int(op.cin), C.c_int(op.k))))
-                continue
-            if t.gin_off >= 0:
+            elif t.gin_off >= 0:
                 ok = op.cout % 16 == 0 and op.k in (1, 3) and op.stride in (1, 2) and op.pad == op.k // 2
                 t.dgrad_algo = ALGO_MFMA if ok else ALGO_DIRECT
                 # stride-1 data gradients are plain convs with cin' = cout: bf16x3-split kernel
@@ -247,12 +243,9 @@ class TrainPlan:
                     t.dgrad_algo = ALGO_MFMA_BF3
                     # stride-1 data gradients of BatchNorm'd convs: fp16x2 (dz's magnitude comes from the BN backward)
                     if h2 and op.bn and op.stride == 1 and op.cin % 16 == 0:
-                        d = MvalOp()
-                        d.kind, d.k, d.stride, d.pad, d.cin, d.cout = 0, op.k, 1, op.k - 1 - op.pad, op.cout, op.cin
-                        d.hin, d.win, d.hout, d.wout = hout, wout, hin, win
+                        d = _query_op(0, op.k, 1, op.k - 1 - op.pad, op.cout, op.cin, hout, wout, hin, win)
                         if lib.mval_op_algo_supported(C.byref(d), C.c_int(n), C.c_int(ALGO_MFMA_H2)):
                             t.dgrad_algo = ALGO_MFMA_H2
-                            t.gz_amax_off = self.gz_amax_off
                 # stride-2 3x3 on even sizes: four 2x2 parity convs over dz instead of a 3x3 conv over the zero-dilated dz
                 # (2.25x fewer tap-pixels, and the fp16 split applies); weights packed with mode 4 as k = 4
                 if bf3 and op.k == 3 and op.stride == 2 and op.pad == 1 and sw["MVAL_TRAIN_DGRAD_PARITY"] != "0":
@@ -260,298 +253,216 @@ class TrainPlan:
                         if lib.mval_conv_dgrad_parity_supported(C.c_int(n), C.c_int(hin), C.c_int(win), C.c_int(op.cin), C.c_int(hout),
                                                                 C.c_int(wout), C.c_int(op.cout), C.c_int(cand)):
                             t.dgrad_algo, t.dgrad_form = cand, 1
-                            if cand == ALGO_MFMA_H2:
-                                t.gz_amax_off = self.gz_amax_off
                             break
+            if t.gin_off >= 0:
                 dpack = _PACK_OF[t.dgrad_algo]
                 # the data-gradient conv has cin' = cout, cout' = cin
                 nd = int(lib.mval_packed_weight_floats(C.c_int(dpack), C.c_int(op.cin), C.c_int(op.cout), C.c_int(4 if t.dgrad_form == 1 else op.k)))
                 t.wd_off = ptop
                 ptop += _align(nd)
             self.jobs.append((i, fpack, dpack))
-            self.stat_off.append(stat_top)
             stat_top += 2 * _align(op.cout)
             gz_max = max(gz_max, n * hout * wout * op.cout)
-            wsf_max = max(wsf_max, int(lib.mval_conv_wgrad_workspace_floats(C.c_int(op.cin), C.c_int(op.cout), C.c_int(op.k))))
-        # Round 4: forward convs on the P2 kernels (conv_p2.hip EPI 3) where the op's fp16-split conv qualifies: the producer's
-        # BatchNorm apply also writes the activation as P2 planes (mval_bn_apply_fwd_p2); the residuals of such producers need
-        # magnitude rows (the P2 scale is an a-priori bound + the residuals' exact maxima).  MVAL_TRAIN_P2=0: round 3's h2 forward.
-        P2_ROW = 512
-        producer = {op.dst: k for k, op in enumerate(g.ops)}
-        p2_act = {}
-        self.n_bn_in_conv = 0  # (round 6: ops whose BatchNorm apply runs inside their reader's staging; set below for P2 plans)
-        self.p2_rows = []
-        if h2 and p2 and sw["MVAL_TRAIN_P2"] != "0":
-            for i, op in enumerate(g.ops):
-                t = self.ops[i]
-                k = producer.get(op.src)
-                if not (op.kind == "conv" and op.bn and t.op.algo == ALGO_MFMA_H2 and k is not None and g.ops[k].bn and g.ops[k].cout % 8 == 0
-                        and op.cout % 4 == 0):
-                    continue
-                hin, win, hout, wout = geo[i]
-                d = MvalOp()
-                d.kind, d.k, d.stride, d.pad, d.cin, d.cout = 0, op.k, op.stride, op.pad, op.cin, op.cout
-                d.hin, d.win, d.hout, d.wout = hin, win, hout, wout
-                if not lib.mval_op_algo_supported(C.byref(d), C.c_int(n), C.c_int(4)):  # (MVAL_ALGO_MFMA_P2)
-                    continue
-                if op.src not in p2_act:
-                    planes = self._row_top
-                    self._row_top += _align(n * hin * win * op.cin)
-                    rows = self._row_top
-                    self._row_top += _align(n * P2_ROW)
-                    p2_act[op.src] = (planes, rows)
-                    self.p2_rows.append((rows, n * P2_ROW))
-                t.fwd_p2 = 1
-                t.in_p2_off, t.in_p2_rows_off = p2_act[op.src]
-            for a_, (planes, rows) in p2_act.items():
-                k = producer[a_]
-                pt, po = self.ops[k], g.ops[k]
-                pt.out_p2_off, pt.out_p2_rows_off = planes, rows
-                for r_, name in ((po.res1, "res1_amax_off"), (po.res2, "res2_amax_off")):
-                    if r_ is not None:
-                        if r_ not in amax_row:
-                            amax_row[r_] = self._row_top
-                            self._row_top += TRAIN_AMAX_ROW
-                        setattr(pt, name, amax_row[r_])
-            # weight gradients read x from the planes where the split kernel covers the conv; an activation whose EVERY consumer reads the
-            # planes (P2 forward conv + P2 weight gradient, no residual use, not the network output) is not written as fp32 at all
-            p2w = sw["MVAL_TRAIN_P2_WGRAD"] != "0"
-            fused_bwd = sw["MVAL_TRAIN_BWD_FUSED"] != "0"  # (round 3's BatchNorm backward reads `out` and writes fp32 dz only)
-            consumers = {}
-            for i, op in enumerate(g.ops):
-                consumers.setdefault(op.src, []).append(i)
-                t = self.ops[i]
-                if p2w and t.fwd_p2 and t.gz_amax_off > 0 and lib.mval_conv_wgrad_p2_covers(C.c_int(op.cin), C.c_int(op.cout), C.c_int(op.k), C.c_int(op.stride)):
-                    t.p2_flags |= 1
-            # a residual can be read from the planes as well (mval_bn_apply_fwd_p2_res) when the op that adds it runs the P2 apply: then
-            # a block output whose every reader takes the planes -- the next block's first conv, its weight gradient, the residual add at
-            # that block's end -- is P2-only too (MVAL_TRAIN_P2_RES=0: residuals stay fp32 NHWC)
-            p2res = sw["MVAL_TRAIN_P2_RES"] != "0"
-            res_users = {}
-            for i, op in enumerate(g.ops):
-                for r_, bit in ((op.res1, 16), (op.res2, 32)):
-                    if r_ is not None:
-                        res_users.setdefault(r_, []).append((i, bit))
-            for a_ in p2_act:
-                cons = consumers.get(a_, [])
-                po = g.ops[producer[a_]]
-                # (its own backward must not need `out` either: a ReLU behind residual adds takes its mask from the mask bytes)
-                own_ok = not (po.relu and (po.res1 is not None or po.res2 is not None)) or (sw["MVAL_TRAIN_RELU_MASK"] != "0" and po.up == 0)
-                users = res_users.get(a_, [])
-                users_ok = all(self.ops[i].out_p2_off > 0 and g.ops[i].bn for i, _ in users) and (p2res or not users)
-                if p2w and fused_bwd and own_ok and users_ok and a_ != g.output and cons and all(self.ops[i].fwd_p2 and (self.ops[i].p2_flags & 1) for i in cons):
-                    self.ops[producer[a_]].p2_flags |= 2
-                    for i, bit in users:
-                        t = self.ops[i]
-                        t.p2_flags |= bit
-                        if bit == 16:
-                            t.res1_p2_off, t.res1_p2_rows_off = p2_act[a_]
-                        else:
-                            t.res2_p2_off, t.res2_p2_rows_off = p2_act[a_]
-            # data gradients of stride-1 convs on the P2 kernels: the BatchNorm backward also writes dz as P2 planes into ONE scratch
-            # (planes of the largest dz, rows, reduction scratch); MVAL_TRAIN_P2_DGRAD=0: the h2 data gradients.  (Round 5 also ran the
-            # four parity convs of the stride-2 data gradients on conv_p2_kernel<2, ...> from the dz planes: 65.47 vs 65.2 ms per C3 step --
-            # four persistent launches against the h2 kernel's one: not kept.)
-            if sw["MVAL_TRAIN_P2_DGRAD"] != "0" and fused_bwd:
-                want = []
-                for i, op in enumerate(g.ops):
-                    t = self.ops[i]
-                    hin, win, hout, wout = geo[i]
-                    if not (t.dgrad_algo == ALGO_MFMA_H2 and t.dgrad_form == 0 and op.bn and op.up == 0 and op.stride == 1 and op.cout % 8 == 0 and op.cin % 4 == 0
-                            and t.gin_off >= 0):
-                        continue
-                    d = MvalOp()
-                    d.kind, d.k, d.stride, d.pad, d.cin, d.cout = 0, op.k, 1, op.k // 2, op.cout, op.cin
-                    d.hin, d.win, d.hout, d.wout = hout, wout, hin, win
-                    if op.pad == op.k // 2 and lib.mval_op_algo_supported(C.byref(d), C.c_int(n), C.c_int(4)):
-                        want.append(i)
-                if want:
-                    planes = self._row_top
-                    self._row_top += _align(max(n * geo[i][2] * geo[i][3] * g.ops[i].cout for i in want))
-                    rows = self._row_top
-                    self._row_top += _align(n * P2_ROW + 512 + 64)
-                    self.p2_rows.append((rows, n * P2_ROW + 512 + 64))
-                    for i in want:
-                        self.ops[i].p2_flags |= 4
-                        self.ops[i].gz_p2_off, self.ops[i].gz_p2_rows_off = planes, rows
-                        op = g.ops[i]
-                        # the weight gradient reads dz from the planes too where the split kernel covers the conv: no fp32 copy of dz
-                        if (p2w and op.cout % 8 == 0
-                                and lib.mval_conv_wgrad_split_covers(C.c_int(op.cin), C.c_int(op.cout), C.c_int(op.k), C.c_int(op.stride))
-                                and ((self.ops[i].p2_flags & 1) or self.ops[i].op.in_amax_off > 0)):
-                            self.ops[i].p2_flags |= 8
-            # Round 6: BatchNorm apply inside the consumer (include/mval_hip.h mval_train_op.z_out / zin_rel; hrnet.py:36-52: conv1 -> bn1 -> relu ->
-            # conv2 of every BasicBlock, the 3x3 of a Bottleneck).  A planes-only ReLU output without residual or upsample whose ONE reader is a
-            # 3x3 stride-1 P2 conv on the same lane, with the P2 weight gradient reading dz from planes, is never written: that conv's staging
-            # and its weight gradient's staging apply the BatchNorm from the producer's raw z.  MVAL_TRAIN_BN_IN_CONV=0: the separate apply pass.
-            self.n_bn_in_conv = 0
-            if sw["MVAL_TRAIN_BN_IN_CONV"] != "0":
-                lib.mval_conv_p2_inz_supported.restype = C.c_int
-                for a_ in p2_act:
-                    k = producer[a_]
-                    po, pt = g.ops[k], self.ops[k]
-                    cons = consumers.get(a_, [])
-                    if not ((pt.p2_flags & 2) and po.kind == "conv" and po.bn and po.relu and po.res1 is None and po.res2 is None and po.up == 0
-                            and len(cons) == 1 and not res_users.get(a_) and a_ != g.output):
-                        continue
-                    j = cons[0]
-                    co, ct = g.ops[j], self.ops[j]
-                    if not (co.kind == "conv" and co.k == 3 and co.stride == 1 and co.pad == 1 and ct.fwd_p2 and (ct.p2_flags & 1) and (ct.p2_flags & 8)
-                            and (co.phase, co.lane) == (po.phase, po.lane) and j > k):
-                        continue
-                    hin, win, _, _ = geo[j]
-                    if not lib.mval_conv_p2_inz_supported(C.c_int(co.cin), C.c_int(co.cout), C.c_int(hin), C.c_int(win), C.c_int(n)):
-                        continue
-                    pt.z_out = 1
-                    ct.zin_rel = k - j
-                    self.n_bn_in_conv += 1
+            # (the weight gradient of a transposed conv swaps the activations' roles)
+            ci, co = (op.cout, op.cin) if op.kind == "deconv" else (op.cin, op.cout)
+            wsf_max = max(wsf_max, int(lib.mval_conv_wgrad_workspace_floats(C.c_int(ci), C.c_int(co), C.c_int(op.k))))
+        self._ptop, self._stat_top, self._gz_max, self._wsf_max = ptop, stat_top, gz_max, wsf_max
 
-        # the two BatchNorm A/B switches and the exact-fp32 weight gradients of MVAL_CONV=fp32 are the PLAN's decision and travel in p2_flags
-        # (bit 6: round 3's backward pair, bit 7: statistics by the separate pass, bit 13): net_train.hip does not read the environment
-        bits = ((0 if sw["MVAL_TRAIN_BWD_FUSED"] != "0" else 64) | (0 if sw["MVAL_TRAIN_EPI_STATS"] != "0" else 128)
-                | (0 if bf3 else TRAIN_WGRAD_FP32))
-        for i, op in enumerate(g.ops):  # producers leave max |out| where a split conv will look for it
-            self.ops[i].out_amax_off = amax_row.get(op.dst, 0)
-            self.ops[i].p2_flags |= bits
-        self.uses_p2 = any(t.out_p2_off > 0 or (t.p2_flags & 4) for t in self.ops)
-        # ReLU behind residual adds (BasicBlock / Bottleneck outputs, fuse sums at the conv resolution): the forward apply keeps
-        # (out > 0) as one byte per float4, the backward reads that instead of `out` (a sixteenth of the bytes)
-        if sw["MVAL_TRAIN_RELU_MASK"] != "0":
-            for i, op in enumerate(g.ops):
-                if op.bn and op.relu and op.up == 0 and (op.res1 is not None or op.res2 is not None) and op.cout % 4 == 0:
-                    self.ops[i].mask_off = self._row_top
-                    self._row_top += _align((n * geo[i][2] * geo[i][3] * op.cout // 4 + 3) // 4)
-        # Round 6, the other direction (MVAL_TRAIN_BSUM; MVAL_TRAIN_BN_BWD_IN_DGRAD=0: the reduction pass): the data gradient of a 3x3 stride-1
-        # P2 conv whose input's producer is the op right in front of it in the list is the LAST writer of that producer's output gradient
-        # (every other reader sits behind it in the list and writes earlier in the backward), so its epilogue keeps the sums the producer's
-        # BatchNorm backward would take from a second read of it (P2Args::bs_z): ReLU producers without residual (mask from z: conv1 of a
-        # BasicBlock) and with residuals (mask from the kept bits: conv2 of a block followed by another block; the apply pass then also
-        # scatters the residual gradients).  The library checks the rest at launch (same lane, room for the partials).
-        self.n_bn_bwd_in_dgrad = 0
-        if self.uses_p2 and sw["MVAL_TRAIN_BN_BWD_IN_DGRAD"] != "0" and sw["MVAL_TRAIN_BWD_FUSED"] != "0":
-            lib.mval_conv_p2_bsum_supported.restype = C.c_int
-            for j in range(1, len(g.ops)):
-                co, ct, po, pt = g.ops[j], self.ops[j], g.ops[j - 1], self.ops[j - 1]
-                if not (co.kind == "conv" and co.k == 3 and co.stride == 1 and co.pad == 1 and co.src == po.dst and (ct.p2_flags & 4) and ct.gin_off >= 0
-                        and po.kind == "conv" and po.bn and po.relu and po.up == 0 and (pt.p2_flags & 4) and pt.gin_off >= 0 and pt.gz_p2_off > 0
-                        and (co.phase, co.lane) == (po.phase, po.lane)):
-                    continue
-                if (po.res1 is not None or po.res2 is not None) and not pt.mask_off > 0:
-                    continue
-                hin, win, _, _ = geo[j]
-                if lib.mval_conv_p2_bsum_supported(C.c_int(co.cout), C.c_int(co.cin), C.c_int(hin), C.c_int(win), C.c_int(n)):
-                    ct.p2_flags |= TRAIN_BSUM
-                    self.n_bn_bwd_in_dgrad += 1
-        if g.input in amax_row:
-            raise _lib.MvalError("the network input cannot feed an fp16-split conv")
-        self._assign_lanes(g, n, geo)
-        self.arena_floats = _align(self._row_top)
-        # first writer of every activation-gradient slot (backward order) stores, later ones accumulate;
-        # slots nobody writes (activations without a consumer) are the only ones zero-filled
-        touched = {g.output}
-        for i in range(len(g.ops) - 1, -1, -1):
-            op, t = g.ops[i], self.ops[i]
-            mask = 0
-            for bit, act in ((2, op.res1), (4, op.res2), (1, None if op.src == g.input else op.src)):
-                if act is not None and act not in touched:
-                    touched.add(act)
-                    mask |= bit
-            t.first_touch = mask
-        self.zero_slots = [(act_off[a], n * dims[a][0] * dims[a][1] * g.acts[a].channels)
-                           for a in act_off if a not in touched]
-        self.ones_off = ptop
-        ptop += _align(maxc)
-        self.zeros_off = ptop
-        ptop += _align(maxc)
-        for t in self.ops:
-            if not t.has_bn:
-                t.op.scale_off = self.ones_off
-        self.param_floats = ptop
-        f32 = dict(dtype=torch.float32, device=device)
-        self.arena = torch.empty(self.arena_floats, **f32)
-        for off, cnt in self.p2_rows:  # P2 rows: unused partial slots must read as zero (csrc/conv_p2.h); the scale slot is rewritten every forward
-            self.arena[off : off + cnt].zero_()
-        self.garena = torch.empty(max(self._act_top, 64), **f32)
-        self.params = torch.zeros(self.param_floats, **f32)
-        self.params[self.ones_off : self.ones_off + maxc] = 1.0
-        self.stats = torch.zeros(max(stat_top, 64), **f32)
-        # (lanes: one slice of every scratch buffer per lane, mval_train_*_lanes)
-        self.gz_lane, self.wsf_lane = _align(max(gz_max, 64)), _align(max(wsf_max, 64))
-        self.gz = torch.empty(self.gz_lane * self.n_lanes, **f32)
-        self.wsf = torch.empty(self.wsf_lane * self.n_lanes, **f32)
-        # float64 scratch of the BatchNorm reductions; sized so that the forward conv epilogues' per-workgroup statistics
-        # partials fit (cout x workgroups x 2, workgroups <= pixels / 32 for every tile the large layers use)
-        epi = max((op.cout * ((n * geo[i][2] * geo[i][3] + 31) // 32 + 64) * 2 for i, op in enumerate(g.ops) if op.bn), default=0)
-        # (round 6: ... and the data gradients' reduction partials, cout x slots x 3 with slots = persistent workgroups x pixel waves <= 2 304)
-        bsum = max((g.ops[i - 1].cout * 2304 * 3 for i, t in enumerate(self.ops) if t.p2_flags & TRAIN_BSUM), default=0)
-        self.ws_lane = _align(max(512 * maxc * 2, epi, bsum) + 64)
-        self.ws = torch.empty(self.ws_lane * self.n_lanes, dtype=torch.float64, device=device)
-        self.sums_lane = _align(2 * maxc + 64)
-        self.sums = torch.empty(self.sums_lane * self.n_lanes, **f32)
-        self.param_sig = None
-        self._pack_ptrs, self._pack_jobs = None, None
-        # parameter order of the autograd node: conv.weight [, conv.bias] [, bn.weight, bn.bias] per op
-        holders = model._holders
-        self.param_list, self.grad_slots = [], []
-        gtop = 0
-        cum = []  # gradient floats up to and including op i
-        for op in g.ops:
-            cum.append(gtop)
-            if op.kind == "maxpool":
-                self.grad_slots.append({})
+    def _p2_forward_convs(self):
+        """Round 4: forward convs on the P2 kernels (conv_p2.hip EPI 3) where the op's fp16-split conv qualifies: the producer's
+        BatchNorm apply also writes the activation as P2 planes (mval_bn_apply_fwd_p2); the residuals of such producers need
+        magnitude rows (the P2 scale is an a-priori bound + the residuals' exact maxima).  MVAL_TRAIN_P2=0: round 3's h2 forward.
+        Reads algo; sets fwd_p2 / in_p2_*, the producers' out_p2_* / res*_amax_off, _p2_act, p2_rows (_row_top: planes + rows, then residual rows)."""
+        g, n, lib, p2_act, amax_row = self.graph, self.n, _lib.lib(), self._p2_act, self._amax_row
+        for i, op in enumerate(g.ops):
+            t = self.ops[i]
+            k = self._producer.get(op.src)
+            if not (op.kind == "conv" and op.bn and t.op.algo == ALGO_MFMA_H2 and k is not None and g.ops[k].bn and g.ops[k].cout % 8 == 0
+                    and op.cout % 4 == 0):
                 continue
-            conv = holders[op.conv]
-            slots = {"w": gtop}
-            self.param_list.append(conv.weight)
-            gtop += _align(conv.weight.numel(), 4)
-            if getattr(conv, "bias", None) is not None:
-                slots["b"] = gtop
-                self.param_list.append(conv.bias)
-                gtop += _align(op.cout, 4)
-            if op.bn:
-                bn = holders[op.bn]
-                slots["g"], slots["be"] = gtop, gtop + _align(op.cout, 4)
-                self.param_list += [bn.weight, bn.bias]
-                gtop += 2 * _align(op.cout, 4)
-            self.grad_slots.append(slots)
-            cum[-1] = gtop
-        self.grad_floats = gtop
-        # Segments of the op list for the autograd chain (run_network_train): ~equal shares of the gradient bytes, so
-        # that DistributedDataParallel sees the gradients of the LAST layers while the backward of the earlier ones is
-        # still running and can overlap its bucketed all-reduce (RCCL) with it.  One segment = one autograd node.
-        nseg = max(1, min(6, gtop // (4 << 20)))  # (no point in splitting a few MB of gradients)
-        bounds = [0]
-        for k in range(1, nseg):
-            i = next(i for i, c_ in enumerate(cum) if c_ >= k * gtop / nseg) + 1
-            if bounds[-1] < i < len(g.ops):
-                bounds.append(i)
-        bounds.append(len(g.ops))
-        self.segments = [(a, b) for a, b in zip(bounds, bounds[1:]) if b > a]
-        self.seg_params = []
-        for lo, hi in self.segments:
-            ps = []
-            for op in g.ops[lo:hi]:
-                if op.kind == "maxpool":
-                    continue
-                conv = holders[op.conv]
-                ps.append(conv.weight)
-                if getattr(conv, "bias", None) is not None:
-                    ps.append(conv.bias)
-                if op.bn:
-                    ps += [holders[op.bn].weight, holders[op.bn].bias]
-            self.seg_params.append(ps)
-        assert sum(len(p_) for p_ in self.seg_params) == len(self.param_list)
-        self.bn_counters = [holders[op.bn].num_batches_tracked for op in g.ops if op.bn]
+            hin, win, hout, wout = self.geo[i]
+            d = _query_op(0, op.k, op.stride, op.pad, op.cin, op.cout, hin, win, hout, wout)
+            if not lib.mval_op_algo_supported(C.byref(d), C.c_int(n), C.c_int(ALGO_MFMA_P2)):
+                continue
+            if op.src not in p2_act:
+                planes = self._row_top
+                self._row_top += _align(n * hin * win * op.cin)
+                rows = self._row_top
+                self._row_top += _align(n * P2_ROW)
+                p2_act[op.src] = (planes, rows)
+                self.p2_rows.append((rows, n * P2_ROW))
+            t.fwd_p2 = 1
+            t.in_p2_off, t.in_p2_rows_off = p2_act[op.src]
+        for a_, (planes, rows) in p2_act.items():
+            k = self._producer[a_]
+            pt, po = self.ops[k], g.ops[k]
+            pt.out_p2_off, pt.out_p2_rows_off = planes, rows
+            for r_, name in ((po.res1, "res1_amax_off"), (po.res2, "res2_amax_off")):
+                if r_ is not None:
+                    if r_ not in amax_row:
+                        amax_row[r_] = self._row_top
+                        self._row_top += TRAIN_AMAX_ROW
+                    setattr(pt, name, amax_row[r_])
 
-    # ---- parameters ---------------------------------------------------------------------------
-    def _assign_lanes(self, g, n, geo):
+    def _p2_wgrads_and_planes_only(self):
+        """Weight gradients read x from the planes where the split kernel covers the conv; an activation whose EVERY consumer reads the
+        planes (P2 forward conv + P2 weight gradient, no residual use, not the network output) is not written as fp32 at all.
+        Reads fwd_p2 / out_p2_off / gz_amax_off, _p2_act, the graph lookups; sets TRAIN_WGRAD_X_P2, TRAIN_OUT_P2_ONLY, TRAIN_RES*_P2, res*_p2_*."""
+        g, sw, lib, p2_act = self.graph, self.sw, _lib.lib(), self._p2_act
+        p2w = sw["MVAL_TRAIN_P2_WGRAD"] != "0"
+        fused_bwd = sw["MVAL_TRAIN_BWD_FUSED"] != "0"  # (round 3's BatchNorm backward reads `out` and writes fp32 dz only)
+        for i, op in enumerate(g.ops):
+            t = self.ops[i]
+            if p2w and t.fwd_p2 and t.gz_amax_off > 0 and lib.mval_conv_wgrad_p2_covers(C.c_int(op.cin), C.c_int(op.cout), C.c_int(op.k), C.c_int(op.stride)):
+                t.p2_flags |= TRAIN_WGRAD_X_P2
+        # a residual can be read from the planes as well (mval_bn_apply_fwd_p2_res) when the op that adds it runs the P2 apply: then
+        # a block output whose every reader takes the planes -- the next block's first conv, its weight gradient, the residual add at
+        # that block's end -- is P2-only too (MVAL_TRAIN_P2_RES=0: residuals stay fp32 NHWC)
+        p2res = sw["MVAL_TRAIN_P2_RES"] != "0"
+        for a_ in p2_act:
+            cons = self._consumers.get(a_, [])
+            po = g.ops[self._producer[a_]]
+            # (its own backward must not need `out` either: a ReLU behind residual adds takes its mask from the mask bytes)
+            own_ok = not (po.relu and (po.res1 is not None or po.res2 is not None)) or (sw["MVAL_TRAIN_RELU_MASK"] != "0" and po.up == 0)
+            users = self._res_users.get(a_, [])
+            users_ok = all(self.ops[i].out_p2_off > 0 and g.ops[i].bn for i, _ in users) and (p2res or not users)
+            if (p2w and fused_bwd and own_ok and users_ok and a_ != g.output and cons
+                    and all(self.ops[i].fwd_p2 and (self.ops[i].p2_flags & TRAIN_WGRAD_X_P2) for i in cons)):
+                self.ops[self._producer[a_]].p2_flags |= TRAIN_OUT_P2_ONLY
+                for i, bit in users:
+                    t = self.ops[i]
+                    t.p2_flags |= bit
+                    if bit == TRAIN_RES1_P2:
+                        t.res1_p2_off, t.res1_p2_rows_off = p2_act[a_]
+                    else:
+                        t.res2_p2_off, t.res2_p2_rows_off = p2_act[a_]
+
+    def _dz_scratch(self, idx):
+        """One dz plane scratch for the ops ``idx`` from _row_top: planes of the largest dz, rows (recorded in p2_rows), reduction scratch."""
+        g, n = self.graph, self.n
+        planes = self._row_top
+        self._row_top += _align(max(n * self.geo[i][2] * self.geo[i][3] * g.ops[i].cout for i in idx))
+        rows = self._row_top
+        self._row_top += _align(n * P2_ROW + 512 + 64)
+        self.p2_rows.append((rows, n * P2_ROW + 512 + 64))
+        for i in idx:
+            self.ops[i].gz_p2_off, self.ops[i].gz_p2_rows_off = planes, rows
+
+    def _p2_dgrads(self):
+        """Data gradients of stride-1 convs on the P2 kernels: the BatchNorm backward also writes dz as P2 planes into ONE scratch
+        (planes of the largest dz, rows, reduction scratch); MVAL_TRAIN_P2_DGRAD=0: the h2 data gradients.  (Round 5 also ran the
+        four parity convs of the stride-2 data gradients on conv_p2_kernel<2, ...> from the dz planes: 65.47 vs 65.2 ms per C3 step --
+        four persistent launches against the h2 kernel's one: not kept.)
+        Reads dgrad_algo / dgrad_form, TRAIN_WGRAD_X_P2, in_amax_off; sets TRAIN_DGRAD_P2, TRAIN_WGRAD_DZ_P2, gz_p2_* (one _dz_scratch)."""
+        g, n, sw, lib = self.graph, self.n, self.sw, _lib.lib()
+        if sw["MVAL_TRAIN_P2_DGRAD"] == "0" or sw["MVAL_TRAIN_BWD_FUSED"] == "0":
+            return
+        want = []
+        for i, op in enumerate(g.ops):
+            t = self.ops[i]
+            hin, win, hout, wout = self.geo[i]
+            if not (t.dgrad_algo == ALGO_MFMA_H2 and t.dgrad_form == 0 and op.bn and op.up == 0 and op.stride == 1 and op.cout % 8 == 0 and op.cin % 4 == 0
+                    and t.gin_off >= 0):
+                continue
+            d = _query_op(0, op.k, 1, op.k // 2, op.cout, op.cin, hout, wout, hin, win)
+            if op.pad == op.k // 2 and lib.mval_op_algo_supported(C.byref(d), C.c_int(n), C.c_int(ALGO_MFMA_P2)):
+                want.append(i)
+        if not want:
+            return
+        self._dz_scratch(want)
+        for i in want:
+            t, op = self.ops[i], g.ops[i]
+            t.p2_flags |= TRAIN_DGRAD_P2
+            # the weight gradient reads dz from the planes too where the split kernel covers the conv: no fp32 copy of dz
+            if (sw["MVAL_TRAIN_P2_WGRAD"] != "0" and op.cout % 8 == 0
+                    and lib.mval_conv_wgrad_split_covers(C.c_int(op.cin), C.c_int(op.cout), C.c_int(op.k), C.c_int(op.stride))
+                    and ((t.p2_flags & TRAIN_WGRAD_X_P2) or t.op.in_amax_off > 0)):
+                t.p2_flags |= TRAIN_WGRAD_DZ_P2
+
+    def _bn_apply_in_reader(self):
+        """Round 6: BatchNorm apply inside the consumer (include/mval_hip.h mval_train_op.z_out / zin_rel; hrnet.py:36-52: conv1 -> bn1 -> relu ->
+        conv2 of every BasicBlock, the 3x3 of a Bottleneck).  A planes-only ReLU output without residual or upsample whose ONE reader is a
+        3x3 stride-1 P2 conv on the same lane, with the P2 weight gradient reading dz from planes, is never written: that conv's staging
+        and its weight gradient's staging apply the BatchNorm from the producer's raw z.  MVAL_TRAIN_BN_IN_CONV=0: the separate apply pass.
+        Reads the P2 flags of passes 4 - 6 and the graph lookups; sets z_out / zin_rel, n_bn_in_conv."""
+        g, n, lib = self.graph, self.n, _lib.lib()
+        if self.sw["MVAL_TRAIN_BN_IN_CONV"] == "0":
+            return
+        lib.mval_conv_p2_inz_supported.restype = C.c_int
+        for a_ in self._p2_act:
+            k = self._producer[a_]
+            po, pt = g.ops[k], self.ops[k]
+            cons = self._consumers.get(a_, [])
+            if not ((pt.p2_flags & TRAIN_OUT_P2_ONLY) and po.kind == "conv" and po.bn and po.relu and po.res1 is None and po.res2 is None and po.up == 0
+                    and len(cons) == 1 and not self._res_users.get(a_) and a_ != g.output):
+                continue
+            j = cons[0]
+            co, ct = g.ops[j], self.ops[j]
+            if not (co.kind == "conv" and co.k == 3 and co.stride == 1 and co.pad == 1 and ct.fwd_p2 and (ct.p2_flags & TRAIN_WGRAD_X_P2)
+                    and (ct.p2_flags & TRAIN_WGRAD_DZ_P2) and (co.phase, co.lane) == (po.phase, po.lane) and j > k):
+                continue
+            hin, win, _, _ = self.geo[j]
+            if not lib.mval_conv_p2_inz_supported(C.c_int(co.cin), C.c_int(co.cout), C.c_int(hin), C.c_int(win), C.c_int(n)):
+                continue
+            pt.z_out = 1
+            ct.zin_rel = k - j
+            self.n_bn_in_conv += 1
+
+    def _plan_wide_flags(self):
+        """The two BatchNorm A/B switches and the exact-fp32 weight gradients of MVAL_CONV=fp32 are the PLAN's decision and travel in p2_flags
+        (TRAIN_BN_BWD_PAIR: round 3's backward pair, TRAIN_STATS_PASS: statistics by the separate pass, TRAIN_WGRAD_FP32): net_train.hip does
+        not read the environment.  Reads _amax_row; sets those bits on every op, out_amax_off, uses_p2."""
+        bits = ((0 if self.sw["MVAL_TRAIN_BWD_FUSED"] != "0" else TRAIN_BN_BWD_PAIR) | (0 if self.sw["MVAL_TRAIN_EPI_STATS"] != "0" else TRAIN_STATS_PASS)
+                | (0 if self._bf3 else TRAIN_WGRAD_FP32))
+        for i, op in enumerate(self.graph.ops):  # producers leave max |out| where a split conv will look for it
+            self.ops[i].out_amax_off = self._amax_row.get(op.dst, 0)
+            self.ops[i].p2_flags |= bits
+        self.uses_p2 = any(t.out_p2_off > 0 or (t.p2_flags & TRAIN_DGRAD_P2) for t in self.ops)
+
+    def _relu_masks(self):
+        """ReLU behind residual adds (BasicBlock / Bottleneck outputs, fuse sums at the conv resolution): the forward apply keeps
+        (out > 0) as one byte per float4, the backward reads that instead of `out` (a sixteenth of the bytes).  Sets mask_off (from _row_top)."""
+        if self.sw["MVAL_TRAIN_RELU_MASK"] == "0":
+            return
+        for i, op in enumerate(self.graph.ops):
+            if op.bn and op.relu and op.up == 0 and (op.res1 is not None or op.res2 is not None) and op.cout % 4 == 0:
+                self.ops[i].mask_off = self._row_top
+                self._row_top += _align((self.n * self.geo[i][2] * self.geo[i][3] * op.cout // 4 + 3) // 4)
+
+    def _bn_backward_sums_in_reader(self):
+        """Round 6, the other direction (MVAL_TRAIN_BSUM; MVAL_TRAIN_BN_BWD_IN_DGRAD=0: the reduction pass): the data gradient of a 3x3 stride-1
+        P2 conv whose input's producer is the op right in front of it in the list is the LAST writer of that producer's output gradient
+        (every other reader sits behind it in the list and writes earlier in the backward), so its epilogue keeps the sums the producer's
+        BatchNorm backward would take from a second read of it (P2Args::bs_z): ReLU producers without residual (mask from z: conv1 of a
+        BasicBlock) and with residuals (mask from the kept bits: conv2 of a block followed by another block; the apply pass then also
+        scatters the residual gradients).  The library checks the rest at launch (same lane, room for the partials).
+        Reads uses_p2, TRAIN_DGRAD_P2, gz_p2_off, mask_off; sets TRAIN_BSUM, n_bn_bwd_in_dgrad."""
+        g, sw, lib = self.graph, self.sw, _lib.lib()
+        if not self.uses_p2 or sw["MVAL_TRAIN_BN_BWD_IN_DGRAD"] == "0" or sw["MVAL_TRAIN_BWD_FUSED"] == "0":
+            return
+        lib.mval_conv_p2_bsum_supported.restype = C.c_int
+        for j in range(1, len(g.ops)):
+            co, ct, po, pt = g.ops[j], self.ops[j], g.ops[j - 1], self.ops[j - 1]
+            if not (co.kind == "conv" and co.k == 3 and co.stride == 1 and co.pad == 1 and co.src == po.dst and (ct.p2_flags & TRAIN_DGRAD_P2) and ct.gin_off >= 0
+                    and po.kind == "conv" and po.bn and po.relu and po.up == 0 and (pt.p2_flags & TRAIN_DGRAD_P2) and pt.gin_off >= 0 and pt.gz_p2_off > 0
+                    and (co.phase, co.lane) == (po.phase, po.lane)):
+                continue
+            if (po.res1 is not None or po.res2 is not None) and not pt.mask_off > 0:
+                continue
+            hin, win, _, _ = self.geo[j]
+            if lib.mval_conv_p2_bsum_supported(C.c_int(co.cout), C.c_int(co.cin), C.c_int(hin), C.c_int(win), C.c_int(self.n)):
+                ct.p2_flags |= TRAIN_BSUM
+                self.n_bn_bwd_in_dgrad += 1
+
+    def _assign_lanes(self):
         """Lanes of the training passes (csrc/net_train.hip, mval_train_*_lanes): the ops of a phase that sit on different lanes -- HRNet's
         branches, the chains of a fuse layer (graph.py; hrnet.py:199-287) -- are independent, so they run on separate streams.  Forward:
         every op on a lane > 0 (each writes only its own tensors' slots, rows, masks, statistics).  Backward: only in phases where every
         gradient slot has ALL its writers on one lane (the branch bodies; a fuse layer's chains all add into the branches' output
         gradients and stay serial), so each slot sees its first-touch store and its accumulations in the serial order: same bits as
         MVAL_TRAIN_LANES=0.  What the ops of a lane share -- dz's magnitude row, the dz plane scratch, and the buffers the C call slices
-        per lane -- exists once per lane."""
+        per lane -- exists once per lane.  Sets n_lanes, the MVAL_TRAIN_LANE_* bits, per-lane gz_amax_off rows and dz scratches (_row_top)."""
+        g = self.graph
         self.n_lanes = 1
         # 0: one stream; 1: lanes in the phases without shared gradient slots only; 2: in all phases; 3 (default): and the backward without
         # joins at the phase changes -- every dependency through the slot events
@@ -561,7 +472,6 @@ class TrainPlan:
         nl = min(MAX_LANES, max(op.lane for op in g.ops) + 1)
         if nl <= 1:
             return
-        from .engine import P2_ROW
         flags = lane_flags(g, nl, mode)
         row = {0: self.gz_amax_off}
         scratch = {}
@@ -575,17 +485,110 @@ class TrainPlan:
                     row[op.lane] = self._row_top
                     self._row_top += TRAIN_AMAX_ROW
                 t.gz_amax_off = row[op.lane]
-            if t.p2_flags & 4:
+            if t.p2_flags & TRAIN_DGRAD_P2:
                 scratch.setdefault(op.lane, []).append(i)
-        for lane, idx in scratch.items():
-            planes = self._row_top
-            self._row_top += _align(max(n * geo[i][2] * geo[i][3] * g.ops[i].cout for i in idx))
-            rows = self._row_top
-            self._row_top += _align(n * P2_ROW + 512 + 64)
-            self.p2_rows.append((rows, n * P2_ROW + 512 + 64))
-            for i in idx:
-                self.ops[i].gz_p2_off, self.ops[i].gz_p2_rows_off = planes, rows
+        for idx in scratch.values():
+            self._dz_scratch(idx)
         self.n_lanes = nl
+
+    def _first_touch(self):
+        """First writer of every activation-gradient slot (backward order) stores, later ones accumulate; slots nobody writes (activations
+        without a consumer) are the only ones zero-filled.  Sets first_touch, zero_slots."""
+        g, n = self.graph, self.n
+        touched = {g.output}
+        for i in range(len(g.ops) - 1, -1, -1):
+            op, t = g.ops[i], self.ops[i]
+            mask = 0
+            for bit, act in ((2, op.res1), (4, op.res2), (1, None if op.src == g.input else op.src)):
+                if act is not None and act not in touched:
+                    touched.add(act)
+                    mask |= bit
+            t.first_touch = mask
+        self.zero_slots = [(off, n * self.dims[a][0] * self.dims[a][1] * g.acts[a].channels) for a, off in self._act_off.items() if a not in touched]
+
+    def _allocate(self):
+        """Device buffers, sized by the counters the passes above leave (arena_floats, _act_top, _ptop, _stat_top, _gz_max, _wsf_max, n_lanes);
+        ones / zeros close the parameter buffer."""
+        g, n, maxc, device = self.graph, self.n, self.maxc, self.device
+        self.ones_off = self._ptop
+        self.zeros_off = self.ones_off + _align(maxc)
+        self.param_floats = self.zeros_off + _align(maxc)
+        for t in self.ops:
+            if not t.has_bn:
+                t.op.scale_off = self.ones_off
+        f32 = dict(dtype=torch.float32, device=device)
+        self.arena = torch.empty(self.arena_floats, **f32)
+        for off, cnt in self.p2_rows:  # P2 rows: unused partial slots must read as zero (csrc/conv_p2.h); the scale slot is rewritten every forward
+            self.arena[off : off + cnt].zero_()
+        self.garena = torch.empty(max(self._act_top, 64), **f32)
+        self.params = torch.zeros(self.param_floats, **f32)
+        self.params[self.ones_off : self.ones_off + maxc] = 1.0
+        self.stats = torch.zeros(max(self._stat_top, 64), **f32)
+        # (lanes: one slice of every scratch buffer per lane, mval_train_*_lanes)
+        self.gz_lane, self.wsf_lane = _align(max(self._gz_max, 64)), _align(max(self._wsf_max, 64))
+        self.gz = torch.empty(self.gz_lane * self.n_lanes, **f32)
+        self.wsf = torch.empty(self.wsf_lane * self.n_lanes, **f32)
+        # float64 scratch of the BatchNorm reductions; sized so that the forward conv epilogues' per-workgroup statistics
+        # partials fit (cout x workgroups x 2, workgroups <= pixels / 32 for every tile the large layers use)
+        epi = max((op.cout * ((n * self.geo[i][2] * self.geo[i][3] + 31) // 32 + 64) * 2 for i, op in enumerate(g.ops) if op.bn), default=0)
+        # (round 6: ... and the data gradients' reduction partials, cout x slots x 3 with slots = persistent workgroups x pixel waves <= 2 304)
+        bsum = max((g.ops[i - 1].cout * 2304 * 3 for i, t in enumerate(self.ops) if t.p2_flags & TRAIN_BSUM), default=0)
+        self.ws_lane = _align(max(512 * maxc * 2, epi, bsum) + 64)
+        self.ws = torch.empty(self.ws_lane * self.n_lanes, dtype=torch.float64, device=device)
+        self.sums_lane = _align(2 * maxc + 64)
+        self.sums = torch.empty(self.sums_lane * self.n_lanes, **f32)
+        self.param_sig = self._pack_ptrs = self._pack_jobs = None
+
+    def _op_params(self, op):
+        """(slot name, tensor) of graph op ``op``'s parameters in the autograd node's order: conv.weight [, conv.bias] [, bn.weight, bn.bias]."""
+        if op.kind == "maxpool":
+            return
+        conv = self.model._holders[op.conv]
+        yield "w", conv.weight
+        if getattr(conv, "bias", None) is not None:
+            yield "b", conv.bias
+        if op.bn:
+            bn = self.model._holders[op.bn]
+            yield from (("g", bn.weight), ("be", bn.bias))
+
+    def _autograd_order(self):
+        """Parameter order of the autograd node (_op_params per op), every parameter's slot in the gradient buffer, and the segments.
+        Sets param_list, grad_slots, grad_floats, segments, seg_params, bn_counters."""
+        g = self.graph
+        self.param_list, self.grad_slots = [], []
+        gtop = 0
+        cum = []  # gradient floats up to and including op i
+        for op in g.ops:
+            slots = {}
+            for name, p in self._op_params(op):
+                slots[name] = gtop
+                self.param_list.append(p)
+                gtop += _align(p.numel(), 4)
+            self.grad_slots.append(slots)
+            cum.append(gtop)
+        self.grad_floats = gtop
+        # Segments of the op list for the autograd chain (run_network_train): ~equal shares of the gradient bytes, so
+        # that DistributedDataParallel sees the gradients of the LAST layers while the backward of the earlier ones is
+        # still running and can overlap its bucketed all-reduce (RCCL) with it.  One segment = one autograd node.
+        nseg = max(1, min(6, gtop // (4 << 20)))  # (no point in splitting a few MB of gradients)
+        bounds = [0]
+        for k in range(1, nseg):
+            i = next(i for i, c_ in enumerate(cum) if c_ >= k * gtop / nseg) + 1
+            if bounds[-1] < i < len(g.ops):
+                bounds.append(i)
+        bounds.append(len(g.ops))
+        self.segments = [(a, b) for a, b in zip(bounds, bounds[1:]) if b > a]
+        self.seg_params = [[p for op in g.ops[lo:hi] for _, p in self._op_params(op)] for lo, hi in self.segments]
+        self.bn_counters = [self.model._holders[op.bn].num_batches_tracked for op in g.ops if op.bn]
+
+    # ---- parameters ---------------------------------------------------------------------------
+    def _pack_modes(self, i):
+        """(fmode, dmode, dk) of op i's weight packings.  Conv2d: forward as stored (0), data gradient tap-flipped / channel-swapped (2);
+        ConvTranspose2d: the other way round (forward = conv over the zero-dilated input).  The four-parity form of a stride-2 data
+        gradient is mode 4, packed as k = 4."""
+        op = self.graph.ops[i]
+        fmode, dmode = (2, 0) if op.kind == "deconv" else (0, 2)
+        return (fmode, 4, 4) if self.ops[i].dgrad_form == 1 else (fmode, dmode, op.k)
 
     def _build_pack_table(self, holders, base):
         """Device-side job table of every split-bf16 weight packing of the plan (forward and data-gradient
@@ -601,10 +604,7 @@ class TrainPlan:
             if not (w.is_cuda and w.is_contiguous()):
                 self._pack_jobs = None
                 return
-            fmode, dmode = (2, 0) if op.kind == "deconv" else (0, 2)
-            dk = op.k
-            if t.dgrad_form == 1:  # four-parity form of a stride-2 data gradient: mode 4, packed as k = 4
-                dmode, dk = 4, 4
+            fmode, dmode, dk = self._pack_modes(i)
             todo = []
             if fpack in (PACK_MFMA16_BF3, PACK_MFMA16_H2):  # (bit 8 of the mode: fp16-split packing, mval_pack_split_jobs)
                 todo.append((base + 4 * t.op.w_off, fmode | (0x100 if fpack == PACK_MFMA16_H2 else 0), op.cout, op.cin, op.k))
@@ -626,14 +626,11 @@ class TrainPlan:
         self._pack_n, self._pack_blocks = len(rows), blocks
 
     def _refresh(self):
-        holders = self.model._holders
-        lib = _lib.lib()
-        st = _lib._stream()
+        holders, lib, st = self.model._holders, _lib.lib(), _lib._stream()
         ptrs = tuple(p.data_ptr() for p in self.param_list)
         sig = tuple(p._version for p in self.param_list) + ptrs
         repack = sig != self.param_sig
-        base = self.params.data_ptr()
-        sbase = self.stats.data_ptr()
+        base, sbase = self.params.data_ptr(), self.stats.data_ptr()
         if repack and ptrs != self._pack_ptrs:
             self._build_pack_table(holders, base)
             self._pack_ptrs = ptrs
@@ -652,12 +649,7 @@ class TrainPlan:
             if repack:
                 batched = self._pack_jobs is not None
                 wp = C.c_void_p(w.detach().contiguous().data_ptr())
-                # Conv2d: forward as stored (0), data gradient tap-flipped / channel-swapped (2);
-                # ConvTranspose2d: the other way round (forward = conv over the zero-dilated input)
-                fmode, dmode = (2, 0) if op.kind == "deconv" else (0, 2)
-                dk = op.k
-                if t.dgrad_form == 1:
-                    dmode, dk = 4, 4
+                fmode, dmode, dk = self._pack_modes(i)
                 if not (batched and fpack in (PACK_MFMA16_BF3, PACK_MFMA16_H2)):
                     _lib._check(lib.mval_pack_conv_weights(C.c_int(fpack), C.c_int(fmode), wp, C.c_void_p(base + 4 * t.op.w_off),
                                                            C.c_int(op.cout), C.c_int(op.cin), C.c_int(op.k), st), "pack fwd")
@@ -808,17 +800,10 @@ class TrainPlan:
                 _lib._stream()),
             "mval_train_backward_lanes")
         out = []
-        holders = self.model._holders
         for slots, op in zip(self.grad_slots[lo:hi], g.ops[lo:hi]):
-            if not slots:
-                continue
-            conv = holders[op.conv]
-            out.append(grads[slots["w"] : slots["w"] + conv.weight.numel()].view_as(conv.weight))
-            if "b" in slots:
-                out.append(grads[slots["b"] : slots["b"] + op.cout])
-            if op.bn:
-                out.append(grads[slots["g"] : slots["g"] + op.cout])
-                out.append(grads[slots["be"] : slots["be"] + op.cout])
+            for name, p in self._op_params(op):
+                v = grads[slots[name] : slots[name] + p.numel()]
+                out.append(v.view_as(p) if p.dim() > 1 else v)
         if k == 0:  # the step's last segment
             if self._probe is not None:
                 self._probe_read()

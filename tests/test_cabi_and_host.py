@@ -440,6 +440,10 @@ def test_ctypes_mirror_constants_match_the_header():
     assert define("MVAL_TRAIN_LANE_FWD") == engine_train.TRAIN_LANE_FWD and define("MVAL_TRAIN_LANE_BWD") == engine_train.TRAIN_LANE_BWD
     assert define("MVAL_TRAIN_LANE_ORD") == engine_train.TRAIN_LANE_ORD and define("MVAL_TRAIN_BSUM") == engine_train.TRAIN_BSUM
     assert define("MVAL_TRAIN_WGRAD_FP32") == engine_train.TRAIN_WGRAD_FP32
+    for name in ("WGRAD_X_P2", "OUT_P2_ONLY", "DGRAD_P2", "WGRAD_DZ_P2", "RES1_P2", "RES2_P2", "BN_BWD_PAIR", "STATS_PASS"):  # p2_flags bits 0 - 7
+        assert define("MVAL_TRAIN_" + name) == getattr(engine_train, "TRAIN_" + name), name
+    assert [getattr(engine_train, "TRAIN_" + n) for n in ("WGRAD_X_P2", "OUT_P2_ONLY", "DGRAD_P2", "WGRAD_DZ_P2", "RES1_P2", "RES2_P2", "BN_BWD_PAIR",
+                                                           "STATS_PASS")] == [1, 2, 4, 8, 16, 32, 64, 128]
     # the ctypes mirror of mval_train_op ends with the round-6 fields and has the header's size (8-byte aligned, two int32 at the end)
     assert [f[0] for f in engine_train.MvalTrainOp._fields_][-2:] == ["zin_rel", "z_out"]
     csrc = open(os.path.join(os.path.dirname(__file__), "..", "multi_view_active_learning_amd", "csrc", "conv_common.h")).read()

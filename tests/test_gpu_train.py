@@ -564,7 +564,8 @@ def test_round4_training_paths_against_their_switches(dev, off, monkeypatch):
     m1, _, hm1, l1, _ = _train_once(c, dev)
     plan = next(iter(m1._train_plans.values()))
     n_p2 = sum(int(t.fwd_p2) for t in plan.ops)
-    assert n_p2 > 200 and sum(int(t.p2_flags & 4 != 0) for t in plan.ops) > 150 and sum(int(t.p2_flags & 2 != 0) for t in plan.ops) > 80
+    assert (n_p2 > 200 and sum(int(t.p2_flags & engine_train.TRAIN_DGRAD_P2 != 0) for t in plan.ops) > 150
+            and sum(int(t.p2_flags & engine_train.TRAIN_OUT_P2_ONLY != 0) for t in plan.ops) > 80)
     g1 = {k: p.grad.detach().clone() for k, p in m1.named_parameters()}
     monkeypatch.setenv(off, "0")
     m0, _, hm0, l0, _ = _train_once(c, dev)

@@ -192,7 +192,9 @@ size_t mval_kcenter_workspace_bytes(int64_t n_obs, int D);
  *   labeled [n_labeled] i64 row indices (may be NULL/0) ;
  *   have_min_dist != 0: min_dist [n_obs] already holds the running minimum (continuation) ;
  *   row_norms [n_obs] f64 scratch ; picks [n_select] i64 ; ws >= mval_kcenter_workspace_bytes.
- * First maximum wins ties; nothing is masked (duplicates possible, as in the reference). */
+ * First maximum wins ties; nothing is masked (duplicates possible, as in the reference).
+ * n_labeled == 0 with have_min_dist == 0: every distance starts at +inf, so the first pick is row 0 (the
+ * reference's np.argmax(None) == 0); n_select == 0 leaves picks untouched and min_dist initialised. */
 int mval_kcenter_select(const double* feat, int64_t n_obs, int D, const int64_t* labeled, int64_t n_labeled,
                         int n_select, int have_min_dist, double* row_norms, double* min_dist,
                         int64_t* picks, void* ws, void* stream);

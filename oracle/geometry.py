@@ -150,6 +150,20 @@ def triangulate_ransac(proj_matricies, points, n_iters=64, eps=5.0):
     return x, float(np.mean(err)), len(inliers)
 
 
+def ransac_vote_margin(proj_matricies, points, eps=5.0):
+    """min over (pair, view) of |err - eps| for the votes ``triangulate_ransac`` takes: the vote is a strict
+    ``err < eps`` on a float64 whose last bits depend on the operation order, so a problem whose margin is tiny
+    cannot be compared for an exact inlier count between two implementations (tests leave it out, under a cap)."""
+    proj_matricies = np.asarray(proj_matricies)
+    points = np.asarray(points)
+    margin = np.inf
+    for pr in itertools.combinations(range(len(points)), 2):
+        pr = list(pr)
+        x = triangulate_dlt(proj_matricies[pr], points[pr])
+        margin = min(margin, float(np.min(np.abs(reprojection_errors(x, points, proj_matricies) - eps))))
+    return margin
+
+
 def compute_xe(keypoints_3d, proj_matricies, pred_heatmaps, sigma):
     """utils/triangulation.py:236-257: sum over (view, joint) of
     mean((pred - exp(-|grid - kp|^2 / (2 sigma^2)))^2); kp is the reprojection in

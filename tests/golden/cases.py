@@ -37,6 +37,23 @@ def triangulation_cases():
     )
 
 
+def triangulation_edge_cases():
+    """Lane-group sizes and joint counts that triangulation_cases() leaves out (csrc/triangulate.hip: one problem per
+    PG = pow2 >= C(V,2) lanes): V = 5, 6 -> 10 / 15 pairs, PG = 16; V = 7 -> 21 pairs, PG = 32; V = 9, 10, 11 ->
+    36 / 45 / 55 pairs, PG = 64.  J = 130 with one invalid joint leaves 129 > 128 addends and J = 512 (the documented
+    limit) 512: the recursive branch of numpy's pairwise sum in the per-frame mean.  16 x 16 maps keep those two cheap."""
+    return OrderedDict(
+        v5_outlier=dict(seed=61, b=2, v=5, j=19, h=256, w=256, stride=4, noise=0.05, outliers=1, invalid=()),
+        v6_nonsquare=dict(seed=62, b=2, v=6, j=19, h=256, w=192, stride=4, noise=0.05, outliers=2, invalid=(3, 17)),
+        v7_outliers=dict(seed=63, b=2, v=7, j=19, h=256, w=256, stride=4, noise=0.05, outliers=3, invalid=()),
+        v9_outlier=dict(seed=64, b=2, v=9, j=19, h=256, w=256, stride=4, noise=0.05, outliers=1, invalid=()),
+        v10_outliers=dict(seed=65, b=1, v=10, j=19, h=256, w=256, stride=4, noise=0.05, outliers=2, invalid=()),
+        v11_outliers=dict(seed=66, b=1, v=11, j=19, h=256, w=256, stride=4, noise=0.05, outliers=3, invalid=()),
+        v2_j130=dict(seed=67, b=2, v=2, j=130, h=64, w=64, stride=4, noise=0.02, outliers=0, invalid=(0,)),
+        v2_j512=dict(seed=68, b=1, v=2, j=512, h=64, w=64, stride=4, noise=0.02, outliers=0, invalid=()),
+    )
+
+
 def xe_cases():
     return OrderedDict(
         xe_v4=dict(seed=21, b=2, v=4, j=19, h=256, w=256, stride=4, noise=0.02, outliers=0, invalid=(5,), sigma=1.0),

@@ -12,6 +12,7 @@ What is pinned:
   triangulation_reftest.npz  the reference's own test input (tests/test_triangulation.py:15-69)
   triangulation_synth.npz    ring cameras, V in {2,4,8}, square / non-square maps, invalid joints, outlier views
   triangulation_xe.npz       use_reprojection_xe=True (utils/triangulation.py:236-257)
+  triangulation_edges.npz    V in {5,6,7,9,10,11} (every lane-group size of the device kernel), J = 130 and 512 at V = 2
   scoring.npz                _compute_hp/_compute_mpe/_compute_bsb AVG+STD (strategy.py:1149-1215)
   sal_dict.json              _compute_sal_dict over a 2-batch loader for HP/TRIANGULATION/CORESET/MPE + nlargest picks
   coreset.npz                CoreSet.select_batch picks (+ boundary gaps from the restatement)
@@ -121,6 +122,24 @@ def gen_triangulation(ns):
         out[name + "/metric"] = np.asarray(me, dtype=np.float64)
         print(name, "xe", me)
     np.savez(os.path.join(HERE, "triangulation_xe.npz"), versions=versions(), **out)
+
+
+def gen_triangulation_edges(ns):
+    """cases.triangulation_edge_cases() -> triangulation_edges.npz (outputs only, like triangulation_synth.npz)."""
+    tri = ns.triangulation.triangulation
+    out = {}
+    for name, c in cases.triangulation_edge_cases().items():
+        hm, proj, valid = cases.build_triangulation_case(c)
+        k2, k3, me, ic = [], [], [], []
+        for b in range(hm.shape[0]):
+            r = tri(torch.from_numpy(hm[b]), torch.from_numpy(proj[b]), c["stride"], torch.from_numpy(valid[b]))
+            k2.append(r["keypoints_2d"]); k3.append(r["keypoints_3d"]); me.append(r["metric"]); ic.append(r["inlier_count"])
+        out[name + "/keypoints_2d"] = np.stack(k2)
+        out[name + "/keypoints_3d"] = np.stack(k3)
+        out[name + "/metric"] = np.asarray(me, dtype=np.float64)
+        out[name + "/inlier_count"] = np.asarray(ic, dtype=np.int64)
+        print(name, "inliers", ic, "metric", np.round(me, 4))
+    np.savez_compressed(os.path.join(HERE, "triangulation_edges.npz"), versions=versions(), **out)
 
 
 def gen_scoring(ns):
@@ -462,7 +481,7 @@ def gen_formats(ns):
 
 def main():
     ns = ref_harness.load()
-    which = sys.argv[1:] or ["tri", "scoring", "sal", "coreset", "models", "train", "pck", "preprocess", "sal_filter", "formats"]
+    which = sys.argv[1:] or ["tri", "tri_edges", "scoring", "sal", "coreset", "models", "train", "pck", "preprocess", "sal_filter", "formats"]
     if "formats" in which:
         gen_formats(ns)
     if "pck" in which:
@@ -473,6 +492,8 @@ def main():
         gen_sal_filter(ns)
     if "tri" in which:
         gen_triangulation(ns)
+    if "tri_edges" in which:
+        gen_triangulation_edges(ns)
     if "scoring" in which:
         gen_scoring(ns)
     if "sal" in which:

@@ -40,6 +40,29 @@ def test_triangulation_synth(name):
         assert r["inlier_count"] == z[name + "/inlier_count"][b]
 
 
+@pytest.mark.parametrize("name", list(cases.triangulation_edge_cases()))
+def test_triangulation_edges(name, capsys):
+    """The oracle restatement against the real reference at V = 5, 6, 7, 9, 10, 11 and J = 130, 512
+    (tests/golden/triangulation_edges.npz): the CPU half of tests/test_gpu_post_edges.py's golden test.  No (pair, view)
+    vote of any valid joint lies within 1e-6 px of eps = 5 (asserted: zero undecidable problems), so the exact inlier
+    counts can be asked of any implementation."""
+    c = cases.triangulation_edge_cases()[name]
+    z = np.load(os.path.join(G, "triangulation_edges.npz"))
+    hm, proj, valid = cases.build_triangulation_case(c)
+    undecidable = 0
+    for b in range(hm.shape[0]):
+        r = geometry.triangulation(hm[b], proj[b], c["stride"], valid[b])
+        np.testing.assert_array_equal(r["keypoints_2d"], z[name + "/keypoints_2d"][b])
+        np.testing.assert_allclose(r["keypoints_3d"], z[name + "/keypoints_3d"][b], rtol=1e-9, atol=1e-6)
+        np.testing.assert_allclose(r["metric"], z[name + "/metric"][b], rtol=1e-9)
+        assert r["inlier_count"] == z[name + "/inlier_count"][b]
+        kp = r["keypoints_2d"]
+        undecidable += sum(geometry.ransac_vote_margin(proj[b], kp[:, j]) <= 1e-6 for j in range(c["j"]) if valid[b, j])
+    with capsys.disabled():
+        print(f"\n[triangulation_edges {name}] undecidable (frame, joint) problems: {undecidable} of {int(valid.sum())}")
+    assert undecidable == 0
+
+
 def test_nonsquare_argmax_quirk():
     # peak at (row 10, col 7) of a 64x48 map -> (x, y) = (487 % 64, 487 // 64) * stride (SURVEY A.2)
     hm = np.zeros((1, 1, 64, 48), dtype=np.float32)

@@ -129,13 +129,21 @@ typedef struct mval_view_desc {
   const uint8_t* img;               /* decoded RGB image [h0][w0][3] (device) */
   int32_t h0, w0;
   int32_t left, top, right, bottom; /* square / scaled box (utils/triangulation.py:96-134); may leave the image */
-  int64_t tmp_off;                  /* byte offset of this view's [bottom-top][in_w][3] slab in the workspace's temp part (slabs back to back:
-                                     * multiples of in_w * 3; the vertical pass reads 4 bytes at a time where the slab is 4-byte aligned) */
+  int64_t tmp_off;                  /* byte offset of this view's [bottom-top][in_w][3] slab in the workspace's temp part.  The slabs must not
+                                     * overlap and must end inside the rows the workspace was sized for; usually they lie back to back from 0
+                                     * (multiples of in_w * 3).  tmp_off need NOT be 4-byte aligned: the vertical pass reads 4 bytes at a time
+                                     * where the slab is aligned and byte by byte where it is not, with the same result (tested with first
+                                     * offsets 1, 2, 3: tests/test_gpu_preprocess_edges.py) */
 } mval_view_desc;
 /* ws >= mval_prepare_views_workspace_bytes(n_views, sum of the views' crop heights, in_w, in_h). */
 size_t mval_prepare_views_workspace_bytes(int n_views, int64_t total_crop_rows, int in_w, int in_h);
 /* BGR flip + zero-filled crop + PIL LANCZOS resize (Pillow's 8-bit fixed-point algorithm, bit-exact) +
- * ImageNet normalisation: out [n_views][3][in_h][in_w] f32.  views: DEVICE array. */
+ * ImageNet normalisation: out [n_views][3][in_h][in_w] f32.  views: DEVICE array.
+ *   max_crop_h / max_crop_w must be at least every view's crop height (bottom - top) / crop width (right - left).  With a smaller value
+ *   the results are undefined, though the kernels still write nothing outside out and ws.
+ *   The largest accepted box: ceil(3 * max(1, max_crop_w / in_w, max_crop_h / in_h)) * 2 + 1 <= 64 filter taps, i.e. checked per axis and
+ *   a crop / in ratio of at most 31 / 3 on either (661 -> 64, 2645 -> 256).  A larger box returns -1 and mval_last_error() names the box,
+ *   the tap limit and the input size; nothing is launched. */
 int mval_prepare_views(const mval_view_desc* views, int n_views, int max_crop_h, int max_crop_w, int in_w, int in_h,
                        float* out, void* ws, void* stream);
 /* Gaussian ground-truth heat-maps (dataset.py:198-207): pt [n][2] f64 (x, y in heat-map pixels) ->

@@ -74,43 +74,14 @@ __device__ __forceinline__ int pp_clip8(int v) {
   return v < 0 ? 0 : v > 255 ? 255 : v;
 }
 
-// temp[row][xx][c] for every crop row; reads the raw image through the (zero-filled) box
-__global__ void pp_horizontal_kernel(const mval_view_desc* __restrict__ views, int in_w, int in_h, int max_crop_h,
-                                     const PpCoeff* __restrict__ co, unsigned char* __restrict__ tmp) {
-  const int v = blockIdx.z;
-  const mval_view_desc d = views[v];
-  const int crop_h = d.bottom - d.top;
-  const int r = blockIdx.y * blockDim.y + threadIdx.y, xx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= crop_h || xx >= in_w) return;
-  const int omax = max(in_w, in_h);
-  const PpCoeff& c = co[(v * 2 + 0) * omax + xx];
-  const int y = r + d.top;
-  int s0 = 1 << (PP_BITS - 1), s1 = s0, s2 = s0;
-  if (y >= 0 && y < d.h0) {
-    const unsigned char* row = d.img + (int64_t)y * d.w0 * 3;
-    for (int t = 0; t < c.n; t++) {
-      const int x = c.lo + t + d.left;
-      if (x < 0 || x >= d.w0) continue;
-      const int k = c.k[t];
-      s0 += row[x * 3] * k;
-      s1 += row[x * 3 + 1] * k;
-      s2 += row[x * 3 + 2] * k;
-    }
-  }
-  unsigned char* o = tmp + d.tmp_off + ((int64_t)r * in_w + xx) * 3;
-  o[0] = (unsigned char)pp_clip8(s0);
-  o[1] = (unsigned char)pp_clip8(s1);
-  o[2] = (unsigned char)pp_clip8(s2);
-}
-
-// The same pass with the tile's operands in LDS (round 5; the kernel above stays as the fallback for spans that do not fit).  A workgroup
-// = 64 output columns x 4 rows at a time (one wave per row) over PP_HROWS crop rows: the 64 columns' weights are staged ONCE, tap-major
+// Horizontal pass: temp[row][xx][c] for every crop row; reads the raw image through the (zero-filled) box, the tile's operands in LDS.  A
+// workgroup = 64 output columns x 4 rows at a time (one wave per row) over PP_HROWS crop rows: the 64 columns' weights are staged ONCE, tap-major
 // (k_s[t][column]: the lanes of a wave read consecutive words), and per row the source span of the tile -- the columns' windows overlap
 // heavily: 64 columns at scale 2 read 140 source pixels -- is fetched with consecutive byte loads (zero-filled outside the image, as
 // the box demands) instead of <= 64 x 3 strided byte loads and as many 4-byte weight loads from a 264-byte-strided table per thread.
-// Integer sums are order-free: same bytes out.  128 views 512^2 -> 256^2: 439 -> see profiles/r05/pp_lds.log.
+// Integer sums are order-free: the bytes do not depend on the tiling.
 #define PP_HROWS 64
-#define PP_SPAN 1024  // source pixels per tile row that fit (64 columns at scale <= ~15)
+#define PP_SPAN 1024  // source pixels per staged tile row (the widest accepted span, 64 columns at scale 31 / 3, is 728)
 __global__ __launch_bounds__(256) void pp_horizontal_lds_kernel(const mval_view_desc* __restrict__ views, int in_w, int in_h,
                                                                 const PpCoeff* __restrict__ co, unsigned char* __restrict__ tmp) {
   __shared__ int lo_s[64], n_s[64];
@@ -138,8 +109,9 @@ __global__ __launch_bounds__(256) void pp_horizontal_lds_kernel(const mval_view_
   const int r_end = min(crop_h, ((int)blockIdx.y + 1) * PP_HROWS);
   if (span > PP_SPAN) {
     // The launcher sizes the staged row from the HOST's max_crop_w; the span comes from the view's DEVICE descriptor.  A view whose box is
-    // wider than the host said must not write past px_s: its tiles read their taps straight from the image (pp_horizontal_kernel's loop:
-    // same integer sums, same bytes out).  Uniform per workgroup (span is a function of shared values), so no barrier is skipped.
+    // wider than the host said breaks the contract of mval_prepare_views and must still not write past px_s: this memory guard reads the
+    // (<= PP_KMAX, so truncated) taps straight from the image instead of staging the row.  Its output has no Pillow counterpart; it only
+    // stays inside tmp.  Uniform per workgroup (span is a function of shared values), so no barrier is skipped.
     for (int r = blockIdx.y * PP_HROWS + ty; r < r_end; r += 4) {
       if (!col_ok) continue;
       const int y = r + d.top;
@@ -305,15 +277,13 @@ extern "C" int mval_prepare_views(const mval_view_desc* views, int n_views, int 
   hipLaunchKernelGGL(pp_lut_kernel, dim3(3), dim3(256), 0, s, lut_g);
   hipLaunchKernelGGL(pp_coeff_kernel, dim3((nco + 127) / 128), dim3(128), 0, s, views, n_views, in_w, in_h, co);
   MVAL_CHECK_LAUNCH("mval_prepare_views/coeff");
-  // the source span of 64 output columns: 64 * scale + the filter support on both sides (+ rounding)
-  if ((int)ceil(64.0 * sx + 6.0 * (sx < 1.0 ? 1.0 : sx)) + 4 <= PP_SPAN)
-    hipLaunchKernelGGL(pp_horizontal_lds_kernel, dim3((in_w + 63) / 64, (max_crop_h + PP_HROWS - 1) / PP_HROWS, n_views), dim3(64, 4), 0, s, views,
-                       in_w, in_h, co, tmp);
-  else
-    hipLaunchKernelGGL(pp_horizontal_kernel, dim3((in_w + 63) / 64, (max_crop_h + 3) / 4, n_views), dim3(64, 4), 0, s, views,
-                       in_w, in_h, max_crop_h, co, tmp);
+  // The source span of 64 output columns is 64 * scale + the filter support on both sides (+ rounding): ceil(64 sx + 6 max(1, sx)) + 4
+  // pixels.  That would pass PP_SPAN = 1024 only for sx above ~14.57, and the tap check above has already rejected smax > 31 / 3, where the
+  // span is 728: every accepted call fits the staged row, so there is no second horizontal kernel to fall back to.
+  hipLaunchKernelGGL(pp_horizontal_lds_kernel, dim3((in_w + 63) / 64, (max_crop_h + PP_HROWS - 1) / PP_HROWS, n_views), dim3(64, 4), 0, s, views,
+                     in_w, in_h, co, tmp);
   MVAL_CHECK_LAUNCH("mval_prepare_views/horizontal");
-  // (tmp_off of every view is a multiple of 4 when in_w * 3 is: the caller packs the views' [crop_h][in_w][3] slabs back to back)
+  // dword loads where a temp row is a whole number of dwords; a slab whose tmp_off is not 4-byte aligned is then read byte by byte (same result)
   if ((in_w * 3) % 4 == 0)
     hipLaunchKernelGGL(pp_vertical4_kernel, dim3((in_w * 3 / 4 + 63) / 64, (in_h + 3) / 4, n_views), dim3(64, 4), 0, s, views, in_w, in_h, co, tmp, out,
                        lut_g);

@@ -306,6 +306,23 @@ def preprocess_inputs(c):
     return img, kp3d, cam
 
 
+def resample_image(kind, h, w, seed=0):
+    """(h, w, 3) uint8 test images for the LANCZOS resampler.  "noise": uniform bytes -- a downscale of it by 3.7 or more never left 0..255
+    before the clamp, and one by 2 only in under 0.1 % of the sums.  "stripes": zeros with every seventh column 255 and every fifth row
+    inverted; "checker": a 3-pixel diagonal checkerboard of 0 and 255 -- the negative lobes of the filter take both well below 0 and above 255 (tests/test_gpu_preprocess_edges.py measures the shares)."""
+    if kind == "noise":
+        return np.random.default_rng(seed).integers(0, 256, size=(h, w, 3), dtype=np.uint8)
+    if kind == "stripes":
+        img = np.zeros((h, w, 3), dtype=np.uint8)
+        img[:, ::7] = 255
+        img[::5] = 255 - img[::5]
+        return img
+    if kind == "checker":
+        yy, xx = np.mgrid[0:h, 0:w]
+        return np.repeat(((((xx + yy) // 3) % 2) * 255).astype(np.uint8)[..., None], 3, axis=2)
+    raise ValueError(kind)
+
+
 def sal_filter_cases():
     return OrderedDict(
         clusters=dict(seed=31, n=300, j=19, al_num=20, pseudo_num=40, clusters=10, thr=7, use_clusters=True, pseudo_done=15),

@@ -286,17 +286,33 @@ def test_preprocess_restatement_vs_reference_golden(name):
 
 def test_lanczos_restatement_vs_pillow():
     """The third-party resampler the reference calls (PIL.Image.resize, LANCZOS) is present here: the
-    restatement is pinned against it directly, down- and up-scaling, odd sizes."""
+    restatement is pinned against it directly, down- and up-scaling, odd sizes.
+
+    The second group of sizes is what tests/test_gpu_preprocess_edges.py asks of the oracle: the 63-tap downscales (661 -> 64, 496 -> 48,
+    2645 -> 256), scale 1 on one axis only (Pillow skips that pass), 1 / 2 / 3 -> 64, odd and non-multiple-of-64 output widths, portrait
+    and landscape outputs, and the 200 -> 64 / 96 / 300 clamp cases.  Every size runs on noise and on the two pattern images whose sums
+    leave 0..255 before the clamp (cases.resample_image), so the clamp of the restatement is pinned as well."""
     PIL = pytest.importorskip("PIL")
     from PIL import Image
 
     from oracle import preprocess as opp
 
     rng = np.random.default_rng(0)
-    for (h, w, ow, oh) in [(300, 300, 256, 256), (123, 97, 64, 48), (80, 80, 96, 96), (517, 333, 128, 96)]:
+    sizes = [(300, 300, 256, 256), (123, 97, 64, 48), (80, 80, 96, 96), (517, 333, 128, 96)]
+    for (h, w, ow, oh) in sizes:
         img = rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
         want = np.asarray(Image.fromarray(img).resize((ow, oh), resample=Image.LANCZOS))
         np.testing.assert_array_equal(opp.resize_lanczos_u8(img, ow, oh), want)
+    sizes += [(661, 661, 64, 64), (496, 496, 48, 48), (2645, 2645, 256, 256), (64, 64, 64, 48), (48, 48, 48, 64), (64, 64, 64, 64),
+              (1, 1, 64, 64), (2, 2, 64, 64), (3, 3, 64, 64), (40, 40, 96, 96), (1, 1, 1, 1), (5, 5, 1, 1),
+              (150, 150, 70, 50), (150, 150, 50, 70), (150, 150, 65, 64), (150, 150, 63, 33), (150, 150, 33, 63), (150, 150, 130, 64),
+              (300, 300, 288, 384), (300, 300, 384, 288), (200, 200, 64, 64), (200, 200, 96, 96), (200, 200, 300, 300),
+              (200, 199, 199, 96), (200, 200, 200, 300)]
+    for kind in ("noise", "stripes", "checker"):
+        for (h, w, ow, oh) in sizes:
+            img = cases.resample_image(kind, h, w, seed=h + w)
+            want = np.asarray(Image.fromarray(img).resize((ow, oh), resample=Image.LANCZOS))
+            np.testing.assert_array_equal(opp.resize_lanczos_u8(img, ow, oh), want, err_msg=f"{kind} {w}x{h} -> {ow}x{oh}")
 
 
 @pytest.mark.parametrize("name", list(cases.sal_filter_cases()))

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import Counter
 
 import torch
 
@@ -154,80 +155,130 @@ def _query_op(kind, k, stride, pad, cin, cout, hin, win, hout, wout, **fields):
     return m
 
 
+def _clone(m):
+    """A copy of the MvalOp ``m``."""
+    return MvalOp.from_buffer_copy(m)
+
+
+def _op_array(launch):
+    """Copies of the MvalOps of the list ``launch`` as one ctypes array (what mval_net_create takes)."""
+    return (MvalOp * len(launch))(*launch)
+
+
+def _also_conv(m, which, src):
+    """A fused launch ``m`` also runs the conv of MvalOp ``src`` as its conv number ``which`` (2, 3): the w / scale / shift / bound offsets."""
+    for f in ("w", "scale", "shift", "bound"):
+        setattr(m, f"{f}{which}_off", getattr(src, f + "_off"))
+
+
+def _arena_slots(g, size):
+    """Liveness-based slot reuse: every activation of graph ``g`` but the network input / output gets ``size[id]`` floats from its
+    producer to its last reader; a freed range goes to the best-fitting later activation -> (activation id -> float offset, floats used)."""
+    last_use = {a: i for i, op in enumerate(g.ops) for a in (op.src, op.res1, op.res2) if a is not None}
+    offset, free, top = {}, [], 0  # free: list of (off, size)
+    pending, cur_phase = [], g.ops[0].phase if g.ops else 0
+    for i, op in enumerate(g.ops):
+        if op.phase != cur_phase:
+            # lanes of a phase run concurrently on separate streams: a slot released inside
+            # the phase may only be re-used after the join at the phase change
+            free += pending
+            pending, cur_phase = [], op.phase
+        if op.dst != g.output:
+            need = size[op.dst]
+            best = None
+            for k, (o, s) in enumerate(free):
+                if s >= need and (best is None or s < free[best][1]):
+                    best = k
+            if best is None:
+                offset[op.dst] = top
+                top += need
+            else:
+                o, s = free.pop(best)
+                offset[op.dst] = o
+                if s > need:
+                    free.append((o + need, s - need))
+        for a in {op.src, op.res1, op.res2}:
+            if a is not None and a != g.input and last_use.get(a) == i:
+                pending.append((offset[a], size[a]))
+        # coalesce neighbours
+        free.sort()
+        merged = []
+        for o, s in free:
+            if merged and merged[-1][0] + merged[-1][1] == o:
+                merged[-1] = (merged[-1][0], merged[-1][1] + s)
+            else:
+                merged.append((o, s))
+        free = merged
+    return offset, top
+
+
 class InferencePlan:
     def __init__(self, model, n, h, w, device, sw=None):
-        """sw: the switches the plan is built under (_switches(); default: as the environment sets them now)."""
+        """sw: the switches the plan is built under (_switches(); default: as the environment sets them now).
+
+        The plan is decided by the passes below, one decision each.  THEIR ORDER IS PART OF THE PLAN: arena rows come from the running
+        counter self._amax_top (_take) and parameter floats from self._ptop, so moving a pass, or the order in which one pass hands out
+        rows, moves every later offset.  The passes talk through the ops' fields and these plan attributes: dims / geo (_geometry), _uses
+        (activation -> number of reads), _offset (activation -> arena offset), _row_of (P2: activation -> its n rows), _amax_slot (h2:
+        activation -> its n magnitude rows)."""
         self.model, self.n, self.h, self.w, self.device = model, n, h, w, device
-        sw = self.sw = sw or _switches()
-        direct = sw["MVAL_FORCE_DIRECT"] == "1"  # the all-direct (VALU) plan: the on-device cross-check of the MFMA kernels
-        g = model._graph
-        self.graph = g
-        dims, geo = _geometry(g, h, w)
-        self.out_hw = dims[g.output]
+        self.sw = sw or _switches()
+        g = self.graph = model._graph
+        self.dims, self.geo = _geometry(g, h, w)
+        self.out_hw = self.dims[g.output]
         self.out_channels = g.acts[g.output].channels
-        # ---- arena: liveness-based slot reuse --------------------------------------------------
-        last_use = {}
-        for i, op in enumerate(g.ops):
-            for a in (op.src, op.res1, op.res2):
-                if a is not None:
-                    last_use[a] = i
+        self._uses = Counter(a for op in g.ops for a in (op.src, op.res1, op.res2) if a is not None)
+        self._layout_arena()
+        self._decide_p2()
+        self._choose_algorithms()
+        self._producer_rows()
+        self.graph_ops = self.ops  # one per graph op (what param_jobs index); self.ops becomes the launch list
+        self.ops = self._p2_launch_list() if self.p2 else self._fuse_blocks()
+        self._allocate()
+
+    def _take(self, floats):
+        """``floats`` arena floats behind everything handed out so far -> their offset."""
+        off = self._amax_top
+        self._amax_top += floats
+        return off
+
+    def _fused(self, switch=None):
+        """Fused launches are wanted: MVAL_FUSE_BLOCKS=0 turns every kind off (the on-device cross-check), ``switch``=0 one kind."""
+        return self.sw["MVAL_FUSE_BLOCKS"] != "0" and (switch is None or self.sw[switch] != "0")
+
+    def _layout_arena(self):
+        """Arena slots of the activations.  Reads dims; sets _offset, amax_base and starts _amax_top there: behind the activations lie the
+        max |x| slots (one float each: what the fp16-split convs scale their input by) and what only one plan form needs."""
+        g, n, dims = self.graph, self.n, self.dims
         size = {a.id: _align(n * dims[a.id][0] * dims[a.id][1] * a.channels) for a in g.acts if a.id in dims}
-        offset, free, top = {}, [], 0  # free: list of (off, size)
-        pending, cur_phase = [], g.ops[0].phase if g.ops else 0
-        for i, op in enumerate(g.ops):
-            if op.phase != cur_phase:
-                # lanes of a phase run concurrently on separate streams: a slot released inside
-                # the phase may only be re-used after the join at the phase change
-                free += pending
-                pending, cur_phase = [], op.phase
-            if op.dst != g.output:
-                need = size[op.dst]
-                best = None
-                for k, (o, s) in enumerate(free):
-                    if s >= need and (best is None or s < free[best][1]):
-                        best = k
-                if best is None:
-                    offset[op.dst] = top
-                    top += need
-                else:
-                    o, s = free.pop(best)
-                    offset[op.dst] = o
-                    if s > need:
-                        free.append((o + need, s - need))
-            for a in {op.src, op.res1, op.res2}:
-                if a is not None and a != g.input and last_use.get(a) == i:
-                    pending.append((offset[a], size[a]))
-            # coalesce neighbours
-            free.sort()
-            merged = []
-            for o, s in free:
-                if merged and merged[-1][0] + merged[-1][1] == o:
-                    merged[-1] = (merged[-1][0], merged[-1][1] + s)
-                else:
-                    merged.append((o, s))
-            free = merged
-        # max |x| slots (one float each) behind the activations: what the fp16-split convs scale their input by
+        self._offset, top = _arena_slots(g, size)
         self.amax_base = _align(max(top, 64))
-        # (n rows of AMAX_ROW dwords per activation that an fp16-split conv reads; include/mval_hip.h: MVAL_AMAX_ROW)
         self._amax_top = self.amax_base
-        amax_slot = {}
-        # ---- parameter buffer layout -------------------------------------------------------------
-        lib = _lib.lib()
-        self.ops = (MvalOp * len(g.ops))()
-        self.param_jobs = []  # (op index, packing, w_off, scale_off, shift_off)
-        ptop = 0
-        # P2 plan (csrc/conv_p2.h): every op but the image stem reads and writes fp16-pair planes; all or nothing
-        self.p2 = sw["MVAL_CONV"] == "p2" and not direct and self._p2_covers(lib, g, geo, n, sw)
-        mode = "h2" if sw["MVAL_CONV"] == "p2" else sw["MVAL_CONV"]
-        row_of = {}  # P2: activation id -> float offset of its n rows
+
+    def _decide_p2(self):
+        """P2 plan (csrc/conv_p2.h): every op but the image stem reads and writes fp16-pair planes; all or nothing.  Reads geo and the
+        switches; sets p2 and _row_of: n rows of P2_ROW floats (from _amax_top, in g.acts order) per activation kept in the arena."""
+        g, sw = self.graph, self.sw
+        self.p2 = sw["MVAL_CONV"] == "p2" and sw["MVAL_FORCE_DIRECT"] != "1" and self._p2_covers(_lib.lib(), g, self.geo, self.n, sw)
+        self._row_of = {}
         if self.p2:
             for a in g.acts:
-                if a.id in dims and a.id not in (g.input, g.output):
-                    row_of[a.id] = self._amax_top
-                    self._amax_top += n * P2_ROW
+                if a.id in self.dims and a.id not in (g.input, g.output):
+                    self._row_of[a.id] = self._take(self.n * P2_ROW)
+
+    def _choose_algorithms(self):
+        """Per op: what it is (_fill_op), its algorithm and its parameter layout.  Reads geo, _offset, p2 and the switches; sets ops (one
+        per graph op), their algo, in_amax_off (h2: n rows of AMAX_ROW floats from _amax_top on an activation's first use;
+        include/mval_hip.h: MVAL_AMAX_ROW), w_off / scale_off / shift_off / bound_off (from _ptop), _amax_slot and param_jobs."""
+        g, n, sw, lib = self.graph, self.n, self.sw, _lib.lib()
+        direct = sw["MVAL_FORCE_DIRECT"] == "1"  # the all-direct (VALU) plan: the on-device cross-check of the MFMA kernels
+        mode = "h2" if sw["MVAL_CONV"] == "p2" else sw["MVAL_CONV"]
+        self.ops = (MvalOp * len(g.ops))()
+        self.param_jobs = []  # (op index, packing, w_off, scale_off, shift_off)
+        self._amax_slot, self._ptop = {}, 0
         for i, op in enumerate(g.ops):
             m = self.ops[i]
-            _fill_op(m, g, op, geo[i], offset)
+            _fill_op(m, g, op, self.geo[i], self._offset)
             m.algo, m.no_stem = ALGO_DIRECT, int(direct)
             if not direct and _mfma_ok(op, m.in_nchw) and lib.mval_op_mfma_supported(C.byref(m), C.c_int(n)):
                 m.algo = ALGO_MFMA
@@ -241,49 +292,48 @@ class InferencePlan:
             if self.p2 and op.src != g.input and op.kind != "maxpool":
                 m.algo = ALGO_MFMA_P2
             if m.algo == ALGO_MFMA_H2:
-                if op.src not in amax_slot:
-                    amax_slot[op.src] = self._amax_top
-                    self._amax_top += n * AMAX_ROW
-                m.in_amax_off = amax_slot[op.src]
+                if op.src not in self._amax_slot:
+                    self._amax_slot[op.src] = self._take(n * AMAX_ROW)
+                m.in_amax_off = self._amax_slot[op.src]
             if op.kind in ("conv", "deconv"):
                 pack = _PACK_OF[m.algo]
                 nw = int(lib.mval_packed_weight_floats(C.c_int(pack), C.c_int(op.cout), C.c_int(op.cin), C.c_int(op.k)))
-                m.w_off = ptop
-                ptop += _align(nw)
-                m.scale_off = ptop
-                ptop += _align(op.cout)
-                m.shift_off = ptop
-                ptop += _align(op.cout)
+                sizes = {"w_off": _align(nw), "scale_off": _align(op.cout), "shift_off": _align(op.cout)}
                 if m.algo == ALGO_MFMA_P2 or (self.p2 and op.src == g.input):  # (the stem's bound: the fused P2 stem needs it)
-                    m.bound_off = ptop
-                    ptop += 64
+                    sizes["bound_off"] = 64
+                for field, floats in sizes.items():
+                    setattr(m, field, self._ptop)
+                    self._ptop += floats
                 self.param_jobs.append((i, pack, m.w_off, m.scale_off, m.shift_off))
-        # producers keep max |x| only for tensors an fp16-split conv reads
-        if g.input in amax_slot:
+
+    def _producer_rows(self):
+        """Producers keep max |x| only for tensors an fp16-split conv reads.  Reads _amax_slot; sets the ops' out_amax_off."""
+        g = self.graph
+        if g.input in self._amax_slot:
             raise _lib.MvalError("the network input cannot feed an fp16-split conv (no producer to keep its max |x|)")
         for i, op in enumerate(g.ops):
-            self.ops[i].out_amax_off = amax_slot.get(op.dst, 0)
-        self.graph_ops = self.ops  # one per graph op (what param_jobs index); self.ops becomes the launch list
-        if self.p2:
-            self.ops = self._p2_launch_list(g, n, dims, offset, row_of)
-        else:
-            self.ops = self._fuse_blocks(lib, g, n)
+            self.ops[i].out_amax_off = self._amax_slot.get(op.dst, 0)
+
+    def _allocate(self):
+        """Sizes and allocates the arena and the parameter buffer and hands the launch list to the C-ABI.  Reads _amax_top, _ptop, ops,
+        _row_of; sets arena_floats, param_floats, arena, params, _p2_rows, net."""
+        lib = _lib.lib()
         self.arena_floats = _align(self._amax_top)
-        self.param_floats = max(ptop, 64)
-        self.arena = torch.empty(self.arena_floats, dtype=torch.float32, device=device)
+        self.param_floats = max(self._ptop, 64)
+        self.arena = torch.empty(self.arena_floats, dtype=torch.float32, device=self.device)
         # rows behind the activations start as zeros: P2 rows need it (a partial slot belongs to ONE producing workgroup, the others
         # must read as zero); the [count, partials ...] rows of the h2 kernels then read "no partials" until their producer has run
         self.arena[self.amax_base :].zero_()
-        self.params = torch.zeros(self.param_floats, dtype=torch.float32, device=device)
+        self.params = torch.zeros(self.param_floats, dtype=torch.float32, device=self.device)
         self.param_sig = None
         self._graph, self._graph_failed = None, False
         # P2 plans: (offset of the n rows) of every activation kept in HBM, for the bound-vs-actual check (p2_slack)
-        self._p2_rows = sorted(set(row_of.values())) if self.p2 else []
+        self._p2_rows = sorted(set(self._row_of.values())) if self.p2 else []
         self._slack_pending, self.p2_slack = False, None
         self.net = lib.mval_net_create(self.ops, C.c_int(len(self.ops)))
         if not self.net:
             raise _lib.MvalError("mval_net_create failed: " + lib.mval_last_error().decode())
-        _lib._check(lib.mval_net_set_multi_stream(C.c_void_p(self.net), C.c_int(0 if sw["MVAL_STREAMS"] == "1" else 1)), "mval_net_set_multi_stream")
+        _lib._check(lib.mval_net_set_multi_stream(C.c_void_p(self.net), C.c_int(0 if self.sw["MVAL_STREAMS"] == "1" else 1)), "mval_net_set_multi_stream")
 
     @staticmethod
     def _p2_covers(lib, g, geo, n, sw):
@@ -323,162 +373,144 @@ class InferencePlan:
                 return False
         return stems == 1
 
-    def _p2_launch_list(self, g, n, dims, offset, row_of):
+    def _covered(self, m, algo=ALGO_MFMA_P2):
+        """The ``algo`` kernel of the (fused) launch ``m`` covers its shape at this plan's batch."""
+        return bool(_lib.lib().mval_op_algo_supported(C.byref(m), C.c_int(self.n), C.c_int(algo)))
+
+    def _p2_launch_list(self):
         """Launch list of a P2 plan: the stem conv keeps its fp32 NHWC kernel and writes into a slot of its own, a
         MVAL_OP_TO_P2 launch turns that into planes; every other op is MVAL_ALGO_MFMA_P2 with the rows of its input,
-        residuals and output; BasicBlocks of the 32- / 64-channel branches (hrnet.py:36-52) become ONE MVAL_OP_BLOCK
-        launch (csrc/conv_block_p2.hip; MVAL_FUSE_BLOCKS=0 keeps the pair: the on-device cross-check)."""
-        lib = _lib.lib()
-        fuse = self.sw["MVAL_FUSE_BLOCKS"] != "0"
-        # measured (128 images): 32 channels on 64x64 maps 81 us fused vs 2 x 44 us; 64 channels on 32x32 maps 77 us
-        # fused vs 2 x 33 us -- the two 64-channel convs are no longer HBM-bound one by one, so only the 32-channel
-        # blocks are fused (round 3 measured the fused 64-channel block at 77 us against 2 x 33 for its two P2 convs; 10.38 vs 10.37 ms as a step)
-        fuse_c = {32}
-        fuse_bneck = fuse and self.sw["MVAL_P2_BNECK"] != "0"
-        fuse_up = fuse and self.sw["MVAL_P2_FUSE_UP"] != "0"
-        uses = {}
-        for op in g.ops:
-            for a in (op.src, op.res1, op.res2):
-                if a is not None:
-                    uses[a] = uses.get(a, 0) + 1
-        launch, i = [], 0
-        while i < len(g.ops):
-            op = g.ops[i]
-            m = MvalOp()
-            C.memmove(C.byref(m), C.byref(self.graph_ops[i]), C.sizeof(MvalOp))
-            if op.src == g.input:
-                b = g.ops[i + 1] if i + 1 < len(g.ops) else None
-                if (fuse and self.sw["MVAL_P2_STEM"] != "0" and b is not None and op.kind == b.kind == "conv" and op.k == b.k == 3
-                        and op.stride == b.stride == 2 and op.pad == b.pad == 1 and op.cin == 3 and op.cout == b.cin == b.cout == 64 and op.bn and b.bn
-                        and op.relu and b.relu and b.src == op.dst and uses.get(op.dst, 0) == 1 and b.res1 is None and b.res2 is None
-                        and op.up == b.up == 0 and b.dst != g.output and (op.phase, op.lane) == (b.phase, b.lane)):
-                    # hrnet.py:303-310: both stride-2 stem convs in ONE launch, the 64-channel half-resolution map never leaves the CU
-                    mb = self.graph_ops[i + 1]
-                    st = MvalOp()
-                    C.memmove(C.byref(st), C.byref(m), C.sizeof(MvalOp))
-                    st.kind, st.algo = OP_STEM_P2, ALGO_MFMA_P2
-                    st.hout, st.wout = dims[b.dst]
-                    st.out_off, st.out_amax_off = mb.out_off, row_of[b.dst]
-                    st.in_amax_off = self._amax_top  # rows of the network input: the launch keeps the images' max |x| there
-                    st.w2_off, st.scale2_off, st.shift2_off, st.bound2_off = mb.w_off, mb.scale_off, mb.shift_off, mb.bound_off
-                    if lib.mval_op_algo_supported(C.byref(st), C.c_int(n), C.c_int(ALGO_MFMA_P2)):
-                        self._amax_top += n * P2_ROW
-                        launch.append(st)
-                        i += 2
-                        continue
-                ho, wo = dims[op.dst]
-                stem_floats = _align(n * ho * wo * op.cout)
-                stem_off = self._amax_top  # (behind the rows: only this plan form needs it)
-                self._amax_top += stem_floats
-                stem_rows = self._amax_top
-                self._amax_top += n * AMAX_ROW
-                m.out_off, m.out_amax_off = stem_off, stem_rows
-                launch.append(m)
-                last, src_off, src_rows = op, stem_off, stem_rows
-                b = g.ops[i + 1] if i + 1 < len(g.ops) else None
-                if b is not None and b.kind == "maxpool" and b.src == op.dst:
-                    # pose_resnet.py:35: the max-pool reads the stem's fp32 NHWC output and writes fp32 NHWC (a quarter of the pixels);
-                    # the change to planes follows it (the stem's own rows are not needed then)
-                    mp = MvalOp()
-                    C.memmove(C.byref(mp), C.byref(self.graph_ops[i + 1]), C.sizeof(MvalOp))
-                    hp, wp = dims[b.dst]
-                    mp.in_off = stem_off
-                    mp.out_off = self._amax_top
-                    self._amax_top += _align(n * hp * wp * b.cout)
-                    mp.out_amax_off = self._amax_top
-                    self._amax_top += n * AMAX_ROW
-                    m.out_amax_off = 0
-                    launch[-1] = m
-                    launch.append(mp)
-                    last, src_off, src_rows = b, mp.out_off, mp.out_amax_off
-                    ho, wo = hp, wp
-                    i += 1
-                t = MvalOp()
-                t.kind, t.algo = OP_TO_P2, ALGO_MFMA_P2
-                t.hin, t.win, t.cin, t.hout, t.wout, t.cout = ho, wo, last.cout, ho, wo, last.cout
-                t.in_off, t.in_amax_off = src_off, src_rows
-                t.out_off, t.out_amax_off = offset[last.dst], row_of[last.dst]
-                t.res1_off = t.res2_off = t.w_off = t.scale_off = t.shift_off = -1
-                t.phase, t.lane = m.phase, m.lane
-                launch.append(t)
-                i += 1
-                continue
-            m.in_amax_off = row_of[op.src]
-            m.res1_amax_off = row_of[op.res1] if op.res1 is not None else 0
-            m.res2_amax_off = row_of[op.res2] if op.res2 is not None else 0
-            m.out_amax_off = row_of.get(op.dst, 0)
-            chain = self._up_chain_at(g, i, uses) if fuse_up else None
-            if chain is not None:
-                # hrnet.py:424-447: the consecutive up-sampling terms of a fuse-layer output in ONE launch; the partial sum is read
-                # once and written once instead of once per term
-                last = g.ops[chain[-1]]
-                fu = MvalOp()
-                C.memmove(C.byref(fu), C.byref(m), C.sizeof(MvalOp))
-                fu.kind, fu.relu, fu.up = OP_FUSE_UP, int(last.relu), 0
-                fu.hin, fu.win = fu.hout, fu.wout = dims[last.dst]
-                fu.out_off, fu.out_amax_off = self.graph_ops[chain[-1]].out_off, row_of[last.dst]
-                fu.res1_off, fu.res1_amax_off, fu.res2_off, fu.res2_amax_off = m.res1_off, row_of[op.res1], -1, 0
-                fu.n_terms = len(chain)
-                for j, k in enumerate(chain):
-                    gk, ok_ = self.graph_ops[k], g.ops[k]
-                    fu.t_cin[j], fu.t_up[j] = ok_.cin, ok_.up
-                    fu.t_in_off[j], fu.t_in_amax_off[j] = gk.in_off, row_of[ok_.src]
-                    fu.t_w_off[j], fu.t_scale_off[j], fu.t_shift_off[j], fu.t_bound_off[j] = gk.w_off, gk.scale_off, gk.shift_off, gk.bound_off
-                if lib.mval_op_algo_supported(C.byref(fu), C.c_int(n), C.c_int(ALGO_MFMA_P2)):
-                    launch.append(fu)
-                    i = chain[-1] + 1
-                    continue
-            bn = self._bneck_at(g, i, uses) if fuse_bneck else None
-            if bn is not None:
-                # hrnet.py:75-95 with 64 planes: conv1x1 -> conv3x3 -> conv1x1 (+ residual) in ONE launch; a downsample branch
-                # (1x1 conv of the block's input, emitted between conv2 and conv3) runs first as its own op
-                i2, i3, skip = bn
-                for k in skip:
-                    ms = MvalOp()
-                    C.memmove(C.byref(ms), C.byref(self.graph_ops[k]), C.sizeof(MvalOp))
-                    ks = g.ops[k]
-                    ms.in_amax_off, ms.out_amax_off = row_of[ks.src], row_of[ks.dst]
-                    launch.append(ms)
-                m2, m3, o3 = self.graph_ops[i2], self.graph_ops[i3], g.ops[i3]
-                blk = MvalOp()
-                C.memmove(C.byref(blk), C.byref(m), C.sizeof(MvalOp))
-                blk.kind, blk.cout, blk.relu = OP_BNECK, o3.cout, 1
-                blk.out_off, blk.res1_off, blk.res2_off = m3.out_off, m3.res1_off, -1
-                blk.res1_amax_off, blk.res2_amax_off, blk.out_amax_off = row_of[o3.res1], 0, row_of[o3.dst]
-                blk.w2_off, blk.scale2_off, blk.shift2_off, blk.bound2_off = m2.w_off, m2.scale_off, m2.shift_off, m2.bound_off
-                blk.w3_off, blk.scale3_off, blk.shift3_off, blk.bound3_off = m3.w_off, m3.scale_off, m3.shift_off, m3.bound_off
-                if lib.mval_op_algo_supported(C.byref(blk), C.c_int(n), C.c_int(ALGO_MFMA_P2)):
-                    launch.append(blk)
-                    i = i3 + 1
-                    continue
-                del launch[len(launch) - len(skip):]
-            b = g.ops[i + 1] if i + 1 < len(g.ops) else None
-            if (fuse and b is not None and op.kind == b.kind == "conv" and op.k == b.k == 3 and op.stride == b.stride == 1
-                    and op.cin == op.cout == b.cin == b.cout and op.cin in fuse_c and op.bn and b.bn and op.relu and b.relu and op.res1 is None
-                    and op.res2 is None and op.up == b.up == 0 and b.src == op.dst and b.res1 == op.src and b.res2 is None
-                    and uses.get(op.dst, 0) == 1 and op.dst != g.output and (op.phase, op.lane) == (b.phase, b.lane)):
-                mb = self.graph_ops[i + 1]
-                blk = MvalOp()
-                C.memmove(C.byref(blk), C.byref(m), C.sizeof(MvalOp))
-                blk.kind = OP_BLOCK
-                blk.out_off, blk.res1_off, blk.res2_off = mb.out_off, m.in_off, -1
-                blk.out_amax_off = row_of[b.dst]
-                blk.w2_off, blk.scale2_off, blk.shift2_off, blk.bound2_off = mb.w_off, mb.scale_off, mb.shift_off, mb.bound_off
-                if lib.mval_op_algo_supported(C.byref(blk), C.c_int(n), C.c_int(ALGO_MFMA_P2)):
-                    launch.append(blk)
-                    i += 2
-                    continue
-            launch.append(m)
-            i += 1
-        arr = (MvalOp * len(launch))()
-        for k, m in enumerate(launch):
-            C.memmove(C.byref(arr[k]), C.byref(m), C.sizeof(MvalOp))
-        return arr
+        residuals and output; BasicBlocks of the 32-channel branches (hrnet.py:36-52) become ONE MVAL_OP_BLOCK
+        launch (csrc/conv_block_p2.hip; MVAL_FUSE_BLOCKS=0 keeps the pair: the on-device cross-check).
 
-    @staticmethod
-    def _up_chain_at(g, i, uses):
+        Per graph op the rewrites below are tried in this order; each either appends its launch(es) and returns how many graph ops they
+        stand for, or returns 0 and leaves ``launch`` and _amax_top as it found them.  No rewrite takes it: the op is one launch."""
+        # (_emit_block's defaults: P2 plans fuse only the 32-channel blocks.)  Measured (128 images): 32 channels on 64x64 maps 81 us fused vs
+        # 2 x 44 us; 64 channels on 32x32 maps 77 us fused vs 2 x 33 us -- the two 64-channel convs are no longer HBM-bound one by one
+        # (round 3; 10.38 vs 10.37 ms as a step)
+        rewrites = (self._emit_fused_stem, self._emit_stem, self._emit_up_chain, self._emit_bneck, self._emit_block)
+        launch, i = [], 0
+        while i < len(self.graph_ops):
+            m = self._p2_op(i)
+            for rewrite in rewrites:
+                used = rewrite(launch, i, m)
+                if used:
+                    break
+            else:
+                launch.append(m)
+                used = 1
+            i += used
+        return _op_array(launch)
+
+    def _p2_op(self, k):
+        """Graph op ``k`` as a launch of its own: a copy of its MvalOp with the rows of its input, residuals and output (the stem: none)."""
+        op, m, row_of = self.graph.ops[k], _clone(self.graph_ops[k]), self._row_of
+        if op.src != self.graph.input:
+            m.in_amax_off, m.out_amax_off = row_of[op.src], row_of.get(op.dst, 0)
+            m.res1_amax_off, m.res2_amax_off = (0 if r is None else row_of[r] for r in (op.res1, op.res2))
+        return m
+
+    def _emit_fused_stem(self, launch, i, m):
+        """hrnet.py:303-310: both stride-2 stem convs in ONE launch, the 64-channel half-resolution map never leaves the CU.  Takes the n
+        rows of the network input (the launch keeps the images' max |x| there) only when the kernel covers the size."""
+        g = self.graph
+        op, b = g.ops[i], g.ops[i + 1] if i + 1 < len(g.ops) else None
+        if not (op.src == g.input and self._fused("MVAL_P2_STEM") and b is not None and op.kind == b.kind == "conv" and op.k == b.k == 3
+                and op.stride == b.stride == 2 and op.pad == b.pad == 1 and op.cin == 3 and op.cout == b.cin == b.cout == 64 and op.bn and b.bn
+                and op.relu and b.relu and b.src == op.dst and self._uses[op.dst] == 1 and b.res1 is None and b.res2 is None
+                and op.up == b.up == 0 and b.dst != g.output and (op.phase, op.lane) == (b.phase, b.lane)):
+            return 0
+        mb = self.graph_ops[i + 1]
+        st = _clone(m)
+        st.kind, st.algo = OP_STEM_P2, ALGO_MFMA_P2
+        st.hout, st.wout = self.dims[b.dst]
+        st.out_off, st.out_amax_off = mb.out_off, self._row_of[b.dst]
+        st.in_amax_off = self._amax_top
+        _also_conv(st, 2, mb)
+        if not self._covered(st):
+            return 0
+        self._take(self.n * P2_ROW)
+        launch.append(st)
+        return 2
+
+    def _emit_stem(self, launch, i, m):
+        """The stem conv on its fp32 NHWC kernel [+ pose_resnet.py:35: the max-pool, which reads the stem's fp32 NHWC output and writes fp32
+        NHWC (a quarter of the pixels)] + the change to planes (MVAL_OP_TO_P2).  Slots and magnitude rows of the fp32 maps lie behind the
+        rows (only this plan form needs them), taken as: stem slot, stem rows [, max-pool slot, max-pool rows]."""
+        g, n = self.graph, self.n
+        op, b = g.ops[i], g.ops[i + 1] if i + 1 < len(g.ops) else None
+        if op.src != g.input:
+            return 0
+        ho, wo = self.dims[op.dst]
+        m.out_off = self._take(_align(n * ho * wo * op.cout))
+        m.out_amax_off = self._take(n * AMAX_ROW)
+        last, ml, fp32 = op, m, [m]
+        if b is not None and b.kind == "maxpool" and b.src == op.dst:
+            ho, wo = self.dims[b.dst]
+            mp = _clone(self.graph_ops[i + 1])
+            mp.in_off = m.out_off
+            mp.out_off = self._take(_align(n * ho * wo * b.cout))
+            mp.out_amax_off = self._take(n * AMAX_ROW)
+            m.out_amax_off = 0  # (the change to planes follows the max-pool: the stem's own rows are not needed then)
+            last, ml, fp32 = b, mp, [m, mp]
+        t = MvalOp()
+        t.kind, t.algo = OP_TO_P2, ALGO_MFMA_P2
+        t.hin, t.win, t.cin, t.hout, t.wout, t.cout = ho, wo, last.cout, ho, wo, last.cout
+        t.in_off, t.in_amax_off = ml.out_off, ml.out_amax_off
+        t.out_off, t.out_amax_off = self._offset[last.dst], self._row_of[last.dst]
+        t.res1_off = t.res2_off = t.w_off = t.scale_off = t.shift_off = -1
+        t.phase, t.lane = m.phase, m.lane
+        launch += fp32 + [t]
+        return len(fp32)
+
+    def _emit_up_chain(self, launch, i, m):
+        """hrnet.py:424-447: the consecutive up-sampling terms of a fuse-layer output in ONE launch; the partial sum is read once and
+        written once instead of once per term."""
+        g, row_of = self.graph, self._row_of
+        chain = self._up_chain_at(i) if self._fused("MVAL_P2_FUSE_UP") else None
+        if chain is None:
+            return 0
+        op, last = g.ops[i], g.ops[chain[-1]]
+        fu = _clone(m)
+        fu.kind, fu.relu, fu.up = OP_FUSE_UP, int(last.relu), 0
+        fu.hin, fu.win = fu.hout, fu.wout = self.dims[last.dst]
+        fu.out_off, fu.out_amax_off = self.graph_ops[chain[-1]].out_off, row_of[last.dst]
+        fu.res1_off, fu.res1_amax_off, fu.res2_off, fu.res2_amax_off = m.res1_off, row_of[op.res1], -1, 0
+        fu.n_terms = len(chain)
+        for j, k in enumerate(chain):
+            gk, ok_ = self.graph_ops[k], g.ops[k]
+            fu.t_cin[j], fu.t_up[j] = ok_.cin, ok_.up
+            fu.t_in_off[j], fu.t_in_amax_off[j] = gk.in_off, row_of[ok_.src]
+            fu.t_w_off[j], fu.t_scale_off[j], fu.t_shift_off[j], fu.t_bound_off[j] = gk.w_off, gk.scale_off, gk.shift_off, gk.bound_off
+        if not self._covered(fu):
+            return 0
+        launch.append(fu)
+        return len(chain)
+
+    def _emit_bneck(self, launch, i, m):
+        """hrnet.py:75-95 with 64 planes: conv1x1 -> conv3x3 -> conv1x1 (+ residual) in ONE launch; a downsample branch (1x1 conv of the
+        block's input, emitted between conv2 and conv3) runs first as its own op."""
+        g, row_of = self.graph, self._row_of
+        bn = self._bneck_at(i) if self._fused("MVAL_P2_BNECK") else None
+        if bn is None:
+            return 0
+        i2, i3, skip = bn
+        m3, o3 = self.graph_ops[i3], g.ops[i3]
+        blk = _clone(m)
+        blk.kind, blk.cout, blk.relu = OP_BNECK, o3.cout, 1
+        blk.out_off, blk.res1_off, blk.res2_off = m3.out_off, m3.res1_off, -1
+        blk.res1_amax_off, blk.res2_amax_off, blk.out_amax_off = row_of[o3.res1], 0, row_of[o3.dst]
+        _also_conv(blk, 2, self.graph_ops[i2])
+        _also_conv(blk, 3, m3)
+        if not self._covered(blk):
+            return 0
+        launch += [self._p2_op(k) for k in skip] + [blk]
+        return i3 + 1 - i
+
+    def _up_chain_at(self, i):
         """Ops i, i + 1 [, i + 2] are the consecutive up-sampling 1x1 terms of one fuse-layer output (each adds to the previous one's
         result, only the last may have the ReLU) -> their indices, else None."""
+        g, uses = self.graph, self._uses
         chain = []
         k = i
         while k < len(g.ops) and len(chain) < 3:
@@ -495,10 +527,10 @@ class InferencePlan:
             k += 1
         return chain if len(chain) >= 2 else None
 
-    @staticmethod
-    def _bneck_at(g, i, uses):
+    def _bneck_at(self, i):
         """Ops i .. of the graph form a Bottleneck with 64 planes the fused P2 kernel covers -> (index of conv2, index of conv3,
         indices of ops in between that must run first: the downsample branch), else None."""
+        g, uses = self.graph, self._uses
         a = g.ops[i]
         if not (a.kind == "conv" and a.k == 1 and a.stride == 1 and a.cout == 64 and a.cin in (64, 256) and a.bn and a.relu
                 and a.res1 is None and a.res2 is None and a.up == 0 and uses.get(a.dst, 0) == 1 and i + 2 < len(g.ops)):
@@ -524,45 +556,41 @@ class InferencePlan:
             return None
         return i + 1, j, skip
 
-    def _fuse_blocks(self, lib, g, n):
-        """Launch list: every BasicBlock of the 32- / 64-channel branches (conv3x3+BN+ReLU -> conv3x3+BN+residual+ReLU,
-        hrnet.py:36-52) whose two convs run on the fp16-split kernels becomes ONE MVAL_OP_BLOCK launch
-        (csrc/conv_block.hip); everything else is launched op by op.  MVAL_FUSE_BLOCKS=0 keeps the unfused pair (the
-        on-device cross-check of the fused kernel, tests/test_gpu_models.py)."""
-        fuse = self.sw["MVAL_FUSE_BLOCKS"] != "0"
-        uses = {}
-        for op in g.ops:
-            for a in (op.src, op.res1, op.res2):
-                if a is not None:
-                    uses[a] = uses.get(a, 0) + 1
+    def _emit_block(self, launch, i, ma, channels=frozenset({32}), algo=ALGO_MFMA_P2):
+        """Ops i, i + 1 are a BasicBlock (conv3x3+BN+ReLU -> conv3x3+BN+residual+ReLU, hrnet.py:36-52) of one of ``channels`` whose two
+        convs run as ``algo``: ONE MVAL_OP_BLOCK launch (csrc/conv_block_p2.hip, conv_block.hip) made from ``ma``, the first conv's
+        MvalOp.  (pad 1 holds for every 3x3 conv of a P2 plan too: _p2_covers asked mval_op_algo_supported, which wants pad == k / 2.)"""
+        g = self.graph
+        if not self._fused() or i + 1 >= len(g.ops):
+            return 0
+        a, b, mb = g.ops[i], g.ops[i + 1], self.graph_ops[i + 1]
+        if not (a.kind == b.kind == "conv" and a.k == b.k == 3 and a.stride == b.stride == 1 and a.pad == b.pad == 1
+                and a.cin == a.cout == b.cin == b.cout and a.cin in channels and a.bn and b.bn and a.relu and b.relu
+                and a.res1 is None and a.res2 is None and a.up == b.up == 0 and b.src == a.dst and b.res1 == a.src and b.res2 is None
+                and self._uses[a.dst] == 1 and a.dst != g.output and (a.phase, a.lane) == (b.phase, b.lane)
+                and ma.algo == mb.algo == algo):
+            return 0
+        blk = _clone(ma)
+        blk.kind = OP_BLOCK
+        blk.out_off, blk.res1_off, blk.res2_off = mb.out_off, ma.in_off, -1
+        blk.out_amax_off = self._row_of[b.dst] if self.p2 else mb.out_amax_off
+        _also_conv(blk, 2, mb)
+        if not self._covered(blk, algo):
+            return 0
+        launch.append(blk)
+        return 2
+
+    def _fuse_blocks(self):
+        """Launch list of an h2 plan: every BasicBlock of the 32- / 48- / 64-channel branches whose two convs run on the fp16-split kernels
+        becomes ONE launch (_emit_block); everything else is launched op by op.  MVAL_FUSE_BLOCKS=0 keeps the unfused pair (the on-device
+        cross-check of the fused kernel, tests/test_gpu_models.py)."""
         launch, i = [], 0
-        while i < len(g.ops):
-            a = g.ops[i]
-            b = g.ops[i + 1] if i + 1 < len(g.ops) else None
-            ma = self.graph_ops[i]
-            if (fuse and b is not None and a.kind == b.kind == "conv" and a.k == b.k == 3 and a.stride == b.stride == 1
-                    and a.pad == b.pad == 1 and a.cin == a.cout == b.cin == b.cout and a.cin in (32, 48, 64) and a.bn and b.bn
-                    and a.relu and b.relu and a.res1 is None and a.res2 is None and a.up == b.up == 0 and b.src == a.dst
-                    and b.res1 == a.src and b.res2 is None and uses.get(a.dst, 0) == 1 and a.dst != g.output
-                    and (a.phase, a.lane) == (b.phase, b.lane)
-                    and ma.algo == self.graph_ops[i + 1].algo == ALGO_MFMA_H2):
-                mb = self.graph_ops[i + 1]
-                blk = MvalOp()
-                C.memmove(C.byref(blk), C.byref(ma), C.sizeof(MvalOp))
-                blk.kind = OP_BLOCK
-                blk.out_off, blk.res1_off, blk.res2_off = mb.out_off, ma.in_off, -1
-                blk.out_amax_off = mb.out_amax_off
-                blk.w2_off, blk.scale2_off, blk.shift2_off = mb.w_off, mb.scale_off, mb.shift_off
-                if lib.mval_op_algo_supported(C.byref(blk), C.c_int(n), C.c_int(ALGO_MFMA_H2)):
-                    launch.append(blk)
-                    i += 2
-                    continue
-            launch.append(ma)
-            i += 1
-        arr = (MvalOp * len(launch))()
-        for k, m in enumerate(launch):
-            C.memmove(C.byref(arr[k]), C.byref(m), C.sizeof(MvalOp))
-        return arr
+        while i < len(self.graph_ops):
+            used = self._emit_block(launch, i, self.graph_ops[i], {32, 48, 64}, ALGO_MFMA_H2)
+            if not used:
+                launch.append(self.graph_ops[i])
+            i += used or 1
+        return _op_array(launch)
 
     def __del__(self):
         try:
@@ -617,10 +645,10 @@ class InferencePlan:
                     # ConvTranspose2d weights are (cin, cout, 4, 4) and an output pixel of parity (py, px) sees the taps ky in {3 - py, 1 - py},
                     # kx alike (conv_mfma_split.hip pack mode 3): per cout the largest of the four parities' sums
                     wa = w.abs().double()
-                    sw = torch.stack([wa[:, :, [3 - py, 1 - py]][:, :, :, [3 - px, 1 - px]].sum(dim=(0, 2, 3)) for py in (0, 1) for px in (0, 1)]).max(dim=0).values
+                    wsum = torch.stack([wa[:, :, [3 - py, 1 - py]][:, :, :, [3 - px, 1 - px]].sum(dim=(0, 2, 3)) for py in (0, 1) for px in (0, 1)]).max(dim=0).values
                 else:
-                    sw = w.abs().double().sum(dim=(1, 2, 3))
-                a_ = (sw * self.params[s_off : s_off + op.cout].abs().double()).max() * (1.0 + 1e-6)
+                    wsum = w.abs().double().sum(dim=(1, 2, 3))
+                a_ = (wsum * self.params[s_off : s_off + op.cout].abs().double()).max() * (1.0 + 1e-6)
                 b_ = self.params[b_off : b_off + op.cout].abs().double().max()
                 self.params[gm.bound_off : gm.bound_off + 2] = torch.stack([a_, b_]).to(torch.float32)
         self.param_sig = sig

@@ -27,6 +27,9 @@ TRAIN_ATTRS = ("arena_floats", "param_floats", "n_lanes", "segments", "zero_slot
 INFER_ATTRS = ("param_jobs", "arena_floats", "param_floats", "amax_base", "_p2_rows", "p2")
 SIZES = (("hrnet_w32", (128, 256, 256)), ("hrnet_w32", (32, 256, 256)), ("hrnet_w32", (2, 64, 64)), ("hrnet_w48", (8, 384, 288)),
          ("resnet50", (32, 256, 192)), ("resnet50", (8, 256, 192)))
+# inference plans only: a non-square size whose 1/32-resolution map is 6 columns wide, a one-image batch, and PoseResNet at 64 images
+# (from 32 images on its transposed convs are P2-eligible: the stem + max-pool + MVAL_OP_TO_P2 form)
+INFER_SIZES = (("hrnet_w32", (8, 256, 192)), ("hrnet_w32", (1, 256, 256)), ("resnet50", (64, 256, 192)))
 TRAIN_OTHER = {"MVAL_CONV": ("h2", "bf3", "fp32"), "MVAL_FORCE_DIRECT": ("1",), "MVAL_TRAIN_LANES": ("0", "1", "2")}  # every other switch: ("0",)
 INFER_OTHER = {"MVAL_CONV": ("h2", "bf3", "fp32"), "MVAL_FORCE_DIRECT": ("1",), "MVAL_STREAMS": ("1",), "MVAL_P2": ("0", "force")}
 
@@ -79,10 +82,10 @@ def main():
     cpu = torch.device("cpu")
     models = {}
     cases, t_all = 0, time.time()
-    for arch, (n, hh, ww) in SIZES:
+    for arch, (n, hh, ww) in SIZES + INFER_SIZES:
         m = models.get(arch) or models.setdefault(arch, model(arch))
         todo = []
-        if what in ("train", "all"):
+        if what in ("train", "all") and (arch, (n, hh, ww)) in SIZES:
             base = engine._switches(engine_train._SWITCHES)
             todo += [("train", dict(base, **v), v, p2) for v in variants(base, TRAIN_OTHER) for p2 in (True, False)]
         if what in ("infer", "all"):

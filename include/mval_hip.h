@@ -150,6 +150,39 @@ int mval_prepare_views(const mval_view_desc* views, int n_views, int max_crop_h,
  * out [n][h][w] f32 = (float) exp(-((x - px)^2 + (y - py)^2) / (2 sigma^2)) evaluated in float64. */
 int mval_gt_heatmaps(const double* pt, int64_t n, double sigma, int h, int w, float* out, void* stream);
 
+/* The training split (dataset.py:212-213): resize to uint8, RandAugment (dataset/augmentation.py), then the normalisation.
+ *
+ * mval_resize_views_u8: mval_prepare_views up to the resized BYTES: out [n_views][in_h][in_w][3] u8 in the reference's channel order
+ * (position 0 = blue: the image Pillow is handed).  Same views, limits and workspace (mval_prepare_views_workspace_bytes) as
+ * mval_prepare_views; mval_normalize_views_u8 of its output gives mval_prepare_views' output bit for bit. */
+int mval_resize_views_u8(const mval_view_desc* views, int n_views, int max_crop_h, int max_crop_w, int in_w, int in_h,
+                         uint8_t* out, void* ws, void* stream);
+/* normalize_image (utils/triangulation.py:137-145): img [n_views][h][w][3] u8 -> out [n_views][3][h][w] f32 = (float)((img / 255.0 - mean[ch]) /
+ * std[ch]) evaluated in float64 per channel POSITION. */
+int mval_normalize_views_u8(const uint8_t* img, int n_views, int h, int w, float* out, void* stream);
+
+/* One op of a view's RandAugment list.  Every op is Pillow's (12.2.0), on channel positions, bit for bit:
+ *   AUTOCONTRAST ImageOps.autocontrast    EQUALIZE ImageOps.equalize    INVERT ImageOps.invert
+ *   POSTERIZE    ImageOps.posterize(max(1, int(p[0])))                  SOLARIZE ImageOps.solarize(threshold p[0])
+ *   COLOR / CONTRAST / BRIGHTNESS / SHARPNESS   ImageEnhance.<op>(img).enhance(p[0])
+ *   ROTATE       Image.rotate(angle, BICUBIC): p[0..5] = the affine coefficients Pillow builds on the host (output pixel centre -> input
+ *                position: xin = p0 (x + 0.5) + p1 (y + 0.5) + p2, yin = p3 (x + 0.5) + p4 (y + 0.5) + p5); an angle that is 0 mod 360 is NONE
+ *   NONE         the view is left as it is at this step */
+enum { MVAL_AUG_NONE = 0, MVAL_AUG_AUTOCONTRAST = 1, MVAL_AUG_EQUALIZE = 2, MVAL_AUG_INVERT = 3, MVAL_AUG_POSTERIZE = 4, MVAL_AUG_SOLARIZE = 5,
+       MVAL_AUG_COLOR = 6, MVAL_AUG_CONTRAST = 7, MVAL_AUG_BRIGHTNESS = 8, MVAL_AUG_SHARPNESS = 9, MVAL_AUG_ROTATE = 10 };
+typedef struct mval_aug_op {
+  int32_t kind;
+  int32_t reserved;
+  double p[6];
+} mval_aug_op;
+/* ws >= mval_augment_views_workspace_bytes(n_views, h, w) (0 for a non-positive argument). */
+size_t mval_augment_views_workspace_bytes(int n_views, int h, int w);
+/* In place on img [n_views][h][w][3] u8: view v runs ops[v][0], ops[v][1], ... ops[v][n_steps - 1] (ops: DEVICE array [n_views][n_steps]).
+ * step_kinds: HOST array [n_steps]; bit MVAL_AUG_<kind> of entry k set iff some view runs that kind at step k -- it decides which passes are
+ * launched (at most seven per step, whatever n_views is); a kind present on the device but missing there is skipped. */
+int mval_augment_views(uint8_t* img, const mval_aug_op* ops, const uint32_t* step_kinds, int n_views, int n_steps, int h, int w,
+                       void* ws, void* stream);
+
 /* utils/evaluation.py:198-208 compute_mkpe over S samples: pred [S,J,3] f32, gt [S,gt_rows,J]
  * f32 (rows 0..2 used), valid [S,J] f32 ; out [1] f32 = mean_j (sum_s d_sj / sum_s valid_sj) ;
  * per_sample [S] f32 = the same metric evaluated on each sample alone (strategy.py:1134). */

@@ -294,6 +294,57 @@ extern "C" int mval_prepare_views(const mval_view_desc* views, int n_views, int 
   return 0;
 }
 
+// The vertical pass that stops at the resized BYTES, for the training split (RandAugment runs on the uint8 image between the resize and the
+// normalisation: csrc/augment.hip): out [v][yy][xx][c] u8 in the reference's channel order, c = 2 - raw channel.  One thread per output pixel.
+__global__ __launch_bounds__(256) void pp_vertical_u8_kernel(const mval_view_desc* __restrict__ views, int in_w, int in_h,
+                                                             const PpCoeff* __restrict__ co, const unsigned char* __restrict__ tmp,
+                                                             unsigned char* __restrict__ out) {
+  const int v = blockIdx.z;
+  const mval_view_desc d = views[v];
+  const int yy = blockIdx.y * blockDim.y + threadIdx.y, xx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (yy >= in_h || xx >= in_w) return;
+  const int omax = max(in_w, in_h);
+  const PpCoeff& c = co[(v * 2 + 1) * omax + yy];
+  int s[3] = {1 << (PP_BITS - 1), 1 << (PP_BITS - 1), 1 << (PP_BITS - 1)};
+  const unsigned char* col = tmp + d.tmp_off + (int64_t)xx * 3;
+  for (int t = 0; t < c.n; t++) {
+    const unsigned char* px = col + (int64_t)(c.lo + t) * in_w * 3;
+    const int k = c.k[t];
+    s[0] += px[0] * k;
+    s[1] += px[1] * k;
+    s[2] += px[2] * k;
+  }
+  unsigned char* o = out + (((int64_t)v * in_h + yy) * in_w + xx) * 3;
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) o[ch] = (unsigned char)pp_clip8(s[2 - ch]);
+}
+
+// mval_prepare_views with pp_vertical_u8_kernel as the last pass (same checks, same workspace; the table's 3 KB stay unused)
+extern "C" int mval_resize_views_u8(const mval_view_desc* views, int n_views, int max_crop_h, int max_crop_w, int in_w, int in_h,
+                                    uint8_t* out, void* ws, void* stream) {
+  MVAL_REQUIRE(views && out && ws && n_views > 0 && in_w > 0 && in_h > 0 && max_crop_h > 0 && max_crop_w > 0,
+               "mval_resize_views_u8: bad arguments");
+  const double sx = (double)max_crop_w / in_w, sy = (double)max_crop_h / in_h;
+  const double smax = sx > sy ? sx : sy;
+  MVAL_REQUIRE((int)ceil(3.0 * (smax < 1.0 ? 1.0 : smax)) * 2 + 1 <= PP_KMAX,
+               "mval_resize_views_u8: a %d x %d box needs more than %d filter taps for a %d x %d input", max_crop_w, max_crop_h,
+               PP_KMAX, in_w, in_h);
+  hipStream_t s = mval_stream(stream);
+  const int omax = in_w > in_h ? in_w : in_h;
+  char* ws1 = reinterpret_cast<char*>(ws) + 3 * 256 * sizeof(float);
+  PpCoeff* co = reinterpret_cast<PpCoeff*>(ws1);
+  unsigned char* tmp = reinterpret_cast<unsigned char*>(ws1) + (((size_t)n_views * 2 * omax * sizeof(PpCoeff) + 255) & ~(size_t)255);
+  const int nco = n_views * 2 * omax;
+  hipLaunchKernelGGL(pp_coeff_kernel, dim3((nco + 127) / 128), dim3(128), 0, s, views, n_views, in_w, in_h, co);
+  MVAL_CHECK_LAUNCH("mval_resize_views_u8/coeff");
+  hipLaunchKernelGGL(pp_horizontal_lds_kernel, dim3((in_w + 63) / 64, (max_crop_h + PP_HROWS - 1) / PP_HROWS, n_views), dim3(64, 4), 0, s, views,
+                     in_w, in_h, co, tmp);
+  MVAL_CHECK_LAUNCH("mval_resize_views_u8/horizontal");
+  hipLaunchKernelGGL(pp_vertical_u8_kernel, dim3((in_w + 63) / 64, (in_h + 3) / 4, n_views), dim3(64, 4), 0, s, views, in_w, in_h, co, tmp, out);
+  MVAL_CHECK_LAUNCH("mval_resize_views_u8/vertical");
+  return 0;
+}
+
 // Gaussian ground-truth heat-maps (dataset.py:198-207): pt [n, 2] float64 in heat-map pixels ->
 // out [n, h, w] float32 = (float) exp(-((x - px)^2 + (y - py)^2) / (2 sigma^2)), all in float64.
 __global__ void pp_gt_heatmap_kernel(const double* __restrict__ pt, double two_s2, int h, int w, int64_t total,

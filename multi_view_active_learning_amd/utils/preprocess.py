@@ -1,10 +1,12 @@
 """Per-view input pipeline on the device: the reference's ``ActiveLearningDataset.prepare_single_view``
-(dataset/dataset.py:158-220; "val"/"test" split, i.e. without RandAugment) for a batch of views.
+(dataset/dataset.py:158-220) for a batch of views: the "val"/"test" split by default, the "train" split with a
+``utils.augmentation.RandAugment`` (resize to uint8, the augmentation's Pillow ops on the device, then the normalisation).
 
 Host (numpy float64, the reference's own arithmetic): square / scaled box (utils/triangulation.py:96-134),
 camera update after crop and resize (:44-67), projection of the 3-D joints (:153-165, 433-484).
 Device (csrc/preprocess.hip): BGR flip, zero-filled crop, PIL LANCZOS resize (bit-exact with Pillow's
-8-bit resampler), ImageNet normalisation, Gaussian ground-truth heat-maps.  JPEG decode stays outside.
+8-bit resampler), ImageNet normalisation, Gaussian ground-truth heat-maps; csrc/augment.hip: RandAugment.  JPEG decode stays
+outside.
 """
 from __future__ import annotations
 
@@ -92,11 +94,10 @@ def _upload_descs(raw: bytes, dev):
     return out
 
 
-def resize_views(images, boxes, in_w, in_h):
-    """Pixel half of prepare_single_view for a list of decoded RGB images (uint8 HIP tensors (h0, w0, 3)) and
-    their SQUARE boxes: (V, 3, in_h, in_w) float32 on the device (BGR order, ImageNet-normalised)."""
+def _resize(images, boxes, in_w, in_h, as_u8):
+    what = "resize_views_u8" if as_u8 else "resize_views"
     if not images or any((not torch.is_tensor(im)) or (not im.is_cuda) or im.dtype != torch.uint8 for im in images):
-        raise _lib.MvalError("resize_views: images must be uint8 HIP tensors (h0, w0, 3)")
+        raise _lib.MvalError(what + ": images must be uint8 HIP tensors (h0, w0, 3)")
     dev = images[0].device
     images = [im.contiguous() for im in images]
     descs = (_ViewDesc * len(images))()
@@ -104,7 +105,7 @@ def resize_views(images, boxes, in_w, in_h):
     for d, im, b in zip(descs, images, boxes):
         left, top, right, bottom = (int(v) for v in b)
         if right <= left or bottom <= top:
-            raise ValueError("resize_views: empty box %r" % (b,))
+            raise ValueError(what + ": empty box %r" % (b,))
         d.img, d.h0, d.w0 = im.data_ptr(), im.shape[0], im.shape[1]
         d.left, d.top, d.right, d.bottom = left, top, right, bottom
         d.tmp_off = rows * in_w * 3
@@ -114,12 +115,42 @@ def resize_views(images, boxes, in_w, in_h):
     ws = torch.empty(int(lib.mval_prepare_views_workspace_bytes(C.c_int(len(images)), C.c_int64(rows), C.c_int(in_w), C.c_int(in_h))),
                      dtype=torch.uint8, device=dev)
     dd = _upload_descs(bytes(descs), dev)
-    out = torch.empty((len(images), 3, in_h, in_w), dtype=torch.float32, device=dev)
+    if as_u8:
+        out = torch.empty((len(images), in_h, in_w, 3), dtype=torch.uint8, device=dev)
+        fn, name = lib.mval_resize_views_u8, "mval_resize_views_u8"
+    else:
+        out = torch.empty((len(images), 3, in_h, in_w), dtype=torch.float32, device=dev)
+        fn, name = lib.mval_prepare_views, "mval_prepare_views"
     _lib._check(
-        lib.mval_prepare_views(_lib._p(dd), C.c_int(len(images)), C.c_int(max(d.bottom - d.top for d in descs)),
-                               C.c_int(max(d.right - d.left for d in descs)), C.c_int(in_w), C.c_int(in_h), _lib._p(out),
-                               _lib._p(ws), _lib._stream()),
-        "mval_prepare_views")
+        fn(_lib._p(dd), C.c_int(len(images)), C.c_int(max(d.bottom - d.top for d in descs)),
+           C.c_int(max(d.right - d.left for d in descs)), C.c_int(in_w), C.c_int(in_h), _lib._p(out),
+           _lib._p(ws), _lib._stream()),
+        name)
+    return out
+
+
+def resize_views(images, boxes, in_w, in_h):
+    """Pixel half of prepare_single_view for a list of decoded RGB images (uint8 HIP tensors (h0, w0, 3)) and
+    their SQUARE boxes: (V, 3, in_h, in_w) float32 on the device (BGR order, ImageNet-normalised)."""
+    return _resize(images, boxes, in_w, in_h, False)
+
+
+def resize_views_u8(images, boxes, in_w, in_h):
+    """resize_views up to the resized bytes: (V, in_h, in_w, 3) uint8 on the device in the reference's channel order (BGR),
+    the image the training split hands to its augmentation.  normalize_views_u8 of it equals resize_views bit for bit."""
+    return _resize(images, boxes, in_w, in_h, True)
+
+
+def normalize_views_u8(images_u8):
+    """normalize_image (utils/triangulation.py:137-145): (V, H, W, 3) uint8 HIP tensor -> (V, 3, H, W) float32."""
+    if (not torch.is_tensor(images_u8)) or (not images_u8.is_cuda) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 \
+            or images_u8.shape[3] != 3:
+        raise _lib.MvalError("normalize_views_u8: images must be a uint8 HIP tensor (V, H, W, 3)")
+    images_u8 = images_u8.contiguous()
+    v, h, w, _ = images_u8.shape
+    out = torch.empty((v, 3, h, w), dtype=torch.float32, device=images_u8.device)
+    _lib._check(_lib.lib().mval_normalize_views_u8(_lib._p(images_u8), C.c_int(v), C.c_int(h), C.c_int(w), _lib._p(out), _lib._stream()),
+                "mval_normalize_views_u8")
     return out
 
 
@@ -135,12 +166,14 @@ def gt_heatmaps(pt, sigma, h, w):
     return out
 
 
-def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, gt_stride, sigma):
+def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, gt_stride, sigma, augmentation=None):
     """Batch of views of one or more frames: images (list of uint8 HIP tensors (h0, w0, 3) RGB), boxes (list of
     (left, top, right, bottom)), cameras (list of dicts R, t, K, dist), kp_3d ((>=3, J) array, or one per
     view).  Returns the reference's per-view entries stacked over views: images (V,3,H,W) and gt_heatmap
     (V,J,h,w) on the device; proj_matrices (V,3,4) float64, 2d_keypoints / 2d_after_crop (V,J,2) float32,
-    square_box (V,4) float32 on the host."""
+    square_box (V,4) float32 on the host.
+    augmentation: None (the "val"/"test" split), or a utils.augmentation.RandAugment (the "train" split, dataset.py:212-213): its ops are drawn
+    per view in order and run on the resized uint8 views before the normalisation; gt_heatmap is unchanged (the reference drops the rotated maps)."""
     v = len(images)
     kps = kp_3d if isinstance(kp_3d, (list, tuple)) else [kp_3d] * v
     sq, proj, pts, pts_crop = [], [], [], []
@@ -158,7 +191,10 @@ def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, 
         proj.append(K.dot(np.hstack([R, t])))
         pts.append(_project(K, R, t, cam.get("dist"), skel))
         sq.append(bbox)
-    out_images = resize_views(images, sq, in_w, in_h)
+    if augmentation is None:
+        out_images = resize_views(images, sq, in_w, in_h)
+    else:
+        out_images = normalize_views_u8(augmentation.apply(resize_views_u8(images, sq, in_w, in_h), augmentation.draw(v), inplace=True))
     pt = np.stack(pts)
     hm = gt_heatmaps(torch.from_numpy(pt / gt_stride).to(out_images.device), sigma, in_h // gt_stride, in_w // gt_stride)
     return {

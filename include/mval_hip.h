@@ -70,6 +70,24 @@ int mval_triangulate_ransac(const void* kp2d, int kp_is_f32, const double* proj,
                             double* kp3d, double* joint_err, int32_t* joint_inliers, double* metric,
                             int32_t* inlier_count, int B, int V, int J, double eps, void* stream);
 
+/* The same for rigs of up to 32 views, over an explicit table of view pairs walked IN TABLE ORDER: the winner is the
+ * first table position with the strictly largest inlier set (utils/triangulation.py:299-300).  When C(V,2) exceeds
+ * n_iters the reference shuffles the pair list with python's `random` and keeps the first n_iters (:279-282, from
+ * V = 12 on at the default 64); the host draws those pairs in the reference's order
+ * (utils.triangulation.draw_view_pairs) and the device does the arithmetic.
+ *   pairs [B*J,P,2] u8 (pairs_shared = 0: one table per problem; the rows of an invalid joint are not read) or
+ *   [1,P,2] u8 (pairs_shared = 1: one table for every problem, e.g. all C(V,2) pairs in lexicographic order, which
+ *   gives mval_triangulate_ransac's results bit for bit) ; 1 <= P <= 496 = C(32,2) ; each entry a view index < V
+ *   (a pair naming a view >= V takes no part in the vote; with no usable pair all views are inliers, :303-304).
+ *   2 <= V <= 32 (the inlier mask is 32 bits wide): outside it returns an error and launches nothing.
+ *   Every other argument and output as mval_triangulate_ransac. */
+#define MVAL_PAIRS_MAX_VIEWS 32
+#define MVAL_PAIRS_MAX_PAIRS 496
+int mval_triangulate_ransac_pairs(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                  const uint8_t* pairs, int P, int pairs_shared, double* kp3d, double* joint_err,
+                                  int32_t* joint_inliers, double* metric, int32_t* inlier_count, int B, int V, int J,
+                                  double eps, void* stream);
+
 /* utils/triangulation.py:236-257 _compute_xe: sum over (view, joint) of
  * mean_px (hm - exp(-|grid - kp|^2 / (2 sigma^2)))^2 with kp the reprojection of kp3d
  * (input-pixel units on the heat-map grid, as the reference does).  out [B] f64 ;

@@ -14,9 +14,22 @@
 // no 2n-sized array), then a one-sided Jacobi (Hestenes) iteration on R yields the right
 // singular vector of the smallest singular value to high relative accuracy.  All float64.
 // Latency/ALU-bound; bytes are negligible (V*J*2 ints + V*12 doubles per frame).
+//
+// Two entries.  mval_triangulate_ransac walks all C(V,2) pairs in lexicographic order (V <= 11: C(V,2) <= 64 = the
+// reference's n_iters).  mval_triangulate_ransac_pairs walks an explicit pair table in table order (V <= 32, up to
+// C(32,2) = 496 pairs): the pairs the reference drew from python's RNG (utils/triangulation.py:279-282, drawn on the
+// host by utils.triangulation.draw_view_pairs), or the lexicographic list of a rig whose pairs all fit a larger
+// n_iters.  Up to 64 pairs keep the grouping above; beyond, one wave per problem and lane p takes pairs p, p + 64, ...
+// They share the numeric device functions (r4_*, add_view_rows, dehomogenise, reproj_err, np_pairwise_sum).  The two
+// stages themselves exist TWICE: inline in ransac_dlt_kernel, and as vote_pair / finish_problem for
+// ransac_pairs_kernel -- ransac_dlt_kernel is kept text for text so that the V <= 11 path compiles to the code object
+// it had before the second entry existed.  A fix to one copy of a stage must be made in the other.
 #include "mval_common.h"
 
 #define MAXV 11  // C(11,2) = 55 <= 64 = n_iters: beyond that the reference samples pairs randomly
+static_assert(MVAL_PAIRS_MAX_VIEWS == 32, "the inlier mask is 32 bits wide");
+static_assert(MVAL_PAIRS_MAX_PAIRS == MVAL_PAIRS_MAX_VIEWS * (MVAL_PAIRS_MAX_VIEWS - 1) / 2 && MVAL_PAIRS_MAX_PAIRS < 512,
+              "the reduction key keeps the table position in 9 bits");
 
 struct R4 {
   double r[4][4];  // upper triangular (lower part kept zero)
@@ -224,6 +237,99 @@ __global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ k
   joint_inliers[pr] = n;
 }
 
+// ---- the pair-table entry (ransac_dlt_kernel above stays as it is: its code object does not change) ----------------
+// stage 1 of one lane: triangulate the view pair (a, c) and vote over all V views -> inlier mask (a and c always in it)
+template <typename KP>
+__device__ __forceinline__ unsigned vote_pair(const double* __restrict__ Pb, const KP* __restrict__ kb, int V, int J,
+                                              int a, int c, double eps) {
+  R4 m;
+  r4_zero(m);
+  add_view_rows(m, Pb + a * 12, (double)kb[(int64_t)a * J * 2], (double)kb[(int64_t)a * J * 2 + 1]);
+  add_view_rows(m, Pb + c * 12, (double)kb[(int64_t)c * J * 2], (double)kb[(int64_t)c * J * 2 + 1]);
+  double h[4], X[3];
+  r4_null_vector(m, h);
+  dehomogenise(h, X);
+  unsigned mask = (1u << a) | (1u << c);
+  for (int v = 0; v < V; v++) {
+    double e = reproj_err(Pb + v * 12, X, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
+    if (e < eps) mask |= 1u << v;
+  }
+  return mask;
+}
+
+// stage 2, one lane per problem: final DLT on the sorted inlier views `win`, its mean reprojection error and the count
+template <int NMAX, typename KP>
+__device__ __forceinline__ void finish_problem(const double* __restrict__ Pb, const KP* __restrict__ kb, int V, int J,
+                                               unsigned win, bool is_valid, double* __restrict__ X3,
+                                               double* __restrict__ err_out, int32_t* __restrict__ inl_out) {
+  if (!is_valid) {
+    X3[0] = X3[1] = X3[2] = 0.0;
+    *err_out = 0.0;
+    *inl_out = 0;
+    return;
+  }
+  R4 m;
+  r4_zero(m);
+  for (int v = 0; v < V; v++)
+    if (win >> v & 1) add_view_rows(m, Pb + v * 12, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
+  double h[4], X[3];
+  r4_null_vector(m, h);
+  dehomogenise(h, X);
+  double errs[NMAX];
+  int n = 0;
+  for (int v = 0; v < V; v++)
+    if (win >> v & 1)
+      errs[n++] = reproj_err(Pb + v * 12, X, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
+  X3[0] = X[0];
+  X3[1] = X[1];
+  X3[2] = X[2];
+  *err_out = np_pairwise_sum(errs, n) / (double)n;
+  *inl_out = n;
+}
+
+// The same two stages over an explicit pair table (pairs_stride = P * 2 per problem, 0 for one shared table).  A lane
+// walks its pairs in ascending table position and keeps the first strictly larger set, the butterfly then prefers the
+// lowest position among equal counts: the winner is the first position with the largest set (utils/triangulation.py
+// :299-300).  key = count * 512 + (511 - position) <= 32 * 512 + 511.  An entry that names a view >= V takes no part.
+template <typename KP>
+__global__ __launch_bounds__(64) void ransac_pairs_kernel(const KP* __restrict__ kp2d, const double* __restrict__ proj,
+                                                           const uint8_t* __restrict__ valid,
+                                                           const uint8_t* __restrict__ pairs, int64_t pairs_stride,
+                                                           double* __restrict__ kp3d, double* __restrict__ joint_err,
+                                                           int32_t* __restrict__ joint_inliers, int64_t n_prob, int V,
+                                                           int J, int P, int PG, double eps) {
+  const int lane = threadIdx.x;
+  const int grp = lane / PG, p0 = lane % PG;
+  const int64_t prob = (int64_t)blockIdx.x * (64 / PG) + grp;
+  const bool live = prob < n_prob;
+  const int64_t pr = live ? prob : 0;
+  const int64_t b = pr / J;
+  const int j = (int)(pr % J);
+  const bool is_valid = live && (!valid || valid[b * J + j]);
+  const double* Pb = proj + b * V * 12;
+  const KP* kb = kp2d + (b * V * (int64_t)J + j) * 2;  // + v * J * 2
+  const uint8_t* tab = pairs + pr * pairs_stride;
+
+  int key = -1;
+  unsigned mask = 0;
+  if (is_valid)  // (an invalid joint has no table: the reference skips it before the draw)
+    for (int p = p0; p < P; p += 64) {  // PG < 64 means P <= PG: one trip
+      int a = tab[p * 2], c = tab[p * 2 + 1];
+      if (a >= V || c >= V) continue;
+      unsigned m = vote_pair(Pb, kb, V, J, a, c, eps);
+      int k = __popc(m) * 512 + (511 - p);
+      if ((k >> 9) > (key >> 9)) { key = k; mask = m; }  // key = -1 >> 9 = -1: any set beats none
+    }
+  int best = key;
+  for (int o = PG >> 1; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
+  unsigned win = (key == best) ? mask : 0u;
+  for (int o = PG >> 1; o > 0; o >>= 1) win |= __shfl_xor(win, o, 64);
+
+  if (p0 != 0 || !live) return;
+  if (best < 0) win = (V >= 32) ? 0xffffffffu : ((1u << V) - 1u);  // no usable pair: all views (:303-304)
+  finish_problem<MVAL_PAIRS_MAX_VIEWS>(Pb, kb, V, J, win, is_valid, kp3d + pr * 3, joint_err + pr, joint_inliers + pr);
+}
+
 // per frame: metric = np.mean(errs of valid joints), inlier_count = min (utils/triangulation.py:226,231)
 __global__ void frame_reduce_kernel(const double* __restrict__ joint_err, const int32_t* __restrict__ joint_inliers,
                                     const uint8_t* __restrict__ valid, double* __restrict__ metric,
@@ -264,6 +370,34 @@ extern "C" int mval_triangulate_ransac(const void* kp2d, int kp_is_f32, const do
   hipLaunchKernelGGL(frame_reduce_kernel, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), joint_err,
                      joint_inliers, valid, metric, inlier_count, B, J);
   MVAL_CHECK_LAUNCH("mval_triangulate_ransac/reduce");
+  return 0;
+}
+
+extern "C" int mval_triangulate_ransac_pairs(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                             const uint8_t* pairs, int P, int pairs_shared, double* kp3d,
+                                             double* joint_err, int32_t* joint_inliers, double* metric,
+                                             int32_t* inlier_count, int B, int V, int J, double eps, void* stream) {
+  MVAL_REQUIRE(V >= 2, "mval_triangulate_ransac_pairs: need >= 2 views (reference asserts len(points) >= 2)");
+  MVAL_REQUIRE(V <= MVAL_PAIRS_MAX_VIEWS, "mval_triangulate_ransac_pairs: at most %d views (the inlier mask is 32 bits wide)", MVAL_PAIRS_MAX_VIEWS);
+  MVAL_REQUIRE(pairs && P >= 1 && P <= MVAL_PAIRS_MAX_PAIRS, "mval_triangulate_ransac_pairs: need a pair table of 1..%d pairs", MVAL_PAIRS_MAX_PAIRS);
+  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac_pairs: bad dims");
+  if (B == 0) return 0;
+  int PG = 1;
+  while (PG < P && PG < 64) PG <<= 1;
+  int64_t n_prob = (int64_t)B * J;
+  int per_block = 64 / PG;
+  int64_t stride = pairs_shared ? 0 : (int64_t)P * 2;
+  dim3 grid((unsigned)((n_prob + per_block - 1) / per_block));
+  if (kp_is_f32)
+    hipLaunchKernelGGL(ransac_pairs_kernel<float>, grid, dim3(64), 0, mval_stream(stream), (const float*)kp2d, proj,
+                       valid, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V, J, P, PG, eps);
+  else
+    hipLaunchKernelGGL(ransac_pairs_kernel<int64_t>, grid, dim3(64), 0, mval_stream(stream), (const int64_t*)kp2d, proj,
+                       valid, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V, J, P, PG, eps);
+  MVAL_CHECK_LAUNCH("mval_triangulate_ransac_pairs");
+  hipLaunchKernelGGL(frame_reduce_kernel, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), joint_err,
+                     joint_inliers, valid, metric, inlier_count, B, J);
+  MVAL_CHECK_LAUNCH("mval_triangulate_ransac_pairs/reduce");
   return 0;
 }
 

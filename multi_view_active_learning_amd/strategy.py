@@ -15,6 +15,7 @@ reference's 8 tiny all_gathers per sample (strategy.py:1106-1114).
 from __future__ import annotations
 
 import math
+import random
 from collections import OrderedDict
 from heapq import nlargest
 
@@ -104,7 +105,9 @@ def _stage_batch(dp):
     network is launched, through pinned staging (torch's caching host allocator) with non_blocking copies.  Why: score_batch /
     evaluate_mkpe run inside the side-stream context (parallel.PostStream), and a pageable host -> device copy issued there blocks the
     host until the side stream -- which has just waited for this batch's network -- drains, so the NEXT batch's network could not be
-    enqueued meanwhile.  Returns a shallow copy of ``dp``; host-only runs (no HIP device) get ``dp`` back."""
+    enqueued meanwhile.  A ``joint_valid`` that arrives on the host also stays there as ``joint_valid_host``: the
+    view-pair draw of a rig with more than 11 views (utils.triangulation.draw_view_pairs) reads it, and copying the staged mask back
+    would be such a blocking copy.  Returns a shallow copy of ``dp``; host-only runs (no HIP device) get ``dp`` back."""
     if not torch.cuda.is_available() or not isinstance(dp, dict):
         return dp
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -114,6 +117,8 @@ def _stage_batch(dp):
             continue
         t = torch.as_tensor(dp[k])
         if not t.is_cuda:
+            if k == "joint_valid":
+                out["joint_valid_host"] = t
             t = t.contiguous()
             t = (t if t.is_pinned() else t.pin_memory()).to(dev, non_blocking=True)
         out[k] = t
@@ -224,6 +229,8 @@ class ActiveLearningStrategy:
             hm, dp["proj_matrices"], cfg.POSE_ESTIMATOR.STRIDE, joint_valid,
             cfg.AL.USE_SOFTARGMAX, cfg.AL.USE_REPROJECTION_XE, cfg.AL.REPROJECTION_SIGMA,
             keypoints_2d=None if scored is None else scored[4],
+            pair_rng=random,  # more than n_iters view pairs (12 views on): the reference's draws, frames in batch order
+            valid_joints_host=dp.get("joint_valid_host"),
         )
         pred32 = r["keypoints_3d"].to(torch.float32)  # torch.Tensor(results["keypoints_3d"]) (:1046)
         sal_metric = r["metric"].to(torch.float32).to(torch.float64)  # torch.Tensor([metric]) (:1061)
@@ -340,8 +347,6 @@ class ActiveLearningStrategy:
         (K, 3J) float64 or a fitted ``utils.kmeans.KMeans`` such as ``self.kmeans``, to its root-relative pose -- ONE device launch for all candidates instead of a
         ``kmeans.predict`` per frame) or, without clusters, ``random.sample`` of the best 2 N (python's
         global RNG, exactly like the reference)."""
-        import random
-
         al = set(al_guids)
         done = set(pseudo_label_guids)
         thr = self.al_cfg.SAL.INLIER_THRESHOLD
@@ -390,7 +395,8 @@ class ActiveLearningStrategy:
                 jv = torch.as_tensor(dp["joint_valid"]).reshape(b, j)
                 with post.batch(hm, _lib.argmax_keys_of(hm) if hm.is_cuda else None, dp, jv):
                     r = triangulation.triangulate_batch(hm.reshape(b, -1, j, hh, wh), dp["proj_matrices"],
-                                                        self.al_cfg.POSE_ESTIMATOR.STRIDE, jv)
+                                                        self.al_cfg.POSE_ESTIMATOR.STRIDE, jv, pair_rng=random,
+                                                        valid_joints_host=dp.get("joint_valid_host"))
                     preds.append(r["keypoints_3d"].to(torch.float32))
                     gts.append(torch.as_tensor(dp["3d_keypoints"]).to(hm.device, torch.float32))
                     valids.append(jv.to(hm.device, torch.float32))

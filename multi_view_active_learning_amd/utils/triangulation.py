@@ -6,8 +6,15 @@ reference's utils/triangulation.py (:168-484).
 processes a whole batch of frames with three HIP launches (arg-max decode, pairwise
 RANSAC + DLT, per-frame reduction) instead of V*J device->host syncs and
 J*(C(V,2)+1) LAPACK calls per frame.  float64 geometry, SVD-free (csrc/triangulate.hip).
+
+Rigs with more view pairs than ``n_iters`` (from 12 views on at the default 64): the reference
+shuffles the pair list of every valid joint with python's ``random`` and keeps the first
+``n_iters`` (utils/triangulation.py:279-282).  ``draw_view_pairs`` makes those draws on the host,
+in the reference's order, and the device triangulates the drawn pairs (up to 32 views).
 """
 from __future__ import annotations
+
+import itertools
 
 import numpy as np
 import torch
@@ -29,6 +36,40 @@ def _as_valid_u8(valid, shape, device):
     return v.to(device).contiguous()
 
 
+def draw_view_pairs(valid, V, n_iters, rng):
+    """The view pairs the reference samples for every joint of a batch (utils/triangulation.py:279-282):
+    valid (B, J) -> uint8 ndarray (B, J, P, 2), P = min(n_iters, C(V,2)).
+
+    For b ascending, j ascending, valid joints only (the reference skips an invalid joint before the draw,
+    :210-211), ``rng.shuffle`` permutes a list as long as ``itertools.combinations(range(V), 2)`` and the first
+    ``n_iters`` pairs are kept: ``rng`` (the ``random`` module or a ``random.Random``) is left in the state the
+    reference leaves it in.  The rows of an invalid joint stay zero.  With C(V,2) <= n_iters the reference draws
+    nothing: neither does this, and every row is the lexicographic list."""
+    valid = torch.as_tensor(valid).cpu().numpy() != 0
+    b, j = valid.shape
+    lex = np.array(list(itertools.combinations(range(V), 2)), dtype=np.uint8).reshape(-1, 2)
+    n = len(lex)
+    if n <= n_iters:
+        return np.broadcast_to(lex, (b, j, n, 2)).copy()
+    out = np.zeros((b, j, n_iters, 2), dtype=np.uint8)
+    for bi, ji in zip(*np.nonzero(valid)):  # row-major: b ascending, j ascending
+        order = list(range(n))  # shuffle's draws depend on the length alone
+        rng.shuffle(order)
+        out[bi, ji] = lex[order[:n_iters]]
+    return out
+
+
+_LEX_TABLES = {}  # (V, device) -> (1, C(V,2), 2) uint8: the pair list of a rig whose pairs all fit n_iters
+
+
+def _lexicographic_pairs(v, dev):
+    key = (v, str(dev))
+    if key not in _LEX_TABLES:
+        lex = np.array(list(itertools.combinations(range(v), 2)), dtype=np.uint8).reshape(1, -1, 2)
+        _LEX_TABLES[key] = torch.from_numpy(lex).to(dev)
+    return _LEX_TABLES[key]
+
+
 def triangulate_batch(
     heatmaps,
     proj_matricies,
@@ -41,6 +82,8 @@ def triangulate_batch(
     reprojection_error_epsilon=5,
     mirror_nonsquare_quirk=True,
     keypoints_2d=None,
+    pair_rng=None,
+    valid_joints_host=None,
 ):
     """heatmaps (B,V,J,Hh,Wh) f32 HIP tensor, proj (B,V,3,4), valid (B,J) ->
     dict of HIP tensors: keypoints_3d (B,J,3) f64, keypoints_2d (B,V,J,2) i64|f32,
@@ -52,17 +95,32 @@ def triangulate_batch(
     True reproduces that bit for bit; False uses the geometrically correct width.
 
     ``keypoints_2d``: key-points already decoded from these heat-maps (the fused scoring pass,
-    ``_lib.score_decode_maps``): the decode launch, i.e. a second read of the heat-maps, is skipped."""
+    ``_lib.score_decode_maps``): the decode launch, i.e. a second read of the heat-maps, is skipped.
+
+    ``pair_rng``: with more view pairs than ``n_iters`` the reference samples pairs from python's global
+    ``random``; pass that module (or a ``random.Random``) to draw them here in the reference's order
+    (``draw_view_pairs``: frames in batch order, valid joints ascending).  None raises NotImplementedError
+    there.  Nothing is drawn when all C(V,2) pairs fit ``n_iters``.  At most 32 views.
+
+    ``valid_joints_host``: ``valid_joints`` once more, on the host, for callers that hand the mask in as a device
+    tensor: the draw reads the mask on the host, and copying a device mask back blocks the host on the current
+    stream.  The drawn table goes up through pinned memory without blocking."""
     dev = _device_of(heatmaps)
     if heatmaps.dim() != 5:
         raise ValueError("heatmaps must be (B, V, J, Hh, Wh)")
     b, v, j, hh, wh = heatmaps.shape
     if v < 2:
         raise AssertionError("need at least two views")  # reference: assert len(points) >= 2
-    if v * (v - 1) // 2 > n_iters:
+    if v > _lib.PAIRS_MAX_VIEWS:
+        raise NotImplementedError("at most %d views (got %d): the device's inlier mask is 32 bits wide" % (_lib.PAIRS_MAX_VIEWS, v))
+    sampled = v * (v - 1) // 2 > n_iters
+    if sampled and pair_rng is None:
         raise NotImplementedError(
-            "more view pairs than n_iters: the reference samples pairs from python's global RNG there"
+            "more view pairs than n_iters: the reference samples pairs from python's global RNG there "
+            "(pass pair_rng=random to draw them in its order)"
         )
+    if sampled and n_iters < 1:
+        raise ValueError("n_iters must be at least 1")
     hm = heatmaps.to(torch.float32).contiguous()
     proj = torch.as_tensor(proj_matricies).to(device=dev, dtype=torch.float64).reshape(b, v, 3, 4).contiguous()
     valid = _as_valid_u8(valid_joints, (b, j), dev)
@@ -72,7 +130,16 @@ def triangulate_batch(
         kp2d = _lib.soft_argmax(hm, b * v * j, hh, wh, float(stride)).reshape(b, v, j, 2)
     else:
         kp2d = _lib.argmax_decode(hm, valid, b, v, j, hh, wh, int(stride), hh if mirror_nonsquare_quirk else wh)
-    kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac(kp2d, proj, valid, b, v, j, float(reprojection_error_epsilon))
+    eps = float(reprojection_error_epsilon)
+    if sampled:
+        host_valid = valid_joints_host if valid_joints_host is not None else valid_joints
+        host_valid = torch.ones((b, j)) if host_valid is None else torch.as_tensor(host_valid).reshape(b, j)
+        pairs = torch.from_numpy(draw_view_pairs(host_valid, v, n_iters, pair_rng)).pin_memory().to(dev, non_blocking=True)
+        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs(kp2d, proj, valid, pairs, b, v, j, eps)
+    elif v > 11:  # all pairs, more than the 64 the one-lane-per-pair entry holds
+        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs(kp2d, proj, valid, _lexicographic_pairs(v, dev), b, v, j, eps)
+    else:
+        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac(kp2d, proj, valid, b, v, j, eps)
     if use_reprojection_xe:
         metric = _lib.reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, float(sigma))
     return {
@@ -101,7 +168,11 @@ def triangulation(
     heatmaps (V,J,Hh,Wh), proj (V,3,4), valid (J,) -> {"keypoints_3d": ndarray (J,3) f64,
     "keypoints_2d": ndarray (V,J,2) int64|f32, "metric": float, "inlier_count": int}."""
     if direct_optimization:
-        raise NotImplementedError("direct_optimization (scipy Huber least-squares, off in every reference call site)")
+        raise NotImplementedError(
+            "direct_optimization (scipy Huber least-squares, off in every reference call site): its result is where "
+            "scipy's iteration stops, not a minimum, so there is nothing to hold a device version to"
+        )
+    import random
     r = triangulate_batch(
         heatmaps.unsqueeze(0),
         torch.as_tensor(proj_matricies).unsqueeze(0),
@@ -112,6 +183,7 @@ def triangulation(
         sigma,
         n_iters,
         reprojection_error_epsilon,
+        pair_rng=random,
     )
     inl = int(r["inlier_count"][0].item())
     if inl < 0:

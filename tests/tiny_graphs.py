@@ -1,0 +1,228 @@
+"""Small training graphs for tests/test_train_small_graphs.py: a few fused ops each, built on the same layer-graph IR as HRNet / PoseResNet
+(pose_estimators/graph.py), so that ONE path of the training step -- an operand form of the split weight gradient, the P2 data gradient's
+BatchNorm sums, the parity data gradient, the unfused BatchNorm backward with an upsample, the max-pool and transposed-conv backward -- is
+reached at a chosen shape and checked against float64 autograd far below the whole-network tests' ReLU-flip tolerance.
+
+TinyNet runs a graph on the HIP engine exactly as PoseHighResolutionNet does; graph_forward interprets the same graph in stock torch on the
+CPU (float64 = the truth, float32 = the noise floor of the reference's own arithmetic)."""
+import math
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from multi_view_active_learning_amd.pose_estimators import graph as _graph
+from multi_view_active_learning_amd.pose_estimators import params as _params
+
+BN_MOMENTUM, BN_EPS = 0.1, 1e-5
+OUT_CHANNELS = 5
+
+
+# ---- graph builders: every graph starts with a 3-channel NCHW 3x3 stride-2 conv + BN + ReLU and ends with a biased 1x1 conv to 5 NCHW maps ----
+def _head(g, c):
+    g.input = g.act(3, 1, "nchw")
+    return g.conv(g.input, c, 3, 2, "head", "head_bn", relu=True)
+
+
+def _tail(g, x):
+    g.new_phase()
+    g.output = g.conv(x, OUT_CHANNELS, 1, 1, "final_layer", None, bias=True, layout="nchw")
+    return g
+
+
+def blocks(c):
+    """head, two BasicBlocks (hrnet.py:36-52)."""
+    g = _graph.Graph()
+    x = _head(g, c)
+    x = _graph._basic_block(g, x, "b0")
+    x = _graph._basic_block(g, x, "b1")
+    return _tail(g, x)
+
+
+def bneck(c, planes, stride):
+    """head, one Bottleneck with a projection shortcut (hrnet.py:75-95; the stride on the 3x3 and on the shortcut)."""
+    g = _graph.Graph()
+    x = _head(g, c)
+    x = _graph._bottleneck(g, x, "bn0", planes, stride, downsample=True)
+    return _tail(g, x)
+
+
+def fuse(c0, c1, c2):
+    """head, a transition to three resolutions, then an HRNet fuse layer (hrnet.py:199-287) with two outputs on two lanes of one phase:
+    y0 = relu(x0 + up1(bn(1x1 x1)) + up2(bn(1x1 x2))), y1 = relu(bn(3x3s2 x0) + x1 + up1(bn(1x1 x2))); the net output reads y0 and, through a
+    stride-2 conv whose sum takes y1 as residual, y1."""
+    g = _graph.Graph()
+    x0 = _head(g, c0)
+    g.new_phase()
+    x1 = g.conv(x0, c1, 3, 2, "t1", "t1_bn", relu=True)
+    x2 = g.conv(x1, c2, 3, 2, "t2", "t2_bn", relu=True)
+    g.new_phase()
+    g.cur_lane = 0
+    a = g.conv(x1, c0, 1, 1, "f01", "f01_bn", res1=x0, up=1)
+    y0 = g.conv(x2, c0, 1, 1, "f02", "f02_bn", relu=True, res1=a, up=2)
+    g.cur_lane = 1
+    b = g.conv(x0, c1, 3, 2, "f10", "f10_bn", res1=x1)
+    y1 = g.conv(x2, c1, 1, 1, "f12", "f12_bn", relu=True, res1=b, up=1)
+    g.new_phase()
+    z = g.conv(y1, c0, 1, 1, "m", "m_bn", relu=True, res1=y0, res2=x0, up=1)
+    return _tail(g, z)
+
+
+def deconv(c, cmid, cup):
+    """head, MaxPool2d(3, 2, 1), a 3x3 conv, ConvTranspose2d(k4, s2, p1) + BN + ReLU (pose_resnet.py:35, :69-97)."""
+    g = _graph.Graph()
+    x = _head(g, c)
+    a = g.acts[x]
+    p = g.act(c, a.down * 2)
+    g.ops.append(_graph.Op("maxpool", x, p, c, c, 3, 2, 1))
+    y = g.conv(p, cmid, 3, 1, "c1", "c1_bn", relu=True)
+    d = g.act(cup, g.acts[y].down // 2)
+    g.ops.append(_graph.Op("deconv", y, d, cmid, cup, 4, 2, 1, "up", "up_bn", relu=True))
+    return _tail(g, d)
+
+
+BUILDERS = {"blocks": blocks, "bneck": bneck, "fuse": fuse, "deconv": deconv}
+
+
+# ---- the model on the HIP engine ----
+class TinyNet(nn.Module):
+    """``build(*args)`` fills a graph.Graph; parameters from a seeded generator: gammas uniform in [0.5, 1.5] with random sign, betas
+    N(0, 0.3), conv weights N(0, 1 / sqrt(fan_in)) (the final layer's bias N(0, 0.3) as well)."""
+
+    def __init__(self, build, args, seed):
+        super().__init__()
+        self._graph = build(*args)
+        self._holders = _params.attach_parameters(self, self._graph)
+        rng = np.random.default_rng(seed)
+        f32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float32))
+        with torch.no_grad():
+            for op in self._graph.ops:
+                if op.kind == "maxpool":
+                    continue
+                w = self._holders[op.conv].weight
+                fan_in = op.cin * op.k * op.k
+                w.copy_(f32(rng.standard_normal(tuple(w.shape)) / math.sqrt(fan_in)))
+                if op.bias:
+                    self._holders[op.conv].bias.copy_(f32(rng.standard_normal(op.cout) * 0.3))
+                if op.bn:
+                    bn = self._holders[op.bn]
+                    bn.weight.copy_(f32(rng.uniform(0.5, 1.5, op.cout) * np.where(rng.random(op.cout) < 0.5, -1.0, 1.0)))
+                    bn.bias.copy_(f32(rng.standard_normal(op.cout) * 0.3))
+
+    def forward(self, x):
+        from multi_view_active_learning_amd.engine import run_network
+
+        return run_network(self, x)
+
+
+# ---- the same graph in stock torch ----
+def graph_forward(graph, state_dict, x, dtype, acts=None):
+    """Interprets ``graph`` on the CPU in ``dtype``: F.conv2d / F.conv_transpose2d / F.max_pool2d, F.batch_norm(training=True) (the running
+    statistics of ``state_dict`` are updated in place), nearest F.interpolate for ``up``, residual adds left to right, ReLU.  Tensors of
+    ``state_dict`` are used as they are (leaves that require grad give autograd gradients).  Returns (output NCHW, {op index: pre-activation
+    of that op's ReLU}); ``acts`` (a dict) receives every activation by id."""
+    t = {graph.input: x.to(dtype)}
+    pre = {}
+    for i, op in enumerate(graph.ops):
+        a = t[op.src]
+        if op.kind == "maxpool":
+            y = F.max_pool2d(a, op.k, op.stride, op.pad)
+        else:
+            w = state_dict[op.conv + ".weight"]
+            assert w.dtype == dtype
+            bias = state_dict[op.conv + ".bias"] if op.bias else None
+            if op.kind == "deconv":
+                y = F.conv_transpose2d(a, w, bias, stride=op.stride, padding=op.pad)
+            else:
+                y = F.conv2d(a, w, bias, stride=op.stride, padding=op.pad)
+        if op.bn:
+            y = F.batch_norm(y, state_dict[op.bn + ".running_mean"], state_dict[op.bn + ".running_var"], state_dict[op.bn + ".weight"],
+                             state_dict[op.bn + ".bias"], True, BN_MOMENTUM, BN_EPS)
+        if op.up:
+            y = F.interpolate(y, scale_factor=1 << op.up, mode="nearest")
+        for r in (op.res1, op.res2):
+            if r is not None:
+                y = y + t[r]
+        if op.relu:
+            pre[i] = y
+            y = F.relu(y)
+        t[op.dst] = y
+    if acts is not None:
+        acts.update(t)
+    return t[graph.output], pre
+
+
+class Reference:
+    """One case's CPU side, computed once: float64 and float32 forward + the gradients of sum(out * g) and of sum(out) (the second step's
+    all-ones output gradient), the running statistics after one and after two steps, the ReLU margins and the P2 bound slack."""
+
+    def __init__(self, model, x, g):
+        graph = model._graph
+        self.keys = [k for k, _ in model.named_parameters()]
+        sd0 = {k: v.detach().clone() for k, v in model.state_dict().items()}
+        self.out, self.grad1, self.grad2, self.stats, self.stats2, self.pre, self.acts = {}, {}, {}, {}, {}, {}, {}
+        for dt in (torch.float64, torch.float32):
+            sd = {k: (v.clone().to(dt) if v.dtype.is_floating_point else v.clone()) for k, v in sd0.items()}
+            leaves = [sd[k].requires_grad_(True) for k in self.keys]
+            acts = {}
+            out, pre = graph_forward(graph, sd, x, dt, acts)
+            g1 = torch.autograd.grad((out * g.to(dt)).sum(), leaves, retain_graph=True)
+            g2 = torch.autograd.grad(out.sum(), leaves)
+            self.out[dt] = out.detach()
+            self.grad1[dt] = {k: v.double().numpy() for k, v in zip(self.keys, g1)}
+            self.grad2[dt] = {k: v.double().numpy() for k, v in zip(self.keys, g2)}
+            running = lambda: {k: v.detach().double().numpy().copy() for k, v in sd.items() if k.endswith(("running_mean", "running_var"))}
+            self.stats[dt] = running()
+            with torch.no_grad():  # the second step sees the same batch: the momentum update applied once more
+                graph_forward(graph, sd, x, dt)
+            self.stats2[dt] = running()
+            self.pre[dt] = {i: v.detach() for i, v in pre.items()}
+            self.acts[dt] = {a: v.detach() for a, v in acts.items()}
+        self.sd64 = {k: (v.double() if v.dtype.is_floating_point else v) for k, v in sd0.items()}
+
+    def relu_margins(self):
+        """Per ReLU: min |pre-activation| (float64) / max |float32 - float64| of that tensor.  The comparison is meaningful when no mask can flip
+        within fp32's own error: every ratio above 64."""
+        out = {}
+        for i, p64 in self.pre[torch.float64].items():
+            d = float((self.pre[torch.float32][i].double() - p64).abs().max())
+            out[i] = float(p64.abs().min()) / max(d, 1e-300)
+        return out
+
+    def p2_slack_bits(self, graph, p2_acts, n_images):
+        """b of the default plan's bound: the largest ceil(log2(bound / max |activation|)) over the activations ``p2_acts`` the plan keeps as
+        P2 planes, bound = max_c (|gamma_c| sqrt(M - 1) + |beta_c|) + the residuals' maxima (include/mval_hip.h: the scale rule), in float64."""
+        acts = self.acts[torch.float64]
+        prod = {op.dst: op for op in graph.ops}
+        b = 0
+        for a_ in p2_acts:
+            op = prod[a_]
+            hw = acts[a_].shape[2] * acts[a_].shape[3] >> (2 * op.up)
+            m = n_images * hw
+            bound = float((self.sd64[op.bn + ".weight"].abs() * math.sqrt(m - 1) + self.sd64[op.bn + ".bias"].abs()).max())
+            bound += sum(float(acts[r].abs().max()) for r in (op.res1, op.res2) if r is not None)
+            b = max(b, math.ceil(math.log2(bound / float(acts[a_].abs().max()))))
+        return b
+
+
+def seeded_input(case):
+    """The seeded Gaussian batch (NCHW float32) a case's input starts from (tests/golden/make_small_graph_inputs.py moves it off the ReLUs' zeros)."""
+    n, h, w = case["n"], 2 * case["hw"][0], 2 * case["hw"][1]
+    return torch.randn(n, 3, h, w, generator=torch.Generator().manual_seed(case["seed"]))
+
+
+def wgrad_tile(k, stride, wout, cout):
+    """(k, stride, tw, NT) of the split weight gradient's tile form for a conv (csrc/conv_wgrad_bf3.hip, mval_launch_wgrad_bf3_p2): 16-wide
+    tiles when Wout > 8 and they pad no more columns than 8-wide ones (so Wout 9 .. 16 and 25 .. 32 take 16, Wout <= 8 and 17 .. 24 take 8),
+    NT = 2 cout tiles per wave for 1x1 and for cout > 32."""
+    tw = 16 if (wout > 8 and (wout + 15) // 16 * 16 <= (wout + 7) // 8 * 8) else 8
+    return (k, stride, tw, 2 if (k == 1 or cout > 32) else 1)
+
+
+WGRAD_TILE_FORMS = {(1, 1, 16, 2), (1, 1, 8, 2)} | {(3, s, tw, nt) for s in (1, 2) for tw in (16, 8) for nt in (1, 2)}
+
+
+def rel_l2(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return float(np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-300))

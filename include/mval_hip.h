@@ -258,6 +258,27 @@ int mval_kcenter_select(const double* feat, int64_t n_obs, int D, const int64_t*
                         int n_select, int have_min_dist, double* row_norms, double* min_dist,
                         int64_t* picks, void* ws, void* stream);
 
+/* The distance forms of mval_kcenter_select_metric (sklearn's names: "euclidean"/"l2", "manhattan"/"l1"/"cityblock",
+ * "cosine", "chebyshev"). */
+#define MVAL_KC_EUCLIDEAN 0
+#define MVAL_KC_L1 1
+#define MVAL_KC_COSINE 2
+#define MVAL_KC_CHEBYSHEV 3
+
+/* mval_kcenter_select under another distance: same arguments, same workspace (mval_kcenter_workspace_bytes), same
+ * tie / NaN / empty-set rules.  float64, one accumulator, feature index 0 .. D-1 in that order, nothing contracted to fma:
+ *   MVAL_KC_EUCLIDEAN  forwards to mval_kcenter_select ;
+ *   MVAL_KC_L1         d = sum_k |x_k - c_k| ;
+ *   MVAL_KC_CHEBYSHEV  d = max_k |x_k - c_k| ;
+ *   MVAL_KC_COSINE     sklearn's cosine_distances: every row is divided once by sqrt(sum_k x_k^2) (a norm below
+ *                      10 * DBL_EPSILON, e.g. of a zero row, counts as 1), then d = clip(1 - xh.ch, 0, 2); a row's
+ *                      distance to itself is whatever that rounds to, it is not zeroed.
+ *   row_norms [n_obs] f64: receives the divisors under MVAL_KC_COSINE, is left untouched under L1 / CHEBYSHEV.
+ * Any other metric id fails with a message (mval_last_error). */
+int mval_kcenter_select_metric(int metric, const double* feat, int64_t n_obs, int D, const int64_t* labeled,
+                               int64_t n_labeled, int n_select, int have_min_dist, double* row_norms, double* min_dist,
+                               int64_t* picks, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Heat-map network forward (pose_estimators/hrnet.py:468-501, pose_resnet.py:139-153)
  * ---------------------------------------------------------------------------------- */

@@ -352,9 +352,28 @@ def kcenter_workspace_bytes(n_obs: int, d: int) -> int:
     return int(lib().mval_kcenter_workspace_bytes(C.c_longlong(n_obs), C.c_int(d)))
 
 
-def kcenter_select(feat, labeled_idx, n_select, min_dist=None):
-    """feat (n_obs, D) f64; labeled_idx (L,) int64 or None.  Returns (picks int64 (n_select,),
-    min_dist f64 (n_obs,))."""
+# MVAL_KC_* (include/mval_hip.h): the distance forms of mval_kcenter_select_metric, and sklearn's names for them
+KC_EUCLIDEAN, KC_L1, KC_COSINE, KC_CHEBYSHEV = 0, 1, 2, 3
+KC_METRIC_IDS = {
+    "euclidean": KC_EUCLIDEAN, "l2": KC_EUCLIDEAN,
+    "manhattan": KC_L1, "l1": KC_L1, "cityblock": KC_L1,
+    "cosine": KC_COSINE,
+    "chebyshev": KC_CHEBYSHEV,
+}
+
+
+def kcenter_metric_id(metric) -> int:
+    """The MVAL_KC_* id of one of sklearn's metric names; NotImplementedError (naming the accepted ones) otherwise."""
+    if not isinstance(metric, str) or metric not in KC_METRIC_IDS:
+        raise NotImplementedError(f"core-set metric {metric!r}: accepted are " + ", ".join(repr(k) for k in KC_METRIC_IDS))
+    return KC_METRIC_IDS[metric]
+
+
+def kcenter_select(feat, labeled_idx, n_select, min_dist=None, metric="euclidean"):
+    """feat (n_obs, D) f64; labeled_idx (L,) int64 or None; metric: a name of KC_METRIC_IDS.  Returns (picks int64
+    (n_select,), min_dist f64 (n_obs,)).  "euclidean" / "l2" go to mval_kcenter_select, the others to
+    mval_kcenter_select_metric."""
+    mid = kcenter_metric_id(metric)
     n_obs, d = feat.shape
     dev = feat.device
     picks = torch.empty((n_select,), dtype=torch.int64, device=dev)
@@ -362,15 +381,16 @@ def kcenter_select(feat, labeled_idx, n_select, min_dist=None):
     norms = torch.empty((n_obs,), dtype=torch.float64, device=dev)
     ws = torch.empty((kcenter_workspace_bytes(n_obs, d) // 8 + 1,), dtype=torch.float64, device=dev)
     nl = 0 if labeled_idx is None else int(labeled_idx.numel())
-    _check(
-        lib().mval_kcenter_select(
-            _p(_req(feat, torch.float64, "features")), C.c_longlong(n_obs), C.c_int(d),
-            _p(labeled_idx if nl else None), C.c_longlong(nl), C.c_int(n_select),
-            C.c_int(0 if min_dist is None else 1),
-            _p(norms), _p(md), _p(picks), _p(ws), _stream(),
-        ),
-        "mval_kcenter_select",
+    args = (
+        _p(_req(feat, torch.float64, "features")), C.c_longlong(n_obs), C.c_int(d),
+        _p(labeled_idx if nl else None), C.c_longlong(nl), C.c_int(n_select),
+        C.c_int(0 if min_dist is None else 1),
+        _p(norms), _p(md), _p(picks), _p(ws), _stream(),
     )
+    if mid == KC_EUCLIDEAN:
+        _check(lib().mval_kcenter_select(*args), "mval_kcenter_select")
+    else:
+        _check(lib().mval_kcenter_select_metric(C.c_int(mid), *args), "mval_kcenter_select_metric")
     return picks, md
 
 

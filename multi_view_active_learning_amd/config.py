@@ -52,6 +52,7 @@ def get_default_configs():
     c.AL.MPE_CONFIG = "AVG"
     c.AL.BSB_CONFIG = "AVG"
     c.AL.HP_CONFIG = "AVG"
+    c.AL.CORESET_METRIC = "euclidean"  # not in the reference (it never passes another): the names of _lib.KC_METRIC_IDS
     c.AL.INFERENCE = CN()
     c.AL.INFERENCE.BATCH_SIZE = 2
     c.AL.INFERENCE.NUM_WORKERS = 2

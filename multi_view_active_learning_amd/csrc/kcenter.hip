@@ -15,45 +15,7 @@
 //   * arithmetic is sklearn's expanded form in float64, in sklearn's operation order:
 //     d = sqrt(max(0, (-2 x.c + |x|^2) + |c|^2)); first maximum wins ties; NaN is a maximum
 //     (np.argmax) and propagates through minimum (np.minimum); nothing is masked.
-#include "mval_common.h"
-
-#define KC_THREADS 256
-#define KC_MAX_BLOCKS 1024
-#define KC_MAX_D 512
-
-struct KcPartial {
-  double val;
-  int64_t idx;
-};
-
-__device__ __forceinline__ bool kc_better(double v, int64_t i, double bv, int64_t bi) {
-  bool vn = v != v, bn = bv != bv;
-  if (vn != bn) return vn;
-  if (vn) return i < bi;
-  return (v > bv) || (v == bv && i < bi);
-}
-__device__ __forceinline__ double np_minimum(double a, double b) {
-  if (a != a) return a;
-  if (b != b) return b;
-  return a < b ? a : b;
-}
-
-__device__ __forceinline__ KcPartial kc_block_reduce(KcPartial p, KcPartial* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    double ov = __shfl_xor(p.val, o, 64);
-    long long oi = __shfl_xor((long long)p.idx, o, 64);
-    if (kc_better(ov, oi, p.val, p.idx)) { p.val = ov; p.idx = oi; }
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = p;
-  __syncthreads();
-  KcPartial r = sh[0];
-  for (int w = 1; w < KC_THREADS / 64; w++)
-    if (kc_better(sh[w].val, sh[w].idx, r.val, r.idx)) r = sh[w];
-  __syncthreads();
-  return r;
-}
+#include "kcenter_common.h"
 
 __global__ __launch_bounds__(KC_THREADS) void kc_transpose_norm_kernel(const double* __restrict__ feat,
                                                                        double* __restrict__ featT,
@@ -163,13 +125,6 @@ __global__ __launch_bounds__(KC_THREADS) void kc_step_kernel(const double* __res
   }
   KcPartial r = kc_block_reduce(best, sh);
   if (threadIdx.x == 0) part_out[blockIdx.x] = r;
-}
-
-static int kc_blocks(int64_t n) {
-  int64_t nb = (n + KC_THREADS - 1) / KC_THREADS;
-  if (nb > KC_MAX_BLOCKS) nb = KC_MAX_BLOCKS;
-  if (nb < 1) nb = 1;
-  return (int)nb;
 }
 
 extern "C" size_t mval_kcenter_workspace_bytes(int64_t n_obs, int D) {

@@ -328,13 +328,17 @@ class ActiveLearningStrategy:
                     raise IndexError("list index out of range")
         self._pending_checks = []
 
-    def select_al_guids(self, sal_dict, al_num_frames, labeled_dict=None):
+    def select_al_guids(self, sal_dict, al_num_frames, labeled_dict=None, metric=None):
         """Selection part of _sal_pseudo_labeling (strategy.py:932-949): NaN filter, then
-        CORESET -> CoreSet(pred_3d_keypoints, labeled, root).select_batch(N), else
-        heapq.nlargest(N, ...) (stable: ties keep gather order)."""
+        CORESET -> CoreSet(pred_3d_keypoints, labeled, root, metric).select_batch(N), else
+        heapq.nlargest(N, ...) (stable: ties keep gather order).  ``metric`` None reads
+        AL.CORESET_METRIC where the config has it ("euclidean", what the reference always uses, otherwise); every rank
+        runs the same greedy loop on the gathered predictions, so the metric needs no collective of its own."""
         al_metric_dict = {g: m for g, m in sal_dict["al_metric"].items() if not math.isnan(m)}
         if self.al_cfg.AL.STRATEGY == "CORESET":
-            cs = coreset.CoreSet(sal_dict["pred_3d_keypoints"], labeled_dict, self.joint_root_index)
+            if metric is None:
+                metric = self.al_cfg.AL.CORESET_METRIC if "CORESET_METRIC" in self.al_cfg.AL else "euclidean"
+            cs = coreset.CoreSet(sal_dict["pred_3d_keypoints"], labeled_dict, self.joint_root_index, metric=metric)
             return cs.select_batch(al_num_frames)
         return nlargest(al_num_frames, al_metric_dict, key=al_metric_dict.get)
 

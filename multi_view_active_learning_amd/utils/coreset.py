@@ -1,8 +1,9 @@
 """Core-set (greedy k-center) selection -- drop-in for reference utils/coreset.py:13-95.
 
 The feature table lives in HBM (float64, transposed for coalesced streaming) and each
-greedy step is ONE launch (csrc/kcenter.hip); the reference runs sklearn
-``pairwise_distances`` + numpy on the CPU, redundantly on every rank.
+greedy step is ONE launch (csrc/kcenter.hip; csrc/kcenter_metric.hip for ``metric`` "manhattan" / "l1" /
+"cityblock", "cosine" and "chebyshev"); the reference runs sklearn ``pairwise_distances`` + numpy on the CPU,
+redundantly on every rank.
 """
 from __future__ import annotations
 
@@ -24,8 +25,7 @@ def get_al_dict_for_coreset(labeled_data):
 
 class CoreSet:
     def __init__(self, sal_dict, al_dict, joint_root_index, metric="euclidean", device=None):
-        if metric != "euclidean":
-            raise NotImplementedError("only the euclidean metric (the reference never passes another)")
+        _lib.kcenter_metric_id(metric)  # NotImplementedError for a name that is not one of _lib.KC_METRIC_IDS
         self.sal_dict = OrderedDict(sal_dict)
         self.al_dict = OrderedDict(al_dict)
         # the reference prints list(al_dict.values())[0] (coreset.py:19) -> IndexError when empty
@@ -43,9 +43,10 @@ class CoreSet:
         self.already_selected = []
 
     @classmethod
-    def from_tensors(cls, pool_pose, labeled_pose, joint_root_index, sal_keys=None):
+    def from_tensors(cls, pool_pose, labeled_pose, joint_root_index, sal_keys=None, metric="euclidean"):
         """Fast path without python dicts: pool_pose (n,J,>=3), labeled_pose (L,J,>=3) HIP or
         host arrays ([joint][coord] rows, the reference's per-pose layout)."""
+        _lib.kcenter_metric_id(metric)
         self = cls.__new__(cls)
         pool = torch.as_tensor(pool_pose)
         self.device = pool.device if pool.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -55,7 +56,7 @@ class CoreSet:
         self.features = torch.cat([f_pool, f_lab], dim=0).contiguous()
         n, l = pool.shape[0], lab.shape[0]
         self.sal_keys = list(range(n)) if sal_keys is None else list(sal_keys)
-        self.name, self.metric = "kcenter", "euclidean"
+        self.name, self.metric = "kcenter", metric
         self.min_distances = None
         self.max_distances = None
         self.n_obs = n + l
@@ -77,7 +78,7 @@ class CoreSet:
 
     def _run(self, centers, n_select):
         lab = torch.as_tensor(list(centers), dtype=torch.int64, device=self.device) if len(centers) else None
-        picks, md = _lib.kcenter_select(self.features, lab, n_select, self.min_distances)
+        picks, md = _lib.kcenter_select(self.features, lab, n_select, self.min_distances, self.metric)
         self.min_distances = md
         return picks
 

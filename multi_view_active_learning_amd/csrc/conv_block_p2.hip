@@ -25,49 +25,6 @@
 
 #include "conv_p2.h"
 
-#ifndef P2_VALU_PRIO
-#define P2_VALU_PRIO 2
-#endif
-#ifndef BP_ORDER
-#define BP_ORDER 1      // 0: the next tile's patch granules / the scale row requested at the start of the tile (rounds 3-5); 1: behind weight requests
-#endif
-#ifndef BP_MFMA_PRIO
-#define BP_MFMA_PRIO 1  // s_setprio around every step's MFMA group (conv_p2.hip P2_MFMA_PRIO)
-#endif
-
-typedef p2_f32x4 f32x4;
-typedef p2_f16x8 f16x8;
-typedef p2_f16x4 f16x4;
-typedef p2_u32x4 u32x4;
-typedef p2_u32x2 u32x2;
-
-#ifdef P2_STAMP
-#define BP_T0 unsigned long long bp_t = wall_clock64(), bp_t00 = bp_t; unsigned long long bp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define BP_ACC(k)                                 \
-  do {                                            \
-    const unsigned long long t_ = wall_clock64(); \
-    bp_acc[k] += t_ - bp_t;                       \
-    bp_t = t_;                                    \
-  } while (0)
-#define BP_FLUSH                                                                                     \
-  do {                                                                                               \
-    if (a.dbg && lane == 0) {                                                                        \
-      unsigned long long* d_ = a.dbg + ((int64_t)blockIdx.x * 4 + wave) * 16;                        \
-      d_[0] = bp_t00; d_[4] = wall_clock64(); d_[1] = d_[0];                                         \
-      for (int k_ = 0; k_ < 8; k_++) d_[8 + k_] = bp_acc[k_];                                        \
-    }                                                                                                \
-  } while (0)
-extern unsigned long long* g_p2_dbg_shared;
-#else
-#define BP_T0
-#define BP_ACC(k)
-#define BP_FLUSH
-#endif
-
-__device__ __forceinline__ f32x4 bp_mfma(const u32x4 a, const u32x4 b, const f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 struct P2BlockArgs {
   const _Float16* in;
   _Float16* out;
@@ -76,8 +33,7 @@ struct P2BlockArgs {
   const unsigned* in_row;
   unsigned* out_row;
   int N, H, W;
-  int tiles_x, tiles_y, tiles_total, wgs_x;
-  unsigned tiles_img_magic, tiles_x_magic;
+  P2Walk walk;  // 8 x 16 output tiles
   unsigned long long* dbg;  // diagnostic builds (-DP2_STAMP)
 };
 
@@ -108,21 +64,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave % WN, wm = wave / WN;
 
-  // ---- tile walk (as conv_p2.hip) ------------------------------------------------------------------------------------
-  const int X = a.wgs_x >= 8 ? 8 : 1;
-  const int per = (a.tiles_total + X - 1) / X, wgx = a.wgs_x / X;
-  const int xg = (int)blockIdx.x % X;
-  int tile = xg * per + (int)blockIdx.x / X;
-  const int tile_end = min(a.tiles_total, (xg + 1) * per);
+  // ---- tile walk (conv_p2.h) ------------------------------------------------------------------------------------------
+  int tile, tile_end, wgx;
+  p2_walk_begin(a.walk, tile, tile_end, wgx);
   if (tile >= tile_end) return;
-  const int tiles_img = a.tiles_x * a.tiles_y;
-  auto decode = [&](int t, int& n, int& oy0, int& ox0) {
-    n = a.tiles_img_magic ? (int)__umulhi((unsigned)t, a.tiles_img_magic) : t;
-    const int r = t - n * tiles_img;
-    const int tyi = a.tiles_x_magic ? (int)__umulhi((unsigned)r, a.tiles_x_magic) : r;
-    oy0 = tyi * TH;
-    ox0 = (r - tyi * a.tiles_x) * TW;
-  };
+  const int tiles_img = a.walk.tiles_x * a.walk.tiles_y;
+  auto decode = [&](int t, int& n, int& oy0, int& ox0) { p2_walk_decode<TH, TW>(a.walk, tiles_img, t, n, oy0, ox0); };
 
   // ---- staging plan of the input patch: granule e -> (patch row, block sp = g*8 + plane*4 + c8, column) ----------------
   const unsigned hw16 = (unsigned)(a.H * a.W) * 16u;
@@ -211,19 +158,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
   B1[1][0] = w1f(NCH > 1 ? 0 : 1, NCH > 1 ? 1 : 0, 0); B1[1][1] = w1f(NCH > 1 ? 0 : 1, NCH > 1 ? 1 : 0, 1);
   store_patch();
   __syncthreads();
-  BP_T0;
+  P2F_T0;
 
   for (;;) {
     const int n = tn, oy0 = toy, ox0 = tox;
     const int next_tile = tile + wgx;
     const bool have_next = next_tile < tile_end;
     if (have_next) decode(next_tile, tn, toy, tox);
-    // (round 6, conv_p2.hip P2_ORDER: loads return in order, so the patch granules -- HBM / MALL latency -- requested HERE sat in front of
-    // conv1's weight ring and its third step waited for them.  BP_ORDER 1: they are requested behind conv2's first weight column at the end
-    // of conv1, travel during the BN1 phase and conv2's first column, and are stored into X at the end of the tile)
-    if (BP_ORDER == 0 && !OVERLAY && have_next) load_patch(tn, toy, tox);  // C = 32: the next patch travels during conv1
+    // (round 6, as conv_p2.hip's issue order: loads return in order, so the next tile's patch granules -- HBM / MALL latency -- requested
+    // HERE sat in front of conv1's weight ring and its third step waited for them.  C = 32: they are requested behind conv2's first weight
+    // column at the end of conv1, travel during the BN1 phase and conv2's first column, and are stored into X at the end of the tile;
+    // the scale row is requested behind the ring's first request; profiles/r06/p2_order_prefetch_product_ab.log)
     P2RowRegs row_in;
-    if (BP_ORDER == 0) p2_row_request(a.in_row, n, row_in);
 
     // ---- 1. conv1: step = (tap, chunk) in packed order chunk-minor; x fragments three sub-tiles ahead -------------------
     f32x4 acc1[MS1];
@@ -252,14 +198,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
             const int s2 = step + 2;
             B1[s2 % 3][0] = w1f(s2 / NCH, s2 % NCH, 0);
             B1[s2 % 3][1] = w1f(s2 / NCH, s2 % NCH, 1);
-            if (BP_ORDER != 0 && step == 0) p2_row_request(a.in_row, n, row_in);  // (read after conv1: behind the ring's first request)
+            if (step == 0) p2_row_request(a.in_row, n, row_in);  // (read after conv1: behind the ring's first request)
           } else if (step + 2 == STEPS) {  // the first column of conv2's weights behind the last steps of conv1
 #pragma unroll
             for (int ky = 0; ky < 3; ky++) {
               B2[0][ky][0] = w2f(ky * 3, 0, 0);
               B2[0][ky][1] = w2f(ky * 3, 0, 1);
             }
-            if (BP_ORDER != 0 && !OVERLAY && have_next) load_patch(tn, toy, tox);
+            if (!OVERLAY && have_next) load_patch(tn, toy, tox);
           }
         }
         if (q + RD - 1 < Q) {
@@ -268,17 +214,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
           Xf[q1 % RD][1] = *reinterpret_cast<const u32x4*>(smem + xb1[q1 % MS1] + xoff(q1) + XPL);
         }
         __builtin_amdgcn_sched_barrier(SB);
-        if (BP_MFMA_PRIO) __builtin_amdgcn_s_setprio(BP_MFMA_PRIO);
+        __builtin_amdgcn_s_setprio(P2_MFMA_PRIO);
         f32x4 c = acc1[ms];
-        c = bp_mfma(B1[step % 3][1], Xf[q % RD][0], c);
-        c = bp_mfma(B1[step % 3][0], Xf[q % RD][1], c);
-        acc1[ms] = bp_mfma(B1[step % 3][0], Xf[q % RD][0], c);
-        if (BP_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
+        c = p2_mfma(B1[step % 3][1], Xf[q % RD][0], c);
+        c = p2_mfma(B1[step % 3][0], Xf[q % RD][1], c);
+        acc1[ms] = p2_mfma(B1[step % 3][0], Xf[q % RD][0], c);
+        __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(SB);
       }
     }
 
-    BP_ACC(0);
+    P2F_ACC(0);
     __builtin_amdgcn_s_setprio(P2_VALU_PRIO);  // the vector phases win issue arbitration against the partner wave's MFMA stream
     // ---- residual: the lane's granules of x (its conv2 rows, its channel block) out of the patch, before X is given up --
     u32x4 RX[MS2];
@@ -319,10 +265,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
         __builtin_amdgcn_sched_barrier(SB);
       }
     }
-    BP_ACC(1);
+    P2F_ACC(1);
     __syncthreads();  // M is complete (C = 32: and every wave is done with X)
-    BP_ACC(2);
-    if (BP_ORDER == 0 && !OVERLAY && have_next) store_patch();
+    P2F_ACC(2);
 
     __builtin_amdgcn_s_setprio(0);
     // ---- 3. conv2 with row sharing over M -------------------------------------------------------------------------------------
@@ -362,7 +307,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
         }
         __builtin_amdgcn_sched_barrier(SB);
         const u32x4 xh = Xf[q & 1][0], xl = Xf[q & 1][1];
-        if (BP_MFMA_PRIO) __builtin_amdgcn_s_setprio(BP_MFMA_PRIO);
+        __builtin_amdgcn_s_setprio(P2_MFMA_PRIO);
 #pragma unroll
         for (int t3 = 0; t3 < 3; t3++) {
 #pragma unroll
@@ -370,15 +315,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
             const int ms = pr - ky;
             if (ms < 0 || ms >= MS2) continue;
             const u32x4* wv = B2[col & 1][ky];
-            acc2[ms] = t3 == 0 ? bp_mfma(wv[1], xh, acc2[ms]) : t3 == 1 ? bp_mfma(wv[0], xl, acc2[ms]) : bp_mfma(wv[0], xh, acc2[ms]);
+            acc2[ms] = t3 == 0 ? p2_mfma(wv[1], xh, acc2[ms]) : t3 == 1 ? p2_mfma(wv[0], xl, acc2[ms]) : p2_mfma(wv[0], xh, acc2[ms]);
           }
         }
-        if (BP_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(SB);
       }
     }
 
-    BP_ACC(3);
+    P2F_ACC(3);
     __builtin_amdgcn_s_setprio(P2_VALU_PRIO);
     // ---- epilogue: BN2 + residual + ReLU + max |x| + split, 16-byte stores ---------------------------------------------------
     float amax = 0.f;
@@ -417,24 +362,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
         if (atomicAdd(&wgred[1], 1u) == 3u) {
           const unsigned m = atomicExch(&wgred[0], 0u);
           wgred[1] = 0u;
-          p2_slot_put(a.out_row + (int64_t)n * P2_ROW, (oy0 / TH) * a.tiles_x + ox0 / TW, tiles_img, m);
+          p2_slot_put(a.out_row + (int64_t)n * P2_ROW, (oy0 / TH) * a.walk.tiles_x + ox0 / TW, tiles_img, m);
         }
       }
     }
-    BP_ACC(4);
+    P2F_ACC(4);
     __builtin_amdgcn_s_setprio(0);
     if (!have_next) break;
-    if (BP_ORDER != 0 && !OVERLAY) store_patch();  // (X has been free since the barrier behind the BN1 phase)
+    if (!OVERLAY) store_patch();  // (X has been free since the barrier behind the BN1 phase)
     __syncthreads();  // every wave is done with M (C = 64: X may be written; C = 32: the next patch is in X)
     if (OVERLAY) {  // C = 64: 60 staging registers do not fit beside conv2: the next patch is fetched here (the
       load_patch(tn, toy, tox);  // other workgroup of the CU computes meanwhile)
       store_patch();
       __syncthreads();
     }
-    BP_ACC(5);
+    P2F_ACC(5);
     tile = next_tile;
   }
-  BP_FLUSH;
+  P2F_FLUSH;
 }
 
 static thread_local int g_bp_dry = 0;
@@ -444,12 +389,8 @@ static int launch_block_p2(P2BlockArgs a, hipStream_t s) {
   constexpr int NCH = C / 32;
   constexpr size_t XB = (size_t)NCH * 8 * 240 * 16, MB = (size_t)NCH * 8 * 192 * 16;
   constexpr size_t smem = (C > 32 ? XB : XB + MB) + 16;
-  a.tiles_x = (a.W + 15) / 16;
-  a.tiles_y = (a.H + 7) / 8;
-  const int tiles_img = a.tiles_x * a.tiles_y;
-  a.tiles_total = tiles_img * a.N;
-  a.tiles_img_magic = tiles_img > 1 ? (unsigned)(((uint64_t)1 << 32) / (unsigned)tiles_img + 1) : 0u;
-  a.tiles_x_magic = a.tiles_x > 1 ? (unsigned)(((uint64_t)1 << 32) / (unsigned)a.tiles_x + 1) : 0u;
+  p2_walk_fill(a.walk, a.H, a.W, 8, 16, a.N);
+  const int tiles_img = a.walk.tiles_x * a.walk.tiles_y;
   if (g_bp_dry) return 0;
 #ifdef P2_STAMP
   a.dbg = g_p2_dbg_shared;
@@ -460,13 +401,8 @@ static int launch_block_p2(P2BlockArgs a, hipStream_t s) {
   const char* pe = getenv("MVAL_P2_WGS");
   if (pe && atoi(pe) > 0) per_cu = atoi(pe);
 #endif
-  int wgs = mval_cu_count() * per_cu;
-  if (wgs >= a.tiles_total) wgs = a.tiles_total;
-  else {
-    const int per = (a.tiles_total + 7) / 8, rounds = (per + wgs / 8 - 1) / (wgs / 8);
-    wgs = 8 * ((per + rounds - 1) / rounds);
-  }
-  a.wgs_x = wgs;
+  const int wgs = mval_p2_walk_grid(a.walk.tiles_total, mval_cu_count() * per_cu, 1);
+  a.walk.wgs_x = wgs;
   if (tiles_img > P2_SLOTS) mval_launch_zero_rows(a.out_row, (int64_t)a.N * P2_ROW, s);
   hipLaunchKernelGGL((conv_block_p2_kernel<C>), dim3((unsigned)wgs), dim3(256), smem, s, a);
   return 0;

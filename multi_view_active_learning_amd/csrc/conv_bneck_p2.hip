@@ -29,52 +29,11 @@
 
 #include "conv_p2.h"
 
-#ifndef BN_ORDER
-#define BN_ORDER 1  // 0: conv1's patch chunk requested before the next chunk's weights (rounds 4-5)
-#endif
-
-
-#ifndef P2_VALU_PRIO
-#define P2_VALU_PRIO 2
-#endif
-
-typedef p2_f32x4 f32x4;
-typedef p2_f16x8 f16x8;
-typedef p2_f16x4 f16x4;
-typedef p2_u32x4 u32x4;
-typedef p2_u32x2 u32x2;
-
-#ifdef P2_STAMP
-#define BN_T0 unsigned long long bp_t = wall_clock64(), bp_t00 = bp_t; unsigned long long bp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define BN_ACC(k)                                 \
-  do {                                            \
-    const unsigned long long t_ = wall_clock64(); \
-    bp_acc[k] += t_ - bp_t;                       \
-    bp_t = t_;                                    \
-  } while (0)
-#define BN_FLUSH                                                                                     \
-  do {                                                                                               \
-    if (a.dbg && lane == 0) {                                                                        \
-      unsigned long long* d_ = a.dbg + ((int64_t)blockIdx.x * 4 + wave) * 16;                        \
-      d_[0] = bp_t00; d_[4] = wall_clock64(); d_[1] = d_[0];                                         \
-      for (int k_ = 0; k_ < 8; k_++) d_[8 + k_] = bp_acc[k_];                                        \
-    }                                                                                                \
-  } while (0)
-extern unsigned long long* g_p2_dbg_shared;
-#else
-#define BN_T0
-#define BN_ACC(k)
-#define BN_FLUSH
-#endif
-
-__device__ __forceinline__ f32x4 bn_mfma(const u32x4 a, const u32x4 b, const f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 // the three products of one fp32 product, small terms first
 __device__ __forceinline__ f32x4 bn_mfma3(const u32x4 wh, const u32x4 wl, const u32x4 xh, const u32x4 xl, f32x4 c) {
-  c = bn_mfma(wl, xh, c);
-  c = bn_mfma(wh, xl, c);
-  return bn_mfma(wh, xh, c);
+  c = p2_mfma(wl, xh, c);
+  c = p2_mfma(wh, xl, c);
+  return p2_mfma(wh, xh, c);
 }
 __device__ __forceinline__ f32x4 bn_relu(f32x4 v) {
   v.x = p2_max_nan(v.x, 0.f); v.y = p2_max_nan(v.y, 0.f); v.z = p2_max_nan(v.z, 0.f); v.w = p2_max_nan(v.w, 0.f);
@@ -108,8 +67,7 @@ struct P2BneckArgs {
   const unsigned* res_row;
   unsigned* out_row;
   int N, H, W;
-  int tiles_x, tiles_y, tiles_total, wgs_x;
-  unsigned tiles_img_magic, tiles_x_magic;
+  P2Walk walk;  // 8 x 16 output tiles
   unsigned long long* dbg;  // diagnostic builds (-DP2_STAMP)
 };
 
@@ -148,31 +106,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   auto region = [&](int c) { return (c % 3) == 0 ? 0 : (c % 3) == 1 ? XCB : U0; };
 
-  // ---- tile walk (as conv_p2.hip) ------------------------------------------------------------------------------------
-  const int X = a.wgs_x >= 8 ? 8 : 1;
-  const int per = (a.tiles_total + X - 1) / X, wgx = a.wgs_x / X;
-  const int xg = (int)blockIdx.x % X;
-  int tile = xg * per + (int)blockIdx.x / X;
-  const int tile_end = min(a.tiles_total, (xg + 1) * per);
+  // ---- tile walk (conv_p2.h) ------------------------------------------------------------------------------------------
+  int tile, tile_end, wgx;
+  p2_walk_begin(a.walk, tile, tile_end, wgx);
   if (tile >= tile_end) return;
-  const int tiles_img = a.tiles_x * a.tiles_y;
-  auto decode = [&](int t, int& n, int& oy0, int& ox0) {
-    n = a.tiles_img_magic ? (int)__umulhi((unsigned)t, a.tiles_img_magic) : t;
-    const int r = t - n * tiles_img;
-    const int tyi = a.tiles_x_magic ? (int)__umulhi((unsigned)r, a.tiles_x_magic) : r;
-    oy0 = tyi * TH;
-    ox0 = (r - tyi * a.tiles_x) * TW;
-  };
+  const int tiles_img = a.walk.tiles_x * a.walk.tiles_y;
+  auto decode = [&](int t, int& n, int& oy0, int& ox0) { p2_walk_decode<TH, TW>(a.walk, tiles_img, t, n, oy0, ox0); };
 
   // ---- staging of one 32-channel chunk of the input patch: granule e -> (patch row, block sp = plane*4 + c8, column) ----
   const unsigned hw16 = (unsigned)(a.H * a.W) * 16u;
   const unsigned in_img = 2u * C8I * hw16, out_img = 2u * C8O * hw16, out_plane = C8O * hw16;
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.in), 0, (unsigned)a.N * in_img, 0x00020000);
-#ifdef BNECK_NO_RES  // measurement build only (tools/run: what the residual re-read costs): an empty range -- every residual load returns 0 without a memory access
-  const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.res), 0, 0u, 0x00020000);
-#else
   const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.res), 0, (unsigned)a.N * out_img, 0x00020000);
-#endif
   const __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (unsigned)a.N * out_img, 0x00020000);
   // ONE descriptor over the parameter buffer: weights, BN vectors and bounds are byte offsets into it
   const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.params), 0, 0x7fffffff, 0x00020000);
@@ -233,7 +178,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
   store_x(region(1), 0);
   if (NCH1 > 2) load_x(2, 0);
   __syncthreads();
-  BN_T0;
+  P2F_T0;
 
   for (;;) {
     const int n = tn, oy0 = toy, ox0 = tox;
@@ -262,12 +207,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
         // chunk k: requested at iteration k - 4 into set k & 1, stored at k - 2, multiplied at k (chunks 0 .. 2 of a tile
         // come from the previous tile's phase 3, chunk 3 is requested here)
         if (ch + 2 < NCH1) store_x(region(ch + 2), ch & 1);
-        // (round 6, BN_ORDER 1: loads return in order -- the next chunk's weight fragments (L2) are requested BEFORE the patch chunk four
-        // ahead (HBM / MALL), so the wait for them at the next chunk does not include that chunk's round trip; conv_p2.hip P2_ORDER)
-        if (BN_ORDER == 0) {
-          if (ch == 0 && 3 < NCH1) load_x(3, 1);
-          if (ch + 4 < NCH1) load_x(ch + 4, ch & 1);
-        }
+        // (round 6: loads return in order -- the next chunk's weight fragments (L2) are requested BEFORE the patch chunk four ahead
+        // (HBM / MALL), so the wait for them at the next chunk does not include that chunk's round trip; as conv_p2.hip's issue order,
+        // profiles/r06/p2_order_prefetch_product_ab.log)
         if (ch + 1 < NCH1) {
 #pragma unroll
           for (int nt = 0; nt < 2; nt++) { W1[(ch + 1) & 1][nt][0] = wld(wv + nt * 2048, (ch + 1) * (4 * 2048)); W1[(ch + 1) & 1][nt][1] = wld(wv + nt * 2048 + 1024, (ch + 1) * (4 * 2048)); }
@@ -275,10 +217,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
 #pragma unroll
           for (int ky = 0; ky < 3; ky++) { B2[0][ky][0] = wld(wv2, (ky * 3 * 2) * (4 * 2048)); B2[0][ky][1] = wld(wv2 + 1024, (ky * 3 * 2) * (4 * 2048)); }
         }
-        if (BN_ORDER != 0) {
-          if (ch == 0 && 3 < NCH1) load_x(3, 1);
-          if (ch + 4 < NCH1) load_x(ch + 4, ch & 1);
-        }
+        if (ch == 0 && 3 < NCH1) load_x(3, 1);
+        if (ch + 4 < NCH1) load_x(ch + 4, ch & 1);
         const int xb = xb1 + region(ch);
         u32x4 Xf[2][2];
         Xf[0][0] = *reinterpret_cast<const u32x4*>(smem + xb);
@@ -297,7 +237,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
         __syncthreads();  // chunk ch + 2 is visible, chunk ch's region is free; after the last chunk: M1's halves are free
       }
     }
-    BN_ACC(0);
+    P2F_ACC(0);
     __builtin_amdgcn_s_setprio(P2_VALU_PRIO);  // the vector phases win issue arbitration against the partner wave's MFMA stream
 
     // ---- scales of this image ---------------------------------------------------------------------------------------------
@@ -332,9 +272,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
         }
       }
     }
-    BN_ACC(1);
+    P2F_ACC(1);
     __syncthreads();  // M1 is complete
-    BN_ACC(2);
+    P2F_ACC(2);
     __builtin_amdgcn_s_setprio(0);
 
     // ---- 2. conv2 with row sharing over M1: wave = 16 output channels x 8 rows ----------------------------------------------
@@ -382,12 +322,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
             const int ms = pr - ky;
             if (ms < 0 || ms >= TH) continue;
             const u32x4* wv = B2[col & 1][ky];
-            acc2[ms] = t3 == 0 ? bn_mfma(wv[1], xh, acc2[ms]) : t3 == 1 ? bn_mfma(wv[0], xl, acc2[ms]) : bn_mfma(wv[0], xh, acc2[ms]);
+            acc2[ms] = t3 == 0 ? p2_mfma(wv[1], xh, acc2[ms]) : t3 == 1 ? p2_mfma(wv[0], xl, acc2[ms]) : p2_mfma(wv[0], xh, acc2[ms]);
           }
         }
         __builtin_amdgcn_sched_barrier(SB);
       }
-      BN_ACC(3);
+      P2F_ACC(3);
       // conv3 weights of the first half travel during the vector phase
 #pragma unroll
       for (int ch = 0; ch < 2; ch++)
@@ -403,7 +343,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
         __builtin_amdgcn_sched_barrier(SB);
       }
     }
-    BN_ACC(4);
+    P2F_ACC(4);
     __syncthreads();  // M2 is complete, M1's halves are free: they take the next tile's chunks 0 and 1 during phase 3
     __builtin_amdgcn_s_setprio(0);
 
@@ -454,7 +394,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
           __builtin_amdgcn_sched_barrier(SB);
         }
       }
-      BN_ACC(5);
+      P2F_ACC(5);
       // the other half's weights (or the next tile's first conv1 weights) behind the matrix phase; the staged chunk goes into
       // its region (a half of M1, free since the barrier before phase 3) and the next one is requested
       if (hf == 0) {
@@ -509,7 +449,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
         asm volatile("s_nop 1");
         __builtin_amdgcn_sched_barrier(SB);
       }
-      BN_ACC(6);
+      P2F_ACC(6);
       __builtin_amdgcn_s_setprio(0);
     }
     {
@@ -519,16 +459,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
         if (atomicAdd(&wgred[1], 1u) == 3u) {
           const unsigned m = atomicExch(&wgred[0], 0u);
           wgred[1] = 0u;
-          p2_slot_put(a.out_row + (int64_t)n * P2_ROW, (oy0 / TH) * a.tiles_x + ox0 / TW, tiles_img, m);
+          p2_slot_put(a.out_row + (int64_t)n * P2_ROW, (oy0 / TH) * a.walk.tiles_x + ox0 / TW, tiles_img, m);
         }
       }
     }
     if (!have_next) break;
     __syncthreads();  // every wave is done with M2 (U takes chunk 2), the next tile's chunks 0 and 1 are visible
-    BN_ACC(7);
+    P2F_ACC(7);
     tile = next_tile;
   }
-  BN_FLUSH;
+  P2F_FLUSH;
 }
 
 static thread_local int g_bn_dry = 0;
@@ -536,12 +476,8 @@ static thread_local int g_bn_dry = 0;
 template <int CIN>
 static int launch_bneck_p2(P2BneckArgs a, hipStream_t s) {
   constexpr size_t smem = 2 * 8 * 180 * 16 + 2 * 8 * 128 * 16 + 2048 + 16;
-  a.tiles_x = (a.W + 15) / 16;
-  a.tiles_y = (a.H + 7) / 8;
-  const int tiles_img = a.tiles_x * a.tiles_y;
-  a.tiles_total = tiles_img * a.N;
-  a.tiles_img_magic = tiles_img > 1 ? (unsigned)(((uint64_t)1 << 32) / (unsigned)tiles_img + 1) : 0u;
-  a.tiles_x_magic = a.tiles_x > 1 ? (unsigned)(((uint64_t)1 << 32) / (unsigned)a.tiles_x + 1) : 0u;
+  p2_walk_fill(a.walk, a.H, a.W, 8, 16, a.N);
+  const int tiles_img = a.walk.tiles_x * a.walk.tiles_y;
   if (g_bn_dry) return 0;
 #ifdef P2_STAMP
   a.dbg = g_p2_dbg_shared;
@@ -552,13 +488,8 @@ static int launch_bneck_p2(P2BneckArgs a, hipStream_t s) {
   const char* pe = getenv("MVAL_P2_WGS_BS");
   if (pe && atoi(pe) > 0) per_cu = atoi(pe);
 #endif
-  int wgs = mval_cu_count() * per_cu;
-  if (wgs >= a.tiles_total) wgs = a.tiles_total;
-  else {
-    const int per = (a.tiles_total + 7) / 8, rounds = (per + wgs / 8 - 1) / (wgs / 8);
-    wgs = 8 * ((per + rounds - 1) / rounds);
-  }
-  a.wgs_x = wgs;
+  const int wgs = mval_p2_walk_grid(a.walk.tiles_total, mval_cu_count() * per_cu, 1);
+  a.walk.wgs_x = wgs;
   if (tiles_img > P2_SLOTS) mval_launch_zero_rows(a.out_row, (int64_t)a.N * P2_ROW, s);
   hipLaunchKernelGGL((conv_bneck_p2_kernel<CIN>), dim3((unsigned)wgs), dim3(256), smem, s, a);
   return 0;

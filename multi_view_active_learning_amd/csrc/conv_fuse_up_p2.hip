@@ -21,16 +21,8 @@
 
 #include "conv_p2.h"
 
-typedef p2_f32x4 f32x4;
-typedef p2_f16x8 f16x8;
-typedef p2_f16x4 f16x4;
-typedef p2_u32x4 u32x4;
-typedef p2_u32x2 u32x2;
-
 #define FU_MAX_TERMS 3
-#ifndef FU_TH
-#define FU_TH 8  // rows of the output tile (x 32 columns)
-#endif
+constexpr int FU_TH = 8;  // rows of the output tile (x 32 columns); 16 x 32 tiles: 1 024 workgroups of 140 registers (above)
 
 struct FuseUpTerm {
   const _Float16* in;
@@ -49,10 +41,6 @@ struct FuseUpArgs {
   int N, H, W;
   int tiles_x, tiles_y;
 };
-
-__device__ __forceinline__ f32x4 fu_mfma(const u32x4 a, const u32x4 b, const f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 template <int COUT, int TH = FU_TH, int TW = 32>
 __global__ __launch_bounds__(256) void conv_fuse_up_p2_kernel(FuseUpArgs a) {
@@ -128,9 +116,9 @@ __global__ __launch_bounds__(256) void conv_fuse_up_p2_kernel(FuseUpArgs a) {
         const u32x4 xl = __builtin_amdgcn_raw_buffer_load_b128(xr, __builtin_elementwise_add_sat(xo, (unsigned)s * 4u * hw16 + plane), 0, 0);
         const u32x4 wh = __builtin_amdgcn_raw_buffer_load_b128(pr, wv, s * blk, 0);
         const u32x4 wl = __builtin_amdgcn_raw_buffer_load_b128(pr, wv + 1024, s * blk, 0);
-        acc = fu_mfma(wl, xh, acc);
-        acc = fu_mfma(wh, xl, acc);
-        acc = fu_mfma(wh, xh, acc);
+        acc = p2_mfma(wl, xh, acc);
+        acc = p2_mfma(wh, xl, acc);
+        acc = p2_mfma(wh, xh, acc);
       }
       const float unscale = __uint_as_float(row_j.inv) * ps(t.w_unscale);
       const f32x4 v = acc * (sc * unscale) + sh;

@@ -35,6 +35,23 @@ typedef _Float16 p2_f16x8 __attribute__((ext_vector_type(8)));
 typedef float p2_f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int p2_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int p2_u32x2 __attribute__((ext_vector_type(2)));
+// the short names the P2 units use (the same types as the other conv units' own typedefs of these names)
+typedef p2_f32x4 f32x4;
+typedef p2_f16x8 f16x8;
+typedef p2_f16x4 f16x4;
+typedef p2_u32x4 u32x4;
+typedef p2_u32x2 u32x2;
+
+// s_setprio of a wave's vector phases (epilogues, BN + split between two convs): they win issue arbitration against the partner wave's
+// MFMA stream (round 3) ...
+constexpr int P2_VALU_PRIO = 2;
+// ... and around every step's MFMA group of conv_p2.hip / conv_block_p2.hip: 2.98-3.09 -> 2.57-2.62 us per stage of the loop's
+// skeleton (profiles/r06/p2_loop_order_prefetch.log)
+constexpr int P2_MFMA_PRIO = 1;
+
+__device__ __forceinline__ p2_f32x4 p2_mfma(const p2_u32x4 a, const p2_u32x4 b, const p2_f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(p2_f16x8, a), __builtin_bit_cast(p2_f16x8, b), c, 0, 0, 0);
+}
 
 // 2^s that puts `bound` in [2^13, 2^14) and its inverse (zero / inf / NaN bound: unscaled)
 __device__ __forceinline__ void p2_scale_of(float bound, float& mul, float& inv) {
@@ -52,9 +69,6 @@ __device__ __forceinline__ float p2_max_nan(float v, float floor_) { return __bu
 
 __device__ __forceinline__ void p2_split(const p2_f32x4 v, p2_f16x4& h, p2_f16x4& l) {
   h = __builtin_convertvector(v, p2_f16x4);
-#ifdef P2_NO_FMA_MIX
-  l = __builtin_convertvector(v - __builtin_convertvector(h, p2_f32x4), p2_f16x4);
-#else
   // v - float(h) as ONE v_fma_mix_f32 per value (fma(float(h), -1, v): the same singly-rounded difference as convert +
   // subtract; the compiler does not form it by itself): 8 instead of 12 instructions per split
   const p2_u32x2 hu = __builtin_bit_cast(p2_u32x2, h);
@@ -64,13 +78,9 @@ __device__ __forceinline__ void p2_split(const p2_f32x4 v, p2_f16x4& h, p2_f16x4
   asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r.z) : "v"(hu.y), "v"(v.z));
   asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r.w) : "v"(hu.y), "v"(v.w));
   l = __builtin_convertvector(r, p2_f16x4);
-#endif
 }
 __device__ __forceinline__ p2_f32x4 p2_join(const p2_f16x4 h, const p2_f16x4 l) {
-#ifdef P2_NO_FMA_MIX
-  return __builtin_convertvector(h, p2_f32x4) + __builtin_convertvector(l, p2_f32x4);  // exact (22 bits)
-#else
-  // float(h) * 1 + float(l) in one v_fma_mix_f32 per value (both operands read as fp16 halves): 4 instead of 12
+  // float(h) * 1 + float(l), exact (22 bits), in one v_fma_mix_f32 per value (both operands read as fp16 halves): 4 instead of 12
   const p2_u32x2 hu = __builtin_bit_cast(p2_u32x2, h), lu = __builtin_bit_cast(p2_u32x2, l);
   p2_f32x4 r;
   asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(r.x) : "v"(hu.x), "v"(lu.x));
@@ -78,7 +88,6 @@ __device__ __forceinline__ p2_f32x4 p2_join(const p2_f16x4 h, const p2_f16x4 l) 
   asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(r.z) : "v"(hu.y), "v"(lu.y));
   asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(r.w) : "v"(hu.y), "v"(lu.y));
   return r;
-#endif
 }
 
 // A workgroup's max |x| of what it stored of image n -> its slot of the row.  More producing workgroups per image than
@@ -158,6 +167,74 @@ static inline int p2_resident_wgs(K kernel, std::atomic<int>& slot, size_t smem,
   return nb;
 }
 
+// ---- the persistent tile walk of conv_p2 / block / bneck / stem --------------------------------------------------------------------
+// A launch covers tiles_total = tiles_x * tiles_y * N tiles with wgs_x workgroups per cout group.  Workgroup b belongs to XCD group
+// b % 8 (one workgroup: one group), every group owns a contiguous range of `per` tiles -- neighbouring tiles' halos meet in one L2 --
+// and its wgs_x / 8 workgroups walk that range in steps of wgs_x / 8.  So a count of 8 or more MUST be a multiple of 8: with 12
+// workgroups for 12 tiles the floor wgs_x / 8 = 1 made four tiles run twice -- harmless for stored outputs, wrong for anything a
+// kernel accumulates over its walk (the batch-statistics sums of EPI 3).  mval_p2_walk_grid is the one place that decides the count.
+struct P2Walk {
+  int tiles_x, tiles_y, tiles_total, wgs_x;
+  unsigned tiles_img_magic, tiles_x_magic;  // 2^32 / d + 1 (0: d == 1): tile index -> (image, tile row) without a divide, t * d < 2^32
+};
+static inline void p2_walk_fill(P2Walk& w, int hout, int wout, int th, int tw, int n) {
+  w.tiles_x = (wout + tw - 1) / tw;
+  w.tiles_y = (hout + th - 1) / th;
+  const int tiles_img = w.tiles_x * w.tiles_y;
+  w.tiles_total = tiles_img * n;
+  w.tiles_img_magic = tiles_img > 1 ? (unsigned)(((uint64_t)1 << 32) / (unsigned)tiles_img + 1) : 0u;
+  w.tiles_x_magic = w.tiles_x > 1 ? (unsigned)(((uint64_t)1 << 32) / (unsigned)w.tiles_x + 1) : 0u;
+}
+// Workgroups per cout group (the grid's x) for `resident` workgroups that fit the device at once, shared by `groups` cout groups: as
+// many as stay resident, a multiple of 8; fewer tiles than that: one tile each (8 or more: rounded up to a multiple of 8, the
+// workgroups without a tile return at once); more: equal shares, so that no workgroup walks a round more than the others.  (No
+// workgroup waits for another one: an optimistic `resident` only costs a second round.)  conv_p2.hip; a C symbol for the host test.
+extern "C" int mval_p2_walk_grid(int tiles_total, int resident, int groups);
+// this workgroup's first tile, the end of its range and its step
+__device__ __forceinline__ void p2_walk_begin(const P2Walk w, int& tile, int& tile_end, int& wgx) {
+  const int X = w.wgs_x >= 8 ? 8 : 1;
+  const int per = (w.tiles_total + X - 1) / X;
+  wgx = w.wgs_x / X;
+  const int xg = (int)blockIdx.x % X;
+  tile = xg * per + (int)blockIdx.x / X;
+  tile_end = min(w.tiles_total, (xg + 1) * per);
+}
+// tile t -> image, first output row / column of its TH x TW pixels (tiles_img = w.tiles_x * w.tiles_y: every caller keeps it anyway)
+template <int TH, int TW>
+__device__ __forceinline__ void p2_walk_decode(const P2Walk w, const int tiles_img, int t, int& n, int& oy0, int& ox0) {
+  n = w.tiles_img_magic ? (int)__umulhi((unsigned)t, w.tiles_img_magic) : t;
+  const int r = t - n * tiles_img;
+  const int tyi = w.tiles_x_magic ? (int)__umulhi((unsigned)r, w.tiles_x_magic) : r;
+  oy0 = tyi * TH;
+  ox0 = (r - tyi * w.tiles_x) * TW;
+}
+
+// ---- diagnostic builds (-DP2_STAMP) of the fused kernels: eight phase timers per wave from the 100 MHz wall clock, left in
+// a.dbg[workgroup * 4 + wave][16] = [start, start, -, -, end, -, -, -, timers] (tools/p2_block_stamps.py, p2_bneck_stamps.py,
+// p2_stem_stamps.py).  P2F_T0 starts, P2F_ACC(k) adds the time since the last P2F_T0 / P2F_ACC to timer k, P2F_FLUSH stores.
+#ifdef P2_STAMP
+#define P2F_T0 unsigned long long bp_t = wall_clock64(), bp_t00 = bp_t; unsigned long long bp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define P2F_ACC(k)                                \
+  do {                                            \
+    const unsigned long long t_ = wall_clock64(); \
+    bp_acc[k] += t_ - bp_t;                       \
+    bp_t = t_;                                    \
+  } while (0)
+#define P2F_FLUSH                                                                                    \
+  do {                                                                                               \
+    if (a.dbg && lane == 0) {                                                                        \
+      unsigned long long* d_ = a.dbg + ((int64_t)blockIdx.x * 4 + wave) * 16;                        \
+      d_[0] = bp_t00; d_[4] = wall_clock64(); d_[1] = d_[0];                                         \
+      for (int k_ = 0; k_ < 8; k_++) d_[8 + k_] = bp_acc[k_];                                        \
+    }                                                                                                \
+  } while (0)
+extern unsigned long long* g_p2_dbg_shared;  // conv_p2.hip: the buffer mval_p2_debug_buffer() registered
+#else
+#define P2F_T0
+#define P2F_ACC(k)
+#define P2F_FLUSH
+#endif
+
 struct P2Args {
   const _Float16* in;  // P2 planes of the input tensor
   const float* w;      // MVAL_PACK_MFMA16_H2 fragments (+ trailer)
@@ -195,11 +272,10 @@ struct P2Args {
   // in_sub = 1 (k == 1): the conv reads every second pixel of its input (a stride-2 1 x 1 conv as a stride-1 one over the sub-sampled view:
   // pose_resnet.py's downsample branches); Hin / Win stay the full input size, Hout / Wout = ceil(Hin / 2), ceil(Win / 2)
   int in_sub;
-  int th, tw, tiles_x, tiles_y;
+  int th, tw;
+  P2Walk walk;  // tiles of th x tw output pixels
   int NS_total;
   int amax_tiles;
-  unsigned tiles_img_magic, tiles_x_magic;  // 2^32 / d + 1: tile index -> (image, tile row) without a divide
-  int tiles_total, wgs_x;  // persistent tile walk: tiles_x * tiles_y * N tiles over wgs_x workgroups per cout group
   unsigned long long* dbg;  // diagnostic builds (-DP2_STAMP): per-wave phase time stamps; nullptr otherwise
   // (round 6, training forward, EPI 3, 3x3 stride 1) in_z != nullptr: the input activation does not exist as planes -- it is
   // relu(BatchNorm(in_z)) of the producer's RAW conv output in_z (fp32 NHWC, N x Hin x Win x Cin) with the producer's batch statistics and

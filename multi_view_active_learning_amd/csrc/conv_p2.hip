@@ -25,57 +25,21 @@
 
 #include "conv_p2.h"
 
-// register budget: 2 waves per SIMD (256 VGPRs); -DP2_W3: 3 for the light configurations (measurement)
-#ifdef P2_W3
-#define P2_WAVES(MS, NT, EPI) (((MS) * (NT) <= 4 && (EPI) == 0) ? 3 : 2)
-#else
-// (EPI 3, the training forward: no residual granules, no output split -- 117 .. 147 registers on the light configurations, so a
-// third wave per SIMD fits; MVAL measured below)
-#ifdef P2_EPI3_W3
-#define P2_WAVES(MS, NT, EPI) (((EPI) == 3 && (MS) * (NT) <= 4) ? 3 : 2)
-#else
-#define P2_WAVES(MS, NT, EPI) 2
-#endif
-#endif
-
-#ifndef P2_RES_AUX
-#define P2_RES_AUX 2  // cache policy of the FIRST residual's loads: non-temporal (nt) -- the residual of a BasicBlock is its input's last use, that of a
-                      // fuse chain the partial sum's -- C2 10.08 -> 10.02 ms, C1x16 6.35 -> 6.31, C4 17.82 -> 17.78 (profiles/r05/p2_nt_res*.log); 0 = default policy
-#endif
-#ifndef P2_VALU_PRIO
-#define P2_VALU_PRIO 2
-#endif
+// cache policy of the FIRST residual's loads: non-temporal (nt) -- the residual of a BasicBlock is its input's last use, that of a fuse
+// chain the partial sum's -- C2 10.08 -> 10.02 ms, C1x16 6.35 -> 6.31, C4 17.82 -> 17.78 (profiles/r05/p2_nt_res*.log)
+constexpr int P2_RES_AUX = 2;
 // ---- round 6: issue order and prefetch depth of the main loop (tools/micro/p2_loop.hip, profiles/r06/p2_loop_order_prefetch.log) --------
 // Vector-memory loads return IN ORDER (one vmcnt counter): the wait for a weight fragment also waits for every load issued before it.  Rounds
 // 3-5 requested the next stage's patch granules (and, in a tile's last stage, the epilogue's residual granules and factor rows: HBM / MALL
 // latency) at the START of a stage, in front of the next column's weight fragments (L2) -- so the first weight wait of every stage also
 // waited for them.  In the loop's skeleton: 2.98-3.09 us per stage -> 2.77 (weights first) / 2.51-2.58 (weights two columns ahead) /
-// 2.65 (x fragments two steps ahead) / 2.57-2.62 (s_setprio 1 around the MFMA groups) -> 2.41-2.44 together.
-#ifndef P2_ORDER
-#define P2_ORDER 1      // 0: patch granules / epilogue operands requested before the stage's MFMA loop (rounds 3-5); 1: behind the first weight
-                        // request of the stage; 2: at the start of the stage's second column / step
-#endif
-#ifndef P2_XD
-#define P2_XD 3         // x fragment ring: 2 = one step ahead (rounds 3-5), 3 = two steps ahead (light instantiations only: 8 more registers)
-#endif
-#ifndef P2_WD_RS
-#define P2_WD_RS 3      // row-sharing 3x3 kernels: weight columns in flight + in use: 2 = one column ahead, 3 = two (NT = 1 only: 24 more registers)
-#endif
-#ifndef P2_WD
-#define P2_WD 4         // the other kernels: weight steps in the ring (2 = one step ahead; a step is only MS x NT x 3 MFMAs: 192 cycles at MS x NT = 4)
-#endif
-#ifndef P2_INZ_MAP
-#define P2_INZ_MAP 1    // (INZ staging) 1: a pixel's channel blocks on consecutive lanes; 0: a block's pixels on consecutive lanes (measurement)
-#endif
-#ifndef P2_MFMA_PRIO
-#define P2_MFMA_PRIO 1  // s_setprio around every step's MFMA group (0 = off)
-#endif
-
-typedef p2_f32x4 f32x4;
-typedef p2_f16x8 f16x8;
-typedef p2_f16x4 f16x4;
-typedef p2_u32x4 u32x4;
-typedef p2_u32x2 u32x2;
+// 2.65 (x fragments two steps ahead) / 2.57-2.62 (s_setprio 1 around the MFMA groups, conv_p2.h) -> 2.41-2.44 together.  So a stage's
+// other loads go out behind its first weight request (mfma_stage below), and the light instantiations -- the only ones with the
+// registers for it -- keep deeper rings:
+constexpr int P2_XD = 3;     // x fragment ring: two steps ahead (8 more registers than one step ahead)
+constexpr int P2_WD_RS = 3;  // row-sharing 3x3 kernels: weight columns in flight + in use, two ahead (NT = 1 only: 24 more registers)
+constexpr int P2_WD = 4;     // the other kernels: weight steps in the ring (a step is only MS x NT x 3 MFMAs: 192 cycles at MS x NT = 4);
+constexpr int P2_WD_S2 = 3;  // stride 2 (the patch is four times the tile): one step less
 
 #ifdef P2_STAMP
 // Diagnostic build only: lane 0 of every wave leaves the 100 MHz wall clock at phase boundaries in a.dbg[wave][16].
@@ -106,10 +70,6 @@ extern "C" void mval_p2_debug_buffer(void* p) { g_p2_dbg = g_p2_dbg_shared = rei
 #define P2_ACC(k)
 #define P2_FLUSH
 #endif
-
-__device__ __forceinline__ f32x4 p2_mfma(const u32x4 a, const u32x4 b, const f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 // KS: 1 or 3 (pad KS / 2); S: stride; G: 32-channel chunks staged per barrier (1x1 convs: 2 or 4 -- one tap per
 // chunk is too little MFMA work per barrier); WN x WM waves (couts x pixels); NT cout sub-tiles and MS pixel
@@ -173,12 +133,9 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
   const int ns0 = (by * WN + wn) * NT;
   const bool wave_active = ns0 < a.NS_total;
 
-  // ---- tile walk: workgroup b of this cout group -> XCD group b % X, contiguous tile range per XCD group ----------
-  const int X = a.wgs_x >= 8 ? 8 : 1;
-  const int per = (a.tiles_total + X - 1) / X, wgx = a.wgs_x / X;
-  const int xg = (int)blockIdx.x % X;
-  int tile = xg * per + (int)blockIdx.x / X;
-  const int tile_end = min(a.tiles_total, (xg + 1) * per);
+  // ---- tile walk (conv_p2.h): workgroup b of this cout group -> XCD group b % 8, contiguous tile range per XCD group ----
+  int tile, tile_end, wgx;
+  p2_walk_begin(a.walk, tile, tile_end, wgx);
   // (EPI 3) batch-statistics sums of the lane's four output channels per cout sub-tile, over the workgroup's whole tile walk
   float bsum[EPI == 3 ? NT : 1][4], bsq[EPI == 3 ? NT : 1][4];
   float bgmx[BSUM ? NT : 1][4];  // (BSUM) max |masked gradient| per channel
@@ -245,15 +202,9 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
     stats_put();  // (a workgroup without tiles still owns its slots of the partials)
     return;
   }
-  const int tiles_img = a.tiles_x * a.tiles_y;
+  const int tiles_img = a.walk.tiles_x * a.walk.tiles_y;
   int tn, toy, tox;  // the tile being computed: image, first output row / column
-  auto decode = [&](int t, int& n, int& oy0, int& ox0) {  // (t / d as a multiply: magic = 2^32 / d + 1, t * d < 2^32)
-    n = a.tiles_img_magic ? (int)__umulhi((unsigned)t, a.tiles_img_magic) : t;
-    const int r = t - n * tiles_img;
-    const int tyi = a.tiles_x_magic ? (int)__umulhi((unsigned)r, a.tiles_x_magic) : r;
-    oy0 = tyi * TH;
-    ox0 = (r - tyi * a.tiles_x) * TWE;
-  };
+  auto decode = [&](int t, int& n, int& oy0, int& ox0) { p2_walk_decode<TH, TWE>(a.walk, tiles_img, t, n, oy0, ox0); };
 
   // ---- staging plan: granule e = tid + NTH * i -> (patch row py, block sp = g*8 + plane*4 + c8, column px) ------
   const int C8 = a.Cin >> 3;
@@ -322,13 +273,13 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
 #pragma unroll
     for (int i = 0; i < NEZ; i++) {
       // consecutive lanes = the 4 G channel blocks of ONE pixel (32 bytes each: 128 G contiguous bytes of its NHWC row), then the next pixel
-      // of the patch row: a wave's two load instructions use every byte of the lines they touch.  (P2_INZ_MAP 0, the first form: consecutive
+      // of the patch row: a wave's two load instructions use every byte of the lines they touch.  (The first form: consecutive
       // lanes = consecutive pixels of one block, 16 bytes at a 4 C-byte stride -- 64 sectors per instruction; conv forward +0.6 ms per C3 step)
       const int e = tid + NTH * i;
       // (G = 2 -- the 8 x 8 maps' form -- keeps the first mapping: eight blocks of a pixel are eight LDS stores to one bank group;
       // 256 -> 256 @8x8 measured 34.0 us with the first mapping, 36.3 with this one; profiles/r06/inz_lane_map_ab.log)
       int c8l, py, px;
-      if constexpr (P2_INZ_MAP && G == 1) {
+      if constexpr (G == 1) {
         c8l = e & 3;
         const int t_ = e >> 2;
         py = t_ / PW;
@@ -474,9 +425,9 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
   constexpr bool LIGHT = MS * NT <= 4;
   // (by the register tables, tools/kernel_resources.py: two pixel waves stage 6 granules per thread -- x ring only; the stride-2 patch is four
   // times the tile -- one more weight step, no x ring)
-  constexpr int XD = (LIGHT && S == 1 && P2_XD >= 3) ? 3 : 2;                                   // x fragment ring
-  constexpr int WDR = (RS && NT == 1 && MS <= 4 && WM == 1 && !K48 && P2_WD_RS >= 3) ? 3 : 2;   // row-sharing: weight column ring
-  constexpr int WDN_ = LIGHT ? (P2_WD < 2 ? 2 : S == 2 && P2_WD > 3 ? 3 : P2_WD) : 2;
+  constexpr int XD = (LIGHT && S == 1) ? P2_XD : 2;                                   // x fragment ring
+  constexpr int WDR = (RS && NT == 1 && MS <= 4 && WM == 1 && !K48) ? P2_WD_RS : 2;   // row-sharing: weight column ring
+  constexpr int WDN_ = LIGHT ? (S == 2 ? P2_WD_S2 : P2_WD) : 2;
   constexpr int WDN = WDN_ > STEPS + 1 ? STEPS + 1 : WDN_;                            // other kernels: weight step ring
   constexpr int WD = RS ? WDR : WDN;
   u32x4 B[WD][RS ? 3 : 1][NT][2];  // weight fragments [ring slot][row tap (RS)][cout sub-tile][plane]
@@ -515,10 +466,9 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
   };
 
   // One stage's MFMAs from LDS buffer `buf`; `pre` != 0: request the first weight blocks of stage `st_next` at the end.  `early()` issues the
-  // stage's other loads (the next stage's patch granules; in a tile's last stage also the epilogue's operands) at the point P2_ORDER names.
+  // stage's other loads (the next stage's patch granules; in a tile's last stage also the epilogue's operands) behind the stage's first step.
   auto mfma_stage = [&](auto rem_tag, int buf, int st, bool pre, int st_next, auto&& early) {
     constexpr bool REM = decltype(rem_tag)::value;  // (K48) the remainder stage: two column steps
-    if constexpr (P2_ORDER == 0) early();
     if constexpr (RS) {
       const char* xs = smem + buf * buf_bytes + xb[0];
       const char* xsp = smem + buf * buf_bytes + xb_pair;
@@ -556,7 +506,7 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
         }
         __builtin_amdgcn_sched_barrier(SB);
         const u32x4 xh = Xf[q % XD][0], xl = Xf[q % XD][1];
-        if (P2_MFMA_PRIO) __builtin_amdgcn_s_setprio(P2_MFMA_PRIO);
+        __builtin_amdgcn_s_setprio(P2_MFMA_PRIO);
 #pragma unroll
         for (int nt = 0; nt < NT; nt++) {
 #pragma unroll
@@ -570,14 +520,14 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
             }
           }
         }
-        if (P2_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(SB);
       };
       // the stage's other loads go out between two steps (a call inside ONE unrolled loop left loops of `early` rolled: arrays in scratch)
-      constexpr int QE = P2_ORDER == 1 ? 1 : P2_ORDER == 2 ? MS + 2 : 0;
+      constexpr int QE = 1;  // steps in front of the stage's other loads (a plain body(0) call instead of this loop changes the generated code)
 #pragma unroll
       for (int q = 0; q < QE; q++) body(q);
-      if constexpr (P2_ORDER != 0) early();
+      early();
 #pragma unroll
       for (int q = QE; q < Q; q++) body(q);
       if (WDR == 2 && pre && (NC & 1)) {  // the next stage starts on parity 0
@@ -613,7 +563,7 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
         __builtin_amdgcn_sched_barrier(SB);
         if (G == 1 || st * G + step / TAPS < nchunks) {  // (chunk count not a multiple of G: the tail stage is short)
           const u32x4 xh = Xf[q % XD][0], xl = Xf[q % XD][1];
-          if (P2_MFMA_PRIO) __builtin_amdgcn_s_setprio(P2_MFMA_PRIO);
+          __builtin_amdgcn_s_setprio(P2_MFMA_PRIO);
 #pragma unroll
           for (int nt = 0; nt < NT; nt++) {
             f32x4 c = acc[ms][nt];
@@ -621,14 +571,14 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
             c = p2_mfma(B[step % WDN][0][nt][0], xl, c);
             acc[ms][nt] = p2_mfma(B[step % WDN][0][nt][0], xh, c);
           }
-          if (P2_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
+          __builtin_amdgcn_s_setprio(0);
         }
         __builtin_amdgcn_sched_barrier(SB);
       };
-      constexpr int QE = P2_ORDER == 1 ? 1 : P2_ORDER == 2 ? (STEPS > 1 ? MS : 1) : 0;
+      constexpr int QE = 1;  // steps in front of the stage's other loads (a plain body(0) call instead of this loop changes the generated code)
 #pragma unroll
       for (int q = 0; q < QE; q++) body(q);
-      if constexpr (P2_ORDER != 0) early();
+      early();
 #pragma unroll
       for (int q = QE; q < Q; q++) body(q);
       if (pre && (STEPS % WDN) != 0) {  // the next stage's step u was requested into slot (STEPS + u) % WDN: rotate it to slot u
@@ -714,7 +664,7 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
       else return (yl + sub_ty(ms) < a.Hout && xl + sub_tx(ms) < a.Wout) ? vb[nt] : 0x80000000u;
     };
     auto soff = [&](int ms) -> int { return OW ? 0 : (((sub_ty(ms) << osh) * Wo + (sub_tx(ms) << osh)) * 16); };
-    // the last stage's other loads, issued where P2_ORDER says (round 6: behind the stage's first weight request -- residual granules and
+    // the last stage's other loads, issued behind the stage's first step (round 6: behind the stage's first weight request -- residual granules and
     // factor rows come from HBM / MALL and every later weight wait would wait for them too): the next tile's first patch granules (every
     // wave), then what the epilogue reads
     auto early_last = [&]() {
@@ -832,9 +782,7 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
               else r += res_of(q2[ms], r2_inv);
             }
             put(r, voff(nt, ms), soff(ms));
-#ifndef P2_NO_EPI_SB
             __builtin_amdgcn_sched_barrier(SB);  // one granule at a time: interleaving them all costs ~60 registers
-#endif
           }
         }
       };
@@ -934,7 +882,7 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
           // decode from the epilogue (hrnet.py:344-350,500 -> utils/evaluation.py:13-30): the 16 pixel lanes of a cout
           // quarter fold their keys; the wave's key of (tile, cout) goes to its slot of the map's row
           if (a.argmax_keys) {
-            const int timg = (oy0 / TH) * a.tiles_x + ox0 / TWE;
+            const int timg = (oy0 / TH) * a.walk.tiles_x + ox0 / TWE;
 #pragma unroll
             for (int j = 0; j < 4; j++) {
               const unsigned long long kk = mval_key_row16_max(bi[j] == 0xffffffffu ? 0ull : mval_argmax_key(bv[j], bi[j]));
@@ -987,15 +935,12 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
       // the workgroup's max |x| without a barrier: LDS atomics, the wave that arrives last publishes and re-arms
       const unsigned amax_bits = p2_wave_umax(__float_as_uint(amax));
       if (lane == 0) {
-#ifdef P2_FENCE
-        __threadfence_block();
-#endif
         atomicMax(&wgred[0], amax_bits);  // (a wave's LDS operations execute in order: no fence -- a fence here also
                                           // waits for every store and prefetch in flight, 2 us per tile)
         if (atomicAdd(&wgred[1], 1u) == (unsigned)(WN * WM - 1)) {
           const unsigned m = atomicExch(&wgred[0], 0u);
           wgred[1] = 0u;
-          const int timg = (oy0 / TH) * a.tiles_x + ox0 / TWE;
+          const int timg = (oy0 / TH) * a.walk.tiles_x + ox0 / TWE;
           p2_slot_put(a.out_row + (int64_t)n * P2_ROW, a.slot_base + timg * gy + by, a.slot_total ? a.slot_total : tiles_img * gy, m);
         }
       }
@@ -1015,12 +960,23 @@ __device__ __forceinline__ void conv_p2_body(const P2Args& a, const int by, cons
 }
 
 
+// register budget: 2 waves per SIMD (256 VGPRs).  (Three on the light configurations measured slower: inference C2 10.11 -> 10.36 ms, the
+// training forward C3 60.8 -> 62.9 ms; profiles/r05/step_level_knobs.log)
 template <int KS, int S, int G, int WN, int WM, int NT, int MS, int TW, bool RS, int EPI, int OW = 0, bool K48 = false, bool INZ = false, bool BSUM = false>
-__global__ __launch_bounds__(64 * WN * WM) __attribute__((amdgpu_waves_per_eu(P2_WAVES(MS, NT, EPI), 8))) void conv_p2_kernel(P2Args a) {
+__global__ __launch_bounds__(64 * WN * WM) __attribute__((amdgpu_waves_per_eu(2, 8))) void conv_p2_kernel(P2Args a) {
   conv_p2_body<KS, S, G, WN, WM, NT, MS, TW, RS, EPI, OW, K48, INZ, BSUM>(a, (int)blockIdx.y, (int)gridDim.y);
 }
 
 static thread_local int g_p2_dry = 0;
+
+int mval_p2_walk_grid(int tiles_total, int resident, int groups) {  // (conv_p2.h)
+  int wgs = (resident / groups) & ~7;
+  if (wgs < 8) wgs = 8;
+  if (wgs >= tiles_total) return tiles_total < 8 ? tiles_total : (tiles_total + 7) & ~7;
+  // equal shares: the XCD groups' ranges are walked in steps of wgs / 8
+  const int per = (tiles_total + 7) / 8, rounds = (per + wgs / 8 - 1) / (wgs / 8);
+  return 8 * ((per + rounds - 1) / rounds);
+}
 
 template <int KS, int S, int G, int WN, int WM, int NT, int MS, int TW, bool RS, int EPI, int OW = 0, bool K48 = false, bool INZ = false, bool BSUM = false>
 static int launch_p2e(P2Args a, hipStream_t s) {
@@ -1034,41 +990,27 @@ static int launch_p2e(P2Args a, hipStream_t s) {
   if (INZ && (a.Cin > 512 || a.Cin % (32 * G) != 0)) return 1;
   constexpr int NTH = 64 * WN * WM;
   a.th = TH; a.tw = TWE;
-  a.tiles_x = (a.Wout + TWE - 1) / TWE;
-  a.tiles_y = (a.Hout + TH - 1) / TH;
+  p2_walk_fill(a.walk, a.Hout, a.Wout, TH, TWE, a.N);
   if (OW && a.Wout % OW != 0) return 1;  // (whole odd tiles per row: 18 -> 1, 36 -> 2 tiles of 18 columns)
   const unsigned groups = (unsigned)((a.NS_total + WN * NT - 1) / (WN * NT));
-  a.amax_tiles = a.tiles_x * a.tiles_y;
+  a.amax_tiles = a.walk.tiles_x * a.walk.tiles_y;
   if (a.os && EPI < 2) {  // a parity launch: its quarter of the output rows' partial-maximum slots
     a.slot_total = 4 * a.amax_tiles * (int)groups;
     a.slot_base = (a.oy * 2 + a.ox) * a.amax_tiles * (int)groups;
   }
-  a.tiles_total = a.amax_tiles * a.N;
-  a.tiles_img_magic = a.amax_tiles > 1 ? (unsigned)(((uint64_t)1 << 32) / (unsigned)a.amax_tiles + 1) : 0u;  // (0: divide by one)
-  a.tiles_x_magic = a.tiles_x > 1 ? (unsigned)(((uint64_t)1 << 32) / (unsigned)a.tiles_x + 1) : 0u;
   if (g_p2_dry) return 0;
 #ifdef P2_STAMP
   a.dbg = g_p2_dbg;
 #endif
-  // persistent workgroups: as many as stay resident (the runtime's occupancy answer for this instantiation: LDS and
-  // registers), a multiple of 8 per cout group so that every XCD walks its own contiguous tile range; fewer tiles than
-  // that: one tile each.  (No workgroup waits for another one: an optimistic answer only costs a second round.)
+  // persistent workgroups: as many as stay resident (this instantiation's LDS and registers), shared by the cout groups
   static std::atomic<int> occ{0};
   int per_cu = p2_resident_wgs(&conv_p2_kernel<KS, S, G, WN, WM, NT, MS, TW, RS, EPI, OW, K48, INZ, BSUM>, occ, smem, NTH / 64);
 #ifdef P2_TUNE
   const char* pe = getenv("MVAL_P2_WGS");  // measurement builds only: workgroups per CU
   if (pe && atoi(pe) > 0) per_cu = atoi(pe);
 #endif
-  int wgs = (mval_cu_count() * per_cu / (int)groups) & ~7;
-  if (wgs < 8) wgs = 8;
-  // (a count >= 8 must be a multiple of 8: the kernel walks 8 XCD groups in steps of wgs / 8 -- with 12 workgroups for 12 tiles the
-  // floor made four tiles run twice: harmless for stored outputs, wrong for the batch-statistics sums of EPI 3)
-  if (wgs >= a.tiles_total) wgs = a.tiles_total < 8 ? a.tiles_total : (a.tiles_total + 7) & ~7;
-  else {  // equal shares: the XCD groups' ranges are walked in steps of wgs / 8
-    const int per = (a.tiles_total + 7) / 8, rounds = (per + wgs / 8 - 1) / (wgs / 8);
-    wgs = 8 * ((per + rounds - 1) / rounds);
-  }
-  a.wgs_x = wgs;
+  const int wgs = mval_p2_walk_grid(a.walk.tiles_total, mval_cu_count() * per_cu, (int)groups);
+  a.walk.wgs_x = wgs;
   dim3 grid((unsigned)wgs, groups);
   if (EPI < 2 && (a.slot_total ? a.slot_total : (int64_t)a.amax_tiles * groups) > P2_SLOTS && !a.keep_rows)
     mval_launch_zero_rows(a.out_row, (int64_t)a.N * P2_ROW, s);  // (the kernel rewrites the scale slots)

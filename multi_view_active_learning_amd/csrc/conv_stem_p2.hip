@@ -17,7 +17,7 @@
 //       intermediate; a wave takes every fourth.  BN1 + ReLU + zero outside y1 -> scaled by the per-IMAGE bound A1 max|x| +
 //       B1, split, 16-byte granules into Y1 = [chunk][plane h,l][8-ch block][column parity, row, column / 2][16 B].
 //       (The first form did conv1 on the vector ALUs in exact fp32 -- 594 packed FMAs per lane and tile, 41 % of the
-//       kernel: 388 us against 297 us now; -DST_VALU_CONV1 still builds it.)
+//       kernel: 388 us against 297 us now.)
 //   2.  conv2 on the matrix cores from Y1 (conv_p2.hip arithmetic: three fp16 MFMA products per fp32 product): wave =
 //       16 output channels x 2 rows, a row fragment = 16 consecutive slots of one column parity;
 //       BN2 + ReLU + max |x| + split in registers, 16-byte stores into the output planes.
@@ -25,46 +25,9 @@
 #include <stdlib.h>
 
 #include "conv_p2.h"
-#ifndef P2_STEM_AUX
-#define P2_STEM_AUX 2  // cache policy of the image loads: non-temporal (every image is read by this launch only); with P2_RES_AUX: C2 10.08 -> 10.01 ms
-#endif
-
-#ifndef P2_VALU_PRIO
-#define P2_VALU_PRIO 2
-#endif
-#ifndef ST_VALU_CONV1  // -DST_VALU_CONV1: conv1 on the vector ALUs in exact fp32 (the first form of this kernel: 388 vs 297 us)
-#define ST_MFMA1 1
-#endif
-
-typedef p2_f32x4 f32x4;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef p2_f16x8 f16x8;
-typedef p2_f16x4 f16x4;
-typedef p2_u32x4 u32x4;
-typedef p2_u32x2 u32x2;
-
-#ifdef P2_STAMP
-#define ST_T0 unsigned long long bp_t = wall_clock64(), bp_t00 = bp_t; unsigned long long bp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define ST_ACC(k)                                 \
-  do {                                            \
-    const unsigned long long t_ = wall_clock64(); \
-    bp_acc[k] += t_ - bp_t;                       \
-    bp_t = t_;                                    \
-  } while (0)
-#define ST_FLUSH                                                                                     \
-  do {                                                                                               \
-    if (g_dbg && lane == 0) {                                                                        \
-      unsigned long long* d_ = g_dbg + ((int64_t)blockIdx.x * 4 + wave) * 16;                        \
-      d_[0] = bp_t00; d_[4] = wall_clock64(); d_[1] = d_[0];                                         \
-      for (int k_ = 0; k_ < 8; k_++) d_[8 + k_] = bp_acc[k_];                                        \
-    }                                                                                                \
-  } while (0)
-extern unsigned long long* g_p2_dbg_shared;
-#else
-#define ST_T0
-#define ST_ACC(k)
-#define ST_FLUSH
-#endif
+// cache policy of the image loads: non-temporal (every image is read by this launch only); with the residual loads' policy of conv_p2.hip:
+// C2 10.08 -> 10.01 ms (profiles/r05/p2_nt_res*.log)
+constexpr int P2_STEM_AUX = 2;
 
 struct StemP2Args {
   const float* in;   // [N][3][H][W]
@@ -75,14 +38,10 @@ struct StemP2Args {
   const unsigned* in_row;  // P2 rows of the input image (its max |x|)
   unsigned* out_row;
   int N, H, W, H1, W1, H2, W2;
-  int tiles_x, tiles_y, tiles_total, wgs_x;
-  unsigned tiles_img_magic, tiles_x_magic;
+  P2Walk walk;  // 2 x 16 tiles of `out`
   unsigned long long* dbg;  // diagnostic builds (-DP2_STAMP)
 };
 
-__device__ __forceinline__ f32x4 st_mfma(const u32x4 a, const u32x4 b, const f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 __device__ __forceinline__ int st_fresh(int v) {  // (conv_bneck_p2.hip: keeps per-phase address plans out of the tile loop's registers)
   asm volatile("" : "+v"(v));
   return v;
@@ -118,27 +77,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   constexpr int PB = 3 * IH * IWP * 4;                               // 8 976 bytes
   constexpr int P0 = YB, W0 = P0 + PB;                               // patch, workgroup reduction words
   constexpr int NP = (3 * IH * IW + 255) / 256;                      // patch elements per thread: 9
-  constexpr int RUN = 11;                                            // y1 pixels per lane: a third of a row
-  static_assert(PW == 3 * RUN, "three runs per intermediate row");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned* wgred = reinterpret_cast<unsigned*>(smem + W0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-  // ---- tile walk (as conv_p2.hip) ------------------------------------------------------------------------------------
-  const int X = a.wgs_x >= 8 ? 8 : 1;
-  const int per = (a.tiles_total + X - 1) / X, wgx = a.wgs_x / X;
-  const int xg = (int)blockIdx.x % X;
-  int tile = xg * per + (int)blockIdx.x / X;
-  const int tile_end = min(a.tiles_total, (xg + 1) * per);
+  // ---- tile walk (conv_p2.h) ------------------------------------------------------------------------------------------
+  int tile, tile_end, wgx;
+  p2_walk_begin(a.walk, tile, tile_end, wgx);
   if (tile >= tile_end) return;
-  const int tiles_img = a.tiles_x * a.tiles_y;
-  auto decode = [&](int t, int& n, int& oy0, int& ox0) {
-    n = a.tiles_img_magic ? (int)__umulhi((unsigned)t, a.tiles_img_magic) : t;
-    const int r = t - n * tiles_img;
-    const int tyi = a.tiles_x_magic ? (int)__umulhi((unsigned)r, a.tiles_x_magic) : r;
-    oy0 = tyi * TH;
-    ox0 = (r - tyi * a.tiles_x) * TW;
-  };
+  const int tiles_img = a.walk.tiles_x * a.walk.tiles_y;
+  auto decode = [&](int t, int& n, int& oy0, int& ox0) { p2_walk_decode<TH, TW>(a.walk, tiles_img, t, n, oy0, ox0); };
 
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, (unsigned)min((int64_t)0x7fffffff, (int64_t)a.N * 3 * a.H * a.W * 4), 0x00020000);
   const unsigned hw16 = (unsigned)(a.H2 * a.W2) * 16u, out_img = 2u * 8u * hw16, out_plane = 8u * hw16;
@@ -159,7 +107,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
       pre[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, ok ? (unsigned)(((n * 3 + c) * a.H + iy) * a.W + ix) * 4u : 0x80000000u, 0, P2_STEM_AUX));
     }
   };
-#ifdef ST_MFMA1
   // conv1 on the matrix cores: the patch is kept as the (h, l) fp16 planes of x * 2^sx (sx from the image's max |x|), 2 bytes each
   constexpr int PLB = 3 * IH * IWP * 2;
   auto store_patch = [&](float xmul) {
@@ -177,18 +124,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
       }
     }
   };
-#else
-  auto store_patch = [&](float) {
-    const int T = st_fresh(tid);
-#pragma unroll
-    for (int i = 0; i < NP; i++) {
-      const int e = T + 256 * i;
-      const int c = e / (IH * IW), r = e - c * (IH * IW);
-      const int py = r / IW, px = r - py * IW;
-      if (e < 3 * IH * IW) *reinterpret_cast<float*>(smem + P0 + ((c * IH + py) * IWP + px) * 4) = pre[i];
-    }
-  };
-#endif
 
   // ---- prologue ----------------------------------------------------------------------------------------------------------
   int tn, toy, tox;
@@ -196,15 +131,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   load_patch(tn, toy, tox);
   if (tid == 0) wgred[0] = wgred[1] = 0u;
   const float b1a = a.bound1[0], b1b = a.bound1[1], b2a = a.bound2[0], b2b = a.bound2[1], w2u = *a.w2_unscale;
-  // BN vectors of the lane's channels (conv1: cout quad tid & 15; conv2: the wave's sub-tile), the first image's row
-  const f32x4 sc1 = *reinterpret_cast<const f32x4*>(a.scale1 + (tid & 15) * 4), sh1 = *reinterpret_cast<const f32x4*>(a.shift1 + (tid & 15) * 4);
+  // BN vectors of the lane's channels (conv2: the wave's sub-tile; conv1's come from LDS), the first image's row
   const int c0_2 = wave * 16 + ((lane >> 4) & 1) * 8 + (lane >> 5) * 4;
   const f32x4 sc2 = *reinterpret_cast<const f32x4*>(a.scale2 + c0_2), sh2v = *reinterpret_cast<const f32x4*>(a.shift2 + c0_2);
   P2RowRegs row_in;
   p2_row_request(a.in_row, tn, row_in);
   float x_amax_cur = p2_row_amax(row_in), x_mul_cur, x_inv_cur;
   p2_scale_of(x_amax_cur, x_mul_cur, x_inv_cur);
-#ifdef ST_MFMA1
   // conv1's weights as A fragments [cout sub-tile][plane]: K = 27 taps (k = tap * 3 + c, the [27][64] table's rows) padded to one
   // 32-deep step; rows 4..7 <-> 8..11 permuted as in conv_p2.hip; scaled by a power of two from max |w1|, split (h, l)
   float* bn1 = reinterpret_cast<float*>(smem + W0 + 16);  // scale1[64], shift1[64]
@@ -243,13 +176,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
       WA[ct][1] = __builtin_bit_cast(u32x4, *reinterpret_cast<f16x8*>(l));
     }
   }
-#endif
   store_patch(x_mul_cur);
   __syncthreads();
-#ifdef P2_STAMP
-  unsigned long long* g_dbg = a.dbg;
-#endif
-  ST_T0;
+  P2F_T0;
 
   for (;;) {
     const int n = tn, oy0 = toy, ox0 = tox;
@@ -257,7 +186,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
     const bool have_next = next_tile < tile_end;
     if (have_next) decode(next_tile, tn, toy, tox);
     const float x_amax = x_amax_cur, x_inv = x_inv_cur;
-    (void)x_inv;
     if (have_next) p2_row_request(a.in_row, tn, row_in);  // (the next tile's image: requested a tile ahead)
     const float y1_bound = b1a * x_amax + b1b;
     float m1_mul, m1_inv, out_mul, out_inv;
@@ -265,7 +193,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
     p2_scale_of(b2a * y1_bound + b2b, out_mul, out_inv);
     if (oy0 == 0 && ox0 == 0 && tid == 0) a.out_row[(int64_t)n * P2_ROW + P2_INV_SLOT] = __float_as_uint(out_inv);
 
-#ifdef ST_MFMA1
     // ---- 1. conv1 on the matrix cores: one 32-deep step per sixteen-pixel fragment of the 5 x 33 intermediate (11 fragments, a
     // wave takes every fourth) x four 16-channel sub-tiles; the B fragment is an im2col gather of the lane's eight taps ------------
     {
@@ -293,9 +220,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
 #pragma unroll
         for (int ct = 0; ct < 4; ct++) {
           f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-          acc = st_mfma(WA[ct][1], xh, acc);
-          acc = st_mfma(WA[ct][0], xl, acc);
-          acc = st_mfma(WA[ct][0], xh, acc);
+          acc = p2_mfma(WA[ct][1], xh, acc);
+          acc = p2_mfma(WA[ct][0], xl, acc);
+          acc = p2_mfma(WA[ct][0], xh, acc);
           const int c0 = ct * 16 + cq1;
           const f32x4 s1 = *reinterpret_cast<const f32x4*>(bn1 + c0) * k1, h1 = *reinterpret_cast<const f32x4*>(bn1 + 64 + c0) * m1_mul;
           f32x4 v = acc * s1 + h1;
@@ -312,70 +239,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
         }
       }
     }
-#else
-    // ---- 1. conv1 on the vector ALUs: lane = (cout quad q, run g of 11 pixels of intermediate row g / 3) -----------------------
-    __builtin_amdgcn_s_setprio(P2_VALU_PRIO);
-    {
-      const int T = st_fresh(tid);
-      const int q = T & 15, g = T >> 4;
-      if (g < 3 * PH) {
-        const int py = g / 3, px0 = (g - py * 3) * RUN;
-        f32x4 acc[RUN];
-#pragma unroll
-        for (int p = 0; p < RUN; p++) acc[p] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#ifndef ST_SKIP1
-#pragma unroll 1
-        for (int c = 0; c < 3; c++) {
-#pragma unroll
-          for (int ky = 0; ky < 3; ky++) {
-            // 23 consecutive input pixels feed the row's 11 outputs at all three kx
-            float xv[2 * RUN + 2];
-            const char* row = smem + P0 + ((c * IH + 2 * py + ky) * IWP + 2 * px0) * 4;
-#pragma unroll
-            for (int j = 0; j < RUN + 1; j++) {
-              const f32x2 v = *reinterpret_cast<const f32x2*>(row + j * 8);
-              xv[2 * j] = v.x;
-              xv[2 * j + 1] = v.y;
-            }
-#pragma unroll
-            for (int kx = 0; kx < 3; kx++) {
-              const f32x4 w4 = *reinterpret_cast<const f32x4*>(a.w1 + ((ky * 3 + kx) * 3 + c) * 64 + q * 4);  // (6.9 KB shared by every lane: L1 hits)
-#pragma unroll
-              for (int p = 0; p < RUN; p++) {
-                const f32x2 vv = {xv[2 * p + kx], xv[2 * p + kx]};
-                const f32x2 lo = __builtin_elementwise_fma(vv, (f32x2){w4.x, w4.y}, (f32x2){acc[p].x, acc[p].y});
-                const f32x2 hi = __builtin_elementwise_fma(vv, (f32x2){w4.z, w4.w}, (f32x2){acc[p].z, acc[p].w});
-                acc[p] = (f32x4){lo.x, lo.y, hi.x, hi.y};
-              }
-            }
-          }
-        }
-#endif
-        ST_ACC(0);
-        // BN1 + ReLU + zero outside y1 -> scaled, split, half-granules (4 channels x 2 bytes) of both planes
-        const f32x4 s1 = sc1 * m1_mul, h1 = sh1 * m1_mul;
-        const int yy = 2 * oy0 - 1 + py;
-        const bool row_in_img = yy >= 0 && yy < a.H1;
-        const int gb = (q >> 3) * YCH + ((q >> 1) & 3) * SL * 16 + (q & 1) * 8;
-#pragma unroll
-        for (int p = 0; p < RUN; p++) {
-          const int px = px0 + p, xx = 2 * ox0 - 1 + px;
-          f32x4 v = acc[p] * s1 + h1;
-          v.x = p2_max_nan(v.x, 0.f); v.y = p2_max_nan(v.y, 0.f); v.z = p2_max_nan(v.z, 0.f); v.w = p2_max_nan(v.w, 0.f);
-          if (!(row_in_img && xx >= 0 && xx < a.W1)) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-          f16x4 h, l;
-          p2_split(v, h, l);
-          const int slot = ((px & 1) * PH + py) * PWh + (px >> 1);
-          *reinterpret_cast<u32x2*>(smem + gb + slot * 16) = __builtin_bit_cast(u32x2, h);
-          *reinterpret_cast<u32x2*>(smem + gb + YPL + slot * 16) = __builtin_bit_cast(u32x2, l);
-        }
-      }
-    }
-#endif
-    ST_ACC(1);
+    P2F_ACC(1);
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();  // Y1 is complete, the patch is free
-    ST_ACC(2);
+    P2F_ACC(2);
     if (have_next) load_patch(tn, toy, tox);  // the next tile's patch travels during the matrix phase
 
     // ---- 2. conv2 on the matrix cores: wave = 16 output channels x 2 rows; step = (tap, chunk) ------------------------------------
@@ -396,7 +263,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
       u32x4 B[3][2];
       B[0][0] = wf(0, 0); B[0][1] = wf(0, 1);
       B[1][0] = wf(1, 0); B[1][1] = wf(1, 1);
-#ifndef ST_SKIP2
 #pragma unroll
       for (int step = 0; step < STEPS; step++) {
         if (step + 2 < STEPS) { B[(step + 2) % 3][0] = wf(step + 2, 0); B[(step + 2) % 3][1] = wf(step + 2, 1); }
@@ -409,14 +275,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
 #pragma unroll
         for (int ms = 0; ms < TH; ms++) {
           f32x4 c = acc2[ms];
-          c = st_mfma(B[step % 3][1], Xf[ms][0], c);
-          c = st_mfma(B[step % 3][0], Xf[ms][1], c);
-          acc2[ms] = st_mfma(B[step % 3][0], Xf[ms][0], c);
+          c = p2_mfma(B[step % 3][1], Xf[ms][0], c);
+          c = p2_mfma(B[step % 3][0], Xf[ms][1], c);
+          acc2[ms] = p2_mfma(B[step % 3][0], Xf[ms][0], c);
         }
       }
-#endif
     }
-    ST_ACC(3);
+    P2F_ACC(3);
     __builtin_amdgcn_s_setprio(P2_VALU_PRIO);
     // ---- BN2 + ReLU + max |x| + split, 16-byte stores ------------------------------------------------------------------------------
     float amax = 0.f;
@@ -449,22 +314,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
         if (atomicAdd(&wgred[1], 1u) == 3u) {
           const unsigned m = atomicExch(&wgred[0], 0u);
           wgred[1] = 0u;
-          p2_slot_put(a.out_row + (int64_t)n * P2_ROW, (oy0 / TH) * a.tiles_x + ox0 / TW, tiles_img, m);
+          p2_slot_put(a.out_row + (int64_t)n * P2_ROW, (oy0 / TH) * a.walk.tiles_x + ox0 / TW, tiles_img, m);
         }
       }
     }
     __builtin_amdgcn_s_setprio(0);
-    ST_ACC(4);
+    P2F_ACC(4);
     if (!have_next) break;
     x_amax_cur = p2_row_amax(row_in);  // (the next tile's image)
     p2_scale_of(x_amax_cur, x_mul_cur, x_inv_cur);
     store_patch(x_mul_cur);  // (every wave passed the barrier behind conv1: the patch buffer is free)
-    ST_ACC(5);
+    P2F_ACC(5);
     __syncthreads();  // every wave is done with Y1, the next patch is visible
-    ST_ACC(6);
+    P2F_ACC(6);
     tile = next_tile;
   }
-  ST_FLUSH;
+  P2F_FLUSH;
 }
 
 int mval_conv_stem_p2_supported(int N, int H, int W) {
@@ -485,12 +350,8 @@ int mval_launch_conv_stem_p2(const float* in, void* out, const float* w1, const 
   a.N = N; a.H = H; a.W = W;
   a.H1 = (H - 1) / 2 + 1; a.W1 = (W - 1) / 2 + 1;
   a.H2 = (a.H1 - 1) / 2 + 1; a.W2 = (a.W1 - 1) / 2 + 1;
-  a.tiles_x = (a.W2 + 15) / 16;
-  a.tiles_y = (a.H2 + 1) / 2;
-  const int tiles_img = a.tiles_x * a.tiles_y;
-  a.tiles_total = tiles_img * N;
-  a.tiles_img_magic = tiles_img > 1 ? (unsigned)(((uint64_t)1 << 32) / (unsigned)tiles_img + 1) : 0u;
-  a.tiles_x_magic = a.tiles_x > 1 ? (unsigned)(((uint64_t)1 << 32) / (unsigned)a.tiles_x + 1) : 0u;
+  p2_walk_fill(a.walk, a.H2, a.W2, 2, 16, N);
+  const int tiles_img = a.walk.tiles_x * a.walk.tiles_y;
   // max |x| per image: 64 partial slots of the input's rows
   hipLaunchKernelGGL(image_amax_rows_kernel, dim3(64, (unsigned)N), dim3(256), 0, s, in, (int64_t)3 * H * W, in_row);
   constexpr size_t smem = 2 * 8 * 170 * 16 + 3 * 11 * 68 * 4 + 16 + 512;
@@ -500,16 +361,11 @@ int mval_launch_conv_stem_p2(const float* in, void* out, const float* w1, const 
   const char* pe = getenv("MVAL_P2_WGS_BS");
   if (pe && atoi(pe) > 0) per_cu = atoi(pe);
 #endif
-  int wgs = mval_cu_count() * per_cu;
-  if (wgs >= a.tiles_total) wgs = a.tiles_total;
-  else {
-    const int per = (a.tiles_total + 7) / 8, rounds = (per + wgs / 8 - 1) / (wgs / 8);
-    wgs = 8 * ((per + rounds - 1) / rounds);
-  }
+  const int wgs = mval_p2_walk_grid(a.walk.tiles_total, mval_cu_count() * per_cu, 1);
 #ifdef P2_STAMP
   a.dbg = g_p2_dbg_shared;
 #endif
-  a.wgs_x = wgs;
+  a.walk.wgs_x = wgs;
   if (tiles_img > P2_SLOTS) mval_launch_zero_rows(out_row, (int64_t)N * P2_ROW, s);
   hipLaunchKernelGGL(conv_stem_p2_kernel, dim3((unsigned)wgs), dim3(256), smem, s, a);
   return 0;

@@ -120,7 +120,9 @@ def test_p2_conv_vs_float64(dev, case):
         assert rms <= 1.25 * rms32 + 1e-8, (rms, rms32)
 
 
-@pytest.mark.parametrize("shape", [(3, 32, 64, 64), (2, 64, 32, 32), (2, 32, 21, 37), (1, 64, 9, 16), (5, 32, 8, 16), (2, 64, 24, 40), (2, 32, 96, 72)],
+@pytest.mark.parametrize("shape", [(3, 32, 64, 64), (2, 64, 32, 32), (2, 32, 21, 37), (1, 64, 9, 16), (5, 32, 8, 16), (2, 64, 24, 40), (2, 32, 96, 72),
+                                   # 12 tiles of 8 x 16: 8 or more and no multiple of 8 -- the grid is rounded up to 16 and four workgroups have no tile
+                                   (1, 32, 48, 32), (1, 64, 48, 32)],
                          ids=lambda s: "n%d_c%d_%dx%d" % s)
 def test_p2_basic_block_vs_float64(dev, shape):
     """MVAL_OP_BLOCK over P2 activations (hrnet.py:19-52 in one launch) against float64, against the same block as two
@@ -152,7 +154,9 @@ def test_p2_basic_block_vs_float64(dev, shape):
 
 
 @pytest.mark.parametrize("shape", [(2, 256, 64, 64, False), (2, 64, 64, 64, True), (3, 256, 21, 37, False), (1, 64, 9, 16, True), (2, 256, 96, 72, False),
-                                   (2, 256, 64, 48, True), (5, 64, 8, 16, True)], ids=lambda s: "n%d_c%d_%dx%d_r%d" % s)
+                                   (2, 256, 64, 48, True), (5, 64, 8, 16, True),
+                                   (1, 64, 48, 32, True)],  # 12 tiles (test_p2_basic_block_vs_float64)
+                         ids=lambda s: "n%d_c%d_%dx%d_r%d" % s)
 def test_p2_bottleneck_vs_float64(dev, shape):
     """MVAL_OP_BNECK over P2 activations (hrnet.py:75-95 with 64 planes in one launch: the blocks of HRNet's layer1) against
     float64, against the same block as three P2 conv launches (not less accurate), kept max |x|, and image 0 alone gives the
@@ -189,7 +193,9 @@ def test_p2_bottleneck_vs_float64(dev, shape):
     assert torch.equal(alone[0], got[0])
 
 
-@pytest.mark.parametrize("shape", [(2, 256, 256), (3, 64, 64), (1, 384, 288), (2, 100, 76), (1, 16, 64)], ids=lambda s: "n%d_%dx%d" % s)
+@pytest.mark.parametrize("shape", [(2, 256, 256), (3, 64, 64), (1, 384, 288), (2, 100, 76), (1, 16, 64),
+                                   # 48 x 64 outputs in 2 x 16 tiles (2 x 96 tiles), and 12 tiles in all (2 x 6 on 12 x 16 outputs): a grid of 16 for 12 tiles
+                                   (2, 192, 256), (2, 48, 64)], ids=lambda s: "n%d_%dx%d" % s)
 def test_p2_stem_vs_float64(dev, shape):
     """MVAL_OP_STEM_P2 (hrnet.py:303-310: both stride-2 stem convs in one launch, fp32 NCHW image -> P2 planes) against
     float64, against the stand-alone fp32 stem kernel followed by a P2 conv launch (not less accurate), kept max |x|, and

@@ -122,6 +122,16 @@ int mval_score_maps(int kind, const float* heatmaps, float* stat, int32_t* n_pea
 int mval_score_decode_maps(int kind, const float* heatmaps, const uint8_t* valid, float* stat, int32_t* n_peaks,
                            int64_t* kp2d, int B, int V, int J, int hh, int wh, int stride, int split_width, void* stream);
 
+/* ALL THREE statistics AND (kp2d non-NULL) the hard arg-max key-point of every map from one staged read of each heat-map:
+ * what comparing the strategies on one pool needs per map.  Every output equals, bit for bit, what the single-kind entries
+ * above write (each statistic runs the same float operations in the same order); a map whose candidate list overflows
+ * for one statistic has that statistic alone redone by the second pass.
+ *   heatmaps [B,V,J,hh,wh] f32 ; valid [B,J] u8 or NULL (only read for kp2d) ;
+ *   stat [3][B*V*J] f32: MVAL_SCORE_HP, _MPE, _BSB in that order ; n_peaks [2][B*V*J] i32: MPE, BSB (as mval_score_maps
+ *   writes them) ; kp2d [B,V,J,2] i64 (x, y) or NULL = no decode (stride and split_width are ignored then). */
+int mval_score_decode_maps_all(const float* heatmaps, const uint8_t* valid, float* stat, int32_t* n_peaks, int64_t* kp2d,
+                               int B, int V, int J, int hh, int wh, int stride, int split_width, void* stream);
+
 /* AVG / STD over the valid (view, joint) maps of each frame in the reference's python /
  * numpy evaluation order and precision (strategy.py:1151-1155,1188-1193,1210-1215;
  * SURVEY A.8).  per_map [B,V,J] f32 ; valid [B,J] u8 or NULL ; out [B] f64. */

@@ -272,6 +272,23 @@ def score_decode_maps(kind, hm, valid, b, v, j, hh, wh, stride, split_width):
     return out, cnt, kp
 
 
+def score_decode_maps_all(hm, valid, b, v, j, hh, wh, stride, split_width, decode=True):
+    """HP, MPE and BSB of every map (+ the hard arg-max key-points when ``decode``) from ONE read of the heat-maps:
+    (stat (3, n) float32 in SCORE_HP/_MPE/_BSB order, n_peaks (2, n) int32 for MPE and BSB, kp2d (B,V,J,2) int64 or None)."""
+    n_maps = b * v * j
+    out = torch.empty((3, n_maps), dtype=torch.float32, device=hm.device)
+    cnt = torch.empty((2, n_maps), dtype=torch.int32, device=hm.device)
+    kp = torch.empty((b, v, j, 2), dtype=torch.int64, device=hm.device) if decode else None
+    _check(
+        lib().mval_score_decode_maps_all(
+            _p(_req(hm, torch.float32, "heatmaps")), _p(valid), _p(out), _p(cnt), _p(kp),
+            C.c_int(b), C.c_int(v), C.c_int(j), C.c_int(hh), C.c_int(wh), C.c_int(stride), C.c_int(split_width), _stream(),
+        ),
+        "mval_score_decode_maps_all",
+    )
+    return out, cnt, kp
+
+
 def score_reduce(per_map, valid, b, v, j, mode):
     out = torch.empty((b,), dtype=torch.float64, device=per_map.device)
     _check(

@@ -77,28 +77,14 @@ struct ScoreDecodeArgs {
   int V, J, stride, split_width;
 };
 
-template <int KIND, bool DECODE>
-__global__ __launch_bounds__(SC_THREADS) void score_maps_kernel(const float* __restrict__ hm, float* __restrict__ stat,
-                                                                int32_t* __restrict__ n_peaks, int hh, int wh,
-                                                                ScoreDecodeArgs d, int cap, int rescue) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const int ld = wh + 1;
-  float* tile = reinterpret_cast<float*>(smem_raw);                      // hh * ld
-  // (the HP kernel has no candidate list: its workgroups need only the tile, so twice as many fit a CU)
-  float* cval = tile + (((hh * ld) + 3) & ~3);                           // cap
-  int* cidx = reinterpret_cast<int*>(cval + (KIND == MVAL_SCORE_HP ? 0 : cap));  // cap
-  ScoreSmem* sm = reinterpret_cast<ScoreSmem*>(cidx + (KIND == MVAL_SCORE_HP ? 0 : cap));
-  const int tid = threadIdx.x;
-  const int64_t map = blockIdx.x;
-  // second pass (candidate list as large as the map's interior, one workgroup per CU): only the maps whose list
-  // overflowed SC_MAX_PEAKS in the first pass -- wide plateaus: flat backgrounds -- are redone
-  if (rescue && n_peaks[map] != -1) return;
-  const float* p = hm + map * (int64_t)hh * wh;
-  const int npix = hh * wh;
+// The stages of a scoring workgroup.  score_maps_kernel (one statistic) and score_maps_all_kernel (all three) are built from the same
+// stages, so a statistic goes through the same float operations in the same order whichever kernel computes it.
 
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
-  float vmin = INFINITY;  // min of the map the peaks are searched in (MPE: the heat-map, here; BSB: its row softmax, below)
+// Stage the map into the padded tile; WANT_MIN: the minimum of the raw map (what MPE's peaks have to exceed); DECODE: the thread's
+// arg-max candidate (bv, bi).
+template <bool WANT_MIN, bool DECODE>
+__device__ __forceinline__ void sc_stage(const float* __restrict__ p, float* tile, int hh, int wh, float& vmin, float& bv, int& bi) {
+  const int tid = threadIdx.x, ld = wh + 1, npix = hh * wh;
   if ((npix & 3) == 0 && (wh & 3) == 0) {  // float4 loads (maps are 16-byte aligned then); a quad never straddles rows
     const float4* p4 = reinterpret_cast<const float4*>(p);
     for (int i = tid; i < (npix >> 2); i += SC_THREADS) {
@@ -107,7 +93,7 @@ __global__ __launch_bounds__(SC_THREADS) void score_maps_kernel(const float* __r
       const int y = base / wh, x = base - y * wh;
       float* t = tile + y * ld + x;
       t[0] = q.x; t[1] = q.y; t[2] = q.z; t[3] = q.w;
-      if (KIND == MVAL_SCORE_MPE) vmin = fminf(fminf(vmin, fminf(q.x, q.y)), fminf(q.z, q.w));
+      if (WANT_MIN) vmin = fminf(fminf(vmin, fminf(q.x, q.y)), fminf(q.z, q.w));
       if (DECODE) {
         // a thread meets its pixels in increasing index order, so "strictly greater, or the first NaN" is the whole
         // torch.argmax order here (the cross-lane reduction below uses the full comparison)
@@ -122,76 +108,88 @@ __global__ __launch_bounds__(SC_THREADS) void score_maps_kernel(const float* __r
       const int y = i / wh, x = i - y * wh;
       const float q = p[i];
       tile[y * ld + x] = q;
-      if (KIND == MVAL_SCORE_MPE) vmin = fminf(vmin, q);
+      if (WANT_MIN) vmin = fminf(vmin, q);
       if (DECODE && (q > bv || (q != q && bv == bv))) { bv = q; bi = i; }
     }
   }
-  if (tid == 0) { sm->n_cand = 0; sm->overflow = 0; sm->adjacent = 0; }
-  if (DECODE) {
+}
+
+// arg-max across the lanes of each wave, left in red[16..23] for sc_argmax_write (after a barrier)
+struct ScArg { float v; int i; };
+__device__ __forceinline__ ScArg sc_argmax_wave(float bv, int bi, ScoreSmem* sm) {
+  const int tid = threadIdx.x;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (sc_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    // (slots 16.. of red[]: the reductions further down use 0..3, so no barrier is needed between the two)
-    if ((tid & 63) == 0) { sm->red[16 + (tid >> 6)] = bv; sm->red[20 + (tid >> 6)] = __int_as_float(bi); }
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (sc_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
   }
-  __syncthreads();
-  if (DECODE && tid == 0) {
-    for (int w = 1; w < SC_THREADS / 64; w++) {
-      const float ov = sm->red[16 + w];
-      const int oi = __float_as_int(sm->red[20 + w]);
-      if (sc_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (bi == 0x7fffffff) bi = 0;  // all -inf: first element
-    const int j = (int)(map % d.J);
-    const int64_t b = map / ((int64_t)d.V * d.J);
-    const bool ok = !d.valid || d.valid[b * d.J + j];
-    d.kp2d[map * 2] = ok ? (int64_t)(bi % d.split_width) * d.stride : 0;
-    d.kp2d[map * 2 + 1] = ok ? (int64_t)(bi / d.split_width) * d.stride : 0;
+  // (slots 16.. of red[]: the reductions further down use 0..3, so no barrier is needed between the two)
+  if ((tid & 63) == 0) { sm->red[16 + (tid >> 6)] = bv; sm->red[20 + (tid >> 6)] = __int_as_float(bi); }
+  return {bv, bi};
+}
+__device__ __forceinline__ void sc_argmax_write(float bv, int bi, const ScoreSmem* sm, int64_t map, const ScoreDecodeArgs& d) {
+  if (threadIdx.x != 0) return;
+  for (int w = 1; w < SC_THREADS / 64; w++) {
+    const float ov = sm->red[16 + w];
+    const int oi = __float_as_int(sm->red[20 + w]);
+    if (sc_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
   }
+  if (bi == 0x7fffffff) bi = 0;  // all -inf: first element
+  const int j = (int)(map % d.J);
+  const int64_t b = map / ((int64_t)d.V * d.J);
+  const bool ok = !d.valid || d.valid[b * d.J + j];
+  d.kp2d[map * 2] = ok ? (int64_t)(bi % d.split_width) * d.stride : 0;
+  d.kp2d[map * 2 + 1] = ok ? (int64_t)(bi / d.split_width) * d.stride : 0;
+}
 
-  // ---- row-wise softmax statistics (HP, BSB): T lanes per row ---------------------------------
-  if (KIND == MVAL_SCORE_HP || KIND == MVAL_SCORE_BSB) {
-    int T = 1;
-    while (T < 16 && T * 2 * hh <= SC_THREADS) T <<= 1;  // 4 lanes per row on 64-row maps, 2 on 96-row maps
-    const int sub = tid & (T - 1);
-    float best = 0.f;
-    const int rows_per_pass = SC_THREADS / T;
-    for (int r0 = 0; r0 < hh; r0 += rows_per_pass) {  // every thread makes every pass: the shuffles need whole lane groups
-      const int r = r0 + tid / T;
-      const bool live = r < hh;
-      float* row = tile + (live ? r : 0) * ld;
-      // lane `sub` owns the contiguous column segment [c0, c1): with the odd row stride (wh + 1) the 64 lanes of a
-      // wave (16 rows x 4 segments on 64-wide maps) then hit 64 different banks (interleaved columns: 2-4-way conflicts)
-      const int seg = (wh + T - 1) / T, c0 = sub * seg, c1 = min(wh, c0 + seg);
-      float m = -INFINITY;
-      for (int c = c0; c < c1; c++) m = fmaxf(m, row[c]);
-      for (int o = T >> 1; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-      // the reference sums exp(x - m) over a row left to right in float32 (torch softmax on CPU vectorises, so the
-      // last bits differ anyway: tests allow 3e-6 relative); partial sums over the lanes' segments here
-      float s = 0.f;
-      for (int c = c0; c < c1; c++) s += expf(row[c] - m);
-      for (int o = T >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-      if (KIND == MVAL_SCORE_BSB && live) {
-        for (int c = c0; c < c1; c++) {
-          const float q = expf(row[c] - m) / s;
-          row[c] = q;
-          vmin = fminf(vmin, q);
-        }
+// ---- row-wise softmax statistics (HP, BSB): T lanes per row ---------------------------------
+// Returns the thread's max over its rows of 1 / sum_c exp(x_rc - max_c x_rc) (HP, before the block reduction).  OVERWRITE (BSB):
+// the tile becomes its row softmax and vmin is folded with the values written.
+template <bool OVERWRITE>
+__device__ __forceinline__ float sc_row_softmax(float* tile, int hh, int wh, float& vmin) {
+  const int tid = threadIdx.x, ld = wh + 1;
+  int T = 1;
+  while (T < 16 && T * 2 * hh <= SC_THREADS) T <<= 1;  // 4 lanes per row on 64-row maps, 2 on 96-row maps
+  const int sub = tid & (T - 1);
+  float best = 0.f;
+  const int rows_per_pass = SC_THREADS / T;
+  for (int r0 = 0; r0 < hh; r0 += rows_per_pass) {  // every thread makes every pass: the shuffles need whole lane groups
+    const int r = r0 + tid / T;
+    const bool live = r < hh;
+    float* row = tile + (live ? r : 0) * ld;
+    // lane `sub` owns the contiguous column segment [c0, c1): with the odd row stride (wh + 1) the 64 lanes of a
+    // wave (16 rows x 4 segments on 64-wide maps) then hit 64 different banks (interleaved columns: 2-4-way conflicts)
+    const int seg = (wh + T - 1) / T, c0 = sub * seg, c1 = min(wh, c0 + seg);
+    float m = -INFINITY;
+    for (int c = c0; c < c1; c++) m = fmaxf(m, row[c]);
+    for (int o = T >> 1; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    // the reference sums exp(x - m) over a row left to right in float32 (torch softmax on CPU vectorises, so the
+    // last bits differ anyway: tests allow 3e-6 relative); partial sums over the lanes' segments here
+    float s = 0.f;
+    for (int c = c0; c < c1; c++) s += expf(row[c] - m);
+    for (int o = T >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (OVERWRITE && live) {
+      for (int c = c0; c < c1; c++) {
+        const float q = expf(row[c] - m) / s;
+        row[c] = q;
+        vmin = fminf(vmin, q);
       }
-      if (live) best = fmaxf(best, 1.0f / s);
     }
-    if (KIND == MVAL_SCORE_HP) {
-      best = block_reduce_max(best, sm->red);
-      if (tid == 0) { stat[map] = 1.0f - best; n_peaks[map] = 0; }
-      return;
-    }
-    __syncthreads();
+    if (live) best = fmaxf(best, 1.0f / s);
   }
+  return best;
+}
 
-  // ---- peak_local_max(min_distance=2) -------------------------------------------------
+// ---- peak_local_max(min_distance=2) of the tile -------------------------------------------------
+// The counters of a peak search; a barrier has to lie between this and sc_candidates (and behind the last reader of an earlier search).
+__device__ __forceinline__ void sc_peaks_reset(ScoreSmem* sm) {
+  if (threadIdx.x == 0) { sm->n_cand = 0; sm->overflow = 0; sm->adjacent = 0; }
+}
+// Candidates (5x5 maxima above the minimum) into cval / cidx, unordered; `vmin`: the thread's part of the tile's minimum.  Ends with a
+// barrier; sm->overflow says afterwards whether they fitted `cap`, sm->n_cand how many there are.
+__device__ __forceinline__ void sc_candidates(const float* tile, float* cval, int* cidx, ScoreSmem* sm, int hh, int wh, int cap, float vmin) {
+  const int tid = threadIdx.x, ld = wh + 1;
   vmin = block_reduce_min(vmin, sm->red);
   const int ih = hh - 4, iw = wh - 4;  // interior after the 2-px border exclusion
   auto put = [&](float v, int idx) {
@@ -238,10 +236,11 @@ __global__ __launch_bounds__(SC_THREADS) void score_maps_kernel(const float* __r
     }
   }
   __syncthreads();
-  if (sm->overflow) {
-    if (tid == 0) { stat[map] = NAN; n_peaks[map] = -1; }
-    return;
-  }
+}
+// Sort (value desc, index asc) and spacing pass of a candidate list that fitted: returns the number of peaks, left in cval / cidx.
+// Ends with a barrier; sm->adjacent says afterwards whether the spacing pass has used the tile's memory.
+__device__ __forceinline__ int sc_sort_and_space(float* tile, float* cval, int* cidx, ScoreSmem* sm, int hh, int wh) {
+  const int tid = threadIdx.x, ld = wh + 1;
   int n = sm->n_cand;
   if (n <= SC_THREADS) {
     // short lists (what network outputs give: a handful to ~200 candidates): RANK sort -- thread i counts the candidates that come
@@ -357,16 +356,12 @@ __global__ __launch_bounds__(SC_THREADS) void score_maps_kernel(const float* __r
     if (lane == 0) sm->n_cand = kept;
   }
   __syncthreads();
-  n = sm->n_cand;  // (unchanged without ties)
+  return sm->n_cand;  // (unchanged without ties)
+}
 
-  if (KIND == MVAL_SCORE_BSB) {
-    if (tid == 0) {
-      n_peaks[map] = n;
-      stat[map] = (n >= 2) ? fabsf(cval[0] - cval[1]) : NAN;  // reference: IndexError when < 2 peaks
-    }
-    return;
-  }
-  // ---- MPE entropy (strategy.py:1171-1175) --------------------------------------------
+// ---- MPE entropy of the n sorted peaks in cval (strategy.py:1171-1175); the result is thread 0's -----------------------------------
+__device__ __forceinline__ float sc_entropy(float* cval, int n, ScoreSmem* sm) {
+  const int tid = threadIdx.x;
   for (int i = tid; i < n; i += SC_THREADS) cval[i] = expf(cval[i]);
   __syncthreads();
   if (tid == 0) sm->ssum = serial_sum_lds(cval, n);  // python sum(): left to right in float32
@@ -378,10 +373,139 @@ __global__ __launch_bounds__(SC_THREADS) void score_maps_kernel(const float* __r
     cval[i] = (-pr) * (float)log((double)pr);
   }
   __syncthreads();
-  if (tid == 0) {
-    stat[map] = serial_sum_lds(cval, n);  // no peaks -> python int 0
-    n_peaks[map] = n;
+  return tid == 0 ? serial_sum_lds(cval, n) : 0.f;  // no peaks -> python int 0
+}
+
+template <int KIND, bool DECODE>
+__global__ __launch_bounds__(SC_THREADS) void score_maps_kernel(const float* __restrict__ hm, float* __restrict__ stat,
+                                                                int32_t* __restrict__ n_peaks, int hh, int wh,
+                                                                ScoreDecodeArgs d, int cap, int rescue) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int ld = wh + 1;
+  float* tile = reinterpret_cast<float*>(smem_raw);                      // hh * ld
+  // (the HP kernel has no candidate list: its workgroups need only the tile, so twice as many fit a CU)
+  float* cval = tile + (((hh * ld) + 3) & ~3);                           // cap
+  int* cidx = reinterpret_cast<int*>(cval + (KIND == MVAL_SCORE_HP ? 0 : cap));  // cap
+  ScoreSmem* sm = reinterpret_cast<ScoreSmem*>(cidx + (KIND == MVAL_SCORE_HP ? 0 : cap));
+  const int tid = threadIdx.x;
+  const int64_t map = blockIdx.x;
+  // second pass (candidate list as large as the map's interior, one workgroup per CU): only the maps whose list
+  // overflowed SC_MAX_PEAKS in the first pass -- wide plateaus: flat backgrounds -- are redone
+  if (rescue && n_peaks[map] != -1) return;
+
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  float vmin = INFINITY;  // min of the map the peaks are searched in (MPE: the heat-map, here; BSB: its row softmax, below)
+  sc_stage<KIND == MVAL_SCORE_MPE, DECODE>(hm + map * (int64_t)hh * wh, tile, hh, wh, vmin, bv, bi);
+  sc_peaks_reset(sm);
+  if (DECODE) { const ScArg a = sc_argmax_wave(bv, bi, sm); bv = a.v; bi = a.i; }
+  __syncthreads();
+  if (DECODE) sc_argmax_write(bv, bi, sm, map, d);
+
+  if (KIND == MVAL_SCORE_HP || KIND == MVAL_SCORE_BSB) {
+    float best = sc_row_softmax<KIND == MVAL_SCORE_BSB>(tile, hh, wh, vmin);
+    if (KIND == MVAL_SCORE_HP) {
+      best = block_reduce_max(best, sm->red);
+      if (tid == 0) { stat[map] = 1.0f - best; n_peaks[map] = 0; }
+      return;
+    }
+    __syncthreads();
   }
+
+  sc_candidates(tile, cval, cidx, sm, hh, wh, cap, vmin);
+  if (sm->overflow) {
+    if (tid == 0) { stat[map] = NAN; n_peaks[map] = -1; }
+    return;
+  }
+  const int n = sc_sort_and_space(tile, cval, cidx, sm, hh, wh);
+  if (KIND == MVAL_SCORE_BSB) {
+    if (tid == 0) {
+      n_peaks[map] = n;
+      stat[map] = (n >= 2) ? fabsf(cval[0] - cval[1]) : NAN;  // reference: IndexError when < 2 peaks
+    }
+    return;
+  }
+  const float h = sc_entropy(cval, n, sm);
+  if (tid == 0) { stat[map] = h; n_peaks[map] = n; }
+}
+
+// All three statistics (and, DECODE, the key-point) of a map from ONE staged copy: the hard arg-max and MPE on the raw tile, then the
+// row softmax (HP) overwrites it for BSB.  MPE's spacing pass takes the tile's memory on maps with plateaus (sc_sort_and_space): those maps
+// alone are staged a second time, from L2.  LDS: the tile and ONE candidate list, which MPE and BSB use in turn.
+//   stat [3][n_maps] (HP, MPE, BSB) ; n_peaks [2][n_maps] (MPE, BSB).
+// RESCUE (second pass, candidate list as large as the map's interior): a workgroup redoes the statistics whose n_peaks is -1 -- MPE,
+// BSB or both -- and writes nothing else: HP, the key-point and a statistic that did fit keep what the first pass wrote.
+template <bool DECODE, bool RESCUE>
+__global__ __launch_bounds__(SC_THREADS) void score_maps_all_kernel(const float* __restrict__ hm, float* __restrict__ stat,
+                                                                    int32_t* __restrict__ n_peaks, int64_t n_maps, int hh, int wh,
+                                                                    ScoreDecodeArgs d, int cap) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int ld = wh + 1;
+  float* tile = reinterpret_cast<float*>(smem_raw);     // hh * ld
+  float* cval = tile + (((hh * ld) + 3) & ~3);          // cap
+  int* cidx = reinterpret_cast<int*>(cval + cap);       // cap
+  ScoreSmem* sm = reinterpret_cast<ScoreSmem*>(cidx + cap);
+  const int tid = threadIdx.x;
+  const int64_t map = blockIdx.x;
+  float* stat_mpe = stat + n_maps + map;
+  float* stat_bsb = stat + 2 * n_maps + map;
+  int32_t* cnt_mpe = n_peaks + map;
+  int32_t* cnt_bsb = n_peaks + n_maps + map;
+  const bool do_mpe = !RESCUE || *cnt_mpe == -1, do_bsb = !RESCUE || *cnt_bsb == -1;  // (the same for every thread of the workgroup)
+  if (!do_mpe && !do_bsb) return;
+  const float* p = hm + map * (int64_t)hh * wh;
+
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  float vmin = INFINITY;
+  sc_stage<true, DECODE>(p, tile, hh, wh, vmin, bv, bi);
+  sc_peaks_reset(sm);
+  if (DECODE) { const ScArg a = sc_argmax_wave(bv, bi, sm); bv = a.v; bi = a.i; }
+  __syncthreads();
+  if (DECODE) sc_argmax_write(bv, bi, sm, map, d);
+
+  if (do_mpe) {
+    sc_candidates(tile, cval, cidx, sm, hh, wh, cap, vmin);
+    if (sm->overflow) {
+      if (tid == 0) { *stat_mpe = NAN; *cnt_mpe = -1; }
+    } else {
+      const int n = sc_sort_and_space(tile, cval, cidx, sm, hh, wh);
+      const bool clobbered = sm->adjacent != 0;
+      const float h = sc_entropy(cval, n, sm);
+      if (tid == 0) { *stat_mpe = h; *cnt_mpe = n; }
+      if (clobbered) {  // (every thread is past its last use of the tile: sc_sort_and_space ends with a barrier)
+        sc_stage<false, false>(p, tile, hh, wh, vmin, bv, bi);
+        __syncthreads();
+      }
+    }
+  }
+  if (!do_bsb) return;
+
+  vmin = INFINITY;  // BSB's peaks are searched in the row softmax: its minimum
+  float best = sc_row_softmax<true>(tile, hh, wh, vmin);
+  if (!RESCUE) {
+    best = block_reduce_max(best, sm->red);
+    if (tid == 0) stat[map] = 1.0f - best;
+  }
+  __syncthreads();  // (every reader of MPE's counters and thread 0's serial entropy sum over cval are behind it: the list is free)
+  if (do_mpe) sc_peaks_reset(sm);  // (the barrier inside sc_candidates lies between this and the first candidate)
+  sc_candidates(tile, cval, cidx, sm, hh, wh, cap, vmin);
+  if (sm->overflow) {
+    if (tid == 0) { *stat_bsb = NAN; *cnt_bsb = -1; }
+    return;
+  }
+  const int n = sc_sort_and_space(tile, cval, cidx, sm, hh, wh);
+  if (tid == 0) {
+    *cnt_bsb = n;
+    *stat_bsb = (n >= 2) ? fabsf(cval[0] - cval[1]) : NAN;  // reference: IndexError when < 2 peaks
+  }
+}
+
+// the candidate list never needs more than the interior (hh-4)(wh-4), rounded up to the sort's power of two
+static int score_full_cap(int hh, int wh) {
+  int full = 4;  // (at least one 16-byte group: the rank sort reads the list four candidates at a time)
+  while (full < (hh - 4) * (wh - 4)) full <<= 1;
+  return full;
 }
 
 template <bool DECODE>
@@ -389,9 +513,7 @@ static int launch_score(int kind, const float* heatmaps, float* stat, int32_t* n
                         const ScoreDecodeArgs& d, hipStream_t s) {
   const size_t tile_b = (size_t)((hh * (wh + 1) + 3) & ~3) * 4, fixed_b = sizeof(ScoreSmem) + 16;
   dim3 grid((unsigned)n_maps), block(SC_THREADS);
-  // the candidate list never needs more than the interior (hh-4)(wh-4), rounded up to the sort's power of two
-  int full = 4;  // (at least one 16-byte group: the rank sort reads the list four candidates at a time)
-  while (full < (hh - 4) * (wh - 4)) full <<= 1;
+  const int full = score_full_cap(hh, wh);
   for (int pass = 0; pass < 2; pass++) {
     const int cap = pass == 0 ? (full < SC_MAX_PEAKS ? full : SC_MAX_PEAKS) : full;
     if (pass == 1 && (kind == MVAL_SCORE_HP || full <= SC_MAX_PEAKS)) break;
@@ -409,6 +531,29 @@ static int launch_score(int kind, const float* heatmaps, float* stat, int32_t* n
       hipLaunchKernelGGL((score_maps_kernel<MVAL_SCORE_MPE, DECODE>), grid, block, smem, s, heatmaps, stat, n_peaks, hh, wh, d, cap, pass);
     else
       hipLaunchKernelGGL((score_maps_kernel<MVAL_SCORE_BSB, DECODE>), grid, block, smem, s, heatmaps, stat, n_peaks, hh, wh, d, cap, pass);
+  }
+  return 0;
+}
+
+// first pass: every map, all statistics; second pass (only where a list can overflow at all): the overflowed statistics alone
+template <bool DECODE>
+static int launch_score_all(const float* heatmaps, float* stat, int32_t* n_peaks, int64_t n_maps, int hh, int wh,
+                            const ScoreDecodeArgs& d, hipStream_t s) {
+  const size_t tile_b = (size_t)((hh * (wh + 1) + 3) & ~3) * 4, fixed_b = sizeof(ScoreSmem) + 16;
+  dim3 grid((unsigned)n_maps), block(SC_THREADS);
+  const int full = score_full_cap(hh, wh);
+  for (int pass = 0; pass < 2; pass++) {
+    const int cap = pass == 0 ? (full < SC_MAX_PEAKS ? full : SC_MAX_PEAKS) : full;
+    if (pass == 1 && full <= SC_MAX_PEAKS) break;
+    const size_t smem = tile_b + (size_t)cap * 8 + fixed_b;
+    if (smem > 160 * 1024) return pass == 0 ? 1 : 0;  // (no room for the rescue: overflowed maps keep NaN / -1)
+    const void* fn = pass == 0 ? (const void*)score_maps_all_kernel<DECODE, false> : (const void*)score_maps_all_kernel<false, true>;
+    if (smem > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+      return pass == 0 ? 1 : 0;
+    if (pass == 0)
+      hipLaunchKernelGGL((score_maps_all_kernel<DECODE, false>), grid, block, smem, s, heatmaps, stat, n_peaks, n_maps, hh, wh, d, cap);
+    else
+      hipLaunchKernelGGL((score_maps_all_kernel<false, true>), grid, block, smem, s, heatmaps, stat, n_peaks, n_maps, hh, wh, d, cap);
   }
   return 0;
 }
@@ -436,6 +581,21 @@ extern "C" int mval_score_decode_maps(int kind, const float* heatmaps, const uin
   MVAL_REQUIRE(launch_score<true>(kind, heatmaps, stat, n_peaks, n_maps, hh, wh, d, mval_stream(stream)) == 0,
                "mval_score_decode_maps: heat-map %dx%d does not fit LDS", hh, wh);
   MVAL_CHECK_LAUNCH("mval_score_decode_maps");
+  return 0;
+}
+
+extern "C" int mval_score_decode_maps_all(const float* heatmaps, const uint8_t* valid, float* stat, int32_t* n_peaks, int64_t* kp2d,
+                                          int B, int V, int J, int hh, int wh, int stride, int split_width, void* stream) {
+  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0, "mval_score_decode_maps_all: bad dims");
+  MVAL_REQUIRE(!kp2d || split_width > 0, "mval_score_decode_maps_all: split_width must be positive");
+  MVAL_REQUIRE(heatmaps && stat && n_peaks, "mval_score_decode_maps_all: heatmaps, stat and n_peaks must not be NULL");
+  const int64_t n_maps = (int64_t)B * V * J;
+  if (n_maps == 0) return 0;
+  ScoreDecodeArgs d = {valid, kp2d, V, J, stride, split_width};
+  const int rc = kp2d ? launch_score_all<true>(heatmaps, stat, n_peaks, n_maps, hh, wh, d, mval_stream(stream))
+                      : launch_score_all<false>(heatmaps, stat, n_peaks, n_maps, hh, wh, d, mval_stream(stream));
+  MVAL_REQUIRE(rc == 0, "mval_score_decode_maps_all: heat-map %dx%d does not fit LDS", hh, wh);
+  MVAL_CHECK_LAUNCH("mval_score_decode_maps_all");
   return 0;
 }
 

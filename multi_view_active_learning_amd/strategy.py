@@ -64,6 +64,65 @@ def score_decode_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid, s
     return out, per_map.reshape(b, v, j), n_peaks.reshape(b, v, j), valid, kp2d
 
 
+def score_decode_heatmaps_all(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True, decode=True):
+    """``score_decode_heatmaps_batch`` for several kinds from ONE read of the heat-maps (csrc/scoring.hip,
+    score_maps_all_kernel): ``configs`` maps "HP" / "MPE" / "BSB" to "AVG" / "STD".  One fused launch, then
+    ``mval_score_reduce`` per kind.  Returns an OrderedDict kind -> (out, per_map, n_peaks, valid, keypoints_2d), each
+    entry what ``score_decode_heatmaps_batch(kind, config, ...)`` returns (keypoints_2d None without ``decode``)."""
+    modes = OrderedDict((kind, _reduce_mode(kind, configs[kind])) for kind in configs)
+    for kind in modes:
+        if kind not in _KIND:
+            raise NotImplementedError("no heat-map statistic %r" % (kind,))
+    b, v, j, hh, wh = heatmaps.shape
+    hm = heatmaps.to(torch.float32).contiguous()
+    valid = (torch.as_tensor(joint_valid) != 0).to(torch.uint8).reshape(b, j).to(hm.device).contiguous()
+    stat, n_peaks, kp2d = _lib.score_decode_maps_all(hm, valid, b, v, j, hh, wh, int(stride),
+                                                     hh if mirror_nonsquare_quirk else wh, decode=decode)
+    counts = {"HP": None, "MPE": n_peaks[0], "BSB": n_peaks[1]}
+    res = OrderedDict()
+    for kind, mode in modes.items():
+        per_map = stat[_KIND[kind]]
+        cnt = torch.zeros_like(n_peaks[0]) if counts[kind] is None else counts[kind]  # (HP has no peaks: mval_score_maps writes 0)
+        res[kind] = (_lib.score_reduce(per_map, valid, b, v, j, mode), per_map.reshape(b, v, j), cnt.reshape(b, v, j), valid, kp2d)
+    return res
+
+
+AL_STRATEGIES = ("HP", "MPE", "BSB", "TRIANGULATION", "CORESET", "RANDOM")
+
+
+def check_strategies(strategies):
+    """The strategy list of a multi-strategy pass as a tuple: known names (NotImplementedError, as ``score_batch`` raises
+    for an unknown AL.STRATEGY), at least one, no duplicates (ValueError)."""
+    names = tuple(strategies)
+    for s in names:
+        if s not in AL_STRATEGIES:
+            raise NotImplementedError("unknown AL strategy %r (one of %s)" % (s, ", ".join(AL_STRATEGIES)))
+    if not names:
+        raise ValueError("at least one AL strategy expected")
+    if len(set(names)) != len(names):
+        raise ValueError("duplicate AL strategy in %r" % (names,))
+    return names
+
+
+def split_strategy_tables(per_rank, n_strategies):
+    """Per-rank tables of a multi-strategy pass, [pose, frame_id, -, sal_metric, inlier_count, mkpe, keypoints_3d(3J),
+    al_metric of strategy 0 .. E-1], -> one list of per-rank ``tables_to_sal_dict`` tables per strategy: the base
+    columns with that strategy's al_metric in column 2."""
+    out = []
+    for e in range(n_strategies):
+        tabs = []
+        for tab in per_rank:
+            tab = np.asarray(tab)
+            w = tab.shape[1] - n_strategies
+            if w < 6 or (w - 6) % 3:
+                raise ValueError("split_strategy_tables: %d columns do not hold 6 + 3J + %d" % (tab.shape[1], n_strategies))
+            t = tab[:, :w].copy()
+            t[:, 2] = tab[:, w + e]
+            tabs.append(t)
+        out.append(tabs)
+    return out
+
+
 def tables_to_sal_dict(per_rank, batch_sizes, sal_dict=None):
     """Packed per-rank tables [pose, frame_id, al_metric, sal_metric, inlier_count, mkpe,
     keypoints_3d(3J)] -> the reference's five dicts, inserted in its gather order
@@ -314,6 +373,100 @@ class ActiveLearningStrategy:
         if err is not None:
             raise err
         return tables_to_sal_dict(per_rank, per_rank_sizes, sal_dict)
+
+    def score_batch_all(self, heatmaps, dp, strategies):
+        """``score_batch`` for several strategies from one network output: one fused heat-map launch (when HP, MPE or BSB is
+        among them), one triangulation.  Returns a (B, 6 + 3J + E) float64 HIP table: ``score_batch``'s columns with
+        column 2 left 0, then the al_metric of each strategy, each what ``score_batch`` writes under that AL.STRATEGY."""
+        cfg = self.al_cfg
+        dev = heatmaps.device
+        pose = torch.as_tensor(dp["pose"]).reshape(-1)
+        b = pose.shape[0]
+        _, j, hh, wh = heatmaps.shape
+        hm = heatmaps.reshape(b, -1, j, hh, wh)
+        joint_valid = torch.as_tensor(dp["joint_valid"]).reshape(b, j)
+        configs = OrderedDict((s, getattr(cfg.AL, s + "_CONFIG")) for s in strategies if s in _KIND)
+        scored, kp2d = {}, None
+        if configs:
+            scored = score_decode_heatmaps_all(configs, hm, joint_valid, cfg.POSE_ESTIMATOR.STRIDE, decode=not cfg.AL.USE_SOFTARGMAX)
+            kp2d = next(iter(scored.values()))[4]
+        r = triangulation.triangulate_batch(
+            hm, dp["proj_matrices"], cfg.POSE_ESTIMATOR.STRIDE, joint_valid,
+            cfg.AL.USE_SOFTARGMAX, cfg.AL.USE_REPROJECTION_XE, cfg.AL.REPROJECTION_SIGMA,
+            keypoints_2d=kp2d,
+            pair_rng=random,
+            valid_joints_host=dp.get("joint_valid_host"),
+        )
+        pred32 = r["keypoints_3d"].to(torch.float32)
+        sal_metric = r["metric"].to(torch.float32).to(torch.float64)
+        als = []
+        for s in strategies:  # the precision rules of score_batch, strategy by strategy
+            if s == "RANDOM":
+                al = torch.cat([torch.rand(1) for _ in range(b)]).to(torch.float64).to(dev)
+            elif s == "TRIANGULATION":
+                al = r["metric"].to(torch.float64)
+            elif s == "CORESET":
+                al = torch.zeros(b, dtype=torch.float64, device=dev)
+            else:
+                al, _, n_peaks, valid = scored[s][:4]
+                self._pending_checks.append((s, n_peaks, valid))
+                if configs[s] == "AVG" or s != "HP":
+                    al = al.to(torch.float32).to(torch.float64)
+            als.append(al[:, None])
+        gt = torch.as_tensor(dp["3d_keypoints"]).to(dev)
+        mk = evaluation.mkpe_per_sample(pred32, gt, joint_valid.to(dev))
+        self._pending_checks.append(("INLIER", r["inlier_count"], None))
+        return torch.cat(
+            [
+                pose.to(dev, torch.float64)[:, None],
+                torch.as_tensor(dp["frame_id"]).reshape(b).to(dev, torch.float64)[:, None],
+                torch.zeros((b, 1), dtype=torch.float64, device=dev),
+                sal_metric[:, None],
+                r["inlier_count"].to(torch.float64)[:, None],
+                mk.to(torch.float64)[:, None],
+                pred32.to(torch.float64).reshape(b, 3 * j),
+            ] + als,
+            dim=1,
+        )
+
+    def _compute_sal_dicts(self, data_loader, pose_estimator, strategies):
+        """One pass over the pool for SEVERAL strategies: an OrderedDict strategy -> sal_dict in the order given, each equal
+        (values and key order) to ``_compute_sal_dict`` with AL.STRATEGY set to that strategy.  Per batch one network call,
+        one fused heat-map launch, one triangulation; per pass the one size exchange and one gather of ``gather_tables``
+        (the table is E columns wider).  Errors of a strategy that was not asked for are not raised."""
+        strategies = check_strategies(strategies)
+        self._pending_checks = []
+        tables, sizes = [], []
+        from .parallel import PostStream, _collectives_on, gather_tables
+
+        post = PostStream()
+        with torch.no_grad():
+            for dp in data_loader:
+                dp = _stage_batch(dp)
+                heatmaps = self._compute_batch_heatmap(pose_estimator, dp)
+                with post.batch(heatmaps, _lib.argmax_keys_of(heatmaps) if torch.is_tensor(heatmaps) and heatmaps.is_cuda else None, dp):
+                    t = self.score_batch_all(heatmaps, dp, strategies)
+                tables.append(t)
+                sizes.append(t.shape[0])
+        post.join()
+
+        if not tables:
+            if not _collectives_on():
+                keys = ("al_metric", "sal_metric", "inlier_count", "pred_3d_keypoints", "mkpe")
+                return OrderedDict((s, {k: OrderedDict() for k in keys}) for s in strategies)
+            # an empty shard still takes part in the pass's collective (the other ranks would hang otherwise)
+            dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+            tables = [torch.zeros((0, 6 + 3 * self.num_joints + len(strategies)), dtype=torch.float64, device=dev)]
+        err = None  # (raised after the collectives, as in _compute_sal_dict)
+        try:
+            self._raise_deferred_errors()
+        except Exception as e:  # noqa: BLE001
+            err = e
+        per_rank, per_rank_sizes = gather_tables(torch.cat(tables, dim=0), sizes, error_flag=int(err is not None))
+        if err is not None:
+            raise err
+        split = split_strategy_tables(per_rank, len(strategies))
+        return OrderedDict((s, tables_to_sal_dict(tabs, per_rank_sizes)) for s, tabs in zip(strategies, split))
 
     def _raise_deferred_errors(self):
         """Error behaviour of the reference's per-sample loop, checked once per pass."""

@@ -2,7 +2,10 @@
    --product-loop [frames=512]: the PRODUCT's pool loop instead -- ActiveLearningStrategy._compute_sal_dict (strategy.py:1004-1147) over a
    loader of HOST tensors (what the reference's DataLoader yields: pageable images (B, V, 3, 384, 288) fp32, float64 cameras), HRNet-W48,
    8 views, 8 frames per batch, MPE scoring: frames x views / s of the loop a user of workflow.py runs, next to bench.py --workload c4
-   (which feeds device-resident frames)."""
+   (which feeds device-resident frames).
+   --all: the fused launch (mval_score_decode_maps_all: HP, MPE, BSB and the key-points from one staged read) next to the three
+   mval_score_decode_maps launches it replaces, at the C2 and C4 heat-map sizes, on uniform noise and on network-like maps; the two
+   alternate inside every repeat, outputs are compared bit for bit first; one JSON line per size and input."""
 import sys, os, torch, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if "--product-loop" in sys.argv:
@@ -47,6 +50,41 @@ if "--product-loop" in sys.argv:
 from multi_view_active_learning_amd import _lib
 from multi_view_active_learning_amd import synth
 dev = torch.device("cuda:0")
+if "--all" in sys.argv:
+    import json
+    KINDS = (_lib.SCORE_HP, _lib.SCORE_MPE, _lib.SCORE_BSB)
+    def window(fn, reps):  # device events around `reps` back-to-back calls -> seconds per call
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps): fn()
+        e1.record(); e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+    for label, (f, v, j, hh, wh) in (("C2", (32, 4, 19, 64, 64)), ("C4", (8, 8, 19, 96, 72))):
+        valid = torch.ones(f, j, dtype=torch.uint8, device=dev)
+        g = torch.Generator(device=dev).manual_seed(1)
+        yy, xx = torch.meshgrid(torch.arange(hh, device=dev, dtype=torch.float32), torch.arange(wh, device=dev, dtype=torch.float32), indexing="ij")
+        cy = torch.rand(f, v, j, 2, 1, 1, device=dev, generator=g) * hh
+        cx = torch.rand(f, v, j, 2, 1, 1, device=dev, generator=g) * wh
+        amp = torch.tensor([1.0, 0.4], device=dev).view(1, 1, 1, 2, 1, 1)
+        bumps = (amp * torch.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * 2.0 ** 2))).sum(3)
+        inputs = (("uniform noise", torch.rand(f, v, j, hh, wh, device=dev, generator=g)),
+                  ("two Gaussian bumps + 0.002 noise floor", (bumps + 0.002 * torch.rand(f, v, j, hh, wh, device=dev, generator=g)).contiguous()))
+        for what, hm in inputs:
+            fused = lambda: _lib.score_decode_maps_all(hm, valid, f, v, j, hh, wh, 4, hh)
+            three = lambda: [_lib.score_decode_maps(k, hm, valid, f, v, j, hh, wh, 4, hh) for k in KINDS]
+            a, b3 = fused(), three()
+            for k in KINDS:  # faster and different is not faster
+                assert torch.equal(a[0][k].view(torch.int32), b3[k][0].view(torch.int32)) and torch.equal(a[2], b3[k][2])
+            assert torch.equal(a[1][0], b3[1][1]) and torch.equal(a[1][1], b3[2][1])
+            for _ in range(20): fused(); three()
+            tf, t3 = [], []
+            for _ in range(9):  # alternating windows of 100 calls each
+                tf.append(window(fused, 100)); t3.append(window(three, 100))
+            us = lambda t: {"median": round(float(np.median(t)) * 1e6, 2), "min": round(min(t) * 1e6, 2), "max": round(max(t) * 1e6, 2)}
+            print(json.dumps({"size": label, "maps": f"{f * v}x{j} of {hh}x{wh}", "input": what, "peaks_per_map_mpe": round(a[1][0].float().mean().item(), 1),
+                              "fused_us": us(tf), "three_launches_us": us(t3), "windows": 9, "calls_per_window": 100,
+                              "fused_over_three": round(float(np.median(tf) / np.median(t3)), 3)}))
+    sys.exit(0)
 def proj(f, v, hh, wh):
     return torch.from_numpy(np.stack([synth.ring_cameras(v, hh * 4, wh * 4, seed=s) for s in range(f)])).to(dev)
 for (f, v, j, hh, wh) in ((32, 4, 19, 64, 64), (8, 8, 19, 96, 72), (256, 4, 19, 64, 64)):

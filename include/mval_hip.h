@@ -150,6 +150,22 @@ int mval_masked_mse_fwd(const float* h, const float* g, const uint8_t* valid, fl
 int mval_masked_mse_bwd(const float* h, const float* g, const uint8_t* valid, const float* grad_out,
                         float* grad_h, int64_t lead, int64_t hw, double denom, void* stream);
 
+/* Workspace bytes of one mval_frame_loss / mval_frame_loss_points call (0 for non-positive sizes). */
+size_t mval_frame_loss_workspace_bytes(int64_t n_frames, int maps_per_frame);
+/* pose_estimators/loss.py:22-24 for every frame of a batch (the CLUSTER pass, strategy.py:173-187):
+ *   out[b] = (float)( sum over the maps m of frame b with valid[m] != 0, sum over pixels (h - g)^2 / (hh * wh) ).
+ *   heatmaps, gt [n_frames][maps_per_frame][hh][wh] f32 ; valid [n_frames * maps_per_frame] u8 or NULL ; out [n_frames] f32 ;
+ *   per_map: ws >= mval_frame_loss_workspace_bytes, holds every map's sum of squared errors afterwards (0 for a masked map).
+ * h - g and its square are float32 (torch's (h - gt) ** 2), the sums float64 in a fixed order without atomics: a map's
+ * pixels, then a frame's maps in ascending order, / (hh * wh), one rounding to float32.  A frame's result does not depend on
+ * the batch it is in or on its place there.  Two launches. */
+int mval_frame_loss(const float* heatmaps, const float* gt, const uint8_t* valid, float* out, double* per_map,
+                    int64_t n_frames, int maps_per_frame, int hh, int wh, void* stream);
+/* The same with the ground truth rendered per pixel instead of read: pt [n_frames * maps_per_frame][2] f64 (x, y in heat-map
+ * pixels), the maps mval_gt_heatmaps(pt, sigma, hh, wh) writes -- bit-identical to mval_frame_loss on them. */
+int mval_frame_loss_points(const float* heatmaps, const double* pt, double sigma, const uint8_t* valid, float* out,
+                           double* per_map, int64_t n_frames, int maps_per_frame, int hh, int wh, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Per-view input pipeline (dataset/dataset.py:158-220 prepare_single_view, pixel work only)
  * ------------------------------------------------------------------------------------------- */

@@ -42,6 +42,7 @@ def lib() -> C.CDLL:
                 l = C.CDLL(LIB_PATH)
                 l.mval_last_error.restype = C.c_char_p
                 l.mval_kcenter_workspace_bytes.restype = C.c_size_t
+                l.mval_frame_loss_workspace_bytes.restype = C.c_size_t
                 l.mval_kmeans_workspace_bytes.restype = C.c_size_t
                 l.mval_net_create.restype = C.c_void_p
                 l.mval_packed_weight_floats.restype = C.c_size_t
@@ -327,6 +328,43 @@ def masked_mse_bwd(h, g, valid, grad_out, lead, hw, denom):
         "mval_masked_mse_bwd",
     )
     return gh
+
+
+def frame_loss_workspace_bytes(n_frames: int, maps_per_frame: int) -> int:
+    return int(lib().mval_frame_loss_workspace_bytes(C.c_longlong(n_frames), C.c_int(maps_per_frame)))
+
+
+def _frame_loss_outputs(h, n_frames, maps_per_frame):
+    out = torch.empty((n_frames,), dtype=torch.float32, device=h.device)
+    per_map = torch.empty((frame_loss_workspace_bytes(n_frames, maps_per_frame) // 8,), dtype=torch.float64, device=h.device)
+    return out, per_map
+
+
+def frame_loss(h, g, valid, n_frames, maps_per_frame, hh, wh):
+    """h, g (n_frames, maps_per_frame, hh, wh) f32, valid (n_frames * maps_per_frame,) u8 or None -> (per-frame loss
+    (n_frames,) f32, every map's sum of squared errors (n_frames * maps_per_frame,) f64)."""
+    out, per_map = _frame_loss_outputs(h, n_frames, maps_per_frame)
+    _check(
+        lib().mval_frame_loss(
+            _p(_req(h, torch.float32, "heatmaps")), _p(_req(g, torch.float32, "gt")), _p(valid), _p(out), _p(per_map),
+            C.c_longlong(n_frames), C.c_int(maps_per_frame), C.c_int(hh), C.c_int(wh), _stream(),
+        ),
+        "mval_frame_loss",
+    )
+    return out, per_map
+
+
+def frame_loss_points(h, pt, sigma, valid, n_frames, maps_per_frame, hh, wh):
+    """``frame_loss`` against the maps mval_gt_heatmaps renders from pt (n_frames * maps_per_frame, 2) f64, without them."""
+    out, per_map = _frame_loss_outputs(h, n_frames, maps_per_frame)
+    _check(
+        lib().mval_frame_loss_points(
+            _p(_req(h, torch.float32, "heatmaps")), _p(_req(pt, torch.float64, "points")), C.c_double(float(sigma)), _p(valid),
+            _p(out), _p(per_map), C.c_longlong(n_frames), C.c_int(maps_per_frame), C.c_int(hh), C.c_int(wh), _stream(),
+        ),
+        "mval_frame_loss_points",
+    )
+    return out, per_map
 
 
 def mkpe(pred, gt, valid, s, j, gt_rows):

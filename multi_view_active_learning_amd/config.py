@@ -53,6 +53,10 @@ def get_default_configs():
     c.AL.BSB_CONFIG = "AVG"
     c.AL.HP_CONFIG = "AVG"
     c.AL.CORESET_METRIC = "euclidean"  # not in the reference (it never passes another): the names of _lib.KC_METRIC_IDS
+    c.AL.CLUSTER = CN()  # EXPR_TYPE "CLUSTER" (strategy.py:137-191): what ActiveLearningStrategy.cluster writes
+    c.AL.CLUSTER.TYPE = "LOSS"  # LOSS | POSE (cluster_type below)
+    c.AL.CLUSTER.SAVE_PATH = ""
+    c.AL.CLUSTER.RESTORE_FROM = ""  # not in the reference's config.py, though its cluster() reads it: a checkpoint to restore first (LOSS)
     c.AL.INFERENCE = CN()
     c.AL.INFERENCE.BATCH_SIZE = 2
     c.AL.INFERENCE.NUM_WORKERS = 2
@@ -73,3 +77,13 @@ def get_default_configs():
     c.POSE_ESTIMATOR = _pose_defaults()
     c.DATA = _data_defaults()
     return c
+
+
+CLUSTER_TYPES = ("LOSS", "POSE")
+
+
+def cluster_type(value):
+    """A valid AL.CLUSTER.TYPE, or NotImplementedError naming the accepted ones."""
+    if value not in CLUSTER_TYPES:
+        raise NotImplementedError("AL.CLUSTER.TYPE %r: accepted are %s" % (value, " and ".join(repr(t) for t in CLUSTER_TYPES)))
+    return value

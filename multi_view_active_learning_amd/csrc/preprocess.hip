@@ -15,6 +15,7 @@
 //   kernel 3  vertical pass + flip + normalise (float64, as numpy does) -> float32 (3, in_h, in_w)
 // HBM-bound streaming: a view moves crop_h * crop_w * 3 bytes in and in_h * in_w * 12 bytes out.
 #include "mval_common.h"
+#include "gt_heatmap.h"
 
 #define PP_BITS 22
 #define PP_KMAX 64
@@ -353,9 +354,7 @@ __global__ void pp_gt_heatmap_kernel(const double* __restrict__ pt, double two_s
   if (i >= total) return;
   const int x = (int)(i % w), y = (int)((i / w) % h);
   const int64_t n = i / ((int64_t)w * h);
-  const double dx = (double)x - pt[n * 2], dy = (double)y - pt[n * 2 + 1];
-  // each float64 operation rounded separately, as torch evaluates sum((grid - labels) ** 2) / (2 sigma^2)
-  out[i] = (float)exp(-__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)) / two_s2);
+  out[i] = mval_gt_heatmap_pixel(x, y, pt[n * 2], pt[n * 2 + 1], two_s2);
 }
 
 extern "C" int mval_gt_heatmaps(const double* pt, int64_t n, double sigma, int h, int w, float* out, void* stream) {

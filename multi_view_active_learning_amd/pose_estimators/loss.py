@@ -36,6 +36,18 @@ class _MaskedMSE(torch.autograd.Function):
         return gh, None, None, None
 
 
+def _per_frame_args(heatmaps, joint_valid):
+    """(B, V, J, h, w) float32 heat-maps, contiguous, and the (B * V * J,) uint8 mask of ``joint_valid`` (or None)."""
+    if heatmaps.dim() != 5:
+        raise _lib.MvalError("per-frame loss: heat-maps must be (B, V, J, h, w), got %s" % (tuple(heatmaps.shape),))
+    h = heatmaps.to(dtype=torch.float32).contiguous()
+    b, v, j = h.shape[:3]
+    if joint_valid is None:
+        return h, None
+    valid = torch.broadcast_to(torch.as_tensor(joint_valid).to(h.device) != 0, (b, v, j))
+    return h, valid.to(torch.uint8).contiguous().reshape(b * v * j)
+
+
 class Pose2DMeanSquaredError:
     def pose_2d_mse(self, heatmaps, gt_heatmaps, joint_valid=None):
         """heatmaps, gt (N, J, H, W); joint_valid broadcastable (N, J, 1, 1) bool/uint8."""
@@ -47,3 +59,25 @@ class Pose2DMeanSquaredError:
         h = heatmap.reshape(1, -1, heatmap.shape[-2], heatmap.shape[-1])
         g = gt_heatmap.reshape(1, -1, gt_heatmap.shape[-2], gt_heatmap.shape[-1])
         return _MaskedMSE.apply(h, g, None, float(heatmap.shape[-1] * heatmap.shape[-2]))
+
+    def pose_2d_mse_per_frame(self, heatmaps, gt_heatmaps, joint_valid=None):
+        """``pose_2d_mse_single_batch(heatmaps[b], gt_heatmaps[b])`` of every frame b from two launches
+        (``mval_frame_loss``): heatmaps, gt (B, V, J, h, w); joint_valid broadcastable to (B, V, J), the maps that count
+        (all by default).  Returns a (B,) float32 HIP tensor; a measurement, no autograd."""
+        h, valid = _per_frame_args(heatmaps.detach(), joint_valid)
+        if tuple(gt_heatmaps.shape) != tuple(h.shape):
+            raise _lib.MvalError("per-frame loss: ground truth %s does not match heat-maps %s" % (tuple(gt_heatmaps.shape), tuple(h.shape)))
+        g = gt_heatmaps.detach().to(dtype=torch.float32).contiguous()
+        b, v, j, hh, wh = h.shape
+        return _lib.frame_loss(h, g, valid, b, v * j, hh, wh)[0]
+
+    def pose_2d_mse_per_frame_from_points(self, heatmaps, points, sigma, joint_valid=None):
+        """``pose_2d_mse_per_frame`` against the Gaussian maps of ``points`` (B, V, J, 2) float64, heat-map pixels, without
+        materialising them (``mval_frame_loss_points``): bit-identical to
+        ``pose_2d_mse_per_frame(heatmaps, utils.preprocess.gt_heatmaps(points, sigma, h, w))``."""
+        h, valid = _per_frame_args(heatmaps.detach(), joint_valid)
+        b, v, j, hh, wh = h.shape
+        if tuple(points.shape) != (b, v, j, 2):
+            raise _lib.MvalError("per-frame loss: points %s are not (%d, %d, %d, 2)" % (tuple(points.shape), b, v, j))
+        pt = points.detach().to(dtype=torch.float64).contiguous()
+        return _lib.frame_loss_points(h, pt, sigma, valid, b, v * j, hh, wh)[0]

@@ -4,6 +4,7 @@
   _compute_mpe/_compute_hp/_compute_bsb :1149-1215
   _compute_sal_dict :1004-1147        selection part of _sal_pseudo_labeling :932-949
   train_step (inner loop body :460-487)   _evaluate_all core :597-636
+  cluster :137-191 (over a loader; cluster_dict is its pass without the file)
 
 Same names, arguments and result types, so that the reference's orchestration code
 (experiment dirs, checkpoints, TensorBoard -- out of scope here) can call them unchanged.
@@ -480,6 +481,123 @@ class ActiveLearningStrategy:
                 if kind == "BSB" and bool(((t < 2) & valid.bool()[:, None, :]).any().item()):
                     raise IndexError("list index out of range")
         self._pending_checks = []
+
+    # ---- the CLUSTER pass (strategy.py:137-191) -----------------------------------------------------------------------
+    @staticmethod
+    def _batch_guid_ids(dp):
+        """A batch's ``pose`` and ``frame_id`` as (B,) tensors; each arrives as (B,) or (B, 1)."""
+        ids = []
+        for k in ("pose", "frame_id"):
+            t = torch.as_tensor(dp[k])
+            if t.dim() > 2 or (t.dim() == 2 and t.shape[1] != 1):
+                raise ValueError("cluster pass: %s must be (B,) or (B, 1), got %s" % (k, tuple(t.shape)))
+            ids.append(t.reshape(-1))
+        if ids[0].shape != ids[1].shape:
+            raise ValueError("cluster pass: %d poses for %d frame ids" % (ids[0].shape[0], ids[1].shape[0]))
+        return ids
+
+    @staticmethod
+    def _stage_cluster_targets(dp):
+        """``_stage_batch`` plus the LOSS pass's target -- ``gt_heatmap`` where the batch has it, else ``2d_keypoints`` -- on
+        the device, uploaded like the small tensors: pinned, non-blocking, on the caller's stream before the network."""
+        out = _stage_batch(dp)
+        key = "gt_heatmap" if "gt_heatmap" in dp else "2d_keypoints"
+        if key in dp and torch.cuda.is_available():
+            t = torch.as_tensor(dp[key])
+            if not t.is_cuda:
+                t = t.contiguous()
+                out = dict(out)
+                out[key] = (t if t.is_pinned() else t.pin_memory()).to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
+        return out
+
+    def _frame_losses(self, heatmaps, dp):
+        """The device stage of the LOSS pass: heatmaps (B*V, J, h, w) -> (B,) float32, frame b's
+        ``pose_2d_mse_single_batch(heatmaps[b], gt_heatmap[b])`` (strategy.py:182-187) for the whole batch in two launches.
+        Against ``gt_heatmap`` (B, V, J, h, w) where the batch carries it (the reference's loader); otherwise against the
+        maps of ``2d_keypoints / POSE_ESTIMATOR.STRIDE`` with DATA.SIGMA (what ``prepare_views`` renders), not materialised."""
+        cfg = self.al_cfg
+        b = self._batch_guid_ids(dp)[0].shape[0]
+        _, j, hh, wh = heatmaps.shape
+        hm = heatmaps.reshape(b, -1, j, hh, wh)
+        if "gt_heatmap" in dp:
+            return self.loss.pose_2d_mse_per_frame(hm, torch.as_tensor(dp["gt_heatmap"]).to(hm.device).reshape(hm.shape))
+        if "2d_keypoints" not in dp:
+            raise KeyError("cluster pass (LOSS): a batch needs 'gt_heatmap' or '2d_keypoints'")
+        pt = torch.as_tensor(dp["2d_keypoints"]).to(hm.device).to(torch.float64).reshape(b, -1, j, 2) / cfg.POSE_ESTIMATOR.STRIDE
+        return self.loss.pose_2d_mse_per_frame_from_points(hm, pt, cfg.DATA.SIGMA)
+
+    def cluster_dict(self, data_loader, pose_estimator=None, cluster_type=None):
+        """The dict of the reference's ``cluster()`` (strategy.py:161-189), keyed "<pose>-<frame_id>" like ``sal_dict``:
+        "POSE" -> ``data["3d_keypoints"][idx].tolist()``, the (>= 3, J) poses ``read_cluster_features`` reads (no network,
+        no device work); "LOSS" -> the frame's heat-map loss under ``pose_estimator`` as a python float.  ``cluster_type``
+        defaults to AL.CLUSTER.TYPE.  A batch's loss runs beside the next batch's network and nothing is copied to the host
+        inside the loop; the pass ends with the one size exchange and one packed gather of ``gather_tables`` (rows
+        [pose, frame_id, loss] or [pose, frame_id, rows * J values]), rebuilt in ``reference_gather_order``, so every rank
+        returns the same dict -- in dataset order under strided shards."""
+        from .config import cluster_type as _cluster_type
+        from .parallel import PostStream, _collectives_on, gather_tables, reference_gather_order
+
+        kind = _cluster_type(self.al_cfg.AL.CLUSTER.TYPE if cluster_type is None else cluster_type)
+        tables, sizes, j = [], [], 0
+        if kind == "POSE":
+            for dp in data_loader:
+                pose, frame = self._batch_guid_ids(dp)
+                kp = torch.as_tensor(dp["3d_keypoints"]).cpu()
+                j = int(kp.shape[-1])
+                tables.append(torch.cat([pose.cpu().to(torch.float64)[:, None], frame.cpu().to(torch.float64)[:, None],
+                                         kp.to(torch.float64).reshape(pose.shape[0], -1)], dim=1))
+                sizes.append(pose.shape[0])
+        else:
+            post = PostStream()
+            with torch.no_grad():
+                for dp in data_loader:
+                    dp = self._stage_cluster_targets(dp)
+                    heatmaps = self._compute_batch_heatmap(pose_estimator, dp)
+                    with post.batch(heatmaps, dp):
+                        loss = self._frame_losses(heatmaps, dp)
+                        pose, frame = self._batch_guid_ids(dp)
+                        tables.append(torch.stack([pose.to(loss.device, torch.float64), frame.to(loss.device, torch.float64),
+                                                   loss.to(torch.float64)], dim=1))
+                    sizes.append(tables[-1].shape[0])
+            post.join()
+        # rows travel flattened with [row width, J] in front of the batch sizes: a rank with an empty shard does not know the
+        # width of the others' rows (POSE: rows * J) and still takes part in the collectives
+        width = tables[0].shape[1] if tables else 3
+        if tables:
+            local = torch.cat(tables, dim=0).reshape(-1)
+        else:
+            on_device = kind == "LOSS" and torch.cuda.is_available()
+            local = torch.zeros((0,), dtype=torch.float64, device=torch.device("cuda", torch.cuda.current_device()) if on_device else "cpu")
+        if _collectives_on() and not local.is_cuda and torch.distributed.get_backend() == "nccl":
+            local = local.to(torch.device("cuda", torch.cuda.current_device()))  # (POSE rows are host data; RCCL gathers device tensors)
+        per_rank, heads = gather_tables(local, [width, j] + sizes)
+        per_rank = [np.asarray(t).reshape(-1, h[0]) for t, h in zip(per_rank, heads)]
+        out = OrderedDict()
+        for r, row in reference_gather_order([h[2:] for h in heads]):
+            e = per_rank[r][row]
+            guid = "%s-%s" % (int(e[0]), int(e[1]))
+            out[guid] = float(e[2]) if kind == "LOSS" else e[2:].reshape(-1, heads[r][1]).tolist()
+        return out
+
+    def cluster(self, pose_estimator, data_loader, rank=0):
+        """The reference's ``cluster()`` (strategy.py:137-191) over a loader: eval mode, for LOSS with a non-empty
+        AL.CLUSTER.RESTORE_FROM that checkpoint restored first, ``cluster_dict``, and on rank 0 the dict written to
+        AL.CLUSTER.SAVE_PATH (``experiment_io.write_cluster_file``).  Returns the dict (the same on every rank)."""
+        from .config import cluster_type as _cluster_type
+        from .utils import experiment_io
+
+        c = self.al_cfg.AL.CLUSTER
+        kind = _cluster_type(c.TYPE)
+        if not c.SAVE_PATH:
+            raise ValueError("AL.CLUSTER.SAVE_PATH is empty: cluster() has nowhere to write")
+        if pose_estimator is not None and hasattr(pose_estimator, "eval"):
+            pose_estimator.eval()
+        if kind == "LOSS" and c.RESTORE_FROM != "":
+            experiment_io.restore_checkpoint(c.RESTORE_FROM, pose_estimator)
+        out = self.cluster_dict(data_loader, pose_estimator, kind)
+        if rank == 0:
+            experiment_io.write_cluster_file(c.SAVE_PATH, out)
+        return out
 
     def select_al_guids(self, sal_dict, al_num_frames, labeled_dict=None, metric=None):
         """Selection part of _sal_pseudo_labeling (strategy.py:932-949): NaN filter, then

@@ -6,6 +6,8 @@ Everything here is host-side file handling that mirrors what the reference write
 * ``<LOG_DIR>/<EXPR_NAME>/SAMPLED-GUID-ITER-<i>``  one line, ``json.dumps(list of guids)`` (strategy.py:127-134)
 * ``<LOG_DIR>/<EXPR_NAME>/SAL-GUID-ITER-<i>``      same, the pseudo-labelled guids            (strategy.py:112-118)
 * ``<LOG_DIR>/<EXPR_NAME>/SAL-DICT-ITER-<i>``      ``json.dumps`` of the five per-guid dicts  (strategy.py:119-125)
+* ``AL.CLUSTER.SAVE_PATH``                         ``json.dump`` of ``{guid: loss}`` or ``{guid: (>=3, J) pose}``  (strategy.py:190-191);
+  the pose form is what ``SAL.CLUSTER_FILE_PATH`` is read from (strategy.py:38-52)
 * ``<LOG_DIR>/<EXPR_NAME>/ITER-<i>/checkpoints/CKPT-*.pth``  ``torch.save({"epoch", "global_step", "state_dict",
   "optimizer"})`` (strategy.py:681-711), read back with ``ckpt["state_dict"]`` and ``strict=True``
   (strategy.py:714-721,147-151,883-888).
@@ -17,6 +19,7 @@ from __future__ import annotations
 import io
 import json
 import os
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -60,7 +63,8 @@ def checkpoint_name(epoch, global_step, mkpe=None):
 
 
 def _write_text(path, text):
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:
         f.write(text)
     return path
@@ -127,6 +131,18 @@ def read_cluster_features(path, joint_root_index):
         kp = np.array(clusters[guid])
         rows.append((kp[0:3, :] - kp[0:3, joint_root_index : joint_root_index + 1]).flatten())
     return np.asarray(rows)
+
+
+def write_cluster_file(path, cluster_dict):
+    """The file of ``ActiveLearningStrategy.cluster`` (strategy.py:190-191): ``json.dump`` of the dict, whose values are
+    python floats (LOSS) or nested lists (POSE) already."""
+    return _write_text(path, json.dumps(cluster_dict))
+
+
+def read_cluster_losses(path):
+    """The LOSS form of the cluster file: ``{guid: per-frame heat-map loss}`` in file order."""
+    with open(path, "r") as f:
+        return OrderedDict((guid, float(v)) for guid, v in json.load(f, object_pairs_hook=OrderedDict).items())
 
 
 # ---- checkpoints ----------------------------------------------------------------------------------------------

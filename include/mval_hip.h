@@ -579,6 +579,10 @@ int mval_conv_wgrad_split_covers(int cin, int cout, int k, int stride);
 int mval_conv_p2_inz_supported(int cin, int cout, int h, int w, int n);
 /* 1 when a 3x3 stride-1 data gradient (cin = the conv's cout, cout = its cin, h x w = its input map) can keep those sums. */
 int mval_conv_p2_bsum_supported(int cin, int cout, int h, int w, int n);
+/* Data-gradient launches of mval_train_backward* that really kept those sums (the flag is a request: without room for the partials the
+   plain form runs and the producer's backward reduces on its own) since the library was loaded or last reset; reset != 0 zeroes the
+   count after reading it.  Host side only. */
+int mval_train_bsum_launches(int reset);
 int mval_conv_dgrad_parity_supported(int N, int hin, int win, int cin, int hout, int wout, int cout, int algo);
 int mval_conv_dgrad_parity(const float* dz, const float* w_packed, const float* ones, const float* zeros, float* dx,
                            int accumulate, int N, int hin, int win, int cin, int hout, int wout, int cout, int algo,

@@ -401,6 +401,15 @@ def pck3d(pred, gt, valid, thresholds, mode):
 
 
 # --------------------------------------------------------------------------
+# training step
+# --------------------------------------------------------------------------
+def train_bsum_launches(reset: bool = False) -> int:
+    """mval_train_bsum_launches: data gradients of the training backward that kept their producer's BatchNorm backward sums since the
+    library was loaded or the count was last reset (TrainPlan.n_bn_bwd_in_dgrad per step unless a launch fell back to the plain form)."""
+    return int(lib().mval_train_bsum_launches(C.c_int(1 if reset else 0)))
+
+
+# --------------------------------------------------------------------------
 # core-set (k-center greedy)
 # --------------------------------------------------------------------------
 def kcenter_workspace_bytes(n_obs: int, d: int) -> int:

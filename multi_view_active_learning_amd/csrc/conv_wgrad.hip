@@ -298,11 +298,12 @@ struct WgradDirectArgs {
 __global__ __launch_bounds__(256) void conv_wgrad_direct_kernel(WgradDirectArgs a) {
   const int E = a.k * a.k * a.Cin * a.Cout;
   const int64_t M = (int64_t)a.N * a.Hout * a.Wout;
+  const int e0 = blockIdx.y * (256 * WD_EPT);  // (more than 256 * WD_EPT outputs -- a 3 -> 96 stem --: one grid row per 2 048 of them)
   float acc[WD_EPT];
   int xo[WD_EPT], co[WD_EPT], dy[WD_EPT], dx[WD_EPT], ci[WD_EPT];
 #pragma unroll
   for (int i = 0; i < WD_EPT; i++) {
-    const int e = threadIdx.x + 256 * i;
+    const int e = e0 + threadIdx.x + 256 * i;
     acc[i] = 0.f;
     co[i] = e % a.Cout;
     ci[i] = (e / a.Cout) % a.Cin;
@@ -329,7 +330,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_direct_kernel(WgradDirectArgs 
   }
 #pragma unroll
   for (int i = 0; i < WD_EPT; i++) {
-    const int e = threadIdx.x + 256 * i;
+    const int e = e0 + threadIdx.x + 256 * i;
     if (e < E) a.slabs[(int64_t)blockIdx.x * E + e] = acc[i];
   }
 }
@@ -457,7 +458,7 @@ int mval_conv_wgrad_on(const float* x, const float* dz, float* dw, float* ws, in
 #undef WG_LAUNCH
     MVAL_CHECK_LAUNCH("mval_conv_wgrad/mfma");
   } else {
-    MVAL_REQUIRE(n_out <= 256 * WD_EPT, "mval_conv_wgrad: operator too large for the direct kernel (%lld outputs)",
+    MVAL_REQUIRE(n_out <= 64 * 256 * WD_EPT, "mval_conv_wgrad: operator too large for the direct kernel (%lld outputs)",
                  (long long)n_out);
     WgradDirectArgs a;
     a.x = x; a.dz = dz; a.slabs = ws;
@@ -465,8 +466,9 @@ int mval_conv_wgrad_on(const float* x, const float* dz, float* dw, float* ws, in
     a.k = k; a.stride = stride; a.pad = pad; a.x_nchw = x_nchw;
     int64_t M = (int64_t)N * Hout * Wout;
     PS = (int)(M < 512 ? M : 512);
+    PS = min(PS, wg_splits(Cin, Cout, 1024));  // (the slabs mval_conv_wgrad_workspace_floats promises)
     a.PS = PS;
-    hipLaunchKernelGGL(conv_wgrad_direct_kernel, dim3(PS), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(conv_wgrad_direct_kernel, dim3(PS, (unsigned)((n_out + 256 * WD_EPT - 1) / (256 * WD_EPT))), dim3(256), 0, s, a);
     MVAL_CHECK_LAUNCH("mval_conv_wgrad/direct");
   }
   int parts = PS / 8;  // >= 8 slabs per lane

@@ -123,6 +123,16 @@ extern "C" int mval_train_p2_probe(uint32_t* dev_out, int n_ops) {
   return 0;
 }
 
+// ---- how many data gradients really kept their producer's BatchNorm backward sums (MVAL_TRAIN_BSUM) ----
+// The plan's flag is a request: a launch with no room for the partials, or a shape the epilogue form does not cover, runs the plain data
+// gradient and the producer's backward its own reduction pass.  Counted on the host since the library was loaded (autograd calls the
+// backward from its own thread: atomic), so that tests can tell the two apart.
+#include <atomic>
+static std::atomic<int> g_bsum_launches{0};
+extern "C" int mval_train_bsum_launches(int reset) {
+  return reset ? g_bsum_launches.exchange(0) : g_bsum_launches.load();
+}
+
 static void geometry(ConvArgs& a, const mval_op& op, int n_images) {
   a.N = n_images;
   a.Hin = op.hin; a.Win = op.win; a.Cin = op.cin;
@@ -616,6 +626,7 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
         if (slots > 0) {
           presum_slots[lane] = slots;
           presum_for[lane] = &ops[i - 1];
+          g_bsum_launches++;
         }
         rc = 0;
       } else if (t.dgrad_form == 1)  // (dgrad_form: the four-parity form of a stride-2 3x3 data gradient)

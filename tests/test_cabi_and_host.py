@@ -34,6 +34,16 @@ def test_every_declared_symbol_is_exported(lib):
     assert lib.mval_packed_weight_floats(ctypes.c_int(0), ctypes.c_int(64), ctypes.c_int(3), ctypes.c_int(7)) == 49 * 3 * 64
 
 
+def test_bsum_launch_counter_reads_and_resets(lib):
+    """mval_train_bsum_launches (include/mval_hip.h): a host-side count that only a training backward moves -- reading leaves it,
+    reset != 0 returns it and zeroes it; the ctypes mirror agrees with the C entry."""
+    from multi_view_active_learning_amd import _lib
+
+    lib.mval_train_bsum_launches(ctypes.c_int(1))
+    assert lib.mval_train_bsum_launches(ctypes.c_int(0)) == 0 and _lib.train_bsum_launches() == 0
+    assert _lib.train_bsum_launches(reset=True) == 0 and lib.mval_train_bsum_launches(ctypes.c_int(1)) == 0
+
+
 def test_product_path_has_no_cpu_fallback():
     from multi_view_active_learning_amd import _lib
     from multi_view_active_learning_amd.pose_estimators import PoseHighResolutionNet

@@ -650,11 +650,12 @@ def test_bn_in_conv_is_bit_identical_to_the_separate_apply(dev, case, monkeypatc
     assert all(torch.equal(b, rf[k]) for k, b in m0.named_buffers() if "running" in k)
     # both halves (the default): the forward is the same bits; the backward's reduction sums are accumulated in another order (fp32 per
     # lane over the workgroup's tile walk, then float64) and the dz scale comes from the channel's own maximum, so the gradients agree to
-    # the noise level the switch tests hold (median 5e-3, worst 5e-2 relative L2: test_round4_training_paths_against_their_switches)
+    # rounding level: worst < 1e-5, median < 2e-6 relative L2 (measured 1.3e-6 .. 1.6e-6 and 3.9e-7 .. 4.8e-7,
+    # profiles/r06/bn_in_conv_both_halves_ab.log; a dropped border row or a wrong mask bit on one small layer is far outside)
     assert torch.equal(hm1, hm0) and torch.equal(l1, l0)
     errs = sorted(_rel(p.grad.cpu().numpy(), m0_p.grad.cpu().numpy()) for (_, p), (_, m0_p) in zip(m1.named_parameters(), m0.named_parameters()))
     print(f"[bn bwd in dgrad] gradient rel-L2 vs the reduction pass: median {errs[len(errs) // 2]:.2e} worst {errs[-1]:.2e}")
-    assert errs[-1] < 5e-2 and errs[len(errs) // 2] < 5e-3, (errs[-1], errs[len(errs) // 2])
+    assert errs[-1] < 1e-5 and errs[len(errs) // 2] < 2e-6, (errs[-1], errs[len(errs) // 2])
     assert all(torch.equal(b, rf[k]) for k, b in m1.named_buffers() if "running" in k)
 
 

@@ -5,7 +5,11 @@ gradient is held to  e <= F * floor + 2e-5  per tensor (e: relative L2 against f
 plans, 4 for the fp16-split plan, 4 * 2^b for the default plan whose P2 scales sit b bits above the activations' maxima).
 
 The host test builds every case's four plans on torch.device("cpu") and asserts from plan.ops that the case reaches the paths it is in the
-table for; the GPU test repeats those assertions on the plan it ran, so no case passes by falling back to another kernel."""
+table for; the GPU test repeats those assertions on the plan it ran, so no case passes by falling back to another kernel -- and since the
+TRAIN_BSUM flag is only a request (a data gradient without room for its partials runs the plain form), it also asserts from
+mval_train_bsum_launches that every flagged launch kept the sums.  The BatchNorm-in-conv halves (the 3x3 P2 conv that applies its
+producer's BatchNorm while staging, the data gradient that keeps the BatchNorm backward's sums) are reached at each of their three tile
+forms and edges, and compared with the separate passes on the same graphs."""
 import functools
 import os
 
@@ -18,23 +22,48 @@ import tiny_graphs as tg
 ALGO_DIRECT, ALGO_MFMA, ALGO_MFMA_BF3, ALGO_MFMA_H2 = 0, 1, 2, 3
 
 # graph, builder arguments (channel widths [, stride]), images, map size behind the stride-2 head (the input is twice that), seed of the
-# parameters (and of the Gaussian batch the stored input was made from).  `inz`: the 3x3 P2 convs of this shape apply their producer's BatchNorm while staging (mval_conv_p2_inz_supported)
-# and their data gradients keep the BatchNorm backward's sums.  Weight-gradient tiles (tiny_graphs.wgrad_tile): 16 wide on the 16-, 12- and 9-wide
+# parameters (and of the Gaussian batch the stored input was made from).  `inz`: the 3x3 P2 convs of this shape apply their producer's BatchNorm while staging (mval_conv_p2_inz_supported);
+# `bsum`: their data gradients keep the BatchNorm backward's sums (mval_conv_p2_bsum_supported, which also admits 48 and 96 channels).  Weight-gradient tiles (tiny_graphs.wgrad_tile): 16 wide on the 16-, 12- and 9-wide
 # maps (16-wide tiles pad no more columns there), 8 wide on 18 / 24 / 37 / 6 / 8; NT = 2 for cout > 32; the 4 x 6 maps are smaller than a tile and
 # give 3 tiles (< PS).
 CASES = {
-    "blocks_c32_16x16": dict(graph="blocks", args=(32,), n=2, hw=(16, 16), seed=1, inz=True),
-    "blocks_c48_12x18": dict(graph="blocks", args=(48,), n=2, hw=(12, 18), seed=1, inz=False),
-    "blocks_c64_8x24": dict(graph="blocks", args=(64,), n=2, hw=(8, 24), seed=1, inz=False),
-    "blocks_c32_21x37": dict(graph="blocks", args=(32,), n=2, hw=(21, 37), seed=1, inz=False),
-    "blocks_c64_4x6_n3": dict(graph="blocks", args=(64,), n=3, hw=(4, 6), seed=1, inz=False),
-    "bneck_s1_16x16": dict(graph="bneck", args=(64, 64, 1), n=2, hw=(16, 16), seed=1, inz=True),
-    "bneck_s2_16x16": dict(graph="bneck", args=(64, 64, 2), n=2, hw=(16, 16), seed=1, inz=False),
-    "bneck_s1_12x18": dict(graph="bneck", args=(64, 64, 1), n=2, hw=(12, 18), seed=1, inz=False),
-    "fuse_32_64_96_16x16": dict(graph="fuse", args=(32, 64, 96), n=2, hw=(16, 16), seed=1, inz=False),
-    "fuse_48_96_64_8x24": dict(graph="fuse", args=(48, 96, 64), n=2, hw=(8, 24), seed=1, inz=False),
-    "deconv_64_64_32_16x16": dict(graph="deconv", args=(64, 64, 32), n=2, hw=(16, 16), seed=1, inz=False),
-    "deconv_64_96_48_12x18": dict(graph="deconv", args=(64, 96, 48), n=2, hw=(12, 18), seed=1, inz=False),
+    "blocks_c32_16x16": dict(graph="blocks", args=(32,), n=2, hw=(16, 16), seed=1, inz=True, bsum=True),
+    "blocks_c48_12x18": dict(graph="blocks", args=(48,), n=2, hw=(12, 18), seed=1, inz=False, bsum=False),
+    "blocks_c64_8x24": dict(graph="blocks", args=(64,), n=2, hw=(8, 24), seed=1, inz=False, bsum=False),
+    "blocks_c32_21x37": dict(graph="blocks", args=(32,), n=2, hw=(21, 37), seed=1, inz=False, bsum=False),
+    "blocks_c64_4x6_n3": dict(graph="blocks", args=(64,), n=3, hw=(4, 6), seed=1, inz=False, bsum=False),
+    "bneck_s1_16x16": dict(graph="bneck", args=(64, 64, 1), n=2, hw=(16, 16), seed=1, inz=True, bsum=True),
+    "bneck_s2_16x16": dict(graph="bneck", args=(64, 64, 2), n=2, hw=(16, 16), seed=1, inz=False, bsum=False),
+    "bneck_s1_12x18": dict(graph="bneck", args=(64, 64, 1), n=2, hw=(12, 18), seed=1, inz=False, bsum=False),
+    "fuse_32_64_96_16x16": dict(graph="fuse", args=(32, 64, 96), n=2, hw=(16, 16), seed=1, inz=False, bsum=False),
+    "fuse_48_96_64_8x24": dict(graph="fuse", args=(48, 96, 64), n=2, hw=(8, 24), seed=1, inz=False, bsum=False),
+    "deconv_64_64_32_16x16": dict(graph="deconv", args=(64, 64, 32), n=2, hw=(16, 16), seed=1, inz=False, bsum=False),
+    "deconv_64_96_48_12x18": dict(graph="deconv", args=(64, 96, 48), n=2, hw=(12, 18), seed=1, inz=False, bsum=False),
+    # the BatchNorm-in-conv halves (INZ: the staging of a 3x3 P2 conv; BSUM: the epilogue of its data gradient) at every tile form and edge
+    # form A (W % 16 == 0, H >= 4, <= 2 cout sub-tiles: 8-row x 16-column tiles, WM = 2): a map lower than a tile; a ragged last tile row
+    # (8 + 4), two tile columns, odd batch; behind a 1x1 producer (mask from z)
+    "blocks_c32_4x16": dict(graph="blocks", args=(32,), n=2, hw=(4, 16), seed=1, inz=True, bsum=True),
+    "blocks_c32_12x32": dict(graph="blocks", args=(32,), n=3, hw=(12, 32), seed=1, inz=True, bsum=True),
+    "bneck_p32_16x16": dict(graph="bneck", args=(64, 32, 1), n=2, hw=(16, 16), seed=1, inz=True, bsum=True),
+    # form B (> 2 cout sub-tiles: 4-row tiles, 4 cout waves): residual + mask bytes; ragged (4 + 2), two columns, odd batch; BSUM alone with 3
+    # sub-tiles (one wave idle; INZ needs Cin % 32 == 0); 6 sub-tiles = two cout groups, the second half empty, INZ over three chunks
+    "blocks_c64_16x16": dict(graph="blocks", args=(64,), n=2, hw=(16, 16), seed=1, inz=True, bsum=True),
+    "blocks_c64_6x32": dict(graph="blocks", args=(64,), n=3, hw=(6, 32), seed=1, inz=True, bsum=True),
+    "blocks_c48_16x16": dict(graph="blocks", args=(48,), n=2, hw=(16, 16), seed=1, inz=False, bsum=True),
+    "blocks_c96_8x16": dict(graph="blocks", args=(96,), n=2, hw=(8, 16), seed=1, inz=True, bsum=True),
+    # form C (8 x 8 maps, G = 2): one tile per image; odd count; BSUM alone (96 % 64 != 0: partial second chunk, two cout groups); two full
+    # chunks and groups; behind a 1x1 producer; and the boundary: 8 x 8 with two sub-tiles takes neither path
+    "blocks_c64_8x8": dict(graph="blocks", args=(64,), n=2, hw=(8, 8), seed=1, inz=True, bsum=True),
+    "blocks_c64_8x8_n5": dict(graph="blocks", args=(64,), n=5, hw=(8, 8), seed=1, inz=True, bsum=True),
+    "blocks_c96_8x8": dict(graph="blocks", args=(96,), n=2, hw=(8, 8), seed=1, inz=False, bsum=True),
+    "blocks_c128_8x8": dict(graph="blocks", args=(128,), n=2, hw=(8, 8), seed=1, inz=True, bsum=True),
+    "bneck_p64_8x8": dict(graph="bneck", args=(64, 64, 1), n=2, hw=(8, 8), seed=1, inz=True, bsum=True),
+    "blocks_c32_8x8": dict(graph="blocks", args=(32,), n=2, hw=(8, 8), seed=1, inz=False, bsum=False),
+    # two lanes keep partials in their own scratch slices at once (form A on lane 0, form C on lane 1)
+    "branches_32_64_16x16": dict(graph="branches", args=(32, 64), n=2, hw=(16, 16), seed=1, inz=True, bsum=True),
+    # the pre-summed apply pass ACCUMULATES into the residual's gradient slot (b0.conv2 is not its first writer), forms A and C
+    "shared_c32_16x16": dict(graph="shared", args=(32,), n=2, hw=(16, 16), seed=1, inz=True, bsum=True),
+    "shared_c64_8x8": dict(graph="shared", args=(64,), n=2, hw=(8, 8), seed=1, inz=True, bsum=True),
 }
 PLANS = {"default": {}, "h2": {"MVAL_TRAIN_P2": "0"}, "bf3": {"MVAL_CONV": "bf3"}, "fp32": {"MVAL_CONV": "fp32"}}
 MARGIN = 64.0
@@ -102,19 +131,21 @@ def _check_plan(case, plan_name, plan):
                 assert has(name, et.TRAIN_WGRAD_X_P2) and has(name, et.TRAIN_WGRAD_DZ_P2) and has(name, et.TRAIN_DGRAD_P2), name
             assert all(has(k, et.TRAIN_OUT_P2_ONLY) for k in ("head", "b0.conv1", "b1.conv1"))
             assert has("b0.conv2", et.TRAIN_RES1_P2) and not has("b1.conv2", et.TRAIN_RES1_P2)  # (the head's output exists as planes only)
-            inz = case["inz"]
+            inz, bsum = case["inz"], case["bsum"]
             assert [int(ops[k][1].z_out) for k in ("b0.conv1", "b1.conv1")] == [int(inz)] * 2
             assert [int(ops[k][1].zin_rel) for k in ("b0.conv2", "b1.conv2")] == [-int(inz)] * 2
             # (BatchNorm sums in the data gradient: producers without residual -- conv1 -- and with residual + mask bytes -- conv2 of block 0)
-            assert [has(k, et.TRAIN_BSUM) for k in ("b0.conv2", "b1.conv1", "b1.conv2")] == [inz] * 3
-            assert plan.n_bn_in_conv == 2 * int(inz) and plan.n_bn_bwd_in_dgrad == 3 * int(inz)
+            assert [has(k, et.TRAIN_BSUM) for k in ("b0.conv2", "b1.conv1", "b1.conv2")] == [bsum] * 3
+            assert not has("b0.conv1", et.TRAIN_BSUM)  # (the head keeps no dz planes)
+            assert plan.n_bn_in_conv == 2 * int(inz) and plan.n_bn_bwd_in_dgrad == 3 * int(bsum)
     elif kind == "bneck":
         stride = case["args"][2]
         assert ops["bn0.conv3"][1].mask_off > 0 and ops["bn0.conv3"][1].first_touch == 3
         assert ops["bn0.downsample.0"][0].stride == stride and ops["bn0.conv2"][0].stride == stride
         lib = _lib.lib()
         covers = lambda op: bool(lib.mval_conv_wgrad_split_covers(C.c_int(op.cin), C.c_int(op.cout), C.c_int(op.k), C.c_int(op.stride)))
-        assert covers(ops["bn0.conv1"][0]) and covers(ops["bn0.conv3"][0])  # (1x1 with >= 64 channels on both sides: the split kernel)
+        wide = case["args"][1] >= 64  # (1x1 with >= 64 channels on both sides: the split kernel; 32 planes: the exact-fp32 weight gradient)
+        assert covers(ops["bn0.conv1"][0]) == wide and covers(ops["bn0.conv3"][0]) == wide
         assert covers(ops["bn0.downsample.0"][0]) == (stride == 1)          # (1x1 stride 2: the exact-fp32 weight-gradient kernel)
         if stride == 2 and plan_name != "fp32":
             assert ops["bn0.conv2"][1].dgrad_form == 1  # the four-parity data gradient inside a plan
@@ -122,13 +153,15 @@ def _check_plan(case, plan_name, plan):
         if plan_name == "default":
             for name in ("bn0.conv1", "bn0.conv2", "bn0.downsample.0", "bn0.conv3"):
                 assert ops[name][1].fwd_p2 == 1, name
-            for name in ("bn0.conv1", "bn0.conv3"):
-                assert has(name, et.TRAIN_WGRAD_X_P2) and has(name, et.TRAIN_WGRAD_DZ_P2) and has(name, et.TRAIN_DGRAD_P2), name
-            assert has("bn0.conv2", et.TRAIN_WGRAD_X_P2) and has("bn0.conv2", et.TRAIN_OUT_P2_ONLY)
+            for name in ("bn0.conv1", "bn0.conv3"):  # (the weight gradient reads planes where the split kernel covers the conv)
+                assert has(name, et.TRAIN_WGRAD_X_P2) == wide and has(name, et.TRAIN_WGRAD_DZ_P2) == wide and has(name, et.TRAIN_DGRAD_P2), name
+            # (conv3's exact-fp32 weight gradient of the narrow block reads conv2's fp32 output: it is kept beside the planes)
+            assert has("bn0.conv2", et.TRAIN_WGRAD_X_P2) and has("bn0.conv2", et.TRAIN_OUT_P2_ONLY) == wide
             if stride == 1:
                 assert has("bn0.downsample.0", et.TRAIN_WGRAD_X_P2) and has("bn0.downsample.0", et.TRAIN_WGRAD_DZ_P2)
                 assert int(ops["bn0.conv1"][1].z_out) == int(case["inz"]) and int(ops["bn0.conv2"][1].zin_rel) == -int(case["inz"])
-                assert has("bn0.conv2", et.TRAIN_BSUM) == case["inz"]
+                assert has("bn0.conv2", et.TRAIN_BSUM) == case["bsum"]
+                assert plan.n_bn_in_conv == int(case["inz"]) and plan.n_bn_bwd_in_dgrad == int(case["bsum"])
             else:
                 assert ops["bn0.conv2"][1].dgrad_algo == ALGO_MFMA_H2 and not has("bn0.conv2", et.TRAIN_DGRAD_P2)
                 assert not has("bn0.downsample.0", et.TRAIN_WGRAD_X_P2)
@@ -156,8 +189,52 @@ def _check_plan(case, plan_name, plan):
         if plan_name == "default":  # dz as planes, x through its magnitude row (the max-pool's output is fp32)
             assert not ops["c1"][1].fwd_p2 and has("c1", et.TRAIN_DGRAD_P2) and has("c1", et.TRAIN_WGRAD_DZ_P2) and not has("c1", et.TRAIN_WGRAD_X_P2)
             assert ops["c1"][1].op.in_amax_off > 0
+    elif kind in ("branches", "shared"):
+        pre = ("a0", "a1", "b0", "b1") if kind == "branches" else ("b0", "b1")
+        conv1, conv2 = [p + ".conv1" for p in pre], [p + ".conv2" for p in pre]
+        assert all(ops[k][1].mask_off > 0 for k in conv2) and not any(ops[k][1].mask_off > 0 for k in conv1)
+        if kind == "branches":
+            assert plan.n_lanes == 2 and len(g.ops) == 12
+            for name, (op, t) in ops.items():  # the second pair of blocks is lane 1 of the blocks' phase, forward and backward
+                assert op.lane == int(name.startswith("b")) and has(name, et.TRAIN_LANE_FREE), name
+                assert has(name, et.TRAIN_LANE_FWD) == has(name, et.TRAIN_LANE_BWD) == (op.lane == 1), name
+            assert len({ops[k][0].phase for k in conv1 + conv2}) == 1 and ops["m"][0].up == 1 and ops["m"][1].mask_off == 0
+            assert plan.geo[g.ops.index(ops["a0.conv1"][0])][:2] == tuple(2 * v for v in plan.geo[g.ops.index(ops["b0.conv1"][0])][:2])
+            # first touch (bit 0 data gradient, 1 res1) in backward order: m stores b1's and a1's output gradients; on each lane conv2 of a
+            # block stores its residual's slot and conv1 adds to it; t1 adds its data gradient to what a0 left in the head output's slot
+            assert [ops[k][1].first_touch for k in ["m"] + conv2 + conv1 + ["t1"]] == [3, 3, 3, 3, 3, 0, 0, 0, 0, 0]
+            if plan_name != "fp32":
+                assert ops["t1"][1].dgrad_form == 1
+        else:
+            assert plan.n_lanes == 1 and len(g.ops) == 7 and ops["m"][0].src == ops["head"][0].dst and ops["m"][0].res1 == ops["b1.conv2"][0].dst
+            # in backward order m stores the head output's gradient slot (and b1's): b0.conv2's residual gradient is ADDED to that slot
+            # (bit 1 clear), as is b0.conv1's data gradient
+            assert [ops[k][1].first_touch for k in ("m", "b1.conv2", "b1.conv1", "b0.conv2", "b0.conv1")] == [3, 3, 0, 1, 0]
+            assert ops["m"][1].mask_off > 0
+        if plan_name == "default":
+            inz, bsum = case["inz"], case["bsum"]
+            for name in conv1 + conv2:
+                t = ops[name][1]
+                assert t.fwd_p2 == 1 and t.op.algo == ALGO_MFMA_H2 and t.dgrad_algo == ALGO_MFMA_H2 and t.dgrad_form == 0, name
+                assert has(name, et.TRAIN_WGRAD_X_P2) and has(name, et.TRAIN_WGRAD_DZ_P2) and has(name, et.TRAIN_DGRAD_P2), name
+            assert [int(ops[k][1].z_out) for k in conv1] == [int(inz)] * len(pre) and not any(ops[k][1].z_out for k in conv2 + ["m"])
+            assert [int(ops[k][1].zin_rel) for k in conv2] == [-int(inz)] * len(pre) and not any(ops[k][1].zin_rel for k in conv1 + ["m"])
+            # every 3x3 but the first of a lane follows its producer in the list (the first follows t1 / the other lane / the head)
+            first = [pre[0] + ".conv1"] + (["b0.conv1"] if kind == "branches" else [])
+            want = {name for name in conv1 + conv2 if name not in first} if bsum else set()
+            assert {name for name in ops if has(name, et.TRAIN_BSUM)} == want
+            assert plan.n_bn_in_conv == len(pre) * int(inz) and plan.n_bn_bwd_in_dgrad == len(want)
+            if kind == "branches":
+                assert plan.n_bn_in_conv == 4 and plan.n_bn_bwd_in_dgrad == 6
     if plan_name == "default":
         assert plan.uses_p2
+
+
+def _n_bsum(case):
+    """Data gradients of the default plan that keep BatchNorm backward sums: every 3x3 that follows its producer in the op list."""
+    if not case["bsum"]:
+        return 0
+    return {"blocks": 3, "bneck": 1, "branches": 6, "shared": 3}[case["graph"]]
 
 
 def _host_plan(case, plan_name):
@@ -256,7 +333,7 @@ def test_small_graph_training_step_vs_float64(dev, case_id, plan_name, monkeypat
     """One forward + backward of the case on the plan `plan_name` (default; MVAL_TRAIN_P2=0: the h2 kernels; MVAL_CONV=bf3; MVAL_CONV=fp32):
     the output, every parameter gradient and every BatchNorm running statistic against float64 autograd; then a second step with an
     all-ones output gradient into the same model without zero_grad: the gradients are the sum of the two float64 gradients."""
-    from multi_view_active_learning_amd import engine_train as et
+    from multi_view_active_learning_amd import _lib, engine_train as et
 
     case = CASES[case_id]
     x, g, ref = _reference(case_id)
@@ -269,10 +346,13 @@ def test_small_graph_training_step_vs_float64(dev, case_id, plan_name, monkeypat
     f64, f32 = torch.float64, torch.float32
     model = _model(case).to(dev).train()
     xd = x.to(dev)
+    _lib.train_bsum_launches(reset=True)
     out = model(xd)
     out.backward(g.to(dev))
     plan = next(iter(model._train_plans.values()))
     _check_plan(case, plan_name, plan)
+    # every data gradient the plan flags really kept the sums (no launch fell back to the plain form), and no other did
+    assert _lib.train_bsum_launches() == plan.n_bn_bwd_in_dgrad == (_n_bsum(case) if plan_name == "default" else 0)
     assert not model.__dict__.get("_train_p2_off", False), plan.p2_slack
     want_out = ref.out[f64].numpy()
     np.testing.assert_allclose(out.detach().cpu().numpy(), want_out, rtol=2e-5, atol=2e-5 * float(np.abs(want_out).max()))
@@ -289,6 +369,7 @@ def test_small_graph_training_step_vs_float64(dev, case_id, plan_name, monkeypat
     out2 = model(xd)
     out2.backward(torch.ones_like(out2))
     assert next(iter(model._train_plans.values())) is plan and plan.steps == 2
+    assert _lib.train_bsum_launches(reset=True) == 2 * plan.n_bn_bwd_in_dgrad
     assert torch.equal(out2.detach(), out.detach())
     both = lambda d: {k: ref.grad1[d][k] + ref.grad2[d][k] for k in ref.keys}
     r2 = _gradient_check(f"{case_id} / {plan_name} step 1 + 2", model, both(f64), both(f32), factor)
@@ -301,3 +382,77 @@ def test_small_graph_training_step_vs_float64(dev, case_id, plan_name, monkeypat
     _RATIOS[f"{case_id}/{plan_name}"] = dict(F=factor, step1=dict(median=float(np.median(r1)), max=float(max(r1))),
                                              step12=dict(median=float(np.median(r2)), max=float(max(r2))))
     _report("small_graph_error_ratios.json", _RATIOS)
+
+
+def _one_step(case, x, g, dev, monkeypatch, env):
+    """One forward + backward of a fresh model (the case's seeded parameters) on the default plan under the switches `env`:
+    (plan, output, parameter gradients, running statistics, data gradients that kept BatchNorm sums)."""
+    from multi_view_active_learning_amd import _lib, engine_train as et
+
+    for k in et._SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    model = _model(case).to(dev).train()
+    _lib.train_bsum_launches(reset=True)
+    out = model(x.to(dev))
+    out.backward(g.to(dev))
+    count = _lib.train_bsum_launches(reset=True)
+    plan = next(iter(model._train_plans.values()))
+    assert not model.__dict__.get("_train_p2_off", False), plan.p2_slack
+    grads = {k: p.grad.detach().clone() for k, p in model.named_parameters()}
+    stats = {k: v.detach().clone() for k, v in model.state_dict().items() if k.endswith(("running_mean", "running_var"))}
+    return plan, out.detach().clone(), grads, stats, count
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case_id", [k for k, c in CASES.items() if c["inz"] or c["bsum"]])
+def test_small_graph_bn_in_conv_halves_vs_separate_passes(dev, case_id, monkeypatch):
+    """The two BatchNorm-in-conv halves against the separate passes, on every tile form and edge of the table: one forward + backward of
+    the default plan from the same model state as D (defaults), F (MVAL_TRAIN_BN_BWD_IN_DGRAD=0: the forward half alone) and S (also
+    MVAL_TRAIN_BN_IN_CONV=0: BatchNorm apply and backward reduction as passes of their own).
+
+    F vs S: the conv's staging computes relu(BatchNorm(z)) with the apply kernel's arithmetic, so the output, every parameter gradient and
+    every running statistic are the same bits (tests/test_gpu_train.py holds this on whole networks; here at every tile form).
+    D vs F: the output and the running statistics are the same bits; the gradients differ in the order of the fp32 partial sums and in
+    where dz's P2 scale comes from -- rounding-level effects -- so against float64 every gradient has  e_D <= 2 * max(e_F, floor)  (floor:
+    torch-CPU float32's error).  The bound is relative to the reference, not to the other kernel: a dropped border row, a wrong mask bit
+    or a missed residual scatter is orders of magnitude outside it.  D's data gradients keep the sums exactly plan.n_bn_bwd_in_dgrad
+    times (mval_train_bsum_launches), F's never.  Measured on an MI355X: e_D / max(e_F, floor) at most 1.16 (blocks_c32_12x32, b0.bn1.weight),
+    per-case maxima 1.00 .. 1.16, medians 0.90 .. 1.00 (small_graph_error_ratios.json, key bn_in_conv_ab)."""
+    from multi_view_active_learning_amd import engine_train as et
+
+    case = CASES[case_id]
+    x, g, ref = _reference(case_id)
+    f64, f32 = torch.float64, torch.float32
+    plan_d, out_d, g_d, st_d, n_d = _one_step(case, x, g, dev, monkeypatch, {})
+    plan_f, out_f, g_f, st_f, n_f = _one_step(case, x, g, dev, monkeypatch, {"MVAL_TRAIN_BN_BWD_IN_DGRAD": "0"})
+    plan_s, out_s, g_s, st_s, n_s = _one_step(case, x, g, dev, monkeypatch, {"MVAL_TRAIN_BN_BWD_IN_DGRAD": "0", "MVAL_TRAIN_BN_IN_CONV": "0"})
+    _check_plan(case, "default", plan_d)
+    assert not any(t.p2_flags & et.TRAIN_BSUM for t in plan_f.ops) and plan_f.n_bn_bwd_in_dgrad == 0
+    assert not any(t.p2_flags & et.TRAIN_BSUM for t in plan_s.ops) and not any(t.z_out or t.zin_rel for t in plan_s.ops) and plan_s.n_bn_in_conv == 0
+    assert plan_f.n_bn_in_conv == plan_d.n_bn_in_conv and [(t.z_out, t.zin_rel) for t in plan_f.ops] == [(t.z_out, t.zin_rel) for t in plan_d.ops]
+    assert n_d == plan_d.n_bn_bwd_in_dgrad == _n_bsum(case) and n_f == 0 and n_s == 0, (n_d, n_f, n_s)
+    if case["inz"]:  # the forward half (without it F and S are the same plan)
+        assert torch.equal(out_f, out_s)
+        bad = [k for k in g_s if not torch.equal(g_f[k], g_s[k])]
+        assert not bad, bad
+        assert all(torch.equal(st_f[k], st_s[k]) for k in st_s) and len(st_s) > 0
+    # the backward half
+    assert torch.equal(out_d, out_f)
+    assert all(torch.equal(st_d[k], st_f[k]) for k in st_f) and len(st_f) > 0
+    ratios, bad = {}, []
+    for k in ref.keys:
+        want = ref.grad1[f64][k]
+        e_d, e_f = tg.rel_l2(g_d[k].cpu().numpy(), want), tg.rel_l2(g_f[k].cpu().numpy(), want)
+        floor = tg.rel_l2(ref.grad1[f32][k], want)
+        ratios[k] = e_d / max(e_f, floor, 1e-300)
+        if not e_d <= 2.0 * max(e_f, floor):
+            bad.append((k, e_d, e_f, floor))
+    worst = max(ratios, key=ratios.get)
+    print(f"[small graphs] {case_id} BN-in-conv A/B: e_D / max(e_F, floor) median {np.median(list(ratios.values())):.2f} max {ratios[worst]:.2f} ({worst}); "
+          f"sums kept by {n_d} / {n_f} / {n_s} data gradients (D / F / S)")
+    _RATIOS.setdefault("bn_in_conv_ab", {})[case_id] = dict(median=float(np.median(list(ratios.values()))), max=float(ratios[worst]), worst=worst,
+                                                            bsum_launches=dict(D=n_d, F=n_f, S=n_s))
+    _report("small_graph_error_ratios.json", _RATIOS)
+    assert not bad, (case_id, bad)

@@ -82,7 +82,37 @@ def deconv(c, cmid, cup):
     return _tail(g, d)
 
 
-BUILDERS = {"blocks": blocks, "bneck": bneck, "fuse": fuse, "deconv": deconv}
+def branches(c0, c1):
+    """head, a stride-2 transition, then two BasicBlocks on each of two resolutions as two lanes of one phase (an HRNet stage's branches,
+    hrnet.py:150-197), joined by a 1x1 conv from the low branch whose upsampled sum takes the high branch as residual."""
+    g = _graph.Graph()
+    x0 = _head(g, c0)
+    g.new_phase()
+    x1 = g.conv(x0, c1, 3, 2, "t1", "t1_bn", relu=True)
+    g.new_phase()
+    g.cur_lane = 0
+    a = _graph._basic_block(g, x0, "a0")
+    a = _graph._basic_block(g, a, "a1")
+    g.cur_lane = 1
+    b = _graph._basic_block(g, x1, "b0")
+    b = _graph._basic_block(g, b, "b1")
+    g.new_phase()
+    z = g.conv(b, c0, 1, 1, "m", "m_bn", relu=True, res1=a, up=1)
+    return _tail(g, z)
+
+
+def shared(c):
+    """head, two BasicBlocks, then a 1x1 conv that reads the HEAD's output again and takes the blocks' output as residual: in the backward
+    pass it writes the head output's gradient slot first, so the first block's residual gradient is added to what is there."""
+    g = _graph.Graph()
+    x = _head(g, c)
+    y = _graph._basic_block(g, x, "b0")
+    y = _graph._basic_block(g, y, "b1")
+    z = g.conv(x, c, 1, 1, "m", "m_bn", relu=True, res1=y)
+    return _tail(g, z)
+
+
+BUILDERS = {"blocks": blocks, "bneck": bneck, "fuse": fuse, "deconv": deconv, "branches": branches, "shared": shared}
 
 
 # ---- the model on the HIP engine ----

@@ -436,6 +436,35 @@ int mval_op_mfma_supported(const mval_op* op, int n_images);
 /* Same question for a given MVAL_ALGO_* (MFMA, MFMA_BF3 or MFMA_H2). */
 int mval_op_algo_supported(const mval_op* op, int n_images, int algo);
 
+/* Which kernel of the split-MFMA conv family (csrc/conv_mfma_split.hip: MVAL_ALGO_MFMA_BF3 / _H2) a launch of the library runs on: the
+ * launcher's own dispatch up to, but without, the launch.  Host arithmetic only (no GPU needed, nothing is launched).
+ *   pl .. g      the kernel's template arguments: planes (3 = bf16x3, 2 = fp16x2), kernel size (2 = the 2x2 parity conv), stride, cout
+ *                waves, pixel waves, cout sub-tiles and pixel sub-tiles per wave, 32-channel chunks per stage
+ *   variant      MVAL_SPLIT_*: 6 or 10 staging slots per thread, row sharing (3x3 stride 1, 16-wide tiles), two chunks per stage (g = 2)
+ *   th, tw, tn   tile rows x columns x images; odd = 1: th x tw is no power of two (magic-divide decode, tn = 1)
+ *   precise      separate accumulator for the correction products (training forward)
+ *   grid_x/y/z   pixel tiles, cout groups, parities (4 = the four parity convs of a transposed conv / parity data gradient in one launch)
+ *   bn_part_ok   the tile form and the epilogue options allow the batch-statistics partials (given room for them);
+ *   bn_part      the launch asks for them and keeps them (mval_train_forward's convs with BatchNorm) */
+enum { MVAL_SPLIT_NE6 = 0, MVAL_SPLIT_NE10 = 1, MVAL_SPLIT_ROW_SHARING = 2, MVAL_SPLIT_TWO_CHUNK = 3 };
+typedef struct mval_split_form {
+  int32_t pl, ks, s, wn, wm, nt, ms, g;
+  int32_t variant;
+  int32_t th, tw, tn, odd;
+  int32_t precise;
+  int32_t grid_x, grid_y, grid_z;
+  int32_t bn_part_ok, bn_part;
+} mval_split_form;
+/* `use` = how the library builds the launch from `op` (geometry in FORWARD terms: x [N,hin,win,cin] -> z [N,hout,wout,cout]):
+ *   MVAL_SPLIT_USE_OP            mval_op_launch of the op (conv, stride-2 1x1, transposed conv k4 s2 p1; up / relu / out_nchw and
+ *                                res1_off / res2_off >= 0 as the op has them)
+ *   MVAL_SPLIT_USE_TRAIN_FWD     the same conv as mval_train_forward runs it before its BatchNorm (raw z, precise, partials requested)
+ *   MVAL_SPLIT_USE_DGRAD         mval_conv_dgrad_scaled of the conv (res1_off >= 0: accumulate)
+ *   MVAL_SPLIT_USE_DGRAD_PARITY  mval_conv_dgrad_parity of the conv (res1_off >= 0: accumulate)
+ * algo: MVAL_ALGO_MFMA_BF3 or MVAL_ALGO_MFMA_H2.  Returns 1 and fills *form, or 0 where the library has no split kernel for the launch. */
+enum { MVAL_SPLIT_USE_OP = 0, MVAL_SPLIT_USE_TRAIN_FWD = 1, MVAL_SPLIT_USE_DGRAD = 2, MVAL_SPLIT_USE_DGRAD_PARITY = 3 };
+int mval_conv_split_form(int use, const mval_op* op, int n_images, int algo, mval_split_form* form);
+
 int mval_op_launch(const mval_op* op, int n_images, float* workspace, const float* params,
                    const float* net_input, float* net_output, void* stream);
 

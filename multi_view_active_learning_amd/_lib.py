@@ -410,6 +410,31 @@ def train_bsum_launches(reset: bool = False) -> int:
 
 
 # --------------------------------------------------------------------------
+# which split-MFMA kernel a launch runs on (host arithmetic: needs no GPU)
+# --------------------------------------------------------------------------
+SPLIT_NE6, SPLIT_NE10, SPLIT_ROW_SHARING, SPLIT_TWO_CHUNK = 0, 1, 2, 3  # MVAL_SPLIT_* (include/mval_hip.h): mval_split_form.variant
+SPLIT_USE_OP, SPLIT_USE_TRAIN_FWD, SPLIT_USE_DGRAD, SPLIT_USE_DGRAD_PARITY = 0, 1, 2, 3  # MVAL_SPLIT_USE_*
+
+
+class SplitForm(C.Structure):
+    """include/mval_hip.h: struct mval_split_form."""
+
+    _fields_ = [(name, C.c_int32) for name in ("pl", "ks", "s", "wn", "wm", "nt", "ms", "g", "variant", "th", "tw", "tn", "odd", "precise",
+                                               "grid_x", "grid_y", "grid_z", "bn_part_ok", "bn_part")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+def conv_split_form(use, op, n_images, algo):
+    """mval_conv_split_form: the kernel form (SplitForm) the library's launch of the MvalOp ``op`` under ``use`` (SPLIT_USE_*) and ``algo``
+    (MVAL_ALGO_MFMA_BF3 / _H2) ends on, or None where it has no split kernel for it."""
+    form = SplitForm()
+    ok = lib().mval_conv_split_form(C.c_int(use), C.byref(op), C.c_int(n_images), C.c_int(algo), C.byref(form))
+    return form if ok else None
+
+
+# --------------------------------------------------------------------------
 # core-set (k-center greedy)
 # --------------------------------------------------------------------------
 def kcenter_workspace_bytes(n_obs: int, d: int) -> int:

@@ -353,14 +353,17 @@ static inline void conv_amax_prepare(ConvArgs& a, int tiles_per_image, int group
 
 // Launcher side of the batch-statistics partials (a.bn_part): keeps them when the tile shape can (conv_tile_store's
 // float4 path with NTH % (NTILE / 4) == 0 and room for the NTH x 8 float scratch in the output tile) and the buffer
-// holds cout x tiles x 2 doubles; otherwise switches them off for this launch.
+// holds cout x tiles x 2 doubles (conv_bn_part_ok, with `cap` doubles of room); otherwise switches them off for this launch.
+template <int MT, int NTILE, int NTH>
+static inline bool conv_bn_part_ok(const ConvArgs& a, unsigned grid_x, unsigned grid_z, int64_t cap) {
+  constexpr int Q = NTILE / 4;
+  return NTH % Q == 0 && MT * (NTILE + 4) >= NTH * 8 && grid_z == 1 && a.up == 0 && !a.out_nchw && (a.Cout & 3) == 0 &&
+         !a.res1 && !a.res2 && !a.relu && (int64_t)a.Cout * grid_x * 2 <= cap;
+}
 template <int MT, int NTILE, int NTH>
 static inline void conv_bn_part_prepare(ConvArgs& a, unsigned grid_x, unsigned grid_z) {
   if (!a.bn_part) return;
-  constexpr int Q = NTILE / 4;
-  const bool ok = NTH % Q == 0 && MT * (NTILE + 4) >= NTH * 8 && grid_z == 1 && a.up == 0 && !a.out_nchw && (a.Cout & 3) == 0 &&
-                  !a.res1 && !a.res2 && !a.relu && (int64_t)a.Cout * grid_x * 2 <= a.bn_part_cap;
-  if (!ok) {
+  if (!conv_bn_part_ok<MT, NTILE, NTH>(a, grid_x, grid_z, a.bn_part_cap)) {
     a.bn_part = nullptr;
     return;
   }
@@ -372,6 +375,11 @@ int mval_launch_conv_mfma(const ConvArgs& a, hipStream_t s);  // conv_mfma.hip; 
 int mval_conv_mfma_supported(const ConvArgs& a);            // same selection logic, no launch
 int mval_launch_conv_split(const ConvArgs& a, hipStream_t s);  // conv_mfma_split.hip (a.planes); returns 1 if unsupported
 int mval_conv_split_supported(const ConvArgs& a);
+int mval_conv_split_form_of(const ConvArgs& a, mval_split_form* form);  // 1 + the form the launcher would run, 0 if unsupported; no launch
+// net.hip: the geometry of an op as mval_op_launch runs it, and what it sets for a split-kernel op besides geometry and buffers (planes; a
+// transposed conv as the four-parity 2x2 form; w_packed may be nullptr)
+void mval_op_geometry(ConvArgs& a, const mval_op* op, int n_images);
+void mval_split_op_args(ConvArgs& a, const mval_op* op, const float* w_packed);
 int mval_pack_bf3(int mode, const float* w, float* packed, int cout, int cin, int k, hipStream_t s);
 int mval_pack_h2(int mode, const float* w, float* packed, int cout, int cin, int k, hipStream_t s);
 // net.hip: rows[i][*] = max(rows[i][*], max |x| over image i) for n_images images of per_image floats each

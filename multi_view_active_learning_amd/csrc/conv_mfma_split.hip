@@ -377,6 +377,7 @@ __global__ __launch_bounds__(64 * WN * WM)
 }
 
 static thread_local int g_bf3_dry = 0;
+static thread_local mval_split_form* g_split_form = nullptr;  // dry runs leave the form they end on here
 
 template <int PL, int KS, int S, int WN, int WM, int NT, int MS, int G = 1>
 static int launch_split(ConvArgs a, int th, int tw, int tn, hipStream_t s) {
@@ -408,42 +409,52 @@ static int launch_split(ConvArgs a, int th, int tw, int tn, hipStream_t s) {
   if (!NE10 && ne > 6) return 1;
   if (G > 1 && (patch_px != MT || ((a.Cin + BF_KC - 1) / BF_KC) % G != 0)) return 1;
   if (PL == 2 && tn != 1) return 1;  // the fp16 split scales per image: one image per tile (maps under 8 rows use bf16x3)
-  if (g_bf3_dry) return 0;
   constexpr bool PAOK = true;  // (both splits have the separate-correction-accumulator form)
   dim3 grid((unsigned)(a.tiles_x * a.tiles_y * ngroups), (unsigned)((a.NS_total + WN * NT - 1) / (WN * NT)),
             (KS == 2 && a.par_w_stride) ? 4u : 1u);
+  // the kernel variant (the launches below follow it)
+  const bool row_sharing = G == 1 && KS == 3 && S == 1 && tw == 16 && tn == 1 && ne <= 6;
+  const int variant = G > 1 ? MVAL_SPLIT_TWO_CHUNK : row_sharing ? MVAL_SPLIT_ROW_SHARING : ne <= 6 ? MVAL_SPLIT_NE6 : MVAL_SPLIT_NE10;
+  const bool precise = PAOK && a.precise;
+  if (g_bf3_dry) {
+    if (mval_split_form* f = g_split_form) {  // mval_conv_split_form: what would run
+      f->pl = PL; f->ks = KS; f->s = S; f->wn = WN; f->wm = WM; f->nt = NT; f->ms = MS; f->g = G;
+      f->variant = variant;
+      f->th = th; f->tw = tw; f->tn = tn; f->odd = a.tw_magic != 0;
+      f->precise = precise;
+      f->grid_x = (int32_t)grid.x; f->grid_y = (int32_t)grid.y; f->grid_z = (int32_t)grid.z;
+      f->bn_part_ok = conv_bn_part_ok<MT, NTILE, NTH>(a, grid.x, grid.z, INT64_MAX);  // (an ample bn_part_cap)
+      f->bn_part = a.bn_part && f->bn_part_ok;
+    }
+    return 0;
+  }
   conv_amax_prepare(a, a.tiles_x * a.tiles_y, (int)(grid.y * grid.z), s);
   conv_bn_part_prepare<MT, NTILE, NTH>(a, grid.x, grid.z);
   if constexpr (G > 1) {
     constexpr int NEG = (G * MT * 8 + NTH - 1) / NTH;
-    if constexpr (PAOK)
-      if (a.precise) {
-        hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, NEG, false, true, G>), grid, dim3(NTH), smem, s, a);
-        return 0;
-      }
-    hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, NEG, false, false, G>), grid, dim3(NTH), smem, s, a);
+    if (precise)
+      hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, NEG, false, true, G>), grid, dim3(NTH), smem, s, a);
+    else
+      hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, NEG, false, false, G>), grid, dim3(NTH), smem, s, a);
     return 0;
   }
   if constexpr (KS == 3 && S == 1) {
-    if (tw == 16 && tn == 1 && ne <= 6) {  // row sharing
-      if constexpr (PAOK)
-        if (a.precise) {
-          hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, 6, true, true>), grid, dim3(NTH), smem, s, a);
-          return 0;
-        }
-      hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, 6, true>), grid, dim3(NTH), smem, s, a);
+    if (variant == MVAL_SPLIT_ROW_SHARING) {
+      if (precise)
+        hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, 6, true, true>), grid, dim3(NTH), smem, s, a);
+      else
+        hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, 6, true>), grid, dim3(NTH), smem, s, a);
       return 0;
     }
   }
-  if constexpr (PAOK)
-    if (a.precise) {
-      if (ne <= 6)
-        hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, 6, false, true>), grid, dim3(NTH), smem, s, a);
-      else if constexpr (NE10)
-        hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, 10, false, true>), grid, dim3(NTH), smem, s, a);
-      return 0;
-    }
-  if (ne <= 6)
+  if (precise) {
+    if (variant == MVAL_SPLIT_NE6)
+      hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, 6, false, true>), grid, dim3(NTH), smem, s, a);
+    else if constexpr (NE10)
+      hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, 10, false, true>), grid, dim3(NTH), smem, s, a);
+    return 0;
+  }
+  if (variant == MVAL_SPLIT_NE6)
     hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, 6>), grid, dim3(NTH), smem, s, a);
   else if constexpr (NE10)
     hipLaunchKernelGGL((conv_split_kernel<PL, KS, S, WN, WM, NT, MS, 10>), grid, dim3(NTH), smem, s, a);
@@ -599,6 +610,13 @@ int mval_conv_split_supported(const ConvArgs& a) {
   int rc = mval_launch_conv_split(a, nullptr);
   g_bf3_dry = 0;
   return rc == 0;
+}
+
+int mval_conv_split_form_of(const ConvArgs& a, mval_split_form* form) {
+  g_split_form = form;
+  const int ok = mval_conv_split_supported(a);
+  g_split_form = nullptr;
+  return ok;
 }
 
 // ---- weight packing: [tap][cin/32][cout/16][plane][lane][8 x 16 bit] --------------------------

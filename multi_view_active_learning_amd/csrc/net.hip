@@ -282,7 +282,7 @@ int mval_launch_conv_direct(const ConvArgs& a, int kind, hipStream_t s) {
 }
 
 // ---- op executor ------------------------------------------------------------------------
-static void fill_geometry(ConvArgs& a, const mval_op* op, int n_images) {
+void mval_op_geometry(ConvArgs& a, const mval_op* op, int n_images) {
   a.N = n_images;
   a.Hin = op->hin; a.Win = op->win; a.Cin = op->cin;
   a.Hout = op->hout; a.Wout = op->wout; a.Cout = op->cout;
@@ -307,7 +307,7 @@ extern "C" int mval_op_mfma_supported(const mval_op* op, int n_images) {
   ConvArgs a = {};
   a.in = a.w = a.scale = a.shift = a.res1 = a.res2 = nullptr;
   a.out = nullptr;
-  fill_geometry(a, op, n_images);
+  mval_op_geometry(a, op, n_images);
   if (op->kind == MVAL_OP_DECONV) deconv_as_conv(a, op);
   return mval_conv_mfma_supported(a);
 }
@@ -325,6 +325,15 @@ static void deconv_parity(ConvArgs& a, const mval_op* op, int parity, const floa
   a.org_dy = parity >> 1; a.org_dx = parity & 1;
   a.os_log2 = 1; a.ooy = parity >> 1; a.oox = parity & 1;
   if (w_packed) a.w = w_packed + (size_t)parity * deconv_parity_floats(op);
+}
+
+void mval_split_op_args(ConvArgs& a, const mval_op* op, const float* w_packed) {
+  a.planes = op->algo == MVAL_ALGO_MFMA_H2 ? 2 : 3;
+  if (op->kind == MVAL_OP_DECONV) {
+    // the four parity convs in one launch (blockIdx.z): on a few images one parity alone leaves most CUs idle
+    deconv_parity(a, op, 0, w_packed);
+    a.par_w_stride = (int)deconv_parity_floats(op);
+  }
 }
 
 extern "C" int mval_op_algo_supported(const mval_op* op, int n_images, int algo) {
@@ -356,13 +365,12 @@ extern "C" int mval_op_algo_supported(const mval_op* op, int n_images, int algo)
   }
   if ((algo != MVAL_ALGO_MFMA_BF3 && algo != MVAL_ALGO_MFMA_H2) || !op || n_images <= 0) return 0;
   if (op->kind != MVAL_OP_CONV && op->kind != MVAL_OP_DECONV) return 0;
+  if (op->kind == MVAL_OP_DECONV && (op->k != 4 || op->stride != 2 || op->pad != 1 || op->up || op->out_nchw)) return 0;
   ConvArgs a = {};
-  fill_geometry(a, op, n_images);
-  a.planes = algo == MVAL_ALGO_MFMA_H2 ? 2 : 3;
-  if (op->kind == MVAL_OP_DECONV) {
-    if (op->k != 4 || op->stride != 2 || op->pad != 1 || op->up || op->out_nchw) return 0;
-    deconv_parity(a, op, 0, nullptr);
-  }
+  mval_op o = *op;
+  o.algo = algo;
+  mval_op_geometry(a, &o, n_images);
+  mval_split_op_args(a, &o, nullptr);  // (as mval_op_launch runs it: the four parities of a transposed conv in one launch)
   return mval_conv_split_supported(a);
 }
 
@@ -393,7 +401,7 @@ static int op_launch(const mval_op* op, int n_images, float* workspace, const fl
   a.w = op->w_off >= 0 ? params + op->w_off : nullptr;
   a.scale = op->scale_off >= 0 ? params + op->scale_off : nullptr;
   a.shift = op->shift_off >= 0 ? params + op->shift_off : nullptr;
-  fill_geometry(a, op, n_images);
+  mval_op_geometry(a, op, n_images);
   MVAL_REQUIRE(a.in && a.out, "mval_op_launch: missing input/output buffer");
   hipStream_t s = mval_stream(stream);
   if (op->kind == MVAL_OP_TO_P2) {
@@ -551,7 +559,7 @@ static int op_launch(const mval_op* op, int n_images, float* workspace, const fl
   a.out_amax = op->out_amax_off > 0 ? reinterpret_cast<unsigned*>(workspace + op->out_amax_off) : nullptr;
   bool amax_kept = false;  // does the kernel that runs keep out_amax itself?
   if (split) {
-    a.planes = op->algo == MVAL_ALGO_MFMA_H2 ? 2 : 3;
+    mval_split_op_args(a, op, a.w);
     if (a.planes == 2) {
       MVAL_REQUIRE(op->in_amax_off > 0 && a.w, "mval_op_launch: the fp16-split conv needs in_amax_off (max |x| of its input)");
       a.in_amax = reinterpret_cast<const unsigned*>(workspace + op->in_amax_off);
@@ -562,10 +570,6 @@ static int op_launch(const mval_op* op, int n_images, float* workspace, const fl
     amax_kept = !op->out_nchw && (op->cout & 3) == 0;
   }
   if (op->kind == MVAL_OP_DECONV && split) {
-    // the four parity convs in one launch (blockIdx.z): on a few images one parity alone leaves most CUs idle
-    const float* w0 = a.w;
-    deconv_parity(a, op, 0, w0);
-    a.par_w_stride = (int)deconv_parity_floats(op);
     int rc = mval_launch_conv_split(a, s);
     MVAL_REQUIRE(rc == 0, "mval_op_launch: no split MFMA kernel for the transposed conv cin%d cout%d", op->cin, op->cout);
   } else if (op->kind == MVAL_OP_CONV && split) {

@@ -156,12 +156,15 @@ static void deconv_as_conv(ConvArgs& a, const mval_op& op) {
   a.pad = op.k - 1 - op.pad;
 }
 
+static bool split_algo(int algo) { return algo == MVAL_ALGO_MFMA_BF3 || algo == MVAL_ALGO_MFMA_H2; }
+static int split_planes(int algo) { return algo == MVAL_ALGO_MFMA_H2 ? 2 : 3; }
+
 static int run_conv(const ConvArgs& a0, int algo, hipStream_t s, const char* what) {
   ConvArgs a = a0;
-  if (algo == MVAL_ALGO_MFMA_BF3 || algo == MVAL_ALGO_MFMA_H2) {
+  if (split_algo(algo)) {
     // bf16x3: scale-free; fp16x2: the caller set a.in_amax (ONE magnitude row for the tensor: in_amax_stride 0) and
     // a.w_unscale.  Both have the bias-free accumulate mode (a.precise) the training forward needs.
-    a.planes = algo == MVAL_ALGO_MFMA_H2 ? 2 : 3;
+    a.planes = split_planes(algo);
     if (a.planes == 2 && (!a.in_amax || !a.w_unscale)) {
       mval_set_error("%s: the fp16-split conv needs its input's magnitude row and the packed weights' trailer", what);
       return -1;
@@ -718,14 +721,8 @@ extern "C" int mval_conv_dgrad_parity(const float* dz, const float* w_packed, co
   return run_conv(a, algo, mval_stream(stream), "mval_conv_dgrad_parity");
 }
 
-extern "C" int mval_conv_dgrad_scaled(const float* dz, const float* w_packed, const float* ones, const float* zeros, float* dx,
-                                      int accumulate, int N, int hin, int win, int cin, int hout, int wout, int cout, int k,
-                                      int stride, int pad, int algo, const uint32_t* dz_amax_row, void* stream) {
-  MVAL_REQUIRE(dz && w_packed && ones && zeros && dx && N > 0, "mval_conv_dgrad: bad arguments");
-  MVAL_REQUIRE(algo == MVAL_ALGO_MFMA || algo == MVAL_ALGO_MFMA_BF3 || stride == 1,
-               "mval_conv_dgrad: strided data gradient needs an MFMA kernel");
-  MVAL_REQUIRE(algo != MVAL_ALGO_MFMA_H2 || (stride == 1 && dz_amax_row), "mval_conv_dgrad: fp16-split form: stride 1 with dz's magnitude row");
-  ConvArgs a = {};
+// The data gradient as a forward conv: the stride-1 conv over dz (zero-dilated by the stride) with cin' = cout, cout' = cin
+static void dgrad_args(ConvArgs& a, int N, int hin, int win, int cin, int hout, int wout, int cout, int k, int stride, int pad) {
   a.N = N;
   a.Hin = hout; a.Win = wout; a.Cin = cout;
   a.Hout = hin; a.Wout = win; a.Cout = cin;
@@ -736,6 +733,17 @@ extern "C" int mval_conv_dgrad_scaled(const float* dz, const float* w_packed, co
   a.G_total = (cout + 15) / 16;
   a.NS_total = (cin + 15) / 16;
   a.precise = 0;  // measured: only the FORWARD needs bias-free accumulation (its outputs enter batch statistics)
+}
+
+extern "C" int mval_conv_dgrad_scaled(const float* dz, const float* w_packed, const float* ones, const float* zeros, float* dx,
+                                      int accumulate, int N, int hin, int win, int cin, int hout, int wout, int cout, int k,
+                                      int stride, int pad, int algo, const uint32_t* dz_amax_row, void* stream) {
+  MVAL_REQUIRE(dz && w_packed && ones && zeros && dx && N > 0, "mval_conv_dgrad: bad arguments");
+  MVAL_REQUIRE(algo == MVAL_ALGO_MFMA || algo == MVAL_ALGO_MFMA_BF3 || stride == 1,
+               "mval_conv_dgrad: strided data gradient needs an MFMA kernel");
+  MVAL_REQUIRE(algo != MVAL_ALGO_MFMA_H2 || (stride == 1 && dz_amax_row), "mval_conv_dgrad: fp16-split form: stride 1 with dz's magnitude row");
+  ConvArgs a = {};
+  dgrad_args(a, N, hin, win, cin, hout, wout, cout, k, stride, pad);
   a.in = dz;
   a.w = w_packed;
   if (algo == MVAL_ALGO_MFMA_H2) {  // the data-gradient conv has cin' = cout, cout' = cin
@@ -748,4 +756,43 @@ extern "C" int mval_conv_dgrad_scaled(const float* dz, const float* w_packed, co
   a.res1 = accumulate ? dx : nullptr;  // in place: each element is read and written by one thread
   a.res2 = nullptr;
   return run_conv(a, algo, mval_stream(stream), "mval_conv_dgrad");
+}
+
+// Which split kernel a launch of this library runs on (include/mval_hip.h): the ConvArgs are filled by the functions the entries
+// themselves use, then the launcher's dry run reports where its dispatch ends.
+extern "C" int mval_conv_split_form(int use, const mval_op* op, int n_images, int algo, mval_split_form* form) {
+  if (!op || !form || n_images <= 0 || !split_algo(algo)) return 0;
+  static const float some = 0.f;  // (a residual / a partials buffer is only asked for, never read)
+  static double some_part = 0.0;
+  *form = {};
+  ConvArgs a = {};
+  if (use == MVAL_SPLIT_USE_OP) {
+    if ((op->kind != MVAL_OP_CONV && op->kind != MVAL_OP_DECONV) || !mval_op_algo_supported(op, n_images, algo)) return 0;
+    mval_op o = *op;
+    o.algo = algo;
+    mval_op_geometry(a, &o, n_images);
+    mval_split_op_args(a, &o, nullptr);
+    a.res1 = o.res1_off >= 0 ? &some : nullptr;
+    a.res2 = o.res2_off >= 0 ? &some : nullptr;
+  } else if (use == MVAL_SPLIT_USE_TRAIN_FWD) {
+    if (op->kind != MVAL_OP_CONV) return 0;  // (transposed convs run on the exact-fp32 kernels in training)
+    geometry(a, *op, n_images);
+    a.planes = split_planes(algo);
+    a.bn_part = &some_part;  // (mval_train_forward asks for the partials of every conv with a BatchNorm)
+    a.bn_part_cap = INT64_MAX;
+  } else if (use == MVAL_SPLIT_USE_DGRAD) {
+    if (op->kind != MVAL_OP_CONV) return 0;
+    dgrad_args(a, n_images, op->hin, op->win, op->cin, op->hout, op->wout, op->cout, op->k, op->stride, op->pad);
+    a.planes = split_planes(algo);
+    a.res1 = op->res1_off >= 0 ? &some : nullptr;
+  } else if (use == MVAL_SPLIT_USE_DGRAD_PARITY) {
+    if (op->kind != MVAL_OP_CONV || op->k != 3 || op->stride != 2 || op->pad != 1 ||
+        !mval_conv_dgrad_parity_supported(n_images, op->hin, op->win, op->cin, op->hout, op->wout, op->cout, algo))
+      return 0;
+    dgrad_parity_args(a, n_images, op->hin, op->win, op->cin, op->hout, op->wout, op->cout, algo);
+    a.res1 = op->res1_off >= 0 ? &some : nullptr;
+  } else {
+    return 0;
+  }
+  return mval_conv_split_form_of(a, form);
 }

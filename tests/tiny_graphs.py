@@ -112,7 +112,16 @@ def shared(c):
     return _tail(g, z)
 
 
-BUILDERS = {"blocks": blocks, "bneck": bneck, "fuse": fuse, "deconv": deconv, "branches": branches, "shared": shared}
+def single(cin, cout, k, stride):
+    """head to cin channels, then ONE conv + BN + ReLU (cin -> cout, k x k, stride) named "c": a training conv of any geometry on its own."""
+    g = _graph.Graph()
+    x = _head(g, cin)
+    g.new_phase()
+    y = g.conv(x, cout, k, stride, "c", "c_bn", relu=True)
+    return _tail(g, y)
+
+
+BUILDERS = {"blocks": blocks, "bneck": bneck, "fuse": fuse, "deconv": deconv, "branches": branches, "shared": shared, "single": single}
 
 
 # ---- the model on the HIP engine ----

@@ -149,6 +149,21 @@ int mval_masked_mse_fwd(const float* h, const float* g, const uint8_t* valid, fl
 /* d loss / d h = grad_out * 2 (h-g) valid / denom.  grad_out [1] f32 ; grad_h [lead,hw] f32. */
 int mval_masked_mse_bwd(const float* h, const float* g, const uint8_t* valid, const float* grad_out,
                         float* grad_h, int64_t lead, int64_t hw, double denom, void* stream);
+/* The same two against ground truth that is rendered per pixel instead of read (training from key-point targets):
+ *   pt [lead][2] f64 (x, y in heat-map pixels) ; map m is what mval_gt_heatmaps(pt + 2 m, 1, sigma_m, hh, wh) writes, with
+ *   sigma_m = sigma_per_map[m] where sigma_per_map (device, [lead] f64) is non-NULL, else sigma.  The sigma in use must be > 0: the
+ *   scalar is checked here, the array by whoever uploads it (a launcher does not synchronise); 2 sigma^2 = 2.0 * (sigma * sigma) in
+ *   separately rounded float64, as the host forms it for mval_gt_heatmaps.
+ * Bit-identical to mval_masked_mse_fwd/_bwd on those maps: same grid, element -> thread map, float64 accumulation order and final
+ * kernel; the float4 walk where hh * wh % 4 == 0 and h is 16-byte aligned, else the scalar walk.  A masked map is neither rendered nor
+ * counted (its points may be NaN) and gets grad_h = +0.0f.  The backward renders the ground truth again; nothing is kept between the
+ * two.  hh * wh <= INT32_MAX - 1024.  Other arguments, ws and lead == 0 as in the read form. */
+int mval_masked_mse_points_fwd(const float* h, const double* pt, double sigma, const double* sigma_per_map,
+                               const uint8_t* valid, float* out, double* ws, int64_t lead, int hh, int wh, double denom,
+                               void* stream);
+int mval_masked_mse_points_bwd(const float* h, const double* pt, double sigma, const double* sigma_per_map,
+                               const uint8_t* valid, const float* grad_out, float* grad_h, int64_t lead, int hh, int wh,
+                               double denom, void* stream);
 
 /* Workspace bytes of one mval_frame_loss / mval_frame_loss_points call (0 for non-positive sizes). */
 size_t mval_frame_loss_workspace_bytes(int64_t n_frames, int maps_per_frame);

@@ -330,6 +330,66 @@ def masked_mse_bwd(h, g, valid, grad_out, lead, hw, denom):
     return gh
 
 
+def _points_sigma(sigma, lead, device, what):
+    """(scalar sigma, per-map sigmas (lead,) f64 on ``device`` or None) of the points form.  The C entry checks the scalar; it
+    cannot look at a device array without a synchronise, so an array is checked here, while it is on the host, and staged through
+    pinned memory.  An array that is already on the device is taken as it is: a sigma <= 0 there makes the loss NaN or inf."""
+    if not (torch.is_tensor(sigma) or hasattr(sigma, "__len__") or hasattr(sigma, "shape")):
+        return float(sigma), None
+    t = torch.as_tensor(sigma).to(torch.float64).reshape(-1)
+    if t.numel() != lead:
+        raise MvalError(f"{what}: {t.numel()} sigmas for {lead} maps")
+    if not t.is_cuda:
+        if lead and not bool((t > 0).all()):
+            raise MvalError(f"{what}: sigma must be positive")
+        t = t.contiguous()
+        t = (t if t.is_pinned() or not torch.cuda.is_available() else t.pin_memory()).to(device, non_blocking=True)
+    return 1.0, t.contiguous()
+
+
+def _points_args(h, pt, lead, hh, wh, what):
+    if h.numel() != lead * hh * wh:
+        raise MvalError(f"{what}: heat-maps {tuple(h.shape)} are not {lead} maps of {hh} x {wh}")
+    if pt.numel() != lead * 2:
+        raise MvalError(f"{what}: points {tuple(pt.shape)} are not ({lead}, 2)")
+    if not pt.is_cuda:
+        raise MvalError(f"{what}: points must be a HIP tensor")
+
+
+def masked_mse_points_fwd(h, pt, sigma, valid, lead, hh, wh, denom):
+    """``masked_mse_fwd`` against the maps mval_gt_heatmaps renders from pt (lead, 2) f64, without them.  sigma: a float, or one
+    per map ((lead,) array or tensor, host or device)."""
+    what = "mval_masked_mse_points_fwd"
+    _points_args(h, pt, lead, hh, wh, what)
+    s, sm = _points_sigma(sigma, lead, h.device, what)
+    out = torch.zeros((), dtype=torch.float32, device=h.device)
+    ws = torch.empty((2048,), dtype=torch.float64, device=h.device)
+    _check(
+        lib().mval_masked_mse_points_fwd(
+            _p(_req(h, torch.float32, "heatmaps")), _p(_req(pt, torch.float64, "points")), C.c_double(s), _p(sm), _p(valid),
+            _p(out), _p(ws), C.c_longlong(lead), C.c_int(hh), C.c_int(wh), C.c_double(denom), _stream(),
+        ),
+        what,
+    )
+    return out
+
+
+def masked_mse_points_bwd(h, pt, sigma, valid, grad_out, lead, hh, wh, denom):
+    what = "mval_masked_mse_points_bwd"
+    _points_args(h, pt, lead, hh, wh, what)
+    s, sm = _points_sigma(sigma, lead, h.device, what)
+    gh = torch.empty_like(h)
+    _check(
+        lib().mval_masked_mse_points_bwd(
+            _p(_req(h, torch.float32, "heatmaps")), _p(_req(pt, torch.float64, "points")), C.c_double(s), _p(sm), _p(valid),
+            _p(_req(grad_out, torch.float32, "grad")), _p(gh),
+            C.c_longlong(lead), C.c_int(hh), C.c_int(wh), C.c_double(denom), _stream(),
+        ),
+        what,
+    )
+    return gh
+
+
 def frame_loss_workspace_bytes(n_frames: int, maps_per_frame: int) -> int:
     return int(lib().mval_frame_loss_workspace_bytes(C.c_longlong(n_frames), C.c_int(maps_per_frame)))
 

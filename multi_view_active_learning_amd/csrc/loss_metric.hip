@@ -1,30 +1,72 @@
 // Masked heat-map MSE (K8, reference pose_estimators/loss.py:14-20) forward/backward and
 // MKPE / MPJPE (K15, reference utils/evaluation.py:198-208).  HBM-bound streaming kernels.
+// The MSE kernels take the ground truth either from memory (mval_masked_mse_fwd/_bwd) or render it per pixel from the
+// joint's position (mval_masked_mse_points_fwd/_bwd: the expression of mval_gt_heatmaps, gt_heatmap.h).  Both forms are
+// one template, so grid, element -> thread map and accumulation order are the same by construction and the points form
+// has the read form's bits on the maps mval_gt_heatmaps writes.
 #include "mval_common.h"
+#include "gt_heatmap.h"
 
 #define MSE_BLOCKS 1024
 
+// Where the ground truth of the points form comes from: pt [lead][2] f64, and 2 sigma^2 of map m -- from sig[m] where sig
+// is given (2.0 * (s * s), each product rounded on its own, as the host forms two_s2 for mval_gt_heatmaps), else two_s2.
+struct MsePoints {
+  const double* pt;
+  const double* sig;
+  double two_s2;
+  int wh;
+};
+
+__device__ __forceinline__ double mse_two_s2(const MsePoints& q, int64_t m) {
+  return q.sig ? __dmul_rn(2.0, __dmul_rn(q.sig[m], q.sig[m])) : q.two_s2;
+}
+
+// pixel p of map m
+__device__ __forceinline__ float mse_render(const MsePoints& q, int p, double px, double py, double two_s2) {
+  return mval_gt_heatmap_pixel(p % q.wh, p / q.wh, px, py, two_s2);
+}
+
+template <bool POINTS>
 __global__ __launch_bounds__(256) void mse_partial_kernel(const float* __restrict__ h, const float* __restrict__ g,
-                                                          const uint8_t* __restrict__ valid, double* __restrict__ ws,
-                                                          int64_t lead, int64_t hw) {
+                                                          const MsePoints q, const uint8_t* __restrict__ valid,
+                                                          double* __restrict__ ws, int64_t lead, int64_t hw) {
   __shared__ double red[4];
   double acc = 0.0;
   const int64_t total = lead * hw;
-  const bool vec = (hw & 3) == 0 && (((uintptr_t)h | (uintptr_t)g) & 15) == 0;
+  const bool vec = (hw & 3) == 0 && (((uintptr_t)h | (uintptr_t)g) & 15) == 0;  // (points form: g == nullptr)
   if (vec) {
     const int64_t n4 = total >> 2;
     const float4* h4 = reinterpret_cast<const float4*>(h);
     const float4* g4 = reinterpret_cast<const float4*>(g);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-      if (valid && !valid[(i << 2) / hw]) continue;
-      float4 a = h4[i], b = g4[i];
+      if (valid && !valid[(i << 2) / hw]) continue;  // a masked map is neither read nor rendered
+      float4 a = h4[i], b;
+      if (POINTS) {
+        const int64_t m = (i << 2) / hw;  // hw % 4 == 0: the four pixels are of one map
+        const int p = (int)((i << 2) - m * hw);
+        const double px = q.pt[m * 2], py = q.pt[m * 2 + 1], t = mse_two_s2(q, m);
+        b.x = mse_render(q, p, px, py, t);
+        b.y = mse_render(q, p + 1, px, py, t);
+        b.z = mse_render(q, p + 2, px, py, t);
+        b.w = mse_render(q, p + 3, px, py, t);
+      } else {
+        b = g4[i];
+      }
       float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z, d3 = a.w - b.w;
       acc += (double)(d0 * d0) + (double)(d1 * d1) + (double)(d2 * d2) + (double)(d3 * d3);
     }
   } else {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
       if (valid && !valid[i / hw]) continue;
-      float d = h[i] - g[i];
+      float b;
+      if (POINTS) {
+        const int64_t m = i / hw;
+        b = mse_render(q, (int)(i - m * hw), q.pt[m * 2], q.pt[m * 2 + 1], mse_two_s2(q, m));
+      } else {
+        b = g[i];
+      }
+      float d = h[i] - b;
       acc += (double)(d * d);
     }
   }
@@ -45,44 +87,97 @@ __global__ __launch_bounds__(256) void mse_final_kernel(const double* __restrict
   if (threadIdx.x == 0) out[0] = (float)(((red[0] + red[1]) + (red[2] + red[3])) / denom);
 }
 
-extern "C" int mval_masked_mse_fwd(const float* h, const float* g, const uint8_t* valid, float* out, double* ws,
-                                   int64_t lead, int64_t hw, double denom, void* stream) {
-  MVAL_REQUIRE(lead >= 0 && hw > 0 && denom != 0.0, "mval_masked_mse_fwd: bad dims");
+template <bool POINTS>
+static int mse_fwd_launch(const char* name, const float* h, const float* g, const MsePoints& q, const uint8_t* valid,
+                          float* out, double* ws, int64_t lead, int64_t hw, double denom, void* stream) {
   int64_t total = lead * hw;
   int nb = (int)((total / 4 + 255) / 256);
   if (nb < 1) nb = 1;
   if (nb > MSE_BLOCKS) nb = MSE_BLOCKS;
-  hipLaunchKernelGGL(mse_partial_kernel, dim3(nb), dim3(256), 0, mval_stream(stream), h, g, valid, ws, lead, hw);
-  MVAL_CHECK_LAUNCH("mval_masked_mse_fwd");
+  hipLaunchKernelGGL((mse_partial_kernel<POINTS>), dim3(nb), dim3(256), 0, mval_stream(stream), h, g, q, valid, ws, lead, hw);
+  MVAL_CHECK_LAUNCH(name);
   hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, mval_stream(stream), ws, out, nb, denom);
-  MVAL_CHECK_LAUNCH("mval_masked_mse_fwd/final");
+  MVAL_CHECK_LAUNCH(name);
   return 0;
 }
 
+extern "C" int mval_masked_mse_fwd(const float* h, const float* g, const uint8_t* valid, float* out, double* ws,
+                                   int64_t lead, int64_t hw, double denom, void* stream) {
+  MVAL_REQUIRE(lead >= 0 && hw > 0 && denom != 0.0, "mval_masked_mse_fwd: bad dims");
+  return mse_fwd_launch<false>("mval_masked_mse_fwd", h, g, MsePoints{nullptr, nullptr, 0.0, 0}, valid, out, ws, lead, hw, denom,
+                               stream);
+}
+
+template <bool POINTS>
 __global__ __launch_bounds__(256) void mse_bwd_kernel(const float* __restrict__ h, const float* __restrict__ g,
-                                                      const uint8_t* __restrict__ valid,
+                                                      const MsePoints q, const uint8_t* __restrict__ valid,
                                                       const float* __restrict__ grad_out, float* __restrict__ gh,
                                                       int64_t lead, int64_t hw, float denom) {
   const float gs = grad_out[0] / denom;  // d(sum/denom)
   const int64_t total = lead * hw;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     bool ok = !valid || valid[i / hw];
-    float d = h[i] - g[i];
-    gh[i] = ok ? (2.0f * d) * gs : 0.0f;
+    if (POINTS) {  // rendered again, not kept from the forward; a masked map is not rendered
+      float r = 0.0f;
+      if (ok) {
+        const int64_t m = i / hw;
+        float d = h[i] - mse_render(q, (int)(i - m * hw), q.pt[m * 2], q.pt[m * 2 + 1], mse_two_s2(q, m));
+        r = (2.0f * d) * gs;
+      }
+      gh[i] = r;
+    } else {
+      float d = h[i] - g[i];
+      gh[i] = ok ? (2.0f * d) * gs : 0.0f;
+    }
   }
+}
+
+template <bool POINTS>
+static int mse_bwd_launch(const char* name, const float* h, const float* g, const MsePoints& q, const uint8_t* valid,
+                          const float* grad_out, float* grad_h, int64_t lead, int64_t hw, double denom, void* stream) {
+  int64_t total = lead * hw;
+  if (total == 0) return 0;
+  int nb = (int)((total + 255) / 256);
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL((mse_bwd_kernel<POINTS>), dim3(nb), dim3(256), 0, mval_stream(stream), h, g, q, valid, grad_out, grad_h,
+                     lead, hw, (float)denom);
+  MVAL_CHECK_LAUNCH(name);
+  return 0;
 }
 
 extern "C" int mval_masked_mse_bwd(const float* h, const float* g, const uint8_t* valid, const float* grad_out,
                                    float* grad_h, int64_t lead, int64_t hw, double denom, void* stream) {
   MVAL_REQUIRE(lead >= 0 && hw > 0 && denom != 0.0, "mval_masked_mse_bwd: bad dims");
-  int64_t total = lead * hw;
-  if (total == 0) return 0;
-  int nb = (int)((total + 255) / 256);
-  if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(mse_bwd_kernel, dim3(nb), dim3(256), 0, mval_stream(stream), h, g, valid, grad_out, grad_h, lead,
-                     hw, (float)denom);
-  MVAL_CHECK_LAUNCH("mval_masked_mse_bwd");
-  return 0;
+  return mse_bwd_launch<false>("mval_masked_mse_bwd", h, g, MsePoints{nullptr, nullptr, 0.0, 0}, valid, grad_out, grad_h, lead, hw,
+                               denom, stream);
+}
+
+// The points form.  A map's pixel index is an int and lead * hh * wh must not overflow; sigma_per_map lives on the device
+// and cannot be looked at here without a synchronise: its callers check it where it still is on the host (_lib.py).
+#define MSE_POINTS_REQUIRE(name)                                                                                         \
+  do {                                                                                                                   \
+    MVAL_REQUIRE(lead >= 0 && hh > 0 && wh > 0 && denom != 0.0, name ": bad dims");                                      \
+    MVAL_REQUIRE((int64_t)hh * wh <= INT32_MAX - 4 * 256, name ": a map of %d x %d exceeds one launch", hh, wh);         \
+    MVAL_REQUIRE(lead <= INT64_MAX / ((int64_t)hh * wh), name ": %lld maps of %d x %d overflow", (long long)lead, hh, wh); \
+    MVAL_REQUIRE(sigma_per_map || sigma > 0, name ": sigma must be positive");                                           \
+  } while (0)
+
+extern "C" int mval_masked_mse_points_fwd(const float* h, const double* pt, double sigma, const double* sigma_per_map,
+                                          const uint8_t* valid, float* out, double* ws, int64_t lead, int hh, int wh,
+                                          double denom, void* stream) {
+  MSE_POINTS_REQUIRE("mval_masked_mse_points_fwd");
+  MVAL_REQUIRE(out && ws && (lead == 0 || (h && pt)), "mval_masked_mse_points_fwd: null argument");
+  return mse_fwd_launch<true>("mval_masked_mse_points_fwd", h, nullptr, MsePoints{pt, sigma_per_map, 2.0 * (sigma * sigma), wh},
+                              valid, out, ws, lead, (int64_t)hh * wh, denom, stream);
+}
+
+extern "C" int mval_masked_mse_points_bwd(const float* h, const double* pt, double sigma, const double* sigma_per_map,
+                                          const uint8_t* valid, const float* grad_out, float* grad_h, int64_t lead, int hh,
+                                          int wh, double denom, void* stream) {
+  MSE_POINTS_REQUIRE("mval_masked_mse_points_bwd");
+  MVAL_REQUIRE(lead == 0 || (h && pt && grad_out && grad_h), "mval_masked_mse_points_bwd: null argument");
+  return mse_bwd_launch<true>("mval_masked_mse_points_bwd", h, nullptr, MsePoints{pt, sigma_per_map, 2.0 * (sigma * sigma), wh},
+                              valid, grad_out, grad_h, lead, (int64_t)hh * wh, denom, stream);
 }
 
 // ---- MKPE ------------------------------------------------------------------------------

@@ -6,6 +6,7 @@
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from .. import _lib
@@ -36,6 +37,41 @@ class _MaskedMSE(torch.autograd.Function):
         return gh, None, None, None
 
 
+def _valid_per_map(valid, n, j):
+    """joint_valid broadcastable to (N, J, 1, 1) -> the (N * J,) uint8 mask the kernels read (None stays None)."""
+    if valid is None:
+        return None
+    return valid.expand(n, j, 1, 1).reshape(n * j).to(torch.uint8).contiguous()
+
+
+class _MaskedMSEPoints(torch.autograd.Function):
+    """``_MaskedMSE`` against the Gaussian maps of key-points, rendered per pixel in both directions
+    (``mval_masked_mse_points_fwd`` / ``_bwd``).  Saved for the backward: the heat-maps, the points, the sigmas and the mask --
+    no (N, J, h, w) ground truth exists at any time."""
+
+    @staticmethod
+    def forward(ctx, heatmaps, pt, sigma, valid, denom):
+        h = heatmaps.contiguous()
+        n, j, hh, wh = h.shape
+        v = _valid_per_map(valid, n, j)
+        out = _lib.masked_mse_points_fwd(h, pt, sigma, v, n * j, hh, wh, denom)
+        per_map = torch.is_tensor(sigma)
+        none = torch.empty(0, device=h.device)
+        ctx.save_for_backward(h, pt, sigma if per_map else none, v if v is not None else none)
+        ctx.sigma = None if per_map else sigma
+        ctx.has_valid = v is not None
+        ctx.dims = (n * j, hh, wh, denom)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        h, pt, sm, v = ctx.saved_tensors
+        lead, hh, wh, denom = ctx.dims
+        gh = _lib.masked_mse_points_bwd(h, pt, sm if ctx.sigma is None else ctx.sigma, v if ctx.has_valid else None,
+                                        grad_out.contiguous(), lead, hh, wh, denom)
+        return gh, None, None, None, None
+
+
 def _per_frame_args(heatmaps, joint_valid):
     """(B, V, J, h, w) float32 heat-maps, contiguous, and the (B * V * J,) uint8 mask of ``joint_valid`` (or None)."""
     if heatmaps.dim() != 5:
@@ -53,6 +89,31 @@ class Pose2DMeanSquaredError:
         """heatmaps, gt (N, J, H, W); joint_valid broadcastable (N, J, 1, 1) bool/uint8."""
         denom = heatmaps.shape[0] * heatmaps.shape[-1] * heatmaps.shape[-2]
         return _MaskedMSE.apply(heatmaps, gt_heatmaps, joint_valid, float(denom))
+
+    def pose_2d_mse_from_points(self, heatmaps, points, sigma, joint_valid=None):
+        """``pose_2d_mse`` against the Gaussian maps of ``points`` without materialising them, forward and backward
+        (``mval_masked_mse_points_fwd`` / ``_bwd``): loss and ``heatmaps.grad`` are bit-identical to
+        ``pose_2d_mse(heatmaps, utils.preprocess.gt_heatmaps(points, sigma, h, w), joint_valid)``.
+        heatmaps (N, J, h, w); points (N, J, 2) in heat-map pixels, taken to float64 on the heat-maps' device; sigma a float, or a
+        tensor / array broadcastable to (N, J) -- a (N,) one is per image (labelled frames DATA.SIGMA, pseudo-labelled ones
+        DATA.PSEUDO_LABEL_SIGMA in one batch); joint_valid and the divisor (N * h * w, J omitted) as in ``pose_2d_mse``.
+        Every sigma must be > 0: checked for a float and for an array that arrives on the host."""
+        n, j, hh, wh = heatmaps.shape
+        points = torch.as_tensor(points)
+        if tuple(points.shape) != (n, j, 2):
+            raise _lib.MvalError("pose_2d_mse_from_points: points %s are not (%d, %d, 2)" % (tuple(points.shape), n, j))
+        pt = points.detach().to(device=heatmaps.device, dtype=torch.float64).contiguous()
+        if not torch.is_tensor(sigma) and np.ndim(sigma) == 0:
+            sigma = float(sigma)
+            if not sigma > 0:
+                raise _lib.MvalError("pose_2d_mse_from_points: sigma must be positive, got %r" % (sigma,))
+        else:
+            s = torch.as_tensor(sigma).detach().to(torch.float64)
+            if s.dim() == 1 and s.shape[0] == n:
+                s = s.reshape(n, 1)
+            s = torch.broadcast_to(s, (n, j)).reshape(n * j)
+            sigma = _lib._points_sigma(s, n * j, heatmaps.device, "pose_2d_mse_from_points")[1]
+        return _MaskedMSEPoints.apply(heatmaps, pt, sigma, joint_valid, float(n * hh * wh))
 
     def pose_2d_mse_single_batch(self, heatmap, gt_heatmap):
         """loss.py:22-24: sum((h - gt)^2) / (H * W)."""

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from .pose_estimators.loss import Pose2DMeanSquaredError
-from .utils import coreset, evaluation, triangulation
+from .utils import coreset, evaluation, preprocess, triangulation
 
 _KIND = {"HP": _lib.SCORE_HP, "MPE": _lib.SCORE_MPE, "BSB": _lib.SCORE_BSB}
 
@@ -185,6 +185,39 @@ def _stage_batch(dp):
     return out
 
 
+TRAIN_TARGET_KEYS = ("gt_heatmap", "gt_points", "2d_keypoints")
+
+
+def select_train_target(data, al_cfg):
+    """What a training batch is compared against -- (kind, target, sigma), chosen as the CLUSTER pass chooses its target
+    (``_stage_cluster_targets``); no device work:
+      "gt_heatmap"  ``data["gt_heatmap"]`` itself, where the batch has it (the reference's loader); sigma None
+      "points"      else ``data["gt_points"]`` (B, V, J, 2), float64 heat-map pixels -- what ``prepare_views(compact=True)`` returns
+      "points"      else ``data["2d_keypoints"] / POSE_ESTIMATOR.STRIDE`` in float64
+    and a KeyError naming the three keys otherwise.  For "points", sigma is the batch's ``gt_sigma`` ((B,), one per frame) where
+    present, else DATA.SIGMA; a caller that mixes pseudo-labelled frames into a batch sets DATA.PSEUDO_LABEL_SIGMA for those
+    frames (dataset/dataset.py:123-132).
+    ``2d_keypoints`` is float32 in the reference's batch, while its ``gt_heatmap`` is rendered from the float64 projection: the maps
+    of ``2d_keypoints / STRIDE`` are close to the reference's but not its bits.  ``gt_points`` is the exact path."""
+    if "gt_heatmap" in data:
+        return "gt_heatmap", data["gt_heatmap"], None
+    if "gt_points" in data:
+        pts = torch.as_tensor(data["gt_points"]).to(torch.float64)
+    elif "2d_keypoints" in data:
+        pts = torch.as_tensor(data["2d_keypoints"]).to(torch.float64) / al_cfg.POSE_ESTIMATOR.STRIDE
+    else:
+        raise KeyError("train_step: a batch needs one of %s" % ", ".join(repr(k) for k in TRAIN_TARGET_KEYS))
+    return "points", pts, data["gt_sigma"] if "gt_sigma" in data else al_cfg.DATA.SIGMA
+
+
+def _stage_small(t):
+    """A small host tensor on the current device, staged like ``_SMALL_KEYS``: pinned, non-blocking, on the caller's stream."""
+    if t.is_cuda:
+        return t
+    t = t.contiguous()
+    return (t if t.is_pinned() else t.pin_memory()).to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
+
+
 class ActiveLearningStrategy:
     def __init__(self, al_cfg):
         self.al_cfg = al_cfg
@@ -213,8 +246,15 @@ class ActiveLearningStrategy:
     # ---- model glue ---------------------------------------------------------------
     @staticmethod
     def _compute_batch_heatmap(pose_estimator, data):
-        """strategy.py:772-782: (B,V,C,H,W) -> (B*V,C,H,W), frame-major / view-minor."""
+        """strategy.py:772-782: (B,V,C,H,W) -> (B*V,C,H,W), frame-major / view-minor.  A compact batch carries the resized views
+        as uint8 (B,V,H,W,3), a quarter of the bytes, and is normalised on the device (``mval_normalize_views_u8``) into the
+        float32 tensor the reference's loader would have uploaded, bit for bit."""
         images = data["images"].cuda()
+        if images.dtype == torch.uint8:
+            if images.dim() != 5 or images.shape[4] != 3:
+                raise ValueError("uint8 images must be (B, V, H, W, 3), got %s" % (tuple(images.shape),))
+            h, w = images.shape[2], images.shape[3]
+            return pose_estimator(preprocess.normalize_views_u8(images.reshape([-1, h, w, 3])))
         c, h, w = images.shape[2], images.shape[3], images.shape[4]
         return pose_estimator(images.reshape([-1, c, h, w]))
 
@@ -226,15 +266,46 @@ class ActiveLearningStrategy:
             heatmaps, gt_heatmap.reshape([-1, j, h, w]), per_view_joint_valid.reshape([-1, j, 1, 1])
         )
 
+    @staticmethod
+    def _stage_train_points(points, sigma):
+        """The points target (B, V, J, 2) float64 and its sigma on the device.  A per-frame sigma (B,) becomes one per image
+        (B * V,); it is checked here, on the host, because the loss kernels cannot refuse a device array."""
+        points = _stage_small(points)
+        if not torch.is_tensor(sigma) and np.ndim(sigma) == 0:
+            return points, float(sigma)
+        b, v = points.shape[0], points.shape[1]
+        s = torch.as_tensor(sigma).to(torch.float64).reshape(-1)
+        if s.shape[0] != b:
+            raise ValueError("train_step: gt_sigma must be (B,) = (%d,), got %s" % (b, tuple(torch.as_tensor(sigma).shape)))
+        if not s.is_cuda and not bool((s > 0).all()):
+            raise ValueError("train_step: every gt_sigma must be positive")
+        return points, _stage_small(s.reshape(b, 1).expand(b, v).reshape(b * v))
+
+    @staticmethod
+    def _compute_batch_loss_points(points, sigma, heatmaps, per_view_joint_valid, loss):
+        """``_compute_batch_loss`` against the maps of points (B, V, J, 2), not materialised."""
+        j = heatmaps.shape[1]
+        return loss.pose_2d_mse_from_points(heatmaps, points.reshape([-1, j, 2]), sigma, per_view_joint_valid.reshape([-1, j, 1, 1]))
+
     def train_step(self, pose_estimator, optimizer, data, lr_scheduler=None):
         """Body of the training inner loop (strategy.py:460-487): zero_grad -> heat-maps ->
         masked MSE -> host guard (NaN / inf / > LOSS_CLIP_VALUE skips the step)
-        -> backward -> optimizer step -> scheduler step.  Returns (loss_value, stepped)."""
+        -> backward -> optimizer step -> scheduler step.  Returns (loss_value, stepped).
+        The target is ``select_train_target``'s: ``gt_heatmap`` where the batch has it, else the maps of ``gt_points`` (or of
+        ``2d_keypoints / STRIDE``, close to the reference's maps but not their bits) under ``gt_sigma`` / DATA.SIGMA, rendered
+        inside the loss kernels and never materialised; ``images`` may be uint8 (``_compute_batch_heatmap``)."""
         optimizer.zero_grad()
+        kind, target, sigma = select_train_target(data, self.al_cfg)
+        if kind == "points":  # the small tensors go up before the network, like _stage_batch's
+            target, sigma = self._stage_train_points(target, sigma)
         heatmaps = self._compute_batch_heatmap(pose_estimator, data)
-        gt = data["gt_heatmap"].cuda()
+        if kind == "gt_heatmap":
+            gt = target.cuda()
         pv = data["per_view_joint_valid"].to(torch.uint8).cuda()
-        batch_loss = self._compute_batch_loss(gt, heatmaps, pv, self.loss)
+        if kind == "gt_heatmap":
+            batch_loss = self._compute_batch_loss(gt, heatmaps, pv, self.loss)
+        else:
+            batch_loss = self._compute_batch_loss_points(target, sigma, heatmaps, pv, self.loss)
         value = batch_loss.data.item()
         ok = not (math.isnan(value) or math.isinf(value) or value > self.al_cfg.TRAIN.LOSS_CLIP_VALUE)
         if ok:

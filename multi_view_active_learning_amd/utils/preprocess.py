@@ -166,14 +166,18 @@ def gt_heatmaps(pt, sigma, h, w):
     return out
 
 
-def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, gt_stride, sigma, augmentation=None):
+def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, gt_stride, sigma, augmentation=None, compact=False):
     """Batch of views of one or more frames: images (list of uint8 HIP tensors (h0, w0, 3) RGB), boxes (list of
     (left, top, right, bottom)), cameras (list of dicts R, t, K, dist), kp_3d ((>=3, J) array, or one per
     view).  Returns the reference's per-view entries stacked over views: images (V,3,H,W) and gt_heatmap
     (V,J,h,w) on the device; proj_matrices (V,3,4) float64, 2d_keypoints / 2d_after_crop (V,J,2) float32,
     square_box (V,4) float32 on the host.
     augmentation: None (the "val"/"test" split), or a utils.augmentation.RandAugment (the "train" split, dataset.py:212-213): its ops are drawn
-    per view in order and run on the resized uint8 views before the normalisation; gt_heatmap is unchanged (the reference drops the rotated maps)."""
+    per view in order and run on the resized uint8 views before the normalisation; gt_heatmap is unchanged (the reference drops the rotated maps).
+    compact: True returns the batch in its small form -- images as the resized (and, with an augmentation, augmented) uint8 views (V,H,W,3),
+    what ``resize_views_u8`` gives, and gt_points (V,J,2) float64 on the device, the heat-map-pixel positions ``gt_heatmaps`` is handed
+    otherwise, instead of gt_heatmap; the other keys are unchanged.  ``strategy.train_step`` and everything that goes through
+    ``_compute_batch_heatmap`` take such a batch: the views are normalised and the maps rendered on the device, to the same bits."""
     v = len(images)
     kps = kp_3d if isinstance(kp_3d, (list, tuple)) else [kp_3d] * v
     sq, proj, pts, pts_crop = [], [], [], []
@@ -191,15 +195,23 @@ def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, 
         proj.append(K.dot(np.hstack([R, t])))
         pts.append(_project(K, R, t, cam.get("dist"), skel))
         sq.append(bbox)
-    if augmentation is None:
+    if compact:
+        out_images = resize_views_u8(images, sq, in_w, in_h)
+        if augmentation is not None:
+            out_images = augmentation.apply(out_images, augmentation.draw(v), inplace=True)
+    elif augmentation is None:
         out_images = resize_views(images, sq, in_w, in_h)
     else:
         out_images = normalize_views_u8(augmentation.apply(resize_views_u8(images, sq, in_w, in_h), augmentation.draw(v), inplace=True))
     pt = np.stack(pts)
-    hm = gt_heatmaps(torch.from_numpy(pt / gt_stride).to(out_images.device), sigma, in_h // gt_stride, in_w // gt_stride)
+    gt_points = torch.from_numpy(pt / gt_stride).to(out_images.device)
+    if compact:
+        target = {"gt_points": gt_points}
+    else:
+        target = {"gt_heatmap": gt_heatmaps(gt_points, sigma, in_h // gt_stride, in_w // gt_stride)}
     return {
         "images": out_images,
-        "gt_heatmap": hm,
+        **target,
         "proj_matrices": np.stack(proj),
         "2d_keypoints": pt.astype(np.float32),
         "2d_after_crop": np.stack(pts_crop).astype(np.float32),

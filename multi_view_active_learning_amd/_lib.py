@@ -171,12 +171,26 @@ def soft_argmax(hm, n_maps, hh, wh, scale):
     return out
 
 
-def _triangulation_outputs(b, j, dev):
+def _triangulate(entry, kp2d, proj, valid, b, v, j, eps, table=()):
+    """What the two triangulation entries share: key-points float32 or int64, the five outputs, the call.  ``table``: the
+    arguments an entry takes between ``valid`` and the outputs."""
+    kp_is_f32 = 1 if kp2d.dtype == torch.float32 else 0
+    if not kp_is_f32:
+        _req(kp2d, torch.int64, "keypoints_2d")
+    dev = proj.device
     kp3d = torch.empty((b, j, 3), dtype=torch.float64, device=dev)
     jerr = torch.empty((b, j), dtype=torch.float64, device=dev)
     jinl = torch.empty((b, j), dtype=torch.int32, device=dev)
     metric = torch.empty((b,), dtype=torch.float64, device=dev)
     inl = torch.empty((b,), dtype=torch.int32, device=dev)
+    _check(
+        getattr(lib(), entry)(
+            _p(kp2d), C.c_int(kp_is_f32), _p(_req(proj, torch.float64, "proj_matricies")), _p(valid), *table,
+            _p(kp3d), _p(jerr), _p(jinl), _p(metric), _p(inl),
+            C.c_int(b), C.c_int(v), C.c_int(j), C.c_double(eps), _stream(),
+        ),
+        entry,
+    )
     return kp3d, jerr, jinl, metric, inl
 
 
@@ -185,41 +199,16 @@ PAIRS_MAX_VIEWS = 32  # MVAL_PAIRS_MAX_VIEWS (include/mval_hip.h): views mval_tr
 
 def triangulate_ransac_pairs(kp2d, proj, valid, pairs, b, v, j, eps):
     """mval_triangulate_ransac_pairs: pairs (B, J, P, 2) uint8, one table per problem, or (1, P, 2), one shared by all."""
-    kp_is_f32 = 1 if kp2d.dtype == torch.float32 else 0
-    if not kp_is_f32:
-        _req(kp2d, torch.int64, "keypoints_2d")
     _req(pairs, torch.uint8, "pairs")
     shared = pairs.dim() == 3
     if pairs.shape[-1] != 2 or (tuple(pairs.shape[:-2]) != (1,) if shared else tuple(pairs.shape[:-2]) != (b, j)):
         raise MvalError(f"pairs: expected (1, P, 2) or ({b}, {j}, P, 2), got {tuple(pairs.shape)}")
-    kp3d, jerr, jinl, metric, inl = _triangulation_outputs(b, j, proj.device)
-    _check(
-        lib().mval_triangulate_ransac_pairs(
-            _p(kp2d), C.c_int(kp_is_f32), _p(_req(proj, torch.float64, "proj_matricies")), _p(valid),
-            _p(pairs), C.c_int(pairs.shape[-2]), C.c_int(int(shared)),
-            _p(kp3d), _p(jerr), _p(jinl), _p(metric), _p(inl),
-            C.c_int(b), C.c_int(v), C.c_int(j), C.c_double(eps), _stream(),
-        ),
-        "mval_triangulate_ransac_pairs",
-    )
-    return kp3d, jerr, jinl, metric, inl
+    return _triangulate("mval_triangulate_ransac_pairs", kp2d, proj, valid, b, v, j, eps,
+                        table=(_p(pairs), C.c_int(pairs.shape[-2]), C.c_int(int(shared))))
 
 
 def triangulate_ransac(kp2d, proj, valid, b, v, j, eps):
-    dev = proj.device
-    kp_is_f32 = 1 if kp2d.dtype == torch.float32 else 0
-    if not kp_is_f32:
-        _req(kp2d, torch.int64, "keypoints_2d")
-    kp3d, jerr, jinl, metric, inl = _triangulation_outputs(b, j, dev)
-    _check(
-        lib().mval_triangulate_ransac(
-            _p(kp2d), C.c_int(kp_is_f32), _p(_req(proj, torch.float64, "proj_matricies")), _p(valid),
-            _p(kp3d), _p(jerr), _p(jinl), _p(metric), _p(inl),
-            C.c_int(b), C.c_int(v), C.c_int(j), C.c_double(eps), _stream(),
-        ),
-        "mval_triangulate_ransac",
-    )
-    return kp3d, jerr, jinl, metric, inl
+    return _triangulate("mval_triangulate_ransac", kp2d, proj, valid, b, v, j, eps)
 
 
 def reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, sigma):

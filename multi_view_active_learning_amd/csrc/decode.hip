@@ -2,14 +2,7 @@
 // HBM-bound: each heat-map is read exactly once (J*hh*wh*4 bytes per frame x view).
 // One 64-lane wave per map, float4 loads, wave reduction with first-index tie-break.
 #include "mval_common.h"
-
-// order: NaN is the maximum (torch.argmax semantics); ties -> lowest flat index
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) {
-  bool vn = v != v, bn = bv != bv;
-  if (vn != bn) return vn;
-  if (vn) return i < bi;
-  return (v > bv) || (v == bv && i < bi);
-}
+#include "numeric_order.h"  // argmax_better: torch.argmax's order
 
 __global__ __launch_bounds__(256) void argmax_decode_kernel(
     const float* __restrict__ hm, const uint8_t* __restrict__ valid, int64_t* __restrict__ kp2d,
@@ -31,22 +24,22 @@ __global__ __launch_bounds__(256) void argmax_decode_kernel(
     for (int i = lane; i < (npix >> 2); i += 64) {
       float4 q = p4[i];
       int base = i << 2;
-      if (better(q.x, base, bv, bi)) { bv = q.x; bi = base; }
-      if (better(q.y, base + 1, bv, bi)) { bv = q.y; bi = base + 1; }
-      if (better(q.z, base + 2, bv, bi)) { bv = q.z; bi = base + 2; }
-      if (better(q.w, base + 3, bv, bi)) { bv = q.w; bi = base + 3; }
+      if (argmax_better(q.x, base, bv, bi)) { bv = q.x; bi = base; }
+      if (argmax_better(q.y, base + 1, bv, bi)) { bv = q.y; bi = base + 1; }
+      if (argmax_better(q.z, base + 2, bv, bi)) { bv = q.z; bi = base + 2; }
+      if (argmax_better(q.w, base + 3, bv, bi)) { bv = q.w; bi = base + 3; }
     }
   } else {
     for (int i = lane; i < npix; i += 64) {
       float q = p[i];
-      if (better(q, i, bv, bi)) { bv = q; bi = i; }
+      if (argmax_better(q, i, bv, bi)) { bv = q; bi = i; }
     }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     float ov = __shfl_xor(bv, o, 64);
     int oi = __shfl_xor(bi, o, 64);
-    if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    if (argmax_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
   }
   if (lane == 0) {
     if (bi == 0x7fffffff) bi = 0;  // all -inf: first element
@@ -60,7 +53,7 @@ extern "C" int mval_argmax_decode(const float* heatmaps, const uint8_t* valid, i
   MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && split_width > 0, "mval_argmax_decode: bad dims");
   int64_t n_maps = (int64_t)B * V * J;
   if (n_maps == 0) return 0;
-  // an all -inf map must still pick index 0: handled by better() never firing -> bi stays max; fix below
+  // an all -inf map must still pick index 0: handled by argmax_better() never firing -> bi stays max; fix below
   dim3 grid((unsigned)((n_maps + 3) / 4));
   hipLaunchKernelGGL(argmax_decode_kernel, grid, dim3(256), 0, mval_stream(stream), heatmaps, valid, kp2d, n_maps, V,
                      J, hh * wh, stride, split_width);

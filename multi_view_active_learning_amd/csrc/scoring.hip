@@ -10,6 +10,7 @@
 //        p = exp(peaks) / sum(exp(peaks)) ; H = sum -p * log(p)   -- float32, python left-to-right
 //   BSB  q = softmax(map, dim=1) ; |q[peak0] - q[peak1]| of its two highest local peaks
 #include "mval_common.h"
+#include "numeric_order.h"  // argmax_better, np_pairwise_sum
 
 #define SC_THREADS 256
 #define SC_MAX_PEAKS 512
@@ -45,14 +46,6 @@ __device__ __forceinline__ float block_reduce_max(float v, float* red) {
 // (value desc, flat index asc) ordering for the candidate sort
 __device__ __forceinline__ bool cand_before(float va, int ia, float vb, int ib) {
   return (va > vb) || (va == vb && ia < ib);
-}
-
-// order of torch.argmax: NaN is the maximum; ties -> lowest flat index (as csrc/decode.hip)
-__device__ __forceinline__ bool sc_better(float v, int i, float bv, int bi) {
-  const bool vn = v != v, bn = bv != bv;
-  if (vn != bn) return vn;
-  if (vn) return i < bi;
-  return (v > bv) || (v == bv && i < bi);
 }
 
 // python's sum() over a list of float32: strictly left to right.  Eight values per pair of 16-byte LDS reads (the one-at-a-time loop
@@ -122,7 +115,7 @@ __device__ __forceinline__ ScArg sc_argmax_wave(float bv, int bi, ScoreSmem* sm)
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(bv, o, 64);
     const int oi = __shfl_xor(bi, o, 64);
-    if (sc_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    if (argmax_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
   }
   // (slots 16.. of red[]: the reductions further down use 0..3, so no barrier is needed between the two)
   if ((tid & 63) == 0) { sm->red[16 + (tid >> 6)] = bv; sm->red[20 + (tid >> 6)] = __int_as_float(bi); }
@@ -133,7 +126,7 @@ __device__ __forceinline__ void sc_argmax_write(float bv, int bi, const ScoreSme
   for (int w = 1; w < SC_THREADS / 64; w++) {
     const float ov = sm->red[16 + w];
     const int oi = __float_as_int(sm->red[20 + w]);
-    if (sc_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    if (argmax_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
   }
   if (bi == 0x7fffffff) bi = 0;  // all -inf: first element
   const int j = (int)(map % d.J);
@@ -600,28 +593,6 @@ extern "C" int mval_score_decode_maps_all(const float* heatmaps, const uint8_t* 
 }
 
 // ---- AVG / STD over the valid maps of a frame, in python / numpy order -----------------
-template <typename T>
-__device__ T np_pairwise_sum_t(const T* a, int n) {
-  if (n < 8) {
-    T r = 0;
-    for (int i = 0; i < n; i++) r += a[i];
-    return r;
-  }
-  if (n <= 128) {
-    T r[8];
-    for (int k = 0; k < 8; k++) r[k] = a[k];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-      for (int k = 0; k < 8; k++) r[k] += a[i + k];
-    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res += a[i];
-    return res;
-  }
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return np_pairwise_sum_t<T>(a, n2) + np_pairwise_sum_t<T>(a + n2, n - n2);
-}
-
 #define SR_MAX 1024
 
 __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uint8_t* __restrict__ valid,
@@ -651,18 +622,18 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
     for (int v = 0; v < V; v++)
       for (int j = 0; j < J; j++)
         if (!valid || valid[(int64_t)b * J + j]) buf[k++] = (double)pm[v * J + j];
-    double mean = np_pairwise_sum_t<double>(buf, n) / (double)n;
+    double mean = np_pairwise_sum<double>(buf, n) / (double)n;
     for (int i = 0; i < n; i++) { double d = buf[i] - mean; buf[i] = d * d; }
-    out[b] = sqrt(np_pairwise_sum_t<double>(buf, n) / (double)n);
+    out[b] = sqrt(np_pairwise_sum<double>(buf, n) / (double)n);
   } else {  // np.std(float32 array): float32 intermediates
     float buf[SR_MAX];
     int k = 0;
     for (int v = 0; v < V; v++)
       for (int j = 0; j < J; j++)
         if (!valid || valid[(int64_t)b * J + j]) buf[k++] = pm[v * J + j];
-    float mean = (float)((double)np_pairwise_sum_t<float>(buf, n) / (double)n);
+    float mean = (float)((double)np_pairwise_sum<float>(buf, n) / (double)n);
     for (int i = 0; i < n; i++) { float d = buf[i] - mean; buf[i] = d * d; }
-    out[b] = (double)sqrtf(np_pairwise_sum_t<float>(buf, n) / (float)n);
+    out[b] = (double)sqrtf(np_pairwise_sum<float>(buf, n) / (float)n);
   }
 }
 

@@ -20,11 +20,11 @@
 // C(32,2) = 496 pairs): the pairs the reference drew from python's RNG (utils/triangulation.py:279-282, drawn on the
 // host by utils.triangulation.draw_view_pairs), or the lexicographic list of a rig whose pairs all fit a larger
 // n_iters.  Up to 64 pairs keep the grouping above; beyond, one wave per problem and lane p takes pairs p, p + 64, ...
-// They share the numeric device functions (r4_*, add_view_rows, dehomogenise, reproj_err, np_pairwise_sum).  The two
-// stages themselves exist TWICE: inline in ransac_dlt_kernel, and as vote_pair / finish_problem for
-// ransac_pairs_kernel -- ransac_dlt_kernel is kept text for text so that the V <= 11 path compiles to the code object
-// it had before the second entry existed.  A fix to one copy of a stage must be made in the other.
+// Both kernels are built from the same two stages, vote_pair (a lane triangulates one pair and votes) and
+// finish_problem (final DLT over the winner's inlier views), and differ only in where a lane's pairs come from and in
+// the width of the reduction key; the host entries share launch_ransac (key-point dtype dispatch, frame_reduce_kernel).
 #include "mval_common.h"
+#include "numeric_order.h"  // np_pairwise_sum: np.mean's order
 
 #define MAXV 11  // C(11,2) = 55 <= 64 = n_iters: beyond that the reference samples pairs randomly
 static_assert(MVAL_PAIRS_MAX_VIEWS == 32, "the inlier mask is 32 bits wide");
@@ -141,103 +141,6 @@ __device__ __forceinline__ double reproj_err(const double* __restrict__ P, const
   return 0.5 * sqrt(dx * dx + dy * dy);
 }
 
-// numpy's pairwise summation (np.add.reduce on a contiguous double vector), so that
-// np.mean(...) in the reference is reproduced bit for bit given equal addends.
-__device__ double np_pairwise_sum(const double* a, int n) {
-  if (n < 8) {
-    double r = 0.0;
-    for (int i = 0; i < n; i++) r += a[i];
-    return r;
-  }
-  if (n <= 128) {
-    double r[8];
-    for (int k = 0; k < 8; k++) r[k] = a[k];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-      for (int k = 0; k < 8; k++) r[k] += a[i + k];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res += a[i];
-    return res;
-  }
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
-}
-
-template <typename KP>
-__global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ kp2d, const double* __restrict__ proj,
-                                                         const uint8_t* __restrict__ valid, double* __restrict__ kp3d,
-                                                         double* __restrict__ joint_err,
-                                                         int32_t* __restrict__ joint_inliers, int64_t n_prob, int V,
-                                                         int J, int n_pairs, int PG, double eps) {
-  const int lane = threadIdx.x;
-  const int grp = lane / PG, p = lane % PG;
-  const int64_t prob = (int64_t)blockIdx.x * (64 / PG) + grp;
-  const bool live = prob < n_prob;
-  const int64_t pr = live ? prob : 0;
-  const int64_t b = pr / J;
-  const int j = (int)(pr % J);
-  const bool is_valid = live && (!valid || valid[b * J + j]);
-  const double* Pb = proj + b * V * 12;
-  const KP* kb = kp2d + (b * V * (int64_t)J + j) * 2;  // + v * J * 2
-
-  // ---- stage 1: lane p triangulates pair p and votes ----------------------------------
-  unsigned mask = 0;
-  int count = 0;
-  if (p < n_pairs) {
-    int a = 0, rem = p;
-    while (rem >= V - 1 - a) { rem -= V - 1 - a; a++; }
-    int c = a + 1 + rem;
-    R4 m;
-    r4_zero(m);
-    add_view_rows(m, Pb + a * 12, (double)kb[(int64_t)a * J * 2], (double)kb[(int64_t)a * J * 2 + 1]);
-    add_view_rows(m, Pb + c * 12, (double)kb[(int64_t)c * J * 2], (double)kb[(int64_t)c * J * 2 + 1]);
-    double h[4], X[3];
-    r4_null_vector(m, h);
-    dehomogenise(h, X);
-    mask = (1u << a) | (1u << c);
-    for (int v = 0; v < V; v++) {
-      double e = reproj_err(Pb + v * 12, X, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
-      if (e < eps) mask |= 1u << v;
-    }
-    count = __popc(mask);
-  }
-  // first pair with the strictly largest set: key = count * 64 + (63 - p), maximise
-  int key = (p < n_pairs) ? count * 64 + (63 - p) : -1;
-  int best = key;
-  for (int o = PG >> 1; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
-  unsigned win = (key == best) ? mask : 0u;
-  for (int o = PG >> 1; o > 0; o >>= 1) win |= __shfl_xor(win, o, 64);
-
-  // ---- stage 2: final DLT on the sorted inlier views ----------------------------------
-  if (p != 0 || !live) return;
-  double* X3 = kp3d + pr * 3;
-  if (!is_valid) {
-    X3[0] = X3[1] = X3[2] = 0.0;
-    joint_err[pr] = 0.0;
-    joint_inliers[pr] = 0;
-    return;
-  }
-  R4 m;
-  r4_zero(m);
-  for (int v = 0; v < V; v++)
-    if (win >> v & 1) add_view_rows(m, Pb + v * 12, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
-  double h[4], X[3];
-  r4_null_vector(m, h);
-  dehomogenise(h, X);
-  double errs[MAXV];
-  int n = 0;
-  for (int v = 0; v < V; v++)
-    if (win >> v & 1)
-      errs[n++] = reproj_err(Pb + v * 12, X, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
-  X3[0] = X[0];
-  X3[1] = X[1];
-  X3[2] = X[2];
-  joint_err[pr] = np_pairwise_sum(errs, n) / (double)n;
-  joint_inliers[pr] = n;
-}
-
-// ---- the pair-table entry (ransac_dlt_kernel above stays as it is: its code object does not change) ----------------
 // stage 1 of one lane: triangulate the view pair (a, c) and vote over all V views -> inlier mask (a and c always in it)
 template <typename KP>
 __device__ __forceinline__ unsigned vote_pair(const double* __restrict__ Pb, const KP* __restrict__ kb, int V, int J,
@@ -258,6 +161,7 @@ __device__ __forceinline__ unsigned vote_pair(const double* __restrict__ Pb, con
 }
 
 // stage 2, one lane per problem: final DLT on the sorted inlier views `win`, its mean reprojection error and the count
+// (NMAX: the most views a caller's `win` can name)
 template <int NMAX, typename KP>
 __device__ __forceinline__ void finish_problem(const double* __restrict__ Pb, const KP* __restrict__ kb, int V, int J,
                                                unsigned win, bool is_valid, double* __restrict__ X3,
@@ -285,6 +189,41 @@ __device__ __forceinline__ void finish_problem(const double* __restrict__ Pb, co
   X3[2] = X[2];
   *err_out = np_pairwise_sum(errs, n) / (double)n;
   *inl_out = n;
+}
+
+// All C(V,2) pairs in lexicographic order, pair p on lane p of the problem's group (V <= MAXV: n_pairs <= 64).
+template <typename KP>
+__global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ kp2d, const double* __restrict__ proj,
+                                                         const uint8_t* __restrict__ valid, double* __restrict__ kp3d,
+                                                         double* __restrict__ joint_err,
+                                                         int32_t* __restrict__ joint_inliers, int64_t n_prob, int V,
+                                                         int J, int n_pairs, int PG, double eps) {
+  const int lane = threadIdx.x;
+  const int grp = lane / PG, p = lane % PG;
+  const int64_t prob = (int64_t)blockIdx.x * (64 / PG) + grp;
+  const bool live = prob < n_prob;
+  const int64_t pr = live ? prob : 0;
+  const int64_t b = pr / J;
+  const int j = (int)(pr % J);
+  const bool is_valid = live && (!valid || valid[b * J + j]);
+  const double* Pb = proj + b * V * 12;
+  const KP* kb = kp2d + (b * V * (int64_t)J + j) * 2;  // + v * J * 2
+
+  unsigned mask = 0;
+  if (p < n_pairs) {
+    int a = 0, rem = p;
+    while (rem >= V - 1 - a) { rem -= V - 1 - a; a++; }
+    mask = vote_pair(Pb, kb, V, J, a, a + 1 + rem, eps);
+  }
+  // first pair with the strictly largest set: key = count * 64 + (63 - p), maximise
+  int key = (p < n_pairs) ? __popc(mask) * 64 + (63 - p) : -1;
+  int best = key;
+  for (int o = PG >> 1; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
+  unsigned win = (key == best) ? mask : 0u;
+  for (int o = PG >> 1; o > 0; o >>= 1) win |= __shfl_xor(win, o, 64);
+
+  if (p != 0 || !live) return;
+  finish_problem<MAXV>(Pb, kb, V, J, win, is_valid, kp3d + pr * 3, joint_err + pr, joint_inliers + pr);
 }
 
 // The same two stages over an explicit pair table (pairs_stride = P * 2 per problem, 0 for one shared table).  A lane
@@ -347,6 +286,28 @@ __global__ void frame_reduce_kernel(const double* __restrict__ joint_err, const 
   inlier_count[b] = n ? mn : -1;
 }
 
+// What the two entries share behind their argument checks: the grid of PG-lane groups, `launch(kp, grid, n_prob)` -- the
+// entry's kernel for the key-point type of `kp` --, its launch check, and frame_reduce_kernel with its check.
+template <typename Launch>
+static int launch_ransac(const char* name, const void* kp2d, int kp_is_f32, int PG, const uint8_t* valid,
+                         const double* joint_err, const int32_t* joint_inliers, double* metric, int32_t* inlier_count,
+                         int B, int J, hipStream_t s, Launch launch) {
+  const int64_t n_prob = (int64_t)B * J;
+  const int per_block = 64 / PG;
+  const dim3 grid((unsigned)((n_prob + per_block - 1) / per_block));
+  if (kp_is_f32) launch((const float*)kp2d, grid, n_prob);
+  else launch((const int64_t*)kp2d, grid, n_prob);
+  MVAL_CHECK_LAUNCH(name);
+  hipLaunchKernelGGL(frame_reduce_kernel, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers, valid, metric,
+                     inlier_count, B, J);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    mval_set_error("%s/reduce: launch failed: %s", name, hipGetErrorString(e));
+    return -2;
+  }
+  return 0;
+}
+
 extern "C" int mval_triangulate_ransac(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
                                        double* kp3d, double* joint_err, int32_t* joint_inliers, double* metric,
                                        int32_t* inlier_count, int B, int V, int J, double eps, void* stream) {
@@ -354,23 +315,15 @@ extern "C" int mval_triangulate_ransac(const void* kp2d, int kp_is_f32, const do
   MVAL_REQUIRE(V <= MAXV, "mval_triangulate_ransac: V > 11 makes the reference sample pairs from python's RNG (unsupported)");
   MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac: bad dims");
   if (B == 0) return 0;
-  int n_pairs = V * (V - 1) / 2;
+  const int n_pairs = V * (V - 1) / 2;
   int PG = 1;
   while (PG < n_pairs) PG <<= 1;
-  int64_t n_prob = (int64_t)B * J;
-  int per_block = 64 / PG;
-  dim3 grid((unsigned)((n_prob + per_block - 1) / per_block));
-  if (kp_is_f32)
-    hipLaunchKernelGGL(ransac_dlt_kernel<float>, grid, dim3(64), 0, mval_stream(stream), (const float*)kp2d, proj,
-                       valid, kp3d, joint_err, joint_inliers, n_prob, V, J, n_pairs, PG, eps);
-  else
-    hipLaunchKernelGGL(ransac_dlt_kernel<int64_t>, grid, dim3(64), 0, mval_stream(stream), (const int64_t*)kp2d, proj,
-                       valid, kp3d, joint_err, joint_inliers, n_prob, V, J, n_pairs, PG, eps);
-  MVAL_CHECK_LAUNCH("mval_triangulate_ransac");
-  hipLaunchKernelGGL(frame_reduce_kernel, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), joint_err,
-                     joint_inliers, valid, metric, inlier_count, B, J);
-  MVAL_CHECK_LAUNCH("mval_triangulate_ransac/reduce");
-  return 0;
+  const hipStream_t s = mval_stream(stream);
+  return launch_ransac("mval_triangulate_ransac", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric, inlier_count,
+                       B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
+                         hipLaunchKernelGGL(ransac_dlt_kernel, grid, dim3(64), 0, s, kp, proj, valid, kp3d, joint_err,
+                                            joint_inliers, n_prob, V, J, n_pairs, PG, eps);
+                       });
 }
 
 extern "C" int mval_triangulate_ransac_pairs(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
@@ -384,21 +337,13 @@ extern "C" int mval_triangulate_ransac_pairs(const void* kp2d, int kp_is_f32, co
   if (B == 0) return 0;
   int PG = 1;
   while (PG < P && PG < 64) PG <<= 1;
-  int64_t n_prob = (int64_t)B * J;
-  int per_block = 64 / PG;
-  int64_t stride = pairs_shared ? 0 : (int64_t)P * 2;
-  dim3 grid((unsigned)((n_prob + per_block - 1) / per_block));
-  if (kp_is_f32)
-    hipLaunchKernelGGL(ransac_pairs_kernel<float>, grid, dim3(64), 0, mval_stream(stream), (const float*)kp2d, proj,
-                       valid, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V, J, P, PG, eps);
-  else
-    hipLaunchKernelGGL(ransac_pairs_kernel<int64_t>, grid, dim3(64), 0, mval_stream(stream), (const int64_t*)kp2d, proj,
-                       valid, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V, J, P, PG, eps);
-  MVAL_CHECK_LAUNCH("mval_triangulate_ransac_pairs");
-  hipLaunchKernelGGL(frame_reduce_kernel, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), joint_err,
-                     joint_inliers, valid, metric, inlier_count, B, J);
-  MVAL_CHECK_LAUNCH("mval_triangulate_ransac_pairs/reduce");
-  return 0;
+  const int64_t stride = pairs_shared ? 0 : (int64_t)P * 2;
+  const hipStream_t s = mval_stream(stream);
+  return launch_ransac("mval_triangulate_ransac_pairs", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
+                       inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
+                         hipLaunchKernelGGL(ransac_pairs_kernel, grid, dim3(64), 0, s, kp, proj, valid, pairs, stride, kp3d,
+                                            joint_err, joint_inliers, n_prob, V, J, P, PG, eps);
+                       });
 }
 
 // ---- XE metric (utils/triangulation.py:236-257) ---------------------------------------

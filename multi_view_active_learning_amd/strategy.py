@@ -40,36 +40,12 @@ def _reduce_mode(kind: str, config: str) -> int:
     raise NotImplementedError("AL.%s_CONFIG should be either AVG or STD." % kind)
 
 
-def score_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid):
-    """heatmaps (B,V,J,Hh,Wh) f32 HIP, joint_valid (B,J) -> (B,) float64 HIP tensor holding
-    the value the reference's ``_compute_{hp,mpe,bsb}`` returns for each frame (exactly
-    representable float32 where the reference's result is float32)."""
-    b, v, j, hh, wh = heatmaps.shape
-    hm = heatmaps.to(torch.float32).contiguous()
-    per_map, n_peaks = _lib.score_maps(_KIND[kind], hm, b * v * j, hh, wh)
-    valid = (torch.as_tensor(joint_valid) != 0).to(torch.uint8).reshape(b, j).to(hm.device).contiguous()
-    out = _lib.score_reduce(per_map, valid, b, v, j, _reduce_mode(kind, config))
-    return out, per_map.reshape(b, v, j), n_peaks.reshape(b, v, j), valid
-
-
-def score_decode_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True):
-    """``score_heatmaps_batch`` + the hard arg-max decode of ``triangulate_batch`` from ONE read of the heat-maps
-    (csrc/scoring.hip, DECODE): what a pool-scoring pass needs per map (strategy.py:1027-1090 reads every heat-map in
-    get_scaled_pred_corrdinates AND in _compute_{hp,mpe,bsb}).  Returns (out, per_map, n_peaks, valid, keypoints_2d)."""
-    b, v, j, hh, wh = heatmaps.shape
-    hm = heatmaps.to(torch.float32).contiguous()
-    valid = (torch.as_tensor(joint_valid) != 0).to(torch.uint8).reshape(b, j).to(hm.device).contiguous()
-    per_map, n_peaks, kp2d = _lib.score_decode_maps(_KIND[kind], hm, valid, b, v, j, hh, wh, int(stride),
-                                                    hh if mirror_nonsquare_quirk else wh)
-    out = _lib.score_reduce(per_map, valid, b, v, j, _reduce_mode(kind, config))
-    return out, per_map.reshape(b, v, j), n_peaks.reshape(b, v, j), valid, kp2d
-
-
-def score_decode_heatmaps_all(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True, decode=True):
-    """``score_decode_heatmaps_batch`` for several kinds from ONE read of the heat-maps (csrc/scoring.hip,
-    score_maps_all_kernel): ``configs`` maps "HP" / "MPE" / "BSB" to "AVG" / "STD".  One fused launch, then
-    ``mval_score_reduce`` per kind.  Returns an OrderedDict kind -> (out, per_map, n_peaks, valid, keypoints_2d), each
-    entry what ``score_decode_heatmaps_batch(kind, config, ...)`` returns (keypoints_2d None without ``decode``)."""
+def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_quirk=True, decode=False):
+    """The heat-map scorer behind the three public functions below.  ``configs`` maps "HP" / "MPE" / "BSB" to "AVG" / "STD";
+    heatmaps (B,V,J,Hh,Wh) f32 HIP, joint_valid (B,J).  ONE launch reads the heat-maps -- one kind without ``decode``:
+    mval_score_maps; one kind with it: mval_score_decode_maps; several kinds: mval_score_decode_maps_all (csrc/scoring.hip builds
+    them from the same stages: a statistic has the same bits whichever computes it) --, then ``mval_score_reduce`` per kind.
+    Returns an OrderedDict kind -> (out (B,) float64, per_map (B,V,J), n_peaks (B,V,J), valid, keypoints_2d or None)."""
     modes = OrderedDict((kind, _reduce_mode(kind, configs[kind])) for kind in configs)
     for kind in modes:
         if kind not in _KIND:
@@ -77,15 +53,41 @@ def score_decode_heatmaps_all(configs, heatmaps, joint_valid, stride, mirror_non
     b, v, j, hh, wh = heatmaps.shape
     hm = heatmaps.to(torch.float32).contiguous()
     valid = (torch.as_tensor(joint_valid) != 0).to(torch.uint8).reshape(b, j).to(hm.device).contiguous()
-    stat, n_peaks, kp2d = _lib.score_decode_maps_all(hm, valid, b, v, j, hh, wh, int(stride),
-                                                     hh if mirror_nonsquare_quirk else wh, decode=decode)
-    counts = {"HP": None, "MPE": n_peaks[0], "BSB": n_peaks[1]}
-    res = OrderedDict()
-    for kind, mode in modes.items():
-        per_map = stat[_KIND[kind]]
-        cnt = torch.zeros_like(n_peaks[0]) if counts[kind] is None else counts[kind]  # (HP has no peaks: mval_score_maps writes 0)
-        res[kind] = (_lib.score_reduce(per_map, valid, b, v, j, mode), per_map.reshape(b, v, j), cnt.reshape(b, v, j), valid, kp2d)
-    return res
+    split_width = hh if mirror_nonsquare_quirk else wh
+    if len(modes) == 1:
+        (kind,) = modes
+        if decode:
+            stat, cnt, kp2d = _lib.score_decode_maps(_KIND[kind], hm, valid, b, v, j, hh, wh, int(stride), split_width)
+        else:
+            (stat, cnt), kp2d = _lib.score_maps(_KIND[kind], hm, b * v * j, hh, wh), None
+        stats, counts = {kind: stat}, {kind: cnt}  # (HP has no peaks: the kernel writes 0)
+    else:
+        stat, n_peaks, kp2d = _lib.score_decode_maps_all(hm, valid, b, v, j, hh, wh, int(stride), split_width, decode=decode)
+        stats = {kind: stat[_KIND[kind]] for kind in modes}
+        counts = {"HP": torch.zeros_like(n_peaks[0]) if "HP" in modes else None, "MPE": n_peaks[0], "BSB": n_peaks[1]}
+    return OrderedDict((kind, (_lib.score_reduce(stats[kind], valid, b, v, j, mode), stats[kind].reshape(b, v, j),
+                               counts[kind].reshape(b, v, j), valid, kp2d)) for kind, mode in modes.items())
+
+
+def score_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid):
+    """heatmaps (B,V,J,Hh,Wh) f32 HIP, joint_valid (B,J) -> (B,) float64 HIP tensor holding
+    the value the reference's ``_compute_{hp,mpe,bsb}`` returns for each frame (exactly
+    representable float32 where the reference's result is float32); then per_map, n_peaks, valid."""
+    return _score_heatmaps({kind: config}, heatmaps, joint_valid)[kind][:4]
+
+
+def score_decode_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True):
+    """``score_heatmaps_batch`` + the hard arg-max decode of ``triangulate_batch`` from ONE read of the heat-maps
+    (csrc/scoring.hip, DECODE): what a pool-scoring pass needs per map (strategy.py:1027-1090 reads every heat-map in
+    get_scaled_pred_corrdinates AND in _compute_{hp,mpe,bsb}).  Returns (out, per_map, n_peaks, valid, keypoints_2d)."""
+    return _score_heatmaps({kind: config}, heatmaps, joint_valid, stride, mirror_nonsquare_quirk, decode=True)[kind]
+
+
+def score_decode_heatmaps_all(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True, decode=True):
+    """``score_decode_heatmaps_batch`` for several kinds from ONE read of the heat-maps: ``configs`` maps "HP" / "MPE" / "BSB"
+    to "AVG" / "STD".  Returns an OrderedDict kind -> (out, per_map, n_peaks, valid, keypoints_2d), each entry what
+    ``score_decode_heatmaps_batch(kind, config, ...)`` returns (keypoints_2d None without ``decode``)."""
+    return _score_heatmaps(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk, decode)
 
 
 AL_STRATEGIES = ("HP", "MPE", "BSB", "TRIANGULATION", "CORESET", "RANDOM")
@@ -124,6 +126,10 @@ def split_strategy_tables(per_rank, n_strategies):
     return out
 
 
+def _empty_sal_dict():
+    return {k: OrderedDict() for k in ("al_metric", "sal_metric", "inlier_count", "pred_3d_keypoints", "mkpe")}
+
+
 def tables_to_sal_dict(per_rank, batch_sizes, sal_dict=None):
     """Packed per-rank tables [pose, frame_id, al_metric, sal_metric, inlier_count, mkpe,
     keypoints_3d(3J)] -> the reference's five dicts, inserted in its gather order
@@ -134,7 +140,7 @@ def tables_to_sal_dict(per_rank, batch_sizes, sal_dict=None):
     last batch): the walk covers the longest structure and skips what a rank does not have, so
     every rank builds the identical dict from the identical gathered inputs."""
     if sal_dict is None:
-        sal_dict = {k: OrderedDict() for k in ("al_metric", "sal_metric", "inlier_count", "pred_3d_keypoints", "mkpe")}
+        sal_dict = _empty_sal_dict()
     j = (per_rank[0].shape[1] - 6) // 3
     if len(batch_sizes) == 0 or np.isscalar(batch_sizes[0]):
         batch_sizes = [list(batch_sizes)] * len(per_rank)
@@ -339,117 +345,11 @@ class ActiveLearningStrategy:
         return self._score_one("BSB", self.al_cfg.AL.BSB_CONFIG, heatmaps, joint_valid)
 
     # ---- pool scoring ---------------------------------------------------------------
-    def score_batch(self, heatmaps, dp):
-        """Everything the reference does per sample inside _compute_sal_dict
-        (strategy.py:1036-1094,1134), for a whole batch, on device.  heatmaps (B*V,J,h,w).
-        Returns a (B, 6 + 3J) float64 HIP table:
-        [pose, frame_id, al_metric, sal_metric, inlier_count, mkpe, keypoints_3d(3J)]."""
-        cfg = self.al_cfg
-        dev = heatmaps.device
-        pose = torch.as_tensor(dp["pose"]).reshape(-1)
-        b = pose.shape[0]
-        _, j, hh, wh = heatmaps.shape
-        hm = heatmaps.reshape(b, -1, j, hh, wh)
-        joint_valid = torch.as_tensor(dp["joint_valid"]).reshape(b, j)
-        strat = cfg.AL.STRATEGY
-        scored = None
-        if strat in ("MPE", "HP", "BSB") and not cfg.AL.USE_SOFTARGMAX:
-            # one read of every heat-map for both the uncertainty statistic and the key-point decode
-            scored = score_decode_heatmaps_batch(strat, getattr(cfg.AL, strat + "_CONFIG"), hm, joint_valid, cfg.POSE_ESTIMATOR.STRIDE)
-        r = triangulation.triangulate_batch(
-            hm, dp["proj_matrices"], cfg.POSE_ESTIMATOR.STRIDE, joint_valid,
-            cfg.AL.USE_SOFTARGMAX, cfg.AL.USE_REPROJECTION_XE, cfg.AL.REPROJECTION_SIGMA,
-            keypoints_2d=None if scored is None else scored[4],
-            pair_rng=random,  # more than n_iters view pairs (12 views on): the reference's draws, frames in batch order
-            valid_joints_host=dp.get("joint_valid_host"),
-        )
-        pred32 = r["keypoints_3d"].to(torch.float32)  # torch.Tensor(results["keypoints_3d"]) (:1046)
-        sal_metric = r["metric"].to(torch.float32).to(torch.float64)  # torch.Tensor([metric]) (:1061)
-        if strat == "RANDOM":
-            al = torch.cat([torch.rand(1) for _ in range(b)]).to(torch.float64).to(dev)
-        elif strat == "TRIANGULATION":
-            al = r["metric"].to(torch.float64)  # torch.tensor([np.float64]) keeps float64 (:1075)
-        elif strat in ("MPE", "HP", "BSB"):
-            conf = getattr(cfg.AL, strat + "_CONFIG")
-            al, _, n_peaks, valid = scored[:4] if scored is not None else score_heatmaps_batch(strat, conf, hm, joint_valid)
-            self._pending_checks.append((strat, n_peaks, valid))
-            if conf == "AVG" or strat != "HP":
-                al = al.to(torch.float32).to(torch.float64)  # torch.tensor(python float) is float32
-        elif strat == "CORESET":
-            al = torch.zeros(b, dtype=torch.float64, device=dev)
-        else:
-            raise NotImplementedError()
-        gt = torch.as_tensor(dp["3d_keypoints"]).to(dev)
-        mk = evaluation.mkpe_per_sample(pred32, gt, joint_valid.to(dev))
-        self._pending_checks.append(("INLIER", r["inlier_count"], None))
-        table = torch.cat(
-            [
-                pose.to(dev, torch.float64)[:, None],
-                torch.as_tensor(dp["frame_id"]).reshape(b).to(dev, torch.float64)[:, None],
-                al[:, None],
-                sal_metric[:, None],
-                r["inlier_count"].to(torch.float64)[:, None],
-                mk.to(torch.float64)[:, None],
-                pred32.to(torch.float64).reshape(b, 3 * j),
-            ],
-            dim=1,
-        )
-        return table
-
-    def _compute_sal_dict(self, data_loader, pose_estimator):
-        """strategy.py:1004-1147.  Same five OrderedDicts keyed "<pose>-<frame_id>", filled in
-        the reference's gather order (batch -> sample -> rank), but with one device->host
-        copy and (when torch.distributed is initialised) one all_gather for the whole pass."""
-        sal_dict = {
-            "al_metric": OrderedDict(),
-            "sal_metric": OrderedDict(),
-            "inlier_count": OrderedDict(),
-            "pred_3d_keypoints": OrderedDict(),
-            "mkpe": OrderedDict(),
-        }
-        self._pending_checks = []
-        tables, sizes = [], []
-        from .parallel import PostStream, world
-
-        post = PostStream()  # a batch's decode / scoring / triangulation runs beside the next batch's network
-        with torch.no_grad():
-            for dp in data_loader:
-                dp = _stage_batch(dp)  # (small tensors to the device before the network launch: no host-blocking copy on the side stream)
-                heatmaps = self._compute_batch_heatmap(pose_estimator, dp)
-                with post.batch(heatmaps, _lib.argmax_keys_of(heatmaps) if torch.is_tensor(heatmaps) and heatmaps.is_cuda else None, dp):
-                    t = self.score_batch(heatmaps, dp)
-                tables.append(t)
-                sizes.append(t.shape[0])
-        post.join()
-
-        if not tables:
-            from .parallel import _collectives_on
-
-            if not _collectives_on():
-                return sal_dict
-            # an empty shard still takes part in the pass's collective (the other ranks would hang otherwise)
-            j = self.num_joints
-            dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-            tables = [torch.zeros((0, 6 + 3 * j), dtype=torch.float64, device=dev)]
-        # the reference's per-sample error behaviour is checked once per pass -- AFTER the collectives (a rank that raised
-        # before them would leave the others waiting); the flag travels with the size exchange
-        err = None
-        try:
-            self._raise_deferred_errors()
-        except Exception as e:  # noqa: BLE001
-            err = e
-        local = torch.cat(tables, dim=0)
-        from .parallel import gather_tables
-
-        per_rank, per_rank_sizes = gather_tables(local, sizes, error_flag=int(err is not None))  # host arrays + every rank's batch sizes
-        if err is not None:
-            raise err
-        return tables_to_sal_dict(per_rank, per_rank_sizes, sal_dict)
-
-    def score_batch_all(self, heatmaps, dp, strategies):
-        """``score_batch`` for several strategies from one network output: one fused heat-map launch (when HP, MPE or BSB is
-        among them), one triangulation.  Returns a (B, 6 + 3J + E) float64 HIP table: ``score_batch``'s columns with
-        column 2 left 0, then the al_metric of each strategy, each what ``score_batch`` writes under that AL.STRATEGY."""
+    def _score_columns(self, heatmaps, dp, strategies):
+        """Everything the reference does per sample inside _compute_sal_dict (strategy.py:1036-1094,1134), for a whole
+        batch, on device, for each of ``strategies``: one heat-map launch (when HP, MPE or BSB is among them; with the hard
+        arg-max decode unless AL.USE_SOFTARGMAX), one triangulation.  heatmaps (B*V,J,h,w).  Returns float64 HIP columns
+        (ids [pose, frame_id], rest [sal_metric, inlier_count, mkpe, keypoints_3d(3J)], al_metric per strategy)."""
         cfg = self.al_cfg
         dev = heatmaps.device
         pose = torch.as_tensor(dp["pose"]).reshape(-1)
@@ -460,85 +360,122 @@ class ActiveLearningStrategy:
         configs = OrderedDict((s, getattr(cfg.AL, s + "_CONFIG")) for s in strategies if s in _KIND)
         scored, kp2d = {}, None
         if configs:
-            scored = score_decode_heatmaps_all(configs, hm, joint_valid, cfg.POSE_ESTIMATOR.STRIDE, decode=not cfg.AL.USE_SOFTARGMAX)
+            # one read of every heat-map for the uncertainty statistics and the key-point decode
+            scored = _score_heatmaps(configs, hm, joint_valid, cfg.POSE_ESTIMATOR.STRIDE, decode=not cfg.AL.USE_SOFTARGMAX)
             kp2d = next(iter(scored.values()))[4]
         r = triangulation.triangulate_batch(
             hm, dp["proj_matrices"], cfg.POSE_ESTIMATOR.STRIDE, joint_valid,
             cfg.AL.USE_SOFTARGMAX, cfg.AL.USE_REPROJECTION_XE, cfg.AL.REPROJECTION_SIGMA,
             keypoints_2d=kp2d,
-            pair_rng=random,
+            pair_rng=random,  # more than n_iters view pairs (12 views on): the reference's draws, frames in batch order
             valid_joints_host=dp.get("joint_valid_host"),
         )
-        pred32 = r["keypoints_3d"].to(torch.float32)
-        sal_metric = r["metric"].to(torch.float32).to(torch.float64)
+        pred32 = r["keypoints_3d"].to(torch.float32)  # torch.Tensor(results["keypoints_3d"]) (:1046)
+        sal_metric = r["metric"].to(torch.float32).to(torch.float64)  # torch.Tensor([metric]) (:1061)
         als = []
-        for s in strategies:  # the precision rules of score_batch, strategy by strategy
+        for s in strategies:
             if s == "RANDOM":
                 al = torch.cat([torch.rand(1) for _ in range(b)]).to(torch.float64).to(dev)
             elif s == "TRIANGULATION":
-                al = r["metric"].to(torch.float64)
-            elif s == "CORESET":
-                al = torch.zeros(b, dtype=torch.float64, device=dev)
-            else:
+                al = r["metric"].to(torch.float64)  # torch.tensor([np.float64]) keeps float64 (:1075)
+            elif s in _KIND:
                 al, _, n_peaks, valid = scored[s][:4]
                 self._pending_checks.append((s, n_peaks, valid))
                 if configs[s] == "AVG" or s != "HP":
-                    al = al.to(torch.float32).to(torch.float64)
+                    al = al.to(torch.float32).to(torch.float64)  # torch.tensor(python float) is float32
+            elif s == "CORESET":
+                al = torch.zeros(b, dtype=torch.float64, device=dev)
+            else:
+                raise NotImplementedError()
             als.append(al[:, None])
         gt = torch.as_tensor(dp["3d_keypoints"]).to(dev)
         mk = evaluation.mkpe_per_sample(pred32, gt, joint_valid.to(dev))
         self._pending_checks.append(("INLIER", r["inlier_count"], None))
-        return torch.cat(
-            [
-                pose.to(dev, torch.float64)[:, None],
-                torch.as_tensor(dp["frame_id"]).reshape(b).to(dev, torch.float64)[:, None],
-                torch.zeros((b, 1), dtype=torch.float64, device=dev),
-                sal_metric[:, None],
-                r["inlier_count"].to(torch.float64)[:, None],
-                mk.to(torch.float64)[:, None],
-                pred32.to(torch.float64).reshape(b, 3 * j),
-            ] + als,
-            dim=1,
-        )
+        ids = [pose.to(dev, torch.float64)[:, None], torch.as_tensor(dp["frame_id"]).reshape(b).to(dev, torch.float64)[:, None]]
+        rest = [sal_metric[:, None], r["inlier_count"].to(torch.float64)[:, None], mk.to(torch.float64)[:, None],
+                pred32.to(torch.float64).reshape(b, 3 * j)]
+        return ids, rest, als
 
-    def _compute_sal_dicts(self, data_loader, pose_estimator, strategies):
-        """One pass over the pool for SEVERAL strategies: an OrderedDict strategy -> sal_dict in the order given, each equal
-        (values and key order) to ``_compute_sal_dict`` with AL.STRATEGY set to that strategy.  Per batch one network call,
-        one fused heat-map launch, one triangulation; per pass the one size exchange and one gather of ``gather_tables``
-        (the table is E columns wider).  Errors of a strategy that was not asked for are not raised."""
-        strategies = check_strategies(strategies)
-        self._pending_checks = []
-        tables, sizes = [], []
-        from .parallel import PostStream, _collectives_on, gather_tables
+    def score_batch(self, heatmaps, dp):
+        """``_score_columns`` under AL.STRATEGY as a (B, 6 + 3J) float64 HIP table:
+        [pose, frame_id, al_metric, sal_metric, inlier_count, mkpe, keypoints_3d(3J)]."""
+        ids, rest, als = self._score_columns(heatmaps, dp, (self.al_cfg.AL.STRATEGY,))
+        return torch.cat(ids + als + rest, dim=1)
 
-        post = PostStream()
+    def score_batch_all(self, heatmaps, dp, strategies):
+        """``score_batch`` for several strategies from one network output: one heat-map launch, one triangulation.  Returns
+        a (B, 6 + 3J + E) float64 HIP table: ``score_batch``'s columns with column 2 left 0, then the al_metric of each
+        strategy, each what ``score_batch`` writes under that AL.STRATEGY."""
+        ids, rest, als = self._score_columns(heatmaps, dp, strategies)
+        return torch.cat(ids + [torch.zeros_like(als[0])] + rest + als, dim=1)
+
+    def _pool_loop(self, data_loader, pose_estimator, body, inputs=None, stage=_stage_batch):
+        """The loop of a pass over a pool: per batch ``stage(dp)`` (small tensors to the device BEFORE the network launch: no
+        host-blocking copy on the side stream), the network, then ``body(*args)`` on the side stream (parallel.PostStream:
+        beside the next batch's network), where ``args = inputs(heatmaps, dp)`` names every device tensor the body reads --
+        by default the heat-maps, their arg-max keys where the network kept them, and the batch.  Nothing is copied to the
+        host; the caller's stream has joined the side stream when the list of the bodies' results is returned."""
+        from .parallel import PostStream
+
+        if inputs is None:
+            inputs = lambda hm, dp: (hm, _lib.argmax_keys_of(hm) if torch.is_tensor(hm) and hm.is_cuda else None, dp)  # noqa: E731
+        post, results = PostStream(), []
         with torch.no_grad():
             for dp in data_loader:
-                dp = _stage_batch(dp)
-                heatmaps = self._compute_batch_heatmap(pose_estimator, dp)
-                with post.batch(heatmaps, _lib.argmax_keys_of(heatmaps) if torch.is_tensor(heatmaps) and heatmaps.is_cuda else None, dp):
-                    t = self.score_batch_all(heatmaps, dp, strategies)
-                tables.append(t)
-                sizes.append(t.shape[0])
+                dp = stage(dp)
+                args = inputs(self._compute_batch_heatmap(pose_estimator, dp), dp)
+                with post.batch(*args):
+                    results.append(body(*args))
         post.join()
+        return results
 
+    def _gather_score_tables(self, tables, width):
+        """The tail of a scoring pass: the per-batch tables (B, width) -> ``gather_tables``' (per-rank host tables, per-rank
+        batch sizes), or None for an empty loader without a collective to take part in."""
+        from .parallel import _collectives_on, gather_tables
+
+        sizes = [t.shape[0] for t in tables]
         if not tables:
             if not _collectives_on():
-                keys = ("al_metric", "sal_metric", "inlier_count", "pred_3d_keypoints", "mkpe")
-                return OrderedDict((s, {k: OrderedDict() for k in keys}) for s in strategies)
+                return None
             # an empty shard still takes part in the pass's collective (the other ranks would hang otherwise)
             dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-            tables = [torch.zeros((0, 6 + 3 * self.num_joints + len(strategies)), dtype=torch.float64, device=dev)]
-        err = None  # (raised after the collectives, as in _compute_sal_dict)
+            tables = [torch.zeros((0, width), dtype=torch.float64, device=dev)]
+        # the reference's per-sample error behaviour is checked once per pass -- AFTER the collectives (a rank that raised
+        # before them would leave the others waiting); the flag travels with the size exchange
+        err = None
         try:
             self._raise_deferred_errors()
         except Exception as e:  # noqa: BLE001
             err = e
-        per_rank, per_rank_sizes = gather_tables(torch.cat(tables, dim=0), sizes, error_flag=int(err is not None))
+        gathered = gather_tables(torch.cat(tables, dim=0), sizes, error_flag=int(err is not None))
         if err is not None:
             raise err
-        split = split_strategy_tables(per_rank, len(strategies))
-        return OrderedDict((s, tables_to_sal_dict(tabs, per_rank_sizes)) for s, tabs in zip(strategies, split))
+        return gathered
+
+    def _compute_sal_dict(self, data_loader, pose_estimator):
+        """strategy.py:1004-1147.  Same five OrderedDicts keyed "<pose>-<frame_id>", filled in
+        the reference's gather order (batch -> sample -> rank), but with one device->host
+        copy and (when torch.distributed is initialised) one all_gather for the whole pass."""
+        self._pending_checks = []
+        tables = self._pool_loop(data_loader, pose_estimator, lambda hm, _keys, dp: self.score_batch(hm, dp))
+        gathered = self._gather_score_tables(tables, 6 + 3 * self.num_joints)
+        return _empty_sal_dict() if gathered is None else tables_to_sal_dict(*gathered)
+
+    def _compute_sal_dicts(self, data_loader, pose_estimator, strategies):
+        """One pass over the pool for SEVERAL strategies: an OrderedDict strategy -> sal_dict in the order given, each equal
+        (values and key order) to ``_compute_sal_dict`` with AL.STRATEGY set to that strategy.  Per batch one network call,
+        one heat-map launch, one triangulation; per pass the one size exchange and one gather of ``gather_tables``
+        (the table is E columns wider).  Errors of a strategy that was not asked for are not raised."""
+        strategies = check_strategies(strategies)
+        self._pending_checks = []
+        tables = self._pool_loop(data_loader, pose_estimator, lambda hm, _keys, dp: self.score_batch_all(hm, dp, strategies))
+        gathered = self._gather_score_tables(tables, 6 + 3 * self.num_joints + len(strategies))
+        if gathered is None:
+            return OrderedDict((s, _empty_sal_dict()) for s in strategies)
+        split = split_strategy_tables(gathered[0], len(strategies))
+        return OrderedDict((s, tables_to_sal_dict(tabs, gathered[1])) for s, tabs in zip(strategies, split))
+
 
     def _raise_deferred_errors(self):
         """Error behaviour of the reference's per-sample loop, checked once per pass."""
@@ -574,11 +511,8 @@ class ActiveLearningStrategy:
         out = _stage_batch(dp)
         key = "gt_heatmap" if "gt_heatmap" in dp else "2d_keypoints"
         if key in dp and torch.cuda.is_available():
-            t = torch.as_tensor(dp[key])
-            if not t.is_cuda:
-                t = t.contiguous()
-                out = dict(out)
-                out[key] = (t if t.is_pinned() else t.pin_memory()).to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
+            out = dict(out)
+            out[key] = _stage_small(torch.as_tensor(dp[key]))
         return out
 
     def _frame_losses(self, heatmaps, dp):
@@ -606,7 +540,7 @@ class ActiveLearningStrategy:
         [pose, frame_id, loss] or [pose, frame_id, rows * J values]), rebuilt in ``reference_gather_order``, so every rank
         returns the same dict -- in dataset order under strided shards."""
         from .config import cluster_type as _cluster_type
-        from .parallel import PostStream, _collectives_on, gather_tables, reference_gather_order
+        from .parallel import _collectives_on, gather_tables, reference_gather_order
 
         kind = _cluster_type(self.al_cfg.AL.CLUSTER.TYPE if cluster_type is None else cluster_type)
         tables, sizes, j = [], [], 0
@@ -619,18 +553,13 @@ class ActiveLearningStrategy:
                                          kp.to(torch.float64).reshape(pose.shape[0], -1)], dim=1))
                 sizes.append(pose.shape[0])
         else:
-            post = PostStream()
-            with torch.no_grad():
-                for dp in data_loader:
-                    dp = self._stage_cluster_targets(dp)
-                    heatmaps = self._compute_batch_heatmap(pose_estimator, dp)
-                    with post.batch(heatmaps, dp):
-                        loss = self._frame_losses(heatmaps, dp)
-                        pose, frame = self._batch_guid_ids(dp)
-                        tables.append(torch.stack([pose.to(loss.device, torch.float64), frame.to(loss.device, torch.float64),
-                                                   loss.to(torch.float64)], dim=1))
-                    sizes.append(tables[-1].shape[0])
-            post.join()
+            def loss_rows(heatmaps, dp):
+                loss = self._frame_losses(heatmaps, dp)
+                pose, frame = self._batch_guid_ids(dp)
+                return torch.stack([pose.to(loss.device, torch.float64), frame.to(loss.device, torch.float64), loss.to(torch.float64)], dim=1)
+
+            tables = self._pool_loop(data_loader, pose_estimator, loss_rows, inputs=lambda hm, dp: (hm, dp), stage=self._stage_cluster_targets)
+            sizes = [t.shape[0] for t in tables]
         # rows travel flattened with [row width, J] in front of the batch sizes: a rank with an empty shard does not know the
         # width of the others' rows (POSE: rows * J) and still takes part in the collectives
         width = tables[0].shape[1] if tables else 3
@@ -728,26 +657,22 @@ class ActiveLearningStrategy:
     def evaluate_mkpe(self, data_loader, pose_estimator):
         """_evaluate_all's MKPE path: heat-maps -> hard arg-max triangulation -> MPJPE over the
         whole loader (one size exchange + one packed data gather instead of 3 all_gathers per sample)."""
-        preds, gts, valids, sizes = [], [], [], []
-        from .parallel import PostStream
+        def inputs(hm, dp):
+            b = torch.as_tensor(dp["pose"]).reshape(-1).shape[0] if "pose" in dp else dp["images"].shape[0]
+            jv = torch.as_tensor(dp["joint_valid"]).reshape(b, hm.shape[1])
+            return hm, _lib.argmax_keys_of(hm) if hm.is_cuda else None, dp, jv
 
-        post = PostStream()  # (decode + triangulation of a batch beside the next batch's network)
-        with torch.no_grad():
-            for dp in data_loader:
-                dp = _stage_batch(dp)
-                hm = self._compute_batch_heatmap(pose_estimator, dp)
-                b = torch.as_tensor(dp["pose"]).reshape(-1).shape[0] if "pose" in dp else dp["images"].shape[0]
-                _, j, hh, wh = hm.shape
-                jv = torch.as_tensor(dp["joint_valid"]).reshape(b, j)
-                with post.batch(hm, _lib.argmax_keys_of(hm) if hm.is_cuda else None, dp, jv):
-                    r = triangulation.triangulate_batch(hm.reshape(b, -1, j, hh, wh), dp["proj_matrices"],
-                                                        self.al_cfg.POSE_ESTIMATOR.STRIDE, jv, pair_rng=random,
-                                                        valid_joints_host=dp.get("joint_valid_host"))
-                    preds.append(r["keypoints_3d"].to(torch.float32))
-                    gts.append(torch.as_tensor(dp["3d_keypoints"]).to(hm.device, torch.float32))
-                    valids.append(jv.to(hm.device, torch.float32))
-                sizes.append(b)
-        post.join()
+        def triangulate(hm, _keys, dp, jv):  # (decode + triangulation of a batch beside the next batch's network)
+            (b, j), (hh, wh) = jv.shape, hm.shape[2:]
+            r = triangulation.triangulate_batch(hm.reshape(b, -1, j, hh, wh), dp["proj_matrices"],
+                                                self.al_cfg.POSE_ESTIMATOR.STRIDE, jv, pair_rng=random,
+                                                valid_joints_host=dp.get("joint_valid_host"))
+            return (r["keypoints_3d"].to(torch.float32), torch.as_tensor(dp["3d_keypoints"]).to(hm.device, torch.float32),
+                    jv.to(hm.device, torch.float32))
+
+        rows = self._pool_loop(data_loader, pose_estimator, triangulate, inputs)
+        preds, gts, valids = ([r[k] for r in rows] for k in range(3))
+        sizes = [p.shape[0] for p in preds]
         from .parallel import all_gather_reference_order as gather
 
         j = self.num_joints if not preds else preds[0].shape[1]

@@ -193,6 +193,69 @@ def test_sal_dicts_random_draws_and_soft_argmax(dev):
     assert any(float(np.float32(x)) != x for x in hp)  # float64 values, not float32-rounded ones
 
 
+# ---- (c2) one table builder, one scorer: the single-strategy and the multi-strategy path side by side --------------------------
+ALL6 = ("HP", "MPE", "BSB", "TRIANGULATION", "CORESET", "RANDOM")
+# B = 2, V = 3, J = 3, maps 12 x 16, stride 4, two batches (cases.build_sal_loader: ring cameras, one invalid joint per batch)
+SMALL = dict(strategy="HP", seed=60, nbatch=2, b=2, v=3, j=3, h=48, w=64, stride=4, noise=0.3, outliers=1)
+
+
+@pytest.mark.parametrize("soft", [False, True], ids=["hard", "softargmax"])
+def test_score_batch_equals_score_batch_all_column_for_column(dev, soft):
+    """``score_batch`` under each of the six strategies against the columns of ONE ``score_batch_all`` over all six: the
+    al_metric (column 2 against column 6 + 3J + e) and the base columns, torch.equal on the bit patterns (a frame's mkpe is
+    NaN with these inputs, see ``_dicts_equal``, and NaN != NaN under torch.equal on the values).  torch's and python's generators are
+    reseeded before each call (RANDOM draws one torch.rand(1) per frame; V = 3 draws no view pairs).
+    Inputs: seed 60 with noise 0.3, checked on the CPU with oracle/scoring.py when this was written -- over the valid maps
+    of both batches the fewest BSB peaks (peak_local_max of the row softmax, min_distance 2) are 2, the fewest MPE peaks 2,
+    the most candidates 6; the 8 x 12 interior cannot overflow the candidate list of 128 at all."""
+    from multi_view_active_learning_amd.strategy import ActiveLearningStrategy, _stage_batch
+
+    cfg, tl, model = _sal_setup(SMALL, dev)
+    cfg.AL.USE_SOFTARGMAX = soft
+    dp, hm, j = _stage_batch(tl[0]), model()(None), SMALL["j"]
+    st = ActiveLearningStrategy(cfg)
+    st._pending_checks = []
+
+    def seeded(fn, *args):
+        torch.manual_seed(31)
+        random.seed(31)
+        return fn(hm, dp, *args)
+
+    def same(a, b):  # torch.equal on the float64 bit patterns: what torch.equal asks, and a NaN equals itself
+        return torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
+
+    wide = seeded(st.score_batch_all, ALL6)
+    assert wide.shape == (2, 6 + 3 * j + 6) and wide.dtype == torch.float64
+    assert not wide[:, 2].any().item()
+    for e, s in enumerate(ALL6):
+        cfg.AL.STRATEGY = s
+        one = seeded(st.score_batch)
+        assert one.shape == (2, 6 + 3 * j) and one.dtype == torch.float64
+        assert same(one[:, 2], wide[:, 6 + 3 * j + e]), s
+        assert same(one[:, :2], wide[:, :2]) and same(one[:, 3:], wide[:, 3:6 + 3 * j]), s
+    assert (wide[:, 6 + 3 * j + ALL6.index("RANDOM")] != 0).all().item()  # (the draws did arrive)
+    st._raise_deferred_errors()  # no map overflowed, every valid map has its two BSB peaks
+
+
+@pytest.mark.parametrize("names", [("MPE", "CORESET"), ("BSB", "RANDOM")], ids="-".join)
+def test_pass_with_one_statistic_kind_equals_the_single_pass(dev, names):
+    """A multi-strategy pass that names ONE of HP / MPE / BSB runs the one-kind kernel, like the single-strategy pass: its
+    dict for that kind equals ``_compute_sal_dict``'s, all five dicts, values and key order (SMALL's inputs, two batches)."""
+    from multi_view_active_learning_amd.strategy import ActiveLearningStrategy
+
+    cfg, tl, model = _sal_setup(SMALL, dev)
+
+    def seeded(fn, *args):
+        torch.manual_seed(31)
+        random.seed(31)
+        return fn(tl, model(), *args)
+
+    dicts = seeded(ActiveLearningStrategy(cfg)._compute_sal_dicts, names)
+    assert list(dicts) == list(names) and len(dicts[names[0]]["al_metric"]) == 4
+    cfg.AL.STRATEGY = names[0]
+    _dicts_equal(dicts[names[0]], seeded(ActiveLearningStrategy(cfg)._compute_sal_dict))
+
+
 # ---- (d) deferred errors only for what was asked for ------------------------------------------------------------------
 def test_bsb_index_error_only_when_bsb_is_asked_for(dev):
     """One frame whose valid joint has a map with a single peak in its row softmax: -(x - 7)^2 / (1 + |y - 6|) -- every row

@@ -47,6 +47,19 @@ int mval_argmax_decode(const float* heatmaps, const uint8_t* valid, int64_t* kp2
 int mval_argmax_from_keys(const uint64_t* keys, const uint8_t* valid, int64_t* kp2d, int B, int V, int J,
                           int stride, int split_width, void* stream);
 
+/* utils/evaluation.py:45-58 get_pred_coordinates, hard arg-max branch (called from strategy.py:784-789) -- the same
+ * arg-max (first index on ties, NaN counts as maximum), scaled by the image's box (left, top, right, bottom):
+ *   x = f32(idx % hh) * ((box[3] - box[1]) / f32(wh)) ; y = f32(idx / hh) * ((box[2] - box[0]) / f32(hh))
+ * in float32, the subtraction, the division and the multiply each rounded on its own, so the result equals torch's bit
+ * for bit.  Both are the reference's: the split by shape[2] (= hh) for x and y, and the swapped box extents (x scaled by
+ * the vertical extent, y by the horizontal one).
+ *   heatmaps [N,J,hh,wh] f32 ; boxes [N,4] f32 ; xy [N,J,2] f32 (x,y) ; hh * wh < 2^24. */
+int mval_pred_coordinates(const float* heatmaps, const float* boxes, float* xy, int64_t N, int J, int hh, int wh, void* stream);
+/* The same from the arg-max keys of mval_net_forward_keys (no read of the heat-maps):
+ *   keys [N][MVAL_ARGMAX_SLOTS][J] u64, as mval_argmax_from_keys reads them. */
+int mval_pred_coordinates_from_keys(const uint64_t* keys, const float* boxes, float* xy, int64_t N, int J, int hh, int wh,
+                                    void* stream);
+
 /* utils/triangulation.py:191-200 (kornia.spatial_soft_argmax2d(hm, normalized_coordinates=False)
  * * stride): softmax over hh*wh, expectation of the pixel grid; kp2d [n_maps,2] f32 (x,y)*scale. */
 int mval_soft_argmax(const float* heatmaps, float* kp2d, int64_t n_maps, int hh, int wh, float scale, void* stream);
@@ -255,6 +268,14 @@ int mval_mkpe(const float* pred, const float* gt, const float* valid, float* out
  * equal the reference's. */
 int mval_pck3d(const float* pred, const float* gt, const float* valid, const double* thresholds, int T, int mode,
                long long* hits, long long* counts, int64_t S, int J, int gt_rows, void* stream);
+/* 2-D PCKh counters (utils/evaluation.py:65-93 compute_pckh, called from strategy.py:579-581).  pred, gt [S,J,2] f32
+ * (x,y per image and joint); thresholds [T] f64 (device), T <= 65535.  A joint is hit when its distance to the ground
+ * truth is strictly below (float32)(head * (float)threshold[t]), head = the distance between gt joints kp0 and kp1 of the
+ * same image; a NaN on either side is no hit; every image and every joint below n_keypoints counts (no validity mask).
+ * hits [T,n_keypoints] int64; the fraction hits / S is formed by the caller.  float32 with torch's operation order, so
+ * the counts equal the reference's.  Requires J >= 2, 0 <= kp0, kp1 < J, 1 <= n_keypoints <= J. */
+int mval_pckh2d(const float* pred, const float* gt, const double* thresholds, int T, int kp0, int kp1,
+                long long* hits, int64_t S, int J, int n_keypoints, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Core-set selection (utils/coreset.py:35-95)

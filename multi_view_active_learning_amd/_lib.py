@@ -159,6 +159,42 @@ def argmax_decode(hm, valid, b, v, j, hh, wh, stride, split_width):
     return out
 
 
+def pred_coordinates_from_keys(keys, boxes, hh, wh):
+    """mval_pred_coordinates_from_keys: keys (N, ARGMAX_SLOTS, J) int64 bit patterns of maps of hh x wh, boxes (N,4) f32 -> xy (N,J,2) f32."""
+    if keys.dim() != 3 or keys.shape[1] != ARGMAX_SLOTS or tuple(boxes.shape) != (keys.shape[0], 4):
+        raise MvalError(f"pred_coordinates_from_keys: keys (N, {ARGMAX_SLOTS}, J) and boxes (N, 4), got {tuple(keys.shape)} and {tuple(boxes.shape)}")
+    n, _, j = keys.shape
+    out = torch.empty((n, j, 2), dtype=torch.float32, device=keys.device)
+    _check(
+        lib().mval_pred_coordinates_from_keys(_p(_req(keys, torch.int64, "argmax keys")), _p(_req(boxes, torch.float32, "boxes")),
+                                              _p(out), C.c_longlong(n), C.c_int(j), C.c_int(hh), C.c_int(wh), _stream()),
+        "mval_pred_coordinates_from_keys",
+    )
+    return out
+
+
+def pred_coordinates(hm, boxes, keys=None):
+    """mval_pred_coordinates: hm (N,J,hh,wh) f32, boxes (N,4) f32 (left, top, right, bottom) -> xy (N,J,2) f32, the hard arg-max
+    branch of the reference's get_pred_coordinates.  With ``keys`` (N, ARGMAX_SLOTS, J) int64 bit patterns -- the keys the
+    network kept for ``hm`` (argmax_keys_of) -- mval_pred_coordinates_from_keys: ``hm`` then only gives the shape and is not read."""
+    if hm.dim() != 4:
+        raise MvalError(f"pred_coordinates: heat-maps must be (N, J, hh, wh), got {tuple(hm.shape)}")
+    n, j, hh, wh = hm.shape
+    if tuple(boxes.shape) != (n, 4):
+        raise MvalError(f"pred_coordinates: boxes must be ({n}, 4), got {tuple(boxes.shape)}")
+    if keys is not None:
+        if tuple(keys.shape) != (n, ARGMAX_SLOTS, j):
+            raise MvalError(f"pred_coordinates: keys must be ({n}, {ARGMAX_SLOTS}, {j}), got {tuple(keys.shape)}")
+        return pred_coordinates_from_keys(keys, boxes, hh, wh)
+    out = torch.empty((n, j, 2), dtype=torch.float32, device=hm.device)
+    _check(
+        lib().mval_pred_coordinates(_p(_req(hm, torch.float32, "heatmaps")), _p(_req(boxes, torch.float32, "boxes")), _p(out),
+                                    C.c_longlong(n), C.c_int(j), C.c_int(hh), C.c_int(wh), _stream()),
+        "mval_pred_coordinates",
+    )
+    return out
+
+
 def soft_argmax(hm, n_maps, hh, wh, scale):
     out = torch.empty((n_maps, 2), dtype=torch.float32, device=hm.device)
     _check(
@@ -447,6 +483,24 @@ def pck3d(pred, gt, valid, thresholds, mode):
         "mval_pck3d",
     )
     return hits, counts
+
+
+def pckh2d(pred, gt, thresholds, n_keypoints, kp0=0, kp1=1):
+    """2-D PCKh counters: pred, gt (S,J,2) f32, head = the distance between gt joints kp0 and kp1 -> hits (T, n_keypoints) int64
+    (device), one launch for all thresholds."""
+    if pred.dim() != 3 or pred.shape[2] != 2 or pred.shape != gt.shape:
+        raise MvalError(f"pckh2d: pred and gt must both be (S, J, 2), got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    s, j, _ = pred.shape
+    thr = torch.as_tensor(list(thresholds), dtype=torch.float64).to(pred.device)
+    hits = torch.empty((thr.numel(), int(n_keypoints)) if 0 < int(n_keypoints) <= j else (0,), dtype=torch.int64, device=pred.device)
+    _check(
+        lib().mval_pckh2d(
+            _p(_req(pred, torch.float32, "pred")), _p(_req(gt, torch.float32, "gt")), _p(thr), C.c_int(thr.numel()),
+            C.c_int(kp0), C.c_int(kp1), _p(hits), C.c_longlong(s), C.c_int(j), C.c_int(int(n_keypoints)), _stream(),
+        ),
+        "mval_pckh2d",
+    )
+    return hits
 
 
 # --------------------------------------------------------------------------

@@ -87,3 +87,13 @@ def cluster_type(value):
     if value not in CLUSTER_TYPES:
         raise NotImplementedError("AL.CLUSTER.TYPE %r: accepted are %s" % (value, " and ".join(repr(t) for t in CLUSTER_TYPES)))
     return value
+
+
+EVAL_METRICS = ("2DPCKH", "3DPCK", "3DPCKH", "MKPE")  # the four the reference's EVAL.METRIC comment lists
+
+
+def check_eval_metric(value):
+    """A valid EVAL.METRIC, or NotImplementedError naming the accepted ones."""
+    if value not in EVAL_METRICS:
+        raise NotImplementedError("EVAL.METRIC %r: accepted are %s" % (value, ", ".join(repr(m) for m in EVAL_METRICS)))
+    return value

@@ -4,19 +4,8 @@
 #include "mval_common.h"
 #include "numeric_order.h"  // argmax_better: torch.argmax's order
 
-__global__ __launch_bounds__(256) void argmax_decode_kernel(
-    const float* __restrict__ hm, const uint8_t* __restrict__ valid, int64_t* __restrict__ kp2d,
-    int64_t n_maps, int V, int J, int npix, int stride, int split_width) {
-  const int lane = threadIdx.x & 63;
-  const int64_t map = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (map >= n_maps) return;
-  const int j = (int)(map % J);
-  const int64_t b = map / ((int64_t)V * J);
-  if (valid && !valid[b * J + j]) {
-    if (lane == 0) { kp2d[map * 2] = 0; kp2d[map * 2 + 1] = 0; }
-    return;
-  }
-  const float* p = hm + map * (int64_t)npix;
+// the flat arg-max of one map by one wave, in every lane
+__device__ __forceinline__ int wave_argmax(const float* __restrict__ p, int npix, int lane) {
   float bv = -INFINITY;
   int bi = 0x7fffffff;
   if ((npix & 3) == 0 && ((uintptr_t)p & 15) == 0) {
@@ -41,8 +30,23 @@ __global__ __launch_bounds__(256) void argmax_decode_kernel(
     int oi = __shfl_xor(bi, o, 64);
     if (argmax_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
   }
+  return bi == 0x7fffffff ? 0 : bi;  // all -inf (argmax_better never fired): first element
+}
+
+__global__ __launch_bounds__(256) void argmax_decode_kernel(
+    const float* __restrict__ hm, const uint8_t* __restrict__ valid, int64_t* __restrict__ kp2d,
+    int64_t n_maps, int V, int J, int npix, int stride, int split_width) {
+  const int lane = threadIdx.x & 63;
+  const int64_t map = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (map >= n_maps) return;
+  const int j = (int)(map % J);
+  const int64_t b = map / ((int64_t)V * J);
+  if (valid && !valid[b * J + j]) {
+    if (lane == 0) { kp2d[map * 2] = 0; kp2d[map * 2 + 1] = 0; }
+    return;
+  }
+  const int bi = wave_argmax(hm + map * (int64_t)npix, npix, lane);
   if (lane == 0) {
-    if (bi == 0x7fffffff) bi = 0;  // all -inf: first element
     kp2d[map * 2] = (int64_t)(bi % split_width) * stride;
     kp2d[map * 2 + 1] = (int64_t)(bi / split_width) * stride;
   }
@@ -53,7 +57,6 @@ extern "C" int mval_argmax_decode(const float* heatmaps, const uint8_t* valid, i
   MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && split_width > 0, "mval_argmax_decode: bad dims");
   int64_t n_maps = (int64_t)B * V * J;
   if (n_maps == 0) return 0;
-  // an all -inf map must still pick index 0: handled by argmax_better() never firing -> bi stays max; fix below
   dim3 grid((unsigned)((n_maps + 3) / 4));
   hipLaunchKernelGGL(argmax_decode_kernel, grid, dim3(256), 0, mval_stream(stream), heatmaps, valid, kp2d, n_maps, V,
                      J, hh * wh, stride, split_width);
@@ -62,15 +65,9 @@ extern "C" int mval_argmax_decode(const float* heatmaps, const uint8_t* valid, i
 }
 
 // ---- key-points from the arg-max keys the heat-map layer's epilogue kept (mval_common.h) ------------------------------------
-// one wave per map: its MVAL_ARGMAX_SLOTS partial keys -> the largest
-__global__ __launch_bounds__(256) void argmax_from_keys_kernel(const unsigned long long* __restrict__ keys, const uint8_t* __restrict__ valid,
-                                                               int64_t* __restrict__ kp2d, int64_t n_maps, int V, int J, int stride,
-                                                               int split_width) {
-  const int lane = threadIdx.x & 63;
-  const int64_t map = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (map >= n_maps) return;
+// one wave per map: its MVAL_ARGMAX_SLOTS partial keys -> the largest -> the flat arg-max, in every lane
+__device__ __forceinline__ unsigned keys_argmax(const unsigned long long* __restrict__ keys, int64_t map, int J, int lane) {
   const int j = (int)(map % J);
-  const int64_t b = map / ((int64_t)V * J);
   unsigned long long k = 0ull;
   static_assert(MVAL_ARGMAX_SLOTS % 64 == 0, "whole waves over a row");
 #pragma unroll
@@ -79,9 +76,20 @@ __global__ __launch_bounds__(256) void argmax_from_keys_kernel(const unsigned lo
     k = v > k ? v : k;
   }
   k = mval_key_group_max(k, 32);
+  return k == 0ull ? 0u : 0xffffffffu - (unsigned)k;
+}
+
+__global__ __launch_bounds__(256) void argmax_from_keys_kernel(const unsigned long long* __restrict__ keys, const uint8_t* __restrict__ valid,
+                                                               int64_t* __restrict__ kp2d, int64_t n_maps, int V, int J, int stride,
+                                                               int split_width) {
+  const int lane = threadIdx.x & 63;
+  const int64_t map = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (map >= n_maps) return;
+  const int j = (int)(map % J);
+  const int64_t b = map / ((int64_t)V * J);
+  const unsigned bi = keys_argmax(keys, map, J, lane);
   if (lane != 0) return;
   const bool inval = valid && !valid[b * J + j];
-  const unsigned bi = k == 0ull ? 0u : 0xffffffffu - (unsigned)k;
   kp2d[map * 2] = inval ? 0 : (int64_t)(bi % (unsigned)split_width) * stride;
   kp2d[map * 2 + 1] = inval ? 0 : (int64_t)(bi / (unsigned)split_width) * stride;
 }
@@ -94,6 +102,64 @@ extern "C" int mval_argmax_from_keys(const uint64_t* keys, const uint8_t* valid,
   hipLaunchKernelGGL(argmax_from_keys_kernel, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, mval_stream(stream),
                      reinterpret_cast<const unsigned long long*>(keys), valid, kp2d, n_maps, V, J, stride, split_width);
   MVAL_CHECK_LAUNCH("mval_argmax_from_keys");
+  return 0;
+}
+
+// ---- box-scaled key-points (utils/evaluation.py:45-58, the hard arg-max branch of get_pred_coordinates) --------------------
+// float32 as torch computes it, every operation rounded on its own (no FMA contraction): the result is compared bit for bit.
+// Both quirks of the reference are kept: the flat index is split by shape[2] (= hh) for x AND y, and x is scaled by the
+// box's (bottom - top) over wh, y by its (right - left) over hh.
+__device__ __forceinline__ void pred_coordinates_put(float* __restrict__ xy, const float* __restrict__ box, unsigned bi, int hh, int wh) {
+  xy[0] = __fmul_rn((float)(bi % (unsigned)hh), __fdiv_rn(__fsub_rn(box[3], box[1]), (float)wh));
+  xy[1] = __fmul_rn((float)(bi / (unsigned)hh), __fdiv_rn(__fsub_rn(box[2], box[0]), (float)hh));
+}
+
+__global__ __launch_bounds__(256) void pred_coordinates_kernel(const float* __restrict__ hm, const float* __restrict__ boxes,
+                                                               float* __restrict__ xy, int64_t n_maps, int J, int hh, int wh) {
+  const int lane = threadIdx.x & 63;
+  const int64_t map = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (map >= n_maps) return;
+  const int npix = hh * wh;
+  const int bi = wave_argmax(hm + map * (int64_t)npix, npix, lane);
+  if (lane == 0) pred_coordinates_put(xy + map * 2, boxes + (map / J) * 4, (unsigned)bi, hh, wh);
+}
+
+__global__ __launch_bounds__(256) void pred_coordinates_from_keys_kernel(const unsigned long long* __restrict__ keys,
+                                                                         const float* __restrict__ boxes, float* __restrict__ xy,
+                                                                         int64_t n_maps, int J, int hh, int wh) {
+  const int lane = threadIdx.x & 63;
+  const int64_t map = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (map >= n_maps) return;
+  const unsigned bi = keys_argmax(keys, map, J, lane);
+  if (lane == 0) pred_coordinates_put(xy + map * 2, boxes + (map / J) * 4, bi, hh, wh);
+}
+
+// (a map of 2^24 pixels or more would make (float)(idx / hh) inexact, and hh * wh must fit an int)
+#define MVAL_PRED_COORD_DIMS(N, J, hh, wh) ((N) >= 0 && (J) > 0 && (hh) > 0 && (wh) > 0 && (int64_t)(hh) * (wh) < (1 << 24))
+
+extern "C" int mval_pred_coordinates(const float* heatmaps, const float* boxes, float* xy, int64_t N, int J, int hh, int wh,
+                                     void* stream) {
+  MVAL_REQUIRE(MVAL_PRED_COORD_DIMS(N, J, hh, wh), "mval_pred_coordinates: bad dims");
+  const int64_t n_maps = N * J;
+  if (n_maps == 0) return 0;
+  MVAL_REQUIRE(heatmaps && boxes && xy, "mval_pred_coordinates: heatmaps, boxes and xy must not be NULL");
+  MVAL_REQUIRE((n_maps + 3) / 4 <= 0x7fffffff, "mval_pred_coordinates: too many maps");
+  hipLaunchKernelGGL(pred_coordinates_kernel, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, mval_stream(stream), heatmaps,
+                     boxes, xy, n_maps, J, hh, wh);
+  MVAL_CHECK_LAUNCH("mval_pred_coordinates");
+  return 0;
+}
+
+extern "C" int mval_pred_coordinates_from_keys(const uint64_t* keys, const float* boxes, float* xy, int64_t N, int J, int hh,
+                                               int wh, void* stream) {
+  MVAL_REQUIRE(MVAL_PRED_COORD_DIMS(N, J, hh, wh), "mval_pred_coordinates_from_keys: bad dims");
+  const int64_t n_maps = N * J;
+  if (n_maps == 0) return 0;
+  MVAL_REQUIRE(keys && boxes && xy, "mval_pred_coordinates_from_keys: keys, boxes and xy must not be NULL");
+  MVAL_REQUIRE((n_maps + 3) / 4 <= 0x7fffffff, "mval_pred_coordinates_from_keys: too many maps");
+  hipLaunchKernelGGL(pred_coordinates_from_keys_kernel, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, mval_stream(stream),
+                     reinterpret_cast<const unsigned long long*>(keys), boxes, xy, n_maps, J, hh, wh);
+  MVAL_CHECK_LAUNCH("mval_pred_coordinates_from_keys");
   return 0;
 }
 

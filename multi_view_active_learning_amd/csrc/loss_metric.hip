@@ -303,3 +303,50 @@ extern "C" int mval_pck3d(const float* pred, const float* gt, const float* valid
   MVAL_CHECK_LAUNCH("mval_pck3d");
   return 0;
 }
+
+// ---- 2-D PCKh --------------------------------------------------------------------------------
+// utils/evaluation.py:65-93 (compute_pckh), the counter of _evaluate_2d_pckh (strategy.py:548-582).  float32 with torch's
+// operation order, every operation rounded separately, as above:
+//   head = sqrt((g[kp0].x - g[kp1].x)^2 + (g[kp0].y - g[kp1].y)^2) ; d = (float32)(head * (float)threshold[t])
+//   dis  = sqrt((p.x - g.x)^2 + (p.y - g.y)^2) ; hit when dis < d (strict; a NaN on either side is no hit)
+// over every image and every joint below n_keypoints (the reference has no validity mask here).  Laid out as pck3d_kernel:
+// one workgroup per (joint, threshold), each thread walks the samples in steps of 256; integer sums.
+__device__ __forceinline__ float pck_dist2(float ax, float ay, float bx, float by) {
+  const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by);
+  return __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+}
+
+__global__ __launch_bounds__(256) void pckh2d_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                     const double* __restrict__ thresholds, int kp0, int kp1,
+                                                     long long* __restrict__ hits, int64_t S, int J, int n_keypoints) {
+  __shared__ long long sh[256];
+  const int j = blockIdx.x, t = blockIdx.y;
+  const float thr = (float)thresholds[t];
+  long long h = 0;
+  for (int64_t s = threadIdx.x; s < S; s += 256) {
+    const float* g = gt + s * J * 2;
+    const float* pr = pred + (s * J + j) * 2;
+    const float head = pck_dist2(g[2 * kp0], g[2 * kp0 + 1], g[2 * kp1], g[2 * kp1 + 1]);
+    h += pck_dist2(pr[0], pr[1], g[2 * j], g[2 * j + 1]) < __fmul_rn(head, thr);
+  }
+  sh[threadIdx.x] = h;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) hits[(int64_t)t * n_keypoints + j] = sh[0];
+}
+
+extern "C" int mval_pckh2d(const float* pred, const float* gt, const double* thresholds, int T, int kp0, int kp1,
+                           long long* hits, int64_t S, int J, int n_keypoints, void* stream) {
+  MVAL_REQUIRE(S >= 0 && J >= 2 && T > 0 && T <= 65535 && kp0 >= 0 && kp0 < J && kp1 >= 0 && kp1 < J && n_keypoints >= 1 &&
+                   n_keypoints <= J,
+               "mval_pckh2d: bad arguments (S %lld, J %d, T %d, kp0 %d, kp1 %d, n_keypoints %d)", (long long)S, J, T, kp0, kp1,
+               n_keypoints);
+  MVAL_REQUIRE(thresholds && hits && (S == 0 || (pred && gt)), "mval_pckh2d: pred, gt, thresholds and hits must not be NULL");
+  hipLaunchKernelGGL(pckh2d_kernel, dim3(n_keypoints, T), dim3(256), 0, mval_stream(stream), pred, gt, thresholds, kp0, kp1,
+                     hits, S, J, n_keypoints);
+  MVAL_CHECK_LAUNCH("mval_pckh2d");
+  return 0;
+}

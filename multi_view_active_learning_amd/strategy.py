@@ -706,3 +706,78 @@ class ActiveLearningStrategy:
             t, p = evaluation.compute_3d_pckh_figure(pred, gt, j)
             results["pckh_thresholds"], results["pckh_pcks"] = t, p
         return results
+
+    # ---- 2-D PCKh (strategy.py:548-582, 784-789) ----------------------------------------------------------------------
+    def _compute_pred_labels(self, pose_estimator, data, heatmaps):
+        """strategy.py:784-789: the batch's box-scaled hard arg-max key-points, boxes from ``data["square_box"]`` reshaped to
+        (-1, 4) -- as ONE (N, J, 2) float32 HIP tensor from one launch (the reference returns N x J pairs of 0-d tensors).
+        Decoded from the arg-max keys the network kept for ``heatmaps`` where it did (no second read of the maps), from the
+        maps otherwise."""
+        boxes = torch.as_tensor(data["square_box"]).to(heatmaps.device).reshape(-1, 4)
+        keys = _lib.argmax_keys_of(heatmaps) if heatmaps.is_cuda and _lib.epilogue_decode_enabled() else None
+        if keys is not None and tuple(keys.shape) != (heatmaps.shape[0], _lib.ARGMAX_SLOTS, heatmaps.shape[1]):
+            keys = None  # (kept for another factorisation of the maps: see _lib.argmax_decode)
+        return evaluation.pred_coordinates_batch(heatmaps, boxes, keys)[:, : self.num_joints]
+
+    @staticmethod
+    def _stage_pckh_targets(dp):
+        """``_stage_batch`` plus what the 2-D PCKh pass reads -- ``square_box`` and ``2d_after_crop`` -- on the device, uploaded
+        like the small tensors: pinned, non-blocking, on the caller's stream before the network."""
+        out = _stage_batch(dp)
+        if torch.cuda.is_available() and isinstance(dp, dict):
+            out = dict(out)
+            for key in ("square_box", "2d_after_crop"):
+                if key in dp:
+                    out[key] = _stage_small(torch.as_tensor(dp[key]))
+        return out
+
+    def evaluate_2d_pckh(self, data_loader, pose_estimator, thresholds=None):
+        """_evaluate_2d_pckh (strategy.py:548-582): PCKh of the 2-D network itself, per view, over the whole loader ->
+        (thresholds, pcks), ``thresholds`` defaulting to the reference's 0.1 .. 1.0.  Per batch one decode launch beside the
+        next batch's network; per pass ONE packed gather of [pred 2J | gt 2J] float32 rows (the reference: two all_gathers
+        per batch) and one counter launch for all thresholds.  The ground truth is ``2d_after_crop`` reshaped to
+        (-1, J, 2) with J = DATA.NUM_JOINTS, where the reference hard-codes 19 (strategy.py:567).  The gathered tables stay
+        in ``self._eval2d_tables``."""
+        j = self.num_joints
+
+        def decode(hm, _keys, dp):
+            pred = self._compute_pred_labels(pose_estimator, dp, hm)
+            gt = torch.as_tensor(dp["2d_after_crop"]).to(hm.device, torch.float32).reshape(-1, j, 2)
+            if pred.shape != gt.shape:
+                raise ValueError("2-D PCKh: %s predictions for %s ground-truth key-points" % (tuple(pred.shape), tuple(gt.shape)))
+            return torch.cat([pred.reshape(-1, 2 * j), gt.reshape(-1, 2 * j)], dim=1)
+
+        rows = self._pool_loop(data_loader, pose_estimator, decode, stage=self._stage_pckh_targets)
+        from .parallel import all_gather_reference_order as gather
+
+        if rows:
+            local = torch.cat(rows)
+        else:  # an empty shard still takes part in the collective
+            dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+            local = torch.zeros((0, 4 * j), dtype=torch.float32, device=dev)
+        table = gather(local, [r.shape[0] for r in rows])
+        pred, gt = table[:, : 2 * j].reshape(-1, j, 2), table[:, 2 * j :].reshape(-1, j, 2)
+        self._eval2d_tables = (pred, gt)
+        return evaluation.compute_pckh_figure(pred, gt, j, evaluation.PCKH_THRESHOLDS if thresholds is None else thresholds)
+
+    def evaluate(self, data_loader, pose_estimator, metric=None):
+        """The evaluation EVAL.METRIC names (``metric`` overrides it; config.EVAL_METRICS): a dict with "metric",
+        "thresholds" and "pcks", plus "mkpe" whenever the 3-D pass ran --
+          "2DPCKH"  ``evaluate_2d_pckh``
+          "3DPCK"   ``evaluate_mkpe``, then 3-D PCK at 1..5 mm over valid joints (``evaluate_all``'s "pcks")
+          "3DPCKH"  ``evaluate_mkpe``, then 3-D PCKh at 0.1..1.0 (``evaluate_all``'s "pckh_pcks")
+          "MKPE"    ``evaluate_mkpe`` only; thresholds and pcks are None."""
+        from .config import check_eval_metric
+
+        metric = check_eval_metric(self.al_cfg.EVAL.METRIC if metric is None else metric)
+        if metric == "2DPCKH":
+            thresholds, pcks = self.evaluate_2d_pckh(data_loader, pose_estimator)
+            return {"metric": metric, "thresholds": thresholds, "pcks": pcks}
+        mkpe = self.evaluate_mkpe(data_loader, pose_estimator)
+        pred, gt, valid = self._eval_tables
+        thresholds = pcks = None
+        if metric == "3DPCK":
+            thresholds, pcks = evaluation.compute_3d_pck_figure(pred, gt, valid, pred.shape[1])
+        elif metric == "3DPCKH":
+            thresholds, pcks = evaluation.compute_3d_pckh_figure(pred, gt, pred.shape[1])
+        return {"metric": metric, "thresholds": thresholds, "pcks": pcks, "mkpe": mkpe.item()}

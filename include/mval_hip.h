@@ -501,6 +501,29 @@ typedef struct mval_split_form {
 enum { MVAL_SPLIT_USE_OP = 0, MVAL_SPLIT_USE_TRAIN_FWD = 1, MVAL_SPLIT_USE_DGRAD = 2, MVAL_SPLIT_USE_DGRAD_PARITY = 3 };
 int mval_conv_split_form(int use, const mval_op* op, int n_images, int algo, mval_split_form* form);
 
+/* The same question for the exact-fp32 MFMA conv (csrc/conv_mfma.hip: MVAL_ALGO_MFMA), the kernel every other conv is judged against: which
+ * instance of conv_mfma_kernel a launch of the library runs on.  Host arithmetic only (no GPU needed, nothing is launched).
+ *   ks .. ne     the kernel's template arguments: kernel size, stride, channels per chunk (16 / 32), cout waves, pixel waves, cout sub-tiles
+ *                and pixel sub-tiles per wave, staging slots per thread (4 / 6 / 10; 0 = the generic single-buffered staging loop)
+ *   th, tw, tn   tile rows x columns x images (powers of two; th * tw * tn = 16 * ms * wm)
+ *   dil          2 = the input is read as if zero-dilated by 2 (data gradient of a stride-2 conv, forward of a transposed conv)
+ *   nbuf         LDS patch buffers: 2 = double-buffered chunks, 1 = one chunk or the generic staging
+ *   grid_x/y     pixel tiles, cout groups
+ *   bn_part_ok   the tile form and the epilogue options allow the batch-statistics partials (given room for them);
+ *   bn_part      the launch asks for them and keeps them (mval_train_forward's convs with BatchNorm; never a transposed conv)
+ * `use` as for mval_conv_split_form.  For MVAL_OP_DECONV (k4 s2 p1), MVAL_SPLIT_USE_OP and _TRAIN_FWD answer the stride-1 k4 conv over the
+ * zero-dilated input and MVAL_SPLIT_USE_DGRAD the k4 stride-2 conv mval_train_backward runs as its data gradient; MVAL_SPLIT_USE_DGRAD_PARITY
+ * has no exact-fp32 form.  Returns 1 and fills *form, or 0 where the library has no exact-fp32 MFMA kernel for the launch. */
+typedef struct mval_mfma_form {
+  int32_t ks, s, kc, wn, wm, nt, ms, ne;
+  int32_t th, tw, tn;
+  int32_t dil;
+  int32_t nbuf;
+  int32_t grid_x, grid_y;
+  int32_t bn_part_ok, bn_part;
+} mval_mfma_form;
+int mval_conv_mfma_form(int use, const mval_op* op, int n_images, mval_mfma_form* form);
+
 int mval_op_launch(const mval_op* op, int n_images, float* workspace, const float* params,
                    const float* net_input, float* net_output, void* stream);
 

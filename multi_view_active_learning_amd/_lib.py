@@ -537,6 +537,24 @@ def conv_split_form(use, op, n_images, algo):
     return form if ok else None
 
 
+class MfmaForm(C.Structure):
+    """include/mval_hip.h: struct mval_mfma_form."""
+
+    _fields_ = [(name, C.c_int32) for name in ("ks", "s", "kc", "wn", "wm", "nt", "ms", "ne", "th", "tw", "tn", "dil", "nbuf", "grid_x", "grid_y",
+                                               "bn_part_ok", "bn_part")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+def conv_mfma_form(use, op, n_images):
+    """mval_conv_mfma_form: the kernel form (MfmaForm) of the exact-fp32 MFMA conv the library's launch of the MvalOp ``op`` under ``use``
+    (SPLIT_USE_OP / _TRAIN_FWD / _DGRAD) ends on, or None where it has no such kernel for it."""
+    form = MfmaForm()
+    ok = lib().mval_conv_mfma_form(C.c_int(use), C.byref(op), C.c_int(n_images), C.byref(form))
+    return form if ok else None
+
+
 # --------------------------------------------------------------------------
 # core-set (k-center greedy)
 # --------------------------------------------------------------------------

@@ -373,6 +373,7 @@ static inline void conv_bn_part_prepare(ConvArgs& a, unsigned grid_x, unsigned g
 
 int mval_launch_conv_mfma(const ConvArgs& a, hipStream_t s);  // conv_mfma.hip; returns 1 if unsupported
 int mval_conv_mfma_supported(const ConvArgs& a);            // same selection logic, no launch
+int mval_conv_mfma_form_of(const ConvArgs& a, mval_mfma_form* form);  // 1 + the form the launcher would run, 0 if unsupported; no launch
 int mval_launch_conv_split(const ConvArgs& a, hipStream_t s);  // conv_mfma_split.hip (a.planes); returns 1 if unsupported
 int mval_conv_split_supported(const ConvArgs& a);
 int mval_conv_split_form_of(const ConvArgs& a, mval_split_form* form);  // 1 + the form the launcher would run, 0 if unsupported; no launch

@@ -226,6 +226,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
 }
 
 static thread_local int g_dry_run = 0;  // feasibility query: run the selection logic, launch nothing
+static thread_local mval_mfma_form* g_mfma_form = nullptr;  // dry runs leave the form they end on here (mval_conv_mfma_form)
 
 template <int KS, int S, int KC, int WN, int WM, int NT, int MS>
 static int launch_cfg(ConvArgs a, int th, int tw, int tn, hipStream_t s) {
@@ -247,8 +248,20 @@ static int launch_cfg(ConvArgs a, int th, int tw, int tn, hipStream_t s) {
   const size_t otile = (size_t)CONV_OTILE_FLOATS(MT, NTILE) * sizeof(float);  // (with the max |x| reduction scratch)
   if (otile > smem) smem = otile;
   if (smem > 128 * 1024) return 1;  // LDS is 160 KiB per CU on gfx950
-  if (g_dry_run) return 0;
   dim3 grid((unsigned)(a.tiles_x * a.tiles_y * ngroups), (unsigned)((a.NS_total + WN * NT - 1) / (WN * NT)));
+  if (g_dry_run) {
+    if (mval_mfma_form* f = g_mfma_form) {  // mval_conv_mfma_form: what would run (the NE choice is the one of the launches below)
+      f->ks = KS; f->s = S; f->kc = KC; f->wn = WN; f->wm = WM; f->nt = NT; f->ms = MS;
+      f->ne = ne <= 4 ? 4 : ne <= 6 ? 6 : ne <= 10 ? 10 : 0;
+      f->th = th; f->tw = tw; f->tn = tn;
+      f->dil = a.dil;
+      f->nbuf = nbuf;
+      f->grid_x = (int32_t)grid.x; f->grid_y = (int32_t)grid.y;
+      f->bn_part_ok = conv_bn_part_ok<MT, NTILE, 256>(a, grid.x, 1, INT64_MAX);  // (an ample bn_part_cap)
+      f->bn_part = a.bn_part && f->bn_part_ok;
+    }
+    return 0;
+  }
   conv_amax_prepare(a, a.tiles_x * a.tiles_y, (int)grid.y, s);
   conv_bn_part_prepare<MT, NTILE, 256>(a, grid.x, 1);
   // staging registers are sized at compile time (runtime-indexed arrays would go to scratch)
@@ -329,6 +342,15 @@ int mval_launch_conv_mfma(const ConvArgs& a, hipStream_t s) {
 int mval_conv_mfma_supported(const ConvArgs& a) {
   g_dry_run = 1;
   int rc = mval_launch_conv_mfma(a, nullptr);
+  g_dry_run = 0;
+  return rc == 0;
+}
+
+int mval_conv_mfma_form_of(const ConvArgs& a, mval_mfma_form* form) {
+  g_dry_run = 1;
+  g_mfma_form = form;
+  int rc = mval_launch_conv_mfma(a, nullptr);
+  g_mfma_form = nullptr;
   g_dry_run = 0;
   return rc == 0;
 }

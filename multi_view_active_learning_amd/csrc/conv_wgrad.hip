@@ -428,6 +428,13 @@ int mval_conv_wgrad_on(const float* x, const float* dz, float* dw, float* ws, in
     a.N = N; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.Cout = Cout; a.pad = pad;
     const int mt = (stride == 2 || (int64_t)N * Hout * Wout < 65536) ? 64 : 128;
     wg_pick_tile(Hout, Wout, mt, &a.th, &a.tw, &a.tn);
+    // maps of one or two rows: the halos of many images per tile can exceed the staging registers (NEX of the launches below; 3x3 on
+    // 1 x 5: 8 images x 3 x 10 = 240 patch pixels against 192) -- take a taller tile with fewer images, its extra rows lie outside the map
+    const int nex = (k == 3 && stride == 1) ? 6 : (k == 3 || k == 4) ? 12 : stride == 2 ? 8 : mt == 128 ? 4 : 2;
+    while (a.tn > 1 && a.tn * ((a.th - 1) * stride + k) * ((a.tw - 1) * stride + k) * 8 > 256 * nex) {
+      a.tn >>= 1;
+      a.th <<= 1;
+    }
     a.tw_log2 = __builtin_ctz(a.tw);
     a.thw_log2 = __builtin_ctz(a.th * a.tw);
     a.tiles_x = (Wout + a.tw - 1) / a.tw;

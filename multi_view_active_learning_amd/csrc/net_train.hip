@@ -156,6 +156,19 @@ static void deconv_as_conv(ConvArgs& a, const mval_op& op) {
   a.pad = op.k - 1 - op.pad;
 }
 
+// Data gradient of ConvTranspose2d(k, s, p): the plain stride-s conv over dz (at the output resolution) with the channel roles swapped
+static void deconv_dgrad_args(ConvArgs& a, const mval_op& op, int n_images) {
+  a.N = n_images;
+  a.Hin = op.hout; a.Win = op.wout; a.Cin = op.cout;
+  a.Hout = op.hin; a.Wout = op.win; a.Cout = op.cin;
+  a.k = op.k; a.stride = op.stride; a.pad = op.pad;
+  a.up = 0; a.relu = 0; a.in_nchw = 0; a.out_nchw = 0;
+  a.dil = 1;
+  a.th = a.tw = a.tn = a.tw_log2 = a.thw_log2 = a.tiles_x = a.tiles_y = 0;
+  a.G_total = (op.cout + 15) / 16;
+  a.NS_total = (op.cin + 15) / 16;
+}
+
 static bool split_algo(int algo) { return algo == MVAL_ALGO_MFMA_BF3 || algo == MVAL_ALGO_MFMA_H2; }
 static int split_planes(int algo) { return algo == MVAL_ALGO_MFMA_H2 ? 2 : 3; }
 
@@ -542,15 +555,7 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
       if (rc) return rc;
       if (t.gin_off >= 0) {
         ConvArgs a = {};
-        a.N = n_images;
-        a.Hin = op.hout; a.Win = op.wout; a.Cin = op.cout;
-        a.Hout = op.hin; a.Wout = op.win; a.Cout = op.cin;
-        a.k = op.k; a.stride = op.stride; a.pad = op.pad;
-        a.up = 0; a.relu = 0; a.in_nchw = 0; a.out_nchw = 0;
-        a.dil = 1;
-        a.th = a.tw = a.tn = a.tw_log2 = a.thw_log2 = a.tiles_x = a.tiles_y = 0;
-        a.G_total = (op.cout + 15) / 16;
-        a.NS_total = (op.cin + 15) / 16;
+        deconv_dgrad_args(a, op, n_images);
         a.in = gz;
         a.w = params + t.wd_off;
         a.scale = params + ones_off;
@@ -795,4 +800,37 @@ extern "C" int mval_conv_split_form(int use, const mval_op* op, int n_images, in
     return 0;
   }
   return mval_conv_split_form_of(a, form);
+}
+
+// The same for the exact-fp32 MFMA conv (conv_mfma.hip), transposed convs included: their forward is the stride-1 k4 conv over the
+// zero-dilated input, their data gradient the k4 stride-2 conv of mval_train_backward.
+extern "C" int mval_conv_mfma_form(int use, const mval_op* op, int n_images, mval_mfma_form* form) {
+  if (!op || !form || n_images <= 0 || (op->kind != MVAL_OP_CONV && op->kind != MVAL_OP_DECONV)) return 0;
+  static const float some = 0.f;  // (a residual / a partials buffer is only asked for, never read)
+  static double some_part = 0.0;
+  *form = {};
+  ConvArgs a = {};
+  if (use == MVAL_SPLIT_USE_OP) {
+    mval_op_geometry(a, op, n_images);
+    if (op->kind == MVAL_OP_DECONV) deconv_as_conv(a, *op);
+    a.res1 = op->res1_off >= 0 ? &some : nullptr;
+    a.res2 = op->res2_off >= 0 ? &some : nullptr;
+  } else if (use == MVAL_SPLIT_USE_TRAIN_FWD) {
+    geometry(a, *op, n_images);
+    if (op->kind == MVAL_OP_DECONV) {
+      deconv_as_conv(a, *op);
+    } else {
+      a.bn_part = &some_part;  // (mval_train_forward asks for the partials of every conv, not transposed, with a BatchNorm)
+      a.bn_part_cap = INT64_MAX;
+    }
+  } else if (use == MVAL_SPLIT_USE_DGRAD) {
+    if (op->kind == MVAL_OP_DECONV)
+      deconv_dgrad_args(a, *op, n_images);
+    else
+      dgrad_args(a, n_images, op->hin, op->win, op->cin, op->hout, op->wout, op->cout, op->k, op->stride, op->pad);
+    a.res1 = op->res1_off >= 0 ? &some : nullptr;
+  } else {
+    return 0;
+  }
+  return mval_conv_mfma_form_of(a, form);
 }

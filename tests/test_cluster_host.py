@@ -112,7 +112,7 @@ def test_loss_pass_keys_order_and_file_round_trip(name, tmp_path):
     loader, hms = cluster_cases.build_cluster_loader(c)
     it = iter(hms)
     st = _numpy_stages(_cfg(SAVE_PATH=str(tmp_path / "loss.json")),
-                       lambda dp: cluster_cases.frame_loss_f64(next(it).reshape(dp["gt_heatmap"].shape), dp["gt_heatmap"].numpy()))
+                       lambda dp: cluster_cases.frame_loss_f64(next(it).reshape(dp["gt_heatmap"].shape), dp["gt_heatmap"].cpu().numpy()))  # (the pool loop stages the batch on the device where there is one)
     got = st.cluster(None, _torch_loader(loader))
     assert list(got) == list(want) == list(gold["f64"])
     for g, v in got.items():

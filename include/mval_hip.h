@@ -254,6 +254,18 @@ size_t mval_augment_views_workspace_bytes(int n_views, int h, int w);
  * launched (at most seven per step, whatever n_views is); a kind present on the device but missing there is skipped. */
 int mval_augment_views(uint8_t* img, const mval_aug_op* ops, const uint32_t* step_kinds, int n_views, int n_steps, int h, int w,
                        void* ws, void* stream);
+/* The target side of ROTATE (not in the reference as published: its Rotate drops the rotated maps, dataset/augmentation.py:19-25; this is what
+ * the line evidently meant).  In place on maps [n_views][maps_per_view][h][w] f32: at step k, a view whose op is MVAL_AUG_ROTATE has every one of
+ * its maps turned by Pillow's Image.rotate(angle, BICUBIC) on a mode-"F" image of h x w, bit for bit (ImagingGenericTransform with
+ * bicubic_filter32F: float32 coefficient sums along a row, float64 polynomial, float64 between the rows, a float32 cast without a clip; a
+ * position outside the map gives +0.0f); any other kind leaves the view's maps alone.  ops: the DEVICE array [n_views][n_steps] of
+ * mval_augment_views, with p[0..5] built for the MAP's h, w; step_kinds: the HOST array [n_steps] -- a step without the MVAL_AUG_ROTATE bit
+ * launches nothing.  ws >= mval_rotate_maps_workspace_bytes(...) (a second copy of maps; 0 for a non-positive argument).
+ * Limits, checked: n_views <= 65535, maps_per_view <= 65535 (grid dimensions), h * w <= 2^28.  A null pointer, a non-positive size or a size
+ * past these returns -1 with a message and launches nothing. */
+size_t mval_rotate_maps_workspace_bytes(int n_views, int maps_per_view, int h, int w);
+int mval_rotate_maps(float* maps, const mval_aug_op* ops, const uint32_t* step_kinds, int n_views, int n_steps, int maps_per_view, int h, int w,
+                     void* ws, void* stream);
 
 /* utils/evaluation.py:198-208 compute_mkpe over S samples: pred [S,J,3] f32, gt [S,gt_rows,J]
  * f32 (rows 0..2 used), valid [S,J] f32 ; out [1] f32 = mean_j (sum_s d_sj / sum_s valid_sj) ;

@@ -23,6 +23,7 @@ def _data_defaults():
     d.USE_ROTATION = True
     d.USE_IMAGE_AUG = True
     d.USE_CONST_AUG_MAGNITUDE = True
+    d.ROTATE_TARGETS = "none"  # not in the reference (its Rotate drops the rotated heat-maps): utils.augmentation.ROTATE_TARGETS
     return d
 
 
@@ -96,4 +97,14 @@ def check_eval_metric(value):
     """A valid EVAL.METRIC, or NotImplementedError naming the accepted ones."""
     if value not in EVAL_METRICS:
         raise NotImplementedError("EVAL.METRIC %r: accepted are %s" % (value, ", ".join(repr(m) for m in EVAL_METRICS)))
+    return value
+
+
+def check_rotate_targets(value):
+    """A valid DATA.ROTATE_TARGETS (utils.augmentation.ROTATE_TARGETS: what RandAugment's Rotate does to the training targets), or ValueError
+    naming the accepted ones."""
+    from .utils.augmentation import ROTATE_TARGETS
+
+    if value not in ROTATE_TARGETS:
+        raise ValueError("DATA.ROTATE_TARGETS %r: accepted are %s" % (value, ", ".join(repr(m) for m in ROTATE_TARGETS)))
     return value

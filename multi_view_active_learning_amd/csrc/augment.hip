@@ -11,6 +11,7 @@
 //   colour       blend(L, image, f) per pixel
 //   spatial      Sharpness (3x3 SMOOTH + blend) and Rotate (bicubic gather), image -> second buffer
 //   copy back    second buffer -> image for the views of the spatial pass
+// The target side of Rotate (mval_rotate_maps, at the end of the file) turns the float32 heat-maps of the rotated views the same way.
 // Rounding: Pillow's C evaluates the blends and the 3x3 filter in float32 and the bicubic transform in float64, one rounding
 // per operation; hipcc contracts a * b + c to an FMA by default, so this file switches contraction off (see below).
 // Pixels are 3 bytes: a thread owns 4 consecutive pixels (12 bytes = 3 dwords) or 4 consecutive bytes, so that a wave's
@@ -406,5 +407,88 @@ extern "C" int mval_normalize_views_u8(const uint8_t* img, int n_views, int h, i
   const int npix = h * w;
   hipLaunchKernelGGL(aug_normalize_kernel, dim3((npix + 1023) / 1024, n_views), dim3(256), 0, mval_stream(stream), img, npix, out);
   MVAL_CHECK_LAUNCH("mval_normalize_views_u8");
+  return 0;
+}
+
+// ---- the targets: Image.rotate(angle, BICUBIC) on the heat-maps of the views Rotate turned (rotate_targets = "maps") ---------------------
+// maps [V][J][H][W] f32, each a Pillow mode-"F" image of its own: ImagingGenericTransform with affine_transform and bicubic_filter32F.  The
+// coordinates, the outside test and the taps are those of the uint8 image above; the arithmetic is not: the taps of a row are float32 and
+// Geometry.c's BICUBIC forms its coefficient sums from them in float32 (C's float + float), widens, and evaluates the polynomial in float64;
+// the four row results are float64 and take aug_cubic as it stands; the result is cast to float32 without a clip (the negative lobes stay).
+__device__ __forceinline__ double aug_cubic_f32(float v1, float v2, float v3, float v4, double d) {
+  const float p2 = aug_fadd(-v1, v3);
+  const float p3 = aug_fadd(aug_fadd(aug_fmul(2.f, aug_fadd(v1, -v2)), v3), -v4);
+  const float p4 = aug_fadd(aug_fadd(aug_fadd(-v1, v2), -v3), v4);
+  return aug_dadd((double)v2, aug_dmul(d, aug_dadd((double)p2, aug_dmul(d, aug_dadd((double)p3, aug_dmul(d, (double)p4))))));
+}
+
+// one thread per output element, maps -> second buffer.  grid (ceil(H * W / 256), J, V) x 256
+__global__ __launch_bounds__(256) void aug_rotate_maps_kernel(const float* __restrict__ maps, const mval_aug_op* __restrict__ ops, int n_steps, int step,
+                                                              int H, int W, float* __restrict__ out) {
+  const int v = blockIdx.z;
+  const mval_aug_op* op = ops + (int64_t)v * n_steps + step;
+  if (op->kind != MVAL_AUG_ROTATE) return;  // uniform per workgroup
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= H * W) return;
+  const int y = i / W, x = i - y * W;
+  const int64_t base = ((int64_t)v * gridDim.y + blockIdx.y) * H * W;
+  const float* src = maps + base;
+  const double xc = x + 0.5, yc = y + 0.5;
+  double xin = aug_dadd(aug_dadd(aug_dmul(op->p[0], xc), aug_dmul(op->p[1], yc)), op->p[2]);
+  double yin = aug_dadd(aug_dadd(aug_dmul(op->p[3], xc), aug_dmul(op->p[4], yc)), op->p[5]);
+  if (!(xin >= 0.0 && yin >= 0.0 && xin < (double)W && yin < (double)H)) {  // outside (or not a number): the fill value
+    out[base + i] = 0.f;
+    return;
+  }
+  xin = aug_dadd(xin, -0.5);
+  yin = aug_dadd(yin, -0.5);
+  const int fx = (int)floor(xin), fy = (int)floor(yin);
+  const double dx = aug_dadd(xin, -(double)fx), dy = aug_dadd(yin, -(double)fy);
+  int xs[4];
+#pragma unroll
+  for (int t = 0; t < 4; t++) xs[t] = min(max(fx - 1 + t, 0), W - 1);
+  double r[4];
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const float* p = src + (int64_t)min(max(fy - 1 + t, 0), H - 1) * W;
+    r[t] = aug_cubic_f32(p[xs[0]], p[xs[1]], p[xs[2]], p[xs[3]], dx);
+  }
+  out[base + i] = (float)aug_cubic(r[0], r[1], r[2], r[3], dy);
+}
+
+// second buffer -> maps for the views of the rotation.  Same grid.
+__global__ __launch_bounds__(256) void aug_rotate_maps_copy_back_kernel(float* __restrict__ maps, const mval_aug_op* __restrict__ ops, int n_steps, int step,
+                                                                        int npix, const float* __restrict__ buf) {
+  const int v = blockIdx.z;
+  if (ops[(int64_t)v * n_steps + step].kind != MVAL_AUG_ROTATE) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= npix) return;
+  const int64_t e = ((int64_t)v * gridDim.y + blockIdx.y) * npix + i;
+  maps[e] = buf[e];
+}
+
+// workspace: [V][J][H][W] f32 second buffer
+extern "C" size_t mval_rotate_maps_workspace_bytes(int n_views, int maps_per_view, int h, int w) {
+  if (n_views <= 0 || maps_per_view <= 0 || h <= 0 || w <= 0) return 0;
+  return (size_t)n_views * maps_per_view * h * w * sizeof(float);
+}
+
+extern "C" int mval_rotate_maps(float* maps, const mval_aug_op* ops, const uint32_t* step_kinds, int n_views, int n_steps, int maps_per_view, int h,
+                                int w, void* ws, void* stream) {
+  MVAL_REQUIRE(maps && ops && step_kinds && ws && n_views > 0 && n_steps > 0 && maps_per_view > 0 && h > 0 && w > 0, "mval_rotate_maps: bad arguments");
+  MVAL_REQUIRE(n_views <= 65535 && maps_per_view <= 65535, "mval_rotate_maps: %d views of %d maps, at most 65535 of either per call", n_views,
+               maps_per_view);
+  MVAL_REQUIRE((int64_t)h * w <= (int64_t)1 << 28, "mval_rotate_maps: a %d x %d map is too large (at most 2^28 elements)", h, w);
+  hipStream_t s = mval_stream(stream);
+  const int npix = h * w;
+  float* buf = reinterpret_cast<float*>(ws);
+  const dim3 blk(256), grid((npix + 255) / 256, maps_per_view, n_views);
+  for (int k = 0; k < n_steps; k++) {
+    if (!(step_kinds[k] & AUG_BIT(MVAL_AUG_ROTATE))) continue;
+    hipLaunchKernelGGL(aug_rotate_maps_kernel, grid, blk, 0, s, maps, ops, n_steps, k, h, w, buf);
+    MVAL_CHECK_LAUNCH("mval_rotate_maps/rotate");
+    hipLaunchKernelGGL(aug_rotate_maps_copy_back_kernel, grid, blk, 0, s, maps, ops, n_steps, k, npix, buf);
+    MVAL_CHECK_LAUNCH("mval_rotate_maps/copy_back");
+  }
   return 0;
 }

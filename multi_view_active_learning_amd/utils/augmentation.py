@@ -4,6 +4,10 @@
 reference's order, so a seeded run picks what the reference picks; ``RandAugment.apply`` runs a plan on a batch of uint8
 views (csrc/augment.hip: per step one pass per KIND of op present, whatever the number of views).  The image is in the
 reference's channel order at that point (BGR handed to Pillow as "RGB"): the ops see channel positions only.
+
+The reference's Rotate turns the image and drops the heat-maps it rotated.  That is the default; ``rotate_targets`` offers the two ways of
+turning the targets along: ``RandAugment.rotate_maps`` (Pillow's mode-"F" bicubic rotate of every map, on the device, bit for bit) and
+``rotate_points`` (the key-points through the image's affine map, on the host).
 """
 from __future__ import annotations
 
@@ -50,8 +54,10 @@ def rotate_coefficients(angle, w, h):
     return m
 
 
-def plan_descriptors(plan, h, w):
-    """plan (per view a list of (op name, value)) -> (ctypes array [V][K] of mval_aug_op, per-step bit masks of the kinds present)."""
+def plan_descriptors(plan, h, w, full_turns=False):
+    """plan (per view a list of (op name, value)) -> (ctypes array [V][K] of mval_aug_op, per-step bit masks of the kinds present).
+    full_turns=True also takes a Rotate by a multiple of 360 degrees from outside the reference's range: NONE, as every angle that is
+    0 mod 360 (Pillow answers it with a copy)."""
     v = len(plan)
     k = len(plan[0]) if v else 0
     if v == 0 or any(len(ops) != k for ops in plan):
@@ -64,7 +70,7 @@ def plan_descriptors(plan, h, w):
                 raise ValueError("augment: unknown op %r" % (name,))
             val = float(val)
             lo, hi = _RANGES.get(name, (-math.inf, math.inf))
-            if not lo <= val <= hi:  # (also False for a NaN)
+            if not lo <= val <= hi and not (full_turns and name == "Rotate" and val % 360.0 == 0):  # (the range test is also False for a NaN)
                 raise ValueError("augment: %s value %r outside [%g, %g]" % (name, val, lo, hi))
             d = descs[i * k + s]
             d.kind = KINDS[name]
@@ -80,10 +86,43 @@ def plan_descriptors(plan, h, w):
     return descs, masks
 
 
-class RandAugment:
-    """The reference's RandAugment(num_aug, magnitude, rotation, image_aug, const_magnitude=True) for batches of device views."""
+ROTATE_TARGETS = ("none", "maps", "points")
 
-    def __init__(self, num_aug, magnitude, rotation: bool, image_aug: bool, const_magnitude: bool = True):
+
+def rotate_points(points, plan, w, h):
+    """Carry key-points along with the image through a plan's Rotate steps: points (V, J, 2) float64 (x, y) in pixels of the w x h image
+    the plan was applied to -> the positions the same image content has afterwards.  Per Rotate step, with Pillow's coefficients
+    m = rotate_coefficients(angle, w, h) (output pixel centre -> input position), the inverse of that map:
+        u = x + 0.5 - m2, v = y + 0.5 - m5, det = m0 m4 - m1 m3, x' = (m4 u - m1 v) / det - 0.5, y' = (-m3 u + m0 v) / det - 0.5
+    in float64, steps in plan order; other ops and angles that are 0 mod 360 leave the points alone.  Host arithmetic, returns a new array."""
+    pts = np.array(points, dtype=np.float64)
+    if pts.ndim != 3 or pts.shape[2] != 2:
+        raise ValueError("rotate_points: points must be (V, J, 2), got %r" % (pts.shape,))
+    if len(plan) != pts.shape[0]:
+        raise ValueError("rotate_points: %d op lists for %d views" % (len(plan), pts.shape[0]))
+    for i, ops in enumerate(plan):
+        for name, val in ops:
+            m = rotate_coefficients(float(val), w, h) if name == "Rotate" else None
+            if m is None:
+                continue
+            u, v = pts[i, :, 0] + 0.5 - m[2], pts[i, :, 1] + 0.5 - m[5]
+            det = m[0] * m[4] - m[1] * m[3]
+            pts[i, :, 0], pts[i, :, 1] = (m[4] * u - m[1] * v) / det - 0.5, (-m[3] * u + m[0] * v) / det - 0.5
+    return pts
+
+
+class RandAugment:
+    """The reference's RandAugment(num_aug, magnitude, rotation, image_aug, const_magnitude=True) for batches of device views.
+    rotate_targets (not in the reference) says what Rotate does to the training targets: "none" -- nothing, the reference as published
+    (its Rotate drops the rotated heat-maps); "maps" -- every heat-map of a view is rotated as the image was, by Pillow's
+    Image.rotate(angle, BICUBIC) on the map itself, what the reference's code evidently meant (``rotate_maps``); "points" -- the projected
+    key-points go through the inverse of the image's own affine map before the targets are rendered (``rotate_points``, through
+    ``utils.preprocess.prepare_views``).  ``draw`` and the random streams are the same in every mode."""
+
+    def __init__(self, num_aug, magnitude, rotation: bool, image_aug: bool, const_magnitude: bool = True, *, rotate_targets="none"):
+        if rotate_targets not in ROTATE_TARGETS:
+            raise ValueError("RandAugment: rotate_targets %r: accepted are %s" % (rotate_targets, ", ".join(repr(t) for t in ROTATE_TARGETS)))
+        self.rotate_targets = rotate_targets
         if isinstance(num_aug, bool) or not isinstance(num_aug, (int, np.integer)) or num_aug < 0:
             raise ValueError("RandAugment: num_aug must be a non-negative integer, got %r" % (num_aug,))
         if not 0 <= float(magnitude) <= 30:  # beyond 30 the reference's ops assert on their value
@@ -146,7 +185,50 @@ class RandAugment:
                                            _lib._p(ws), _lib._stream()), "mval_augment_views")
         return out
 
+    @classmethod
+    def from_config(cls, data_cfg):
+        """The augmentation of a DATA config node: the five knobs the reference's ActiveLearningDataset hands its RandAugment
+        (dataset/dataset.py:30-36) and DATA.ROTATE_TARGETS ("none" where the node has no such field, as a reference YAML)."""
+        from ..config import check_rotate_targets
+
+        mode = check_rotate_targets(data_cfg.ROTATE_TARGETS if "ROTATE_TARGETS" in data_cfg else "none")
+        return cls(data_cfg.NUM_AUG, data_cfg.AUG_MAGNITUDE, data_cfg.USE_ROTATION, data_cfg.USE_IMAGE_AUG, data_cfg.USE_CONST_AUG_MAGNITUDE,
+                   rotate_targets=mode)
+
+    @staticmethod
+    def rotate_maps(heatmaps, plan, inplace=False):
+        """The target side of a plan's Rotate steps: heatmaps (V, J, h, w) float32 (HIP tensor) with every map of view v rotated by Pillow's
+        Image.rotate(angle, BICUBIC) on a mode-"F" image of h x w, bit for bit, for each Rotate of plan[v] in order (about the map's own
+        centre, as the corrected reference would).  Other ops, and angles that are 0 mod 360, leave a view's maps alone; a plan without an
+        effective rotation returns the input (inplace) or its clone and launches nothing.  No host synchronisation."""
+        if (not torch.is_tensor(heatmaps)) or (not heatmaps.is_cuda) or heatmaps.dtype != torch.float32 or heatmaps.dim() != 4:
+            raise _lib.MvalError("rotate_maps: heat-maps must be a float32 HIP tensor (V, J, h, w)")
+        v, j, h, w = heatmaps.shape
+        if len(plan) != v:
+            raise ValueError("rotate_maps: %d op lists for %d views" % (len(plan), v))
+        descs, masks = plan_descriptors(plan, h, w, full_turns=True)
+        out = heatmaps.contiguous() if inplace else heatmaps.clone(memory_format=torch.contiguous_format)
+        if j == 0 or not any(m & (1 << AUG_ROTATE) for m in masks):
+            return out
+        from .preprocess import _upload_descs
+
+        lib = _lib.lib()
+        lib.mval_rotate_maps_workspace_bytes.restype = C.c_size_t
+        ws = torch.empty(int(lib.mval_rotate_maps_workspace_bytes(C.c_int(v), C.c_int(j), C.c_int(h), C.c_int(w))), dtype=torch.uint8,
+                         device=out.device)
+        dd = _upload_descs(bytes(descs), out.device)
+        step_kinds = (C.c_uint32 * len(masks))(*masks)
+        _lib._check(lib.mval_rotate_maps(_lib._p(out), _lib._p(dd), step_kinds, C.c_int(v), C.c_int(len(masks)), C.c_int(j), C.c_int(h), C.c_int(w),
+                                         _lib._p(ws), _lib._stream()), "mval_rotate_maps")
+        return out
+
     def __call__(self, images_u8, heatmaps):
-        """(augmented copy of images_u8, heatmaps): the reference's Rotate throws its rotated heat-maps away
-        (dataset/augmentation.py:19-25), so the heat-maps come out as they went in."""
-        return self.apply(images_u8, self.draw(int(images_u8.shape[0]))), heatmaps
+        """(augmented copy of images_u8, heatmaps).  rotate_targets "none": the reference's Rotate throws its rotated heat-maps away
+        (dataset/augmentation.py:19-25), so the heat-maps come out as they went in.  "maps": one plan is drawn and used for both, the
+        heat-maps (V, J, h, w) come back as their rotated copy.  "points" has no points to work on here and raises."""
+        if self.rotate_targets == "points":
+            raise ValueError("RandAugment: rotate_targets='points' works on key-points, not on heat-maps: use utils.preprocess.prepare_views("
+                             "..., augmentation=ra), or draw() a plan and hand it to apply() and rotate_points()")
+        plan = self.draw(int(images_u8.shape[0]))
+        out = self.apply(images_u8, plan)
+        return out, (self.rotate_maps(heatmaps, plan) if self.rotate_targets == "maps" else heatmaps)

@@ -173,12 +173,21 @@ def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, 
     (V,J,h,w) on the device; proj_matrices (V,3,4) float64, 2d_keypoints / 2d_after_crop (V,J,2) float32,
     square_box (V,4) float32 on the host.
     augmentation: None (the "val"/"test" split), or a utils.augmentation.RandAugment (the "train" split, dataset.py:212-213): its ops are drawn
-    per view in order and run on the resized uint8 views before the normalisation; gt_heatmap is unchanged (the reference drops the rotated maps).
+    per view in order (one plan, drawn once, before the image ops) and run on the resized uint8 views before the normalisation.  What its
+    Rotate does to the targets is the augmentation's ``rotate_targets``: "none" -- gt_heatmap / gt_points are unchanged (the reference drops the
+    rotated maps); "maps" -- gt_heatmap is ``rotate_maps`` of the rendered maps under the same plan (the reference with its Rotate keeping the
+    maps; no compact form: ValueError before any draw or device work); "points" -- the projected float64 points go through
+    ``utils.augmentation.rotate_points(pt, plan, in_w, in_h)`` before the division by gt_stride, for gt_points and for the maps rendered from
+    them.  2d_keypoints, 2d_after_crop, proj_matrices, square_box and the validity masks stay as they are in every mode: the reference with
+    its Rotate fixed would not change them either.
     compact: True returns the batch in its small form -- images as the resized (and, with an augmentation, augmented) uint8 views (V,H,W,3),
     what ``resize_views_u8`` gives, and gt_points (V,J,2) float64 on the device, the heat-map-pixel positions ``gt_heatmaps`` is handed
     otherwise, instead of gt_heatmap; the other keys are unchanged.  ``strategy.train_step`` and everything that goes through
     ``_compute_batch_heatmap`` take such a batch: the views are normalised and the maps rendered on the device, to the same bits."""
     v = len(images)
+    rotate_targets = "none" if augmentation is None else getattr(augmentation, "rotate_targets", "none")
+    if rotate_targets == "maps" and compact:
+        raise ValueError("prepare_views: rotate_targets='maps' rotates rendered heat-maps and a compact batch has none: use 'points'")
     kps = kp_3d if isinstance(kp_3d, (list, tuple)) else [kp_3d] * v
     sq, proj, pts, pts_crop = [], [], [], []
     for box, cam, kp in zip(boxes, cameras, kps):
@@ -195,20 +204,28 @@ def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, 
         proj.append(K.dot(np.hstack([R, t])))
         pts.append(_project(K, R, t, cam.get("dist"), skel))
         sq.append(bbox)
-    if compact:
-        out_images = resize_views_u8(images, sq, in_w, in_h)
-        if augmentation is not None:
-            out_images = augmentation.apply(out_images, augmentation.draw(v), inplace=True)
-    elif augmentation is None:
-        out_images = resize_views(images, sq, in_w, in_h)
+    plan = None
+    if augmentation is None:
+        out_images = resize_views_u8(images, sq, in_w, in_h) if compact else resize_views(images, sq, in_w, in_h)
     else:
-        out_images = normalize_views_u8(augmentation.apply(resize_views_u8(images, sq, in_w, in_h), augmentation.draw(v), inplace=True))
+        out_images = resize_views_u8(images, sq, in_w, in_h)
+        plan = augmentation.draw(v)
+        out_images = augmentation.apply(out_images, plan, inplace=True)
+        if not compact:
+            out_images = normalize_views_u8(out_images)
     pt = np.stack(pts)
-    gt_points = torch.from_numpy(pt / gt_stride).to(out_images.device)
+    if rotate_targets == "points":
+        from .augmentation import rotate_points
+
+        gt_points = torch.from_numpy(rotate_points(pt, plan, in_w, in_h) / gt_stride).to(out_images.device)
+    else:
+        gt_points = torch.from_numpy(pt / gt_stride).to(out_images.device)
     if compact:
         target = {"gt_points": gt_points}
     else:
         target = {"gt_heatmap": gt_heatmaps(gt_points, sigma, in_h // gt_stride, in_w // gt_stride)}
+        if rotate_targets == "maps":
+            target["gt_heatmap"] = augmentation.rotate_maps(target["gt_heatmap"], plan, inplace=True)
     return {
         "images": out_images,
         **target,

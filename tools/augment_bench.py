@@ -6,7 +6,13 @@ Device: RandAugment.apply on (views, size, size, 3) uint8, device events around 
 the clock starts); also the same with 1/4 of the views, to show that the launches per batch do not grow with the number of views.
 Host: the same plans view by view on Pillow images -- through the reference's own RandAugment when --reference-augmentation names its
 dataset/augmentation.py (that one also rotates the heat-maps it then throws away: 19 maps of size / 4), else through the Pillow calls its
-ops make.  Prints one JSON line."""
+ops make.  Prints one JSON line.
+
+    python tools/augment_bench.py --targets [--views 128] [--maps 19] [--map-size 64] [--reps 20]
+
+The target side instead (rotate_targets="maps"): RandAugment.rotate_maps in place on (views, maps, map-size, map-size) float32 with every view
+rotating once, beside gt_heatmaps at the same shape as the yardstick for a pass that writes the same bytes; the two alternate, each call
+between device events of its own."""
 import argparse
 import importlib.util
 import json
@@ -101,8 +107,34 @@ def device_time(args, imgs, n_views):
     return e0.elapsed_time(e1) / args.reps, sum(n_launch) / len(n_launch), max(n_launch)
 
 
+def targets_time(args):
+    import torch
+
+    from multi_view_active_learning_amd.utils import preprocess
+
+    v, j, n = args.views, args.maps, args.map_size
+    rng = np.random.default_rng(0)
+    pts = torch.from_numpy(rng.uniform(0, n - 1, (v, j, 2))).cuda()
+    plans = [[[("Rotate", float(a))] for a in rng.uniform(1.0, 30.0, v) * rng.choice([-1.0, 1.0], v)] for _ in range(args.reps + 3)]
+    hm = preprocess.gt_heatmaps(pts, 1.0, n, n)
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in plans]
+    for p, (e0, e1, e2) in zip(plans, ev):
+        e0.record()
+        aug.RandAugment.rotate_maps(hm, p, inplace=True)
+        e1.record()
+        hm = preprocess.gt_heatmaps(pts, 1.0, n, n)
+        e2.record()
+    torch.cuda.synchronize()
+    rot = sorted(e0.elapsed_time(e1) for e0, e1, _ in ev[3:])
+    gt = sorted(e1.elapsed_time(e2) for _, e1, e2 in ev[3:])
+    return rot[len(rot) // 2], gt[len(gt) // 2]
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--targets", action="store_true")
+    ap.add_argument("--maps", type=int, default=19)
+    ap.add_argument("--map-size", type=int, default=64)
     ap.add_argument("--views", type=int, default=128)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--num-aug", type=int, default=2)
@@ -111,6 +143,11 @@ def main():
     ap.add_argument("--reference-augmentation", default=None)
     ap.add_argument("--cpu-only", action="store_true")
     args = ap.parse_args()
+    if args.targets:
+        rot, gt = targets_time(args)
+        print(json.dumps(dict(views=args.views, maps=args.maps, map_size=args.map_size, reps=args.reps, rotate_maps_ms=round(rot, 4),
+                              gt_heatmaps_ms=round(gt, 4), ratio=round(rot / gt, 2))))
+        return
     imgs = images(args.views, args.size)
     res = dict(views=args.views, size=args.size, num_aug=args.num_aug, magnitude=args.magnitude)
     if not args.cpu_only:

@@ -536,6 +536,38 @@ typedef struct mval_mfma_form {
 } mval_mfma_form;
 int mval_conv_mfma_form(int use, const mval_op* op, int n_images, mval_mfma_form* form);
 
+/* The same question for the P2 conv (csrc/conv_p2.hip: MVAL_ALGO_MFMA_P2), the kernel of the default inference and training plans: which
+ * instance of conv_p2_kernel a launch of the library runs on and by which runtime path.  Host arithmetic only (no GPU needed, nothing is
+ * launched, the device is not asked for anything -- so the form carries no workgroup count, which depends on the occupancy).
+ *   ks .. bsum   the kernel's template arguments: kernel size (2 = one 2x2 parity conv), stride, 32-channel chunks per stage, cout waves,
+ *                pixel waves, cout sub-tiles and pixel sub-tiles per wave, the power-of-two tile width, row sharing, the epilogue (0 P2
+ *                planes, 1 up-sampled P2 planes, 2 fp32 NCHW, 3 raw fp32 NHWC), the odd tile width (0 = none), the paired remainder stage of
+ *                48 input channels, BatchNorm + ReLU applied while staging, the BatchNorm backward's sums kept by a data gradient
+ *   th, tile_w   the tile's rows and columns (tile_w = ow if set, else tw)
+ *   flat         a 1x1 conv whose H x W map runs as one row of H * W pixels (tiles_x / tiles_y are those of that row)
+ *   in_sub       a stride-2 1x1 conv run as the stride-1 kernel over every second input pixel
+ *   parities     4 = the form is launched four times, once per output parity (a transposed conv), else 1
+ *   groups       cout groups (the grid's y); tiles_x, tiles_y, tiles_total = tiles_x * tiles_y * n_images: the tiles the workgroups walk
+ *   smem_bytes, threads   dynamic LDS and threads of a workgroup
+ * `use` as for mval_conv_split_form, the op's geometry in FORWARD terms:
+ *   MVAL_SPLIT_USE_OP            mval_op_launch of the op; for MVAL_OP_DECONV (k4 s2 p1) the 2x2 stride-1 parity conv over the input grid that
+ *                                is launched four times (the launches differ in pads and weights only)
+ *   MVAL_SPLIT_USE_TRAIN_FWD     the conv as mval_train_forward runs its fwd_p2 ops (raw fp32 NHWC output, statistics partials requested);
+ *                                res1_off == -2 asks for the form that applies the producer's BatchNorm + ReLU while staging (zin_rel)
+ *   MVAL_SPLIT_USE_DGRAD         the data gradient as mval_train_backward runs it on these kernels (channels swapped, stride 1, fp32 NHWC
+ *                                output; res1_off >= 0: accumulate); only stride-1 convs have one
+ *   MVAL_SPLIT_USE_DGRAD_PARITY  no P2 form: 0
+ * Returns 1 and fills *form, or 0 where the library has no P2 kernel for the launch. */
+typedef struct mval_p2_form {
+  int32_t ks, s, g, wn, wm, nt, ms, tw, rs, epi, ow, k48, inz, bsum;
+  int32_t th, tile_w;
+  int32_t flat, in_sub, parities;
+  int32_t groups;
+  int32_t tiles_x, tiles_y, tiles_total;
+  int32_t smem_bytes, threads;
+} mval_p2_form;
+int mval_conv_p2_form(int use, const mval_op* op, int n_images, mval_p2_form* form);
+
 int mval_op_launch(const mval_op* op, int n_images, float* workspace, const float* params,
                    const float* net_input, float* net_output, void* stream);
 

@@ -555,6 +555,24 @@ def conv_mfma_form(use, op, n_images):
     return form if ok else None
 
 
+class P2Form(C.Structure):
+    """include/mval_hip.h: struct mval_p2_form."""
+
+    _fields_ = [(name, C.c_int32) for name in ("ks", "s", "g", "wn", "wm", "nt", "ms", "tw", "rs", "epi", "ow", "k48", "inz", "bsum", "th", "tile_w",
+                                               "flat", "in_sub", "parities", "groups", "tiles_x", "tiles_y", "tiles_total", "smem_bytes", "threads")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+def conv_p2_form(use, op, n_images):
+    """mval_conv_p2_form: the kernel form (P2Form) of the P2 conv the library's launch of the MvalOp ``op`` under ``use`` (SPLIT_USE_OP /
+    _TRAIN_FWD / _DGRAD) ends on, or None where it has no P2 kernel for it."""
+    form = P2Form()
+    ok = lib().mval_conv_p2_form(C.c_int(use), C.byref(op), C.c_int(n_images), C.byref(form))
+    return form if ok else None
+
+
 # --------------------------------------------------------------------------
 # core-set (k-center greedy)
 # --------------------------------------------------------------------------

@@ -303,6 +303,16 @@ struct P2Args {
 };
 
 int mval_launch_conv_p2(const P2Args& a, hipStream_t s);  // conv_p2.hip; 1 = unsupported (dry != 0: no launch)
+int mval_conv_p2_form_of(const P2Args& a, mval_p2_form* form);  // 1 + the form the launcher would run, 0 if unsupported; no launch, no HIP call
+// the geometry of a conv of the training forward on these kernels and of its data gradient (net_train.hip; net.hip mval_conv_p2_form)
+static inline void p2_train_fwd_geometry(P2Args& p, const mval_op& op, int n_images) {
+  p.N = n_images; p.Hin = op.hin; p.Win = op.win; p.Cin = op.cin; p.Hout = op.hout; p.Wout = op.wout; p.Cout = op.cout;
+  p.k = op.k; p.stride = op.stride;
+}
+static inline void p2_dgrad_geometry(P2Args& p, const mval_op& op, int n_images) {
+  p.N = n_images; p.Hin = op.hout; p.Win = op.wout; p.Cin = op.cout; p.Hout = op.hin; p.Wout = op.win; p.Cout = op.cin;
+  p.k = op.k; p.stride = 1;
+}
 int mval_launch_nhwc_to_p2(const float* x, const unsigned* rows_in, _Float16* planes, unsigned* rows, int n_images, int HW, int C,
                             hipStream_t s);
 int mval_conv_p2_supported(int k, int stride, int cin, int cout, int hin, int win, int up, int out_nchw, int n);

@@ -968,6 +968,7 @@ __global__ __launch_bounds__(64 * WN * WM) __attribute__((amdgpu_waves_per_eu(2,
 }
 
 static thread_local int g_p2_dry = 0;
+static thread_local mval_p2_form* g_p2_form = nullptr;  // dry runs leave the form they end on here (mval_conv_p2_form)
 
 int mval_p2_walk_grid(int tiles_total, int resident, int groups) {  // (conv_p2.h)
   int wgs = (resident / groups) & ~7;
@@ -998,7 +999,18 @@ static int launch_p2e(P2Args a, hipStream_t s) {
     a.slot_total = 4 * a.amax_tiles * (int)groups;
     a.slot_base = (a.oy * 2 + a.ox) * a.amax_tiles * (int)groups;
   }
-  if (g_p2_dry) return 0;
+  if (g_p2_dry) {
+    if (mval_p2_form* f = g_p2_form) {  // mval_conv_p2_form: what would run (`flat` is the dispatch's to set)
+      f->ks = KS; f->s = S; f->g = G; f->wn = WN; f->wm = WM; f->nt = NT; f->ms = MS; f->tw = TW; f->rs = RS; f->epi = EPI; f->ow = OW;
+      f->k48 = K48; f->inz = INZ; f->bsum = BSUM;
+      f->th = TH; f->tile_w = TWE;
+      f->in_sub = a.in_sub; f->parities = a.os ? 4 : 1;
+      f->groups = (int)groups;
+      f->tiles_x = a.walk.tiles_x; f->tiles_y = a.walk.tiles_y; f->tiles_total = a.walk.tiles_total;
+      f->smem_bytes = (int)smem; f->threads = NTH;
+    }
+    return 0;
+  }
 #ifdef P2_STAMP
   a.dbg = g_p2_dbg;
 #endif
@@ -1212,6 +1224,7 @@ int mval_launch_conv_p2(const P2Args& a0, hipStream_t s) {
     if (!a.up && !a.in_sub && !oms && (a.Wout & 63) != 0 && a.Hout > 1 && a.Hout * a.Wout >= 64 && a.Hin == a.Hout && a.Win == a.Wout) {
       a.Wout = a.Win = a.Hout * a.Wout;
       a.Hout = a.Hin = 1;
+      if (g_p2_dry && g_p2_form) g_p2_form->flat = 1;
     }
     const int g = og ? og : 2;
     const int ms = oms ? oms : 4;
@@ -1239,6 +1252,16 @@ int mval_launch_conv_p2(const P2Args& a0, hipStream_t s) {
 #undef P2_1X1
   }
   return 1;
+}
+
+int mval_conv_p2_form_of(const P2Args& a, mval_p2_form* form) {
+  *form = {};
+  g_p2_form = form;
+  g_p2_dry = 1;
+  const int rc = mval_launch_conv_p2(a, nullptr);
+  g_p2_dry = 0;
+  g_p2_form = nullptr;
+  return rc == 0;
 }
 
 int mval_conv_p2_parity_supported(int cin, int cout, int h, int w, int n, int nhwc_out) {

@@ -381,6 +381,53 @@ static int op_keeps_argmax_keys(const mval_op* op) {
   return op->algo == MVAL_ALGO_MFMA;  // (conv_mfma.hip's 1x1 kernels: the heat-map layer of the h2 / bf3 / fp32 plans)
 }
 
+// The P2Args of an MVAL_ALGO_MFMA_P2 conv / transposed conv as mval_op_launch runs it (also what mval_conv_p2_form asks the dispatch about)
+static int p2_op_args(const mval_op* o, int n_images, float* workspace, const float* params, float* net_output, unsigned long long* argmax_keys,
+                      P2Args& p) {
+  const float* w = o->w_off >= 0 ? params + o->w_off : nullptr;
+  MVAL_REQUIRE((o->kind == MVAL_OP_CONV || o->kind == MVAL_OP_DECONV) && w && o->scale_off >= 0 && o->shift_off >= 0 && o->in_amax_off > 0 && o->in_off >= 0 &&
+                   (o->out_nchw || (o->out_amax_off > 0 && o->bound_off >= 0)) &&
+                   (o->res1_off < 0 || o->res1_amax_off > 0) && (o->res2_off < 0 || o->res2_amax_off > 0),
+               "mval_op_launch: malformed MVAL_ALGO_MFMA_P2 op");
+  p = {};
+  p.in = reinterpret_cast<const _Float16*>(workspace + o->in_off);
+  p.w = w;
+  p.w_unscale = w + mval_packed_weight_floats(MVAL_PACK_MFMA16_H2, o->cout, o->cin, o->k) - 4;  // (a transposed conv: k = 4, all 16 taps)
+  p.scale = params + o->scale_off; p.shift = params + o->shift_off;
+  p.bound = o->bound_off >= 0 ? params + o->bound_off : nullptr;
+  p.res1 = o->res1_off >= 0 ? reinterpret_cast<const _Float16*>(workspace + o->res1_off) : nullptr;
+  p.res2 = o->res2_off >= 0 ? reinterpret_cast<const _Float16*>(workspace + o->res2_off) : nullptr;
+  p.in_row = reinterpret_cast<const unsigned*>(workspace + o->in_amax_off);
+  p.res1_row = p.res1 ? reinterpret_cast<const unsigned*>(workspace + o->res1_amax_off) : nullptr;
+  p.res2_row = p.res2 ? reinterpret_cast<const unsigned*>(workspace + o->res2_amax_off) : nullptr;
+  if (o->out_nchw) {
+    p.out_f32 = o->out_off >= 0 ? workspace + o->out_off : net_output;
+    p.argmax_keys = argmax_keys;
+  } else {
+    p.out = reinterpret_cast<_Float16*>(workspace + o->out_off);
+    p.out_row = reinterpret_cast<unsigned*>(workspace + o->out_amax_off);
+  }
+  p.N = n_images; p.Hin = o->hin; p.Win = o->win; p.Cin = o->cin;
+  p.Hout = o->hout; p.Wout = o->wout; p.Cout = o->cout;
+  p.k = o->k; p.stride = o->stride; p.up = o->up; p.relu = o->relu;
+  return 0;
+}
+
+// Parity pp of a transposed conv (pose_resnet.py:107-137): output pixel (2a + py, 2b + px) sees 2 x 2 taps of the 4 x 4 kernel (pack mode 3: parity
+// pp's taps are the pp-th quarter of the packed buffer), input rows a - 1 + py .. a + py: four stride-1 convs over the input grid, each written to
+// its parity of the output planes; the launches share the output's rows (one scale from the one bound, a quarter of the slots each)
+static P2Args p2_parity_args(const P2Args& p2, const mval_op* op, int pp) {
+  const size_t quarter = (mval_packed_weight_floats(MVAL_PACK_MFMA16_H2, op->cout, op->cin, 4) & ~(size_t)7) / 4;
+  P2Args q = p2;
+  q.k = 2; q.stride = 1;
+  q.Hout = op->hin; q.Wout = op->win;
+  q.pad_y = 1 - (pp >> 1); q.pad_x = 1 - (pp & 1);
+  q.os = 1; q.oy = pp >> 1; q.ox = pp & 1;
+  q.keep_rows = pp != 0;
+  q.w = p2.w + pp * quarter;
+  return q;
+}
+
 static int op_launch(const mval_op* op, int n_images, float* workspace, const float* params, const float* net_input,
                      float* net_output, unsigned long long* argmax_keys, void* stream);
 
@@ -499,51 +546,12 @@ static int op_launch(const mval_op* op, int n_images, float* workspace, const fl
     return 0;
   }
   if (op->algo == MVAL_ALGO_MFMA_P2) {
-    auto p2_args = [&](const mval_op* o, P2Args& p) -> int {
-      const float* w = o->w_off >= 0 ? params + o->w_off : nullptr;
-      MVAL_REQUIRE((o->kind == MVAL_OP_CONV || o->kind == MVAL_OP_DECONV) && w && o->scale_off >= 0 && o->shift_off >= 0 && o->in_amax_off > 0 && o->in_off >= 0 &&
-                       (o->out_nchw || (o->out_amax_off > 0 && o->bound_off >= 0)) &&
-                       (o->res1_off < 0 || o->res1_amax_off > 0) && (o->res2_off < 0 || o->res2_amax_off > 0),
-                   "mval_op_launch: malformed MVAL_ALGO_MFMA_P2 op");
-      p = {};
-      p.in = reinterpret_cast<const _Float16*>(workspace + o->in_off);
-      p.w = w;
-      p.w_unscale = w + mval_packed_weight_floats(MVAL_PACK_MFMA16_H2, o->cout, o->cin, o->k) - 4;  // (a transposed conv: k = 4, all 16 taps)
-      p.scale = params + o->scale_off; p.shift = params + o->shift_off;
-      p.bound = o->bound_off >= 0 ? params + o->bound_off : nullptr;
-      p.res1 = o->res1_off >= 0 ? reinterpret_cast<const _Float16*>(workspace + o->res1_off) : nullptr;
-      p.res2 = o->res2_off >= 0 ? reinterpret_cast<const _Float16*>(workspace + o->res2_off) : nullptr;
-      p.in_row = reinterpret_cast<const unsigned*>(workspace + o->in_amax_off);
-      p.res1_row = p.res1 ? reinterpret_cast<const unsigned*>(workspace + o->res1_amax_off) : nullptr;
-      p.res2_row = p.res2 ? reinterpret_cast<const unsigned*>(workspace + o->res2_amax_off) : nullptr;
-      if (o->out_nchw) {
-        p.out_f32 = o->out_off >= 0 ? workspace + o->out_off : net_output;
-        p.argmax_keys = argmax_keys;
-      } else {
-        p.out = reinterpret_cast<_Float16*>(workspace + o->out_off);
-        p.out_row = reinterpret_cast<unsigned*>(workspace + o->out_amax_off);
-      }
-      p.N = n_images; p.Hin = o->hin; p.Win = o->win; p.Cin = o->cin;
-      p.Hout = o->hout; p.Wout = o->wout; p.Cout = o->cout;
-      p.k = o->k; p.stride = o->stride; p.up = o->up; p.relu = o->relu;
-      return 0;
-    };
     P2Args p2;
-    int rc = p2_args(op, p2);
+    int rc = p2_op_args(op, n_images, workspace, params, net_output, argmax_keys, p2);
     if (rc) return rc;
     if (op->kind == MVAL_OP_DECONV) {
-      // pose_resnet.py:107-137: output pixel (2a + py, 2b + px) sees 2 x 2 taps of the 4 x 4 kernel (pack mode 3: parity pp's taps are the
-      // pp-th quarter of the packed buffer), input rows a - 1 + py .. a + py: four stride-1 convs over the input grid, each written to its
-      // parity of the output planes; the launches share the output's rows (one scale from the one bound, a quarter of the slots each)
-      const size_t quarter = (mval_packed_weight_floats(MVAL_PACK_MFMA16_H2, op->cout, op->cin, 4) & ~(size_t)7) / 4;
       for (int pp = 0; pp < 4; pp++) {
-        P2Args q = p2;
-        q.k = 2; q.stride = 1;
-        q.Hout = op->hin; q.Wout = op->win;
-        q.pad_y = 1 - (pp >> 1); q.pad_x = 1 - (pp & 1);
-        q.os = 1; q.oy = pp >> 1; q.ox = pp & 1;
-        q.keep_rows = pp != 0;
-        q.w = p2.w + pp * quarter;
+        const P2Args q = p2_parity_args(p2, op, pp);
         rc = mval_launch_conv_p2(q, s);
         MVAL_REQUIRE(rc == 0, "mval_op_launch: no P2 kernel for a parity of the transposed conv cin%d cout%d %dx%d", op->cin, op->cout, op->hin, op->win);
       }
@@ -594,6 +602,36 @@ static int op_launch(const mval_op* op, int n_images, float* workspace, const fl
     mval_launch_amax(a.out, (int64_t)(op->hout << op->up) * (op->wout << op->up) * op->cout, n_images, a.out_amax, s);
   MVAL_CHECK_LAUNCH("mval_op_launch");
   return 0;
+}
+
+// Which instance of the P2 conv a launch of this library runs on, and by which path (include/mval_hip.h): the P2Args are built by the
+// functions the entries themselves use, then the launcher's dry run reports where its dispatch ends.  No HIP call.
+extern "C" int mval_conv_p2_form(int use, const mval_op* op, int n_images, mval_p2_form* form) {
+  if (!op || !form || n_images <= 0 || (op->kind != MVAL_OP_CONV && op->kind != MVAL_OP_DECONV)) return 0;
+  static float some[4];  // (buffers are only asked for, never read or written)
+  static double some_part = 0.0;
+  *form = {};
+  P2Args p = {};
+  if (use == MVAL_SPLIT_USE_OP) {
+    if (!mval_op_algo_supported(op, n_images, MVAL_ALGO_MFMA_P2)) return 0;
+    if (p2_op_args(op, n_images, some, some, some, nullptr, p)) return 0;
+    if (op->kind == MVAL_OP_DECONV) p = p2_parity_args(p, op, 0);
+  } else if (use == MVAL_SPLIT_USE_TRAIN_FWD) {
+    if (op->kind != MVAL_OP_CONV || op->pad != op->k / 2) return 0;  // (transposed convs run on the exact-fp32 kernels in training)
+    p2_train_fwd_geometry(p, *op, n_images);
+    p.out_nhwc = some;
+    p.bn_part = &some_part;  // (mval_train_forward asks for the partials of every conv with a BatchNorm)
+    p.bn_part_cap = INT64_MAX;
+    if (op->res1_off == -2) p.in_z = p.zin_mean = p.zin_invstd = p.zin_gamma = p.zin_beta = some;
+  } else if (use == MVAL_SPLIT_USE_DGRAD) {
+    if (op->kind != MVAL_OP_CONV || op->stride != 1 || op->pad != op->k / 2) return 0;
+    p2_dgrad_geometry(p, *op, n_images);
+    p.out_nhwc = some;
+    p.acc_nhwc = op->res1_off >= 0;
+  } else {
+    return 0;
+  }
+  return mval_conv_p2_form_of(p, form);
 }
 
 #define MVAL_MAX_DEVICES 16

@@ -370,8 +370,7 @@ static int train_forward(const mval_train_op* ops, int n_ops, int n_images, floa
         p.scale = params + ones_off;
         p.shift = params + zeros_off;
         p.out_nhwc = arena + t.z_off;
-        p.N = n_images; p.Hin = op.hin; p.Win = op.win; p.Cin = op.cin; p.Hout = op.hout; p.Wout = op.wout; p.Cout = op.cout;
-        p.k = op.k; p.stride = op.stride;
+        p2_train_fwd_geometry(p, op, n_images);
         if (epi_stats) {
           p.bn_part = ws;
           p.bn_part_cap = ws_doubles;
@@ -606,8 +605,7 @@ static int train_backward(const mval_train_op* ops, int n_ops, int n_images, flo
         p.shift = params + zeros_off;
         p.out_nhwc = garena + t.gin_off;
         p.acc_nhwc = !(t.first_touch & 1);
-        p.N = n_images; p.Hin = op.hout; p.Win = op.wout; p.Cin = op.cout; p.Hout = op.hin; p.Wout = op.win; p.Cout = op.cin;
-        p.k = op.k; p.stride = 1;
+        p2_dgrad_geometry(p, op, n_images);
         int slots = 0;
         if ((t.p2_flags & MVAL_TRAIN_BSUM) && i > 0) {
           // this launch is the LAST writer of the producer's output gradient (the producer is the op in front of this one, so every other

@@ -463,6 +463,25 @@ def test_ctypes_mirror_constants_match_the_header():
         assert enum(name) == val, name
 
 
+def test_form_struct_mirrors_match_the_header():
+    """The three form queries (mval_conv_split_form, _mfma_form, _p2_form): every ctypes mirror has the fields of its struct in the header, in
+    order, all int32, and the entries are exported with the uses the mirror names."""
+    import ctypes as C
+
+    from multi_view_active_learning_amd import _lib
+
+    text = open(os.path.join(REPO, "include", "mval_hip.h")).read()
+    lib = _lib.lib()
+    for struct, mirror in (("mval_split_form", _lib.SplitForm), ("mval_mfma_form", _lib.MfmaForm), ("mval_p2_form", _lib.P2Form)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, flags=re.S).group(1)
+        fields = [name for line in body.split(";") if line.strip() for name in re.sub(r"^\s*int32_t", "", line).replace(" ", "").split(",")]
+        assert fields == [name for name, _ in mirror._fields_], struct
+        assert all(t is C.c_int32 for _, t in mirror._fields_) and C.sizeof(mirror) == 4 * len(fields), struct
+        assert hasattr(lib, struct.replace("mval_", "mval_conv_")), struct
+    uses = [int(re.search(r"\bMVAL_SPLIT_USE_%s\s*=\s*(\d+)" % n, text).group(1)) for n in ("OP", "TRAIN_FWD", "DGRAD", "DGRAD_PARITY")]
+    assert uses == [_lib.SPLIT_USE_OP, _lib.SPLIT_USE_TRAIN_FWD, _lib.SPLIT_USE_DGRAD, _lib.SPLIT_USE_DGRAD_PARITY]
+
+
 def test_training_lane_flags_keep_every_gradient_slot_on_one_ordered_chain():
     """engine_train.lane_flags (host logic behind mval_train_*_lanes, hrnet.py:199-287): on HRNet-W32 / -W48 graphs, in every mode --
     an op runs its backward on a side lane UNORDERED only in phases where each gradient slot it writes has all its writers on that lane;

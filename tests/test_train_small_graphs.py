@@ -64,6 +64,16 @@ CASES = {
     # the pre-summed apply pass ACCUMULATES into the residual's gradient slot (b0.conv2 is not its first writer), forms A and C
     "shared_c32_16x16": dict(graph="shared", args=(32,), n=2, hw=(16, 16), seed=1, inz=True, bsum=True),
     "shared_c64_8x8": dict(graph="shared", args=(64,), n=2, hw=(8, 8), seed=1, inz=True, bsum=True),
+    # one conv behind the head (tiny_graphs.single) at the P2 conv's forms that no graph above reaches (tests/test_gpu_p2_forms.py holds the census):
+    # a 1x1 conv whose 8 x 10 map runs as one flattened row of 16-wide tiles, and its data gradient; the stride-2 1x1 over every second pixel on
+    # 16-wide tiles; 3x3 on the whole 12 x 9 map per tile and on 8 x 6-pixel odd tiles (forward and data gradient), on 7 x 9-pixel odd tiles;
+    # 3x3 stride 2 at 32 couts
+    "single_k1_64_64_8x10": dict(graph="single", args=(64, 64, 1, 1), n=2, hw=(8, 10), seed=1, inz=False, bsum=False),
+    "single_k1s2_64_64_16x32": dict(graph="single", args=(64, 64, 1, 2), n=2, hw=(16, 32), seed=1, inz=False, bsum=False),
+    "single_k3_64_64_12x9": dict(graph="single", args=(64, 64, 3, 1), n=2, hw=(12, 9), seed=1, inz=False, bsum=False),
+    "single_k3_64_64_8x6_n3": dict(graph="single", args=(64, 64, 3, 1), n=3, hw=(8, 6), seed=1, inz=False, bsum=False),
+    "single_k3_64_64_7x9": dict(graph="single", args=(64, 64, 3, 1), n=2, hw=(7, 9), seed=1, inz=False, bsum=False),
+    "single_k3s2_32_32_16x16": dict(graph="single", args=(32, 32, 3, 2), n=2, hw=(16, 16), seed=1, inz=False, bsum=False),
 }
 PLANS = {"default": {}, "h2": {"MVAL_TRAIN_P2": "0"}, "bf3": {"MVAL_CONV": "bf3"}, "fp32": {"MVAL_CONV": "fp32"}}
 MARGIN = 64.0

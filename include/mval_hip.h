@@ -108,6 +108,34 @@ int mval_triangulate_ransac_pairs(const void* kp2d, int kp_is_f32, const double*
 int mval_reprojection_xe(const double* kp3d, const double* proj, const float* heatmaps, double* out, double* ws,
                          int B, int V, int J, int hh, int wh, double sigma, void* stream);
 
+/* Frames with missing views.  view_valid [B,V] u8, nonzero = the view is present in that frame (never NULL: a NULL mask is
+ * an error and nothing is launched -- call the entry without `_views`).  For every frame the result is what the entry without
+ * `_views` gives on that frame's present views alone, bit for bit: nothing of an absent view enters arithmetic, its
+ * key-point row, projection matrix and heat-maps are not read and may hold anything, NaN included.  All frames of a batch
+ * go through one launch, however their present sets differ.
+ *
+ * mval_triangulate_ransac_views (2 <= V <= 11): lane p keeps its lexicographic pair and sits out when one of its views is
+ *   absent; the vote runs over present views.
+ * mval_triangulate_ransac_pairs_views (2 <= V <= 32): the table names ORIGINAL view indices; an entry naming an absent
+ *   view, or a view >= V (the host pads the shorter rows of a per-problem table with 255), takes no part; with no usable
+ *   pair all PRESENT views are inliers.
+ * Both, per frame with n present views: n < 2 and at least one valid joint -> inlier_count -2, metric NaN, kp3d /
+ *   joint_err / joint_inliers 0 (the reference asserts len(points) >= 2 inside the first valid joint; the host wrapper
+ *   raises AssertionError); no valid joint -> inlier_count -1 and metric NaN whatever n is.  joint_inliers counts present
+ *   views only.  Every other argument and output as the entry without `_views`. */
+int mval_triangulate_ransac_views(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                  const uint8_t* view_valid, double* kp3d, double* joint_err, int32_t* joint_inliers,
+                                  double* metric, int32_t* inlier_count, int B, int V, int J, double eps, void* stream);
+int mval_triangulate_ransac_pairs_views(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                        const uint8_t* view_valid, const uint8_t* pairs, int P, int pairs_shared,
+                                        double* kp3d, double* joint_err, int32_t* joint_inliers, double* metric,
+                                        int32_t* inlier_count, int B, int V, int J, double eps, void* stream);
+
+/* mval_reprojection_xe over the present views of each frame: the maps of an absent view are not read, their ws slots are
+ * not written, and the serial (view, joint) sum skips them.  A frame without a present view gives 0. */
+int mval_reprojection_xe_views(const double* kp3d, const double* proj, const float* heatmaps, const uint8_t* view_valid,
+                               double* out, double* ws, int B, int V, int J, int hh, int wh, double sigma, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Uncertainty scorers (strategy.py:1149-1215)
  * ---------------------------------------------------------------------------------- */
@@ -150,6 +178,12 @@ int mval_score_decode_maps_all(const float* heatmaps, const uint8_t* valid, floa
  * SURVEY A.8).  per_map [B,V,J] f32 ; valid [B,J] u8 or NULL ; out [B] f64. */
 int mval_score_reduce(const float* per_map, const uint8_t* valid, double* out, int B, int V, int J,
                       int mode, void* stream);
+
+/* mval_score_reduce over the present views of each frame (view_valid [B,V] u8, never NULL): the statistics of an absent
+ * view's maps are not read; n = valid joints x present views; same loop order (views outer, joints inner) and precision
+ * per mode, so a frame gives what mval_score_reduce gives on its present views alone.  n = 0 -> NaN. */
+int mval_score_reduce_views(const float* per_map, const uint8_t* valid, const uint8_t* view_valid, double* out, int B,
+                            int V, int J, int mode, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Loss / metric

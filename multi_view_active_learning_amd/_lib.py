@@ -247,6 +247,67 @@ def triangulate_ransac(kp2d, proj, valid, b, v, j, eps):
     return _triangulate("mval_triangulate_ransac", kp2d, proj, valid, b, v, j, eps)
 
 
+# Frames with missing views (include/mval_hip.h, the `_views` entries): view_valid (B, V) uint8 on the device, nonzero = present.
+# These four entries carry ctypes argtypes, set on first use, where the older wrappers convert every argument by hand
+# (C.c_int(b), ...): the masked entries differ from their unmasked twins by ONE pointer in the middle of a long list, and with
+# argtypes a call that leaves it out fails in ctypes with an argument-count error instead of shifting every later argument.
+# The older entries are left as they are.
+_VOIDP, _INT, _DOUBLE = C.c_void_p, C.c_int, C.c_double
+_VIEWS_ARGTYPES = {
+    "mval_triangulate_ransac_views": [_VOIDP, _INT] + [_VOIDP] * 8 + [_INT] * 3 + [_DOUBLE, _VOIDP],
+    "mval_triangulate_ransac_pairs_views": [_VOIDP, _INT] + [_VOIDP] * 4 + [_INT] * 2 + [_VOIDP] * 5 + [_INT] * 3 + [_DOUBLE, _VOIDP],
+    "mval_reprojection_xe_views": [_VOIDP] * 6 + [_INT] * 5 + [_DOUBLE, _VOIDP],
+    "mval_score_reduce_views": [_VOIDP] * 4 + [_INT] * 4 + [_VOIDP],
+}
+
+
+def _views_entry(name):
+    f = getattr(lib(), name)
+    if f.argtypes is None:
+        f.argtypes, f.restype = _VIEWS_ARGTYPES[name], C.c_int
+    return f
+
+
+def _req_view_valid(view_valid, b, v):
+    _req(view_valid, torch.uint8, "view_valid")
+    if tuple(view_valid.shape) != (b, v):
+        raise MvalError(f"view_valid: expected ({b}, {v}), got {tuple(view_valid.shape)}")
+    return view_valid
+
+
+def triangulate_ransac_views(kp2d, proj, valid, view_valid, b, v, j, eps):
+    """mval_triangulate_ransac_views: ``triangulate_ransac`` over the present views of each frame (V <= 11)."""
+    _views_entry("mval_triangulate_ransac_views")
+    return _triangulate("mval_triangulate_ransac_views", kp2d, proj, valid, b, v, j, eps,
+                        table=(_p(_req_view_valid(view_valid, b, v)),))
+
+
+def triangulate_ransac_pairs_views(kp2d, proj, valid, view_valid, pairs, b, v, j, eps):
+    """mval_triangulate_ransac_pairs_views: ``triangulate_ransac_pairs`` over the present views of each frame; the table
+    names original view indices, entries >= V (255: padding) or naming an absent view take no part."""
+    _req(pairs, torch.uint8, "pairs")
+    shared = pairs.dim() == 3
+    if pairs.shape[-1] != 2 or (tuple(pairs.shape[:-2]) != (1,) if shared else tuple(pairs.shape[:-2]) != (b, j)):
+        raise MvalError(f"pairs: expected (1, P, 2) or ({b}, {j}, P, 2), got {tuple(pairs.shape)}")
+    _views_entry("mval_triangulate_ransac_pairs_views")
+    return _triangulate("mval_triangulate_ransac_pairs_views", kp2d, proj, valid, b, v, j, eps,
+                        table=(_p(_req_view_valid(view_valid, b, v)), _p(pairs), C.c_int(pairs.shape[-2]), C.c_int(int(shared))))
+
+
+def reprojection_xe_views(kp3d, proj, hm, view_valid, b, v, j, hh, wh, sigma):
+    out = torch.empty((b,), dtype=torch.float64, device=hm.device)
+    ws = torch.empty((b * v * j,), dtype=torch.float64, device=hm.device)
+    _check(
+        _views_entry("mval_reprojection_xe_views")(
+            _p(_req(kp3d, torch.float64, "keypoints_3d")), _p(_req(proj, torch.float64, "proj")),
+            _p(_req(hm, torch.float32, "heatmaps")), _p(_req_view_valid(view_valid, b, v)), _p(out), _p(ws),
+            b, v, j, hh, wh, sigma, _stream(),
+        ),
+        "mval_reprojection_xe_views",
+    )
+    return out
+
+
 def reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, sigma):
     out = torch.empty((b,), dtype=torch.float64, device=hm.device)
     ws = torch.empty((b * v * j,), dtype=torch.float64, device=hm.device)
@@ -323,6 +384,19 @@ def score_reduce(per_map, valid, b, v, j, mode):
             C.c_int(b), C.c_int(v), C.c_int(j), C.c_int(mode), _stream(),
         ),
         "mval_score_reduce",
+    )
+    return out
+
+
+def score_reduce_views(per_map, valid, view_valid, b, v, j, mode):
+    """mval_score_reduce_views: ``score_reduce`` over the present views of each frame."""
+    out = torch.empty((b,), dtype=torch.float64, device=per_map.device)
+    _check(
+        _views_entry("mval_score_reduce_views")(
+            _p(_req(per_map, torch.float32, "per_map")), _p(valid), _p(_req_view_valid(view_valid, b, v)), _p(out),
+            b, v, j, mode, _stream(),
+        ),
+        "mval_score_reduce_views",
     )
     return out
 

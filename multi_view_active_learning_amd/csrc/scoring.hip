@@ -595,42 +595,59 @@ extern "C" int mval_score_decode_maps_all(const float* heatmaps, const uint8_t* 
 // ---- AVG / STD over the valid maps of a frame, in python / numpy order -----------------
 #define SR_MAX 1024
 
+// MASKED: the maps of the views whose view_valid is 0 are left out (and not read): n = valid joints x present views, the same
+// loops over what is left -- what the unmasked kernel computes on the frame's present views alone.
+template <bool MASKED>
 __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uint8_t* __restrict__ valid,
-                                    double* __restrict__ out, int B, int V, int J, int mode) {
+                                    const uint8_t* __restrict__ view_valid, double* __restrict__ out, int B, int V, int J,
+                                    int mode) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const float* pm = per_map + (int64_t)b * V * J;
-  int n = 0;
+  const uint8_t* vv = MASKED ? view_valid + (int64_t)b * V : nullptr;
+  int n = 0, nv = V;
   for (int j = 0; j < J; j++) n += (!valid || valid[(int64_t)b * J + j]) ? 1 : 0;
-  n *= V;
+  if (MASKED) {
+    nv = 0;
+    for (int v = 0; v < V; v++) nv += vv[v] ? 1 : 0;
+  }
+  n *= nv;
   if (n == 0) { out[b] = NAN; return; }  // reference: ZeroDivisionError / nan
   if (mode == MVAL_REDUCE_AVG_F64) {  // sum(python floats) / len
     double s = 0.0;
-    for (int v = 0; v < V; v++)
+    for (int v = 0; v < V; v++) {
+      if (MASKED && !vv[v]) continue;
       for (int j = 0; j < J; j++)
         if (!valid || valid[(int64_t)b * J + j]) s += (double)pm[v * J + j];
+    }
     out[b] = s / (double)n;
   } else if (mode == MVAL_REDUCE_AVG_F32) {  // sum(np.float32) / len  (float32 throughout)
     float s = 0.f;
-    for (int v = 0; v < V; v++)
+    for (int v = 0; v < V; v++) {
+      if (MASKED && !vv[v]) continue;
       for (int j = 0; j < J; j++)
         if (!valid || valid[(int64_t)b * J + j]) s += pm[v * J + j];
+    }
     out[b] = (double)(s / (float)n);
   } else if (mode == MVAL_REDUCE_STD_F64) {  // np.std(float64 array)
     double buf[SR_MAX];
     int k = 0;
-    for (int v = 0; v < V; v++)
+    for (int v = 0; v < V; v++) {
+      if (MASKED && !vv[v]) continue;
       for (int j = 0; j < J; j++)
         if (!valid || valid[(int64_t)b * J + j]) buf[k++] = (double)pm[v * J + j];
+    }
     double mean = np_pairwise_sum<double>(buf, n) / (double)n;
     for (int i = 0; i < n; i++) { double d = buf[i] - mean; buf[i] = d * d; }
     out[b] = sqrt(np_pairwise_sum<double>(buf, n) / (double)n);
   } else {  // np.std(float32 array): float32 intermediates
     float buf[SR_MAX];
     int k = 0;
-    for (int v = 0; v < V; v++)
+    for (int v = 0; v < V; v++) {
+      if (MASKED && !vv[v]) continue;
       for (int j = 0; j < J; j++)
         if (!valid || valid[(int64_t)b * J + j]) buf[k++] = pm[v * J + j];
+    }
     float mean = (float)((double)np_pairwise_sum<float>(buf, n) / (double)n);
     for (int i = 0; i < n; i++) { float d = buf[i] - mean; buf[i] = d * d; }
     out[b] = (double)sqrtf(np_pairwise_sum<float>(buf, n) / (float)n);
@@ -642,8 +659,21 @@ extern "C" int mval_score_reduce(const float* per_map, const uint8_t* valid, dou
   MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && V * J <= SR_MAX, "mval_score_reduce: bad dims (V*J must be <= %d)", SR_MAX);
   MVAL_REQUIRE(mode >= 0 && mode <= 3, "mval_score_reduce: unknown mode %d", mode);
   if (B == 0) return 0;
-  hipLaunchKernelGGL(score_reduce_kernel, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map, valid, out, B,
-                     V, J, mode);
+  const uint8_t* const no_mask = nullptr;
+  hipLaunchKernelGGL(score_reduce_kernel<false>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map, valid,
+                     no_mask, out, B, V, J, mode);
   MVAL_CHECK_LAUNCH("mval_score_reduce");
+  return 0;
+}
+
+extern "C" int mval_score_reduce_views(const float* per_map, const uint8_t* valid, const uint8_t* view_valid, double* out,
+                                       int B, int V, int J, int mode, void* stream) {
+  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && V * J <= SR_MAX, "mval_score_reduce_views: bad dims (V*J must be <= %d)", SR_MAX);
+  MVAL_REQUIRE(mode >= 0 && mode <= 3, "mval_score_reduce_views: unknown mode %d", mode);
+  MVAL_REQUIRE(view_valid, "mval_score_reduce_views: view_valid is NULL (use mval_score_reduce)");
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(score_reduce_kernel<true>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map, valid,
+                     view_valid, out, B, V, J, mode);
+  MVAL_CHECK_LAUNCH("mval_score_reduce_views");
   return 0;
 }

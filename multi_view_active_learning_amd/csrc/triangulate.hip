@@ -23,6 +23,11 @@
 // Both kernels are built from the same two stages, vote_pair (a lane triangulates one pair and votes) and
 // finish_problem (final DLT over the winner's inlier views), and differ only in where a lane's pairs come from and in
 // the width of the reduction key; the host entries share launch_ransac (key-point dtype dispatch, frame_reduce_kernel).
+//
+// Frames with missing views: the `_views` entries take view_valid [B,V] u8 and run the MASKED instantiations of the same
+// kernels.  A frame's present views are the bits of `present`; a pair with an absent view sits out, the vote and the
+// "no usable pair" fallback run over present views only, and nothing of an absent view (key-point row, matrix) is read.
+// MASKED is a template parameter: the unmasked instantiations compile to the code they were without it.
 #include "mval_common.h"
 #include "numeric_order.h"  // np_pairwise_sum: np.mean's order
 
@@ -142,9 +147,10 @@ __device__ __forceinline__ double reproj_err(const double* __restrict__ P, const
 }
 
 // stage 1 of one lane: triangulate the view pair (a, c) and vote over all V views -> inlier mask (a and c always in it)
-template <typename KP>
+// (MASKED: over the views of `present` only)
+template <bool MASKED = false, typename KP>
 __device__ __forceinline__ unsigned vote_pair(const double* __restrict__ Pb, const KP* __restrict__ kb, int V, int J,
-                                              int a, int c, double eps) {
+                                              int a, int c, double eps, unsigned present = 0u) {
   R4 m;
   r4_zero(m);
   add_view_rows(m, Pb + a * 12, (double)kb[(int64_t)a * J * 2], (double)kb[(int64_t)a * J * 2 + 1]);
@@ -154,6 +160,7 @@ __device__ __forceinline__ unsigned vote_pair(const double* __restrict__ Pb, con
   dehomogenise(h, X);
   unsigned mask = (1u << a) | (1u << c);
   for (int v = 0; v < V; v++) {
+    if (MASKED && !(present >> v & 1)) continue;
     double e = reproj_err(Pb + v * 12, X, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
     if (e < eps) mask |= 1u << v;
   }
@@ -191,11 +198,24 @@ __device__ __forceinline__ void finish_problem(const double* __restrict__ Pb, co
   *inl_out = n;
 }
 
+// the present views of a frame as bits (vv: the frame's row of view_valid, V <= 32)
+__device__ __forceinline__ unsigned present_views(const uint8_t* __restrict__ vv, int V) {
+  unsigned m = 0;
+  for (int v = 0; v < V; v++)
+    if (vv[v]) m |= 1u << v;
+  return m;
+}
+
 // All C(V,2) pairs in lexicographic order, pair p on lane p of the problem's group (V <= MAXV: n_pairs <= 64).
-template <typename KP>
+// MASKED: lane p keeps its pair and sits out when one of its views is absent; the pairs that take part are the
+// lexicographic pairs of the present views in the same relative order, so the key picks the winner the unmasked
+// kernel picks on the frame's present views alone.  Fewer than two present views: the problem is written as an
+// invalid joint's (frame_reduce_kernel marks the frame).
+template <bool MASKED, typename KP>
 __global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ kp2d, const double* __restrict__ proj,
-                                                         const uint8_t* __restrict__ valid, double* __restrict__ kp3d,
-                                                         double* __restrict__ joint_err,
+                                                         const uint8_t* __restrict__ valid,
+                                                         const uint8_t* __restrict__ view_valid,
+                                                         double* __restrict__ kp3d, double* __restrict__ joint_err,
                                                          int32_t* __restrict__ joint_inliers, int64_t n_prob, int V,
                                                          int J, int n_pairs, int PG, double eps) {
   const int lane = threadIdx.x;
@@ -209,30 +229,39 @@ __global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ k
   const double* Pb = proj + b * V * 12;
   const KP* kb = kp2d + (b * V * (int64_t)J + j) * 2;  // + v * J * 2
 
+  const unsigned present = MASKED ? present_views(view_valid + b * V, V) : 0u;
+
   unsigned mask = 0;
+  bool voted = false;
   if (p < n_pairs) {
     int a = 0, rem = p;
     while (rem >= V - 1 - a) { rem -= V - 1 - a; a++; }
-    mask = vote_pair(Pb, kb, V, J, a, a + 1 + rem, eps);
+    const int c = a + 1 + rem;
+    voted = !MASKED || ((present >> a & 1) && (present >> c & 1));
+    if (voted) mask = vote_pair<MASKED>(Pb, kb, V, J, a, c, eps, present);
   }
   // first pair with the strictly largest set: key = count * 64 + (63 - p), maximise
-  int key = (p < n_pairs) ? __popc(mask) * 64 + (63 - p) : -1;
+  int key = voted ? __popc(mask) * 64 + (63 - p) : -1;
   int best = key;
   for (int o = PG >> 1; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
   unsigned win = (key == best) ? mask : 0u;
   for (int o = PG >> 1; o > 0; o >>= 1) win |= __shfl_xor(win, o, 64);
 
   if (p != 0 || !live) return;
-  finish_problem<MAXV>(Pb, kb, V, J, win, is_valid, kp3d + pr * 3, joint_err + pr, joint_inliers + pr);
+  // (MASKED, two or more present views: at least one pair voted, so `win` is never the unmasked kernel's empty set)
+  finish_problem<MAXV>(Pb, kb, V, J, win, is_valid && (!MASKED || __popc(present) >= 2), kp3d + pr * 3, joint_err + pr,
+                       joint_inliers + pr);
 }
 
 // The same two stages over an explicit pair table (pairs_stride = P * 2 per problem, 0 for one shared table).  A lane
 // walks its pairs in ascending table position and keeps the first strictly larger set, the butterfly then prefers the
 // lowest position among equal counts: the winner is the first position with the largest set (utils/triangulation.py
 // :299-300).  key = count * 512 + (511 - position) <= 32 * 512 + 511.  An entry that names a view >= V takes no part.
-template <typename KP>
+// MASKED: neither does one that names an absent view, and the fallback is all PRESENT views.
+template <bool MASKED, typename KP>
 __global__ __launch_bounds__(64) void ransac_pairs_kernel(const KP* __restrict__ kp2d, const double* __restrict__ proj,
                                                            const uint8_t* __restrict__ valid,
+                                                           const uint8_t* __restrict__ view_valid,
                                                            const uint8_t* __restrict__ pairs, int64_t pairs_stride,
                                                            double* __restrict__ kp3d, double* __restrict__ joint_err,
                                                            int32_t* __restrict__ joint_inliers, int64_t n_prob, int V,
@@ -248,6 +277,7 @@ __global__ __launch_bounds__(64) void ransac_pairs_kernel(const KP* __restrict__
   const double* Pb = proj + b * V * 12;
   const KP* kb = kp2d + (b * V * (int64_t)J + j) * 2;  // + v * J * 2
   const uint8_t* tab = pairs + pr * pairs_stride;
+  const unsigned present = MASKED ? present_views(view_valid + b * V, V) : 0u;
 
   int key = -1;
   unsigned mask = 0;
@@ -255,7 +285,8 @@ __global__ __launch_bounds__(64) void ransac_pairs_kernel(const KP* __restrict__
     for (int p = p0; p < P; p += 64) {  // PG < 64 means P <= PG: one trip
       int a = tab[p * 2], c = tab[p * 2 + 1];
       if (a >= V || c >= V) continue;
-      unsigned m = vote_pair(Pb, kb, V, J, a, c, eps);
+      if (MASKED && !((present >> a & 1) && (present >> c & 1))) continue;
+      unsigned m = vote_pair<MASKED>(Pb, kb, V, J, a, c, eps, present);
       int k = __popc(m) * 512 + (511 - p);
       if ((k >> 9) > (key >> 9)) { key = k; mask = m; }  // key = -1 >> 9 = -1: any set beats none
     }
@@ -265,16 +296,28 @@ __global__ __launch_bounds__(64) void ransac_pairs_kernel(const KP* __restrict__
   for (int o = PG >> 1; o > 0; o >>= 1) win |= __shfl_xor(win, o, 64);
 
   if (p0 != 0 || !live) return;
-  if (best < 0) win = (V >= 32) ? 0xffffffffu : ((1u << V) - 1u);  // no usable pair: all views (:303-304)
-  finish_problem<MVAL_PAIRS_MAX_VIEWS>(Pb, kb, V, J, win, is_valid, kp3d + pr * 3, joint_err + pr, joint_inliers + pr);
+  if (best < 0) win = MASKED ? present : (V >= 32) ? 0xffffffffu : ((1u << V) - 1u);  // no usable pair: all views (:303-304)
+  finish_problem<MVAL_PAIRS_MAX_VIEWS>(Pb, kb, V, J, win, is_valid && (!MASKED || __popc(present) >= 2), kp3d + pr * 3,
+                                       joint_err + pr, joint_inliers + pr);
 }
 
 // per frame: metric = np.mean(errs of valid joints), inlier_count = min (utils/triangulation.py:226,231)
+// MASKED: a frame with a valid joint and fewer than two present views gets metric NaN and inlier_count -2 (the reference
+// asserts len(points) >= 2 inside the first valid joint, :268); without a valid joint it stays -1 (np.min([]) comes
+// without any assert).
+template <bool MASKED>
 __global__ void frame_reduce_kernel(const double* __restrict__ joint_err, const int32_t* __restrict__ joint_inliers,
-                                    const uint8_t* __restrict__ valid, double* __restrict__ metric,
-                                    int32_t* __restrict__ inlier_count, int B, int J) {
+                                    const uint8_t* __restrict__ valid, const uint8_t* __restrict__ view_valid,
+                                    double* __restrict__ metric, int32_t* __restrict__ inlier_count, int B, int V, int J) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
+  if (MASKED && __popc(present_views(view_valid + (int64_t)b * V, V)) < 2) {
+    bool any = false;
+    for (int j = 0; j < J; j++) any |= !valid || valid[(int64_t)b * J + j];
+    metric[b] = NAN;
+    inlier_count[b] = any ? -2 : -1;
+    return;
+  }
   double buf[512];
   int n = 0, mn = 0x7fffffff;
   for (int j = 0; j < J; j++) {
@@ -291,15 +334,19 @@ __global__ void frame_reduce_kernel(const double* __restrict__ joint_err, const 
 template <typename Launch>
 static int launch_ransac(const char* name, const void* kp2d, int kp_is_f32, int PG, const uint8_t* valid,
                          const double* joint_err, const int32_t* joint_inliers, double* metric, int32_t* inlier_count,
-                         int B, int J, hipStream_t s, Launch launch) {
+                         int B, int J, hipStream_t s, Launch launch, const uint8_t* view_valid = nullptr, int V = 0) {
   const int64_t n_prob = (int64_t)B * J;
   const int per_block = 64 / PG;
   const dim3 grid((unsigned)((n_prob + per_block - 1) / per_block));
   if (kp_is_f32) launch((const float*)kp2d, grid, n_prob);
   else launch((const int64_t*)kp2d, grid, n_prob);
   MVAL_CHECK_LAUNCH(name);
-  hipLaunchKernelGGL(frame_reduce_kernel, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers, valid, metric,
-                     inlier_count, B, J);
+  if (view_valid)
+    hipLaunchKernelGGL(frame_reduce_kernel<true>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers, valid,
+                       view_valid, metric, inlier_count, B, V, J);
+  else
+    hipLaunchKernelGGL(frame_reduce_kernel<false>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers, valid,
+                       view_valid, metric, inlier_count, B, V, J);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     mval_set_error("%s/reduce: launch failed: %s", name, hipGetErrorString(e));
@@ -319,11 +366,32 @@ extern "C" int mval_triangulate_ransac(const void* kp2d, int kp_is_f32, const do
   int PG = 1;
   while (PG < n_pairs) PG <<= 1;
   const hipStream_t s = mval_stream(stream);
+  const uint8_t* const no_mask = nullptr;
   return launch_ransac("mval_triangulate_ransac", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric, inlier_count,
                        B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(ransac_dlt_kernel, grid, dim3(64), 0, s, kp, proj, valid, kp3d, joint_err,
-                                            joint_inliers, n_prob, V, J, n_pairs, PG, eps);
+                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<false>), grid, dim3(64), 0, s, kp, proj, valid,
+                                            no_mask, kp3d, joint_err, joint_inliers, n_prob, V, J, n_pairs, PG, eps);
                        });
+}
+
+extern "C" int mval_triangulate_ransac_views(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                             const uint8_t* view_valid, double* kp3d, double* joint_err,
+                                             int32_t* joint_inliers, double* metric, int32_t* inlier_count, int B, int V,
+                                             int J, double eps, void* stream) {
+  MVAL_REQUIRE(V >= 2, "mval_triangulate_ransac_views: need >= 2 views in the rig (a frame may have fewer present)");
+  MVAL_REQUIRE(V <= MAXV, "mval_triangulate_ransac_views: V > 11 takes a pair table (mval_triangulate_ransac_pairs_views)");
+  MVAL_REQUIRE(view_valid, "mval_triangulate_ransac_views: view_valid is NULL (use mval_triangulate_ransac)");
+  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac_views: bad dims");
+  if (B == 0) return 0;
+  const int n_pairs = V * (V - 1) / 2;
+  int PG = 1;
+  while (PG < n_pairs) PG <<= 1;
+  const hipStream_t s = mval_stream(stream);
+  return launch_ransac("mval_triangulate_ransac_views", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
+                       inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
+                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<true>), grid, dim3(64), 0, s, kp, proj, valid,
+                                            view_valid, kp3d, joint_err, joint_inliers, n_prob, V, J, n_pairs, PG, eps);
+                       }, view_valid, V);
 }
 
 extern "C" int mval_triangulate_ransac_pairs(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
@@ -339,24 +407,54 @@ extern "C" int mval_triangulate_ransac_pairs(const void* kp2d, int kp_is_f32, co
   while (PG < P && PG < 64) PG <<= 1;
   const int64_t stride = pairs_shared ? 0 : (int64_t)P * 2;
   const hipStream_t s = mval_stream(stream);
+  const uint8_t* const no_mask = nullptr;
   return launch_ransac("mval_triangulate_ransac_pairs", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
                        inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(ransac_pairs_kernel, grid, dim3(64), 0, s, kp, proj, valid, pairs, stride, kp3d,
-                                            joint_err, joint_inliers, n_prob, V, J, P, PG, eps);
+                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<false>), grid, dim3(64), 0, s, kp, proj,
+                                            valid, no_mask, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V, J, P,
+                                            PG, eps);
                        });
+}
+
+extern "C" int mval_triangulate_ransac_pairs_views(const void* kp2d, int kp_is_f32, const double* proj,
+                                                   const uint8_t* valid, const uint8_t* view_valid, const uint8_t* pairs,
+                                                   int P, int pairs_shared, double* kp3d, double* joint_err,
+                                                   int32_t* joint_inliers, double* metric, int32_t* inlier_count, int B,
+                                                   int V, int J, double eps, void* stream) {
+  MVAL_REQUIRE(V >= 2, "mval_triangulate_ransac_pairs_views: need >= 2 views in the rig (a frame may have fewer present)");
+  MVAL_REQUIRE(V <= MVAL_PAIRS_MAX_VIEWS, "mval_triangulate_ransac_pairs_views: at most %d views (the inlier mask is 32 bits wide)", MVAL_PAIRS_MAX_VIEWS);
+  MVAL_REQUIRE(view_valid, "mval_triangulate_ransac_pairs_views: view_valid is NULL (use mval_triangulate_ransac_pairs)");
+  MVAL_REQUIRE(pairs && P >= 1 && P <= MVAL_PAIRS_MAX_PAIRS, "mval_triangulate_ransac_pairs_views: need a pair table of 1..%d pairs", MVAL_PAIRS_MAX_PAIRS);
+  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac_pairs_views: bad dims");
+  if (B == 0) return 0;
+  int PG = 1;
+  while (PG < P && PG < 64) PG <<= 1;
+  const int64_t stride = pairs_shared ? 0 : (int64_t)P * 2;
+  const hipStream_t s = mval_stream(stream);
+  return launch_ransac("mval_triangulate_ransac_pairs_views", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
+                       inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
+                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<true>), grid, dim3(64), 0, s, kp, proj,
+                                            valid, view_valid, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V, J,
+                                            P, PG, eps);
+                       }, view_valid, V);
 }
 
 // ---- XE metric (utils/triangulation.py:236-257) ---------------------------------------
 // one wave per (frame, view, joint) map; float64 like the reference's rendered target.
+// MASKED: the maps of an absent view are neither read nor written, and xe_sum_kernel leaves them out of its serial sum --
+// the sum the unmasked entry makes over the frame's present views alone.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void xe_kernel(const double* __restrict__ kp3d, const double* __restrict__ proj,
-                                                 const float* __restrict__ hm, double* __restrict__ per_map,
-                                                 int64_t n_maps, int V, int J, int hh, int wh, double sigma) {
+                                                 const float* __restrict__ hm, const uint8_t* __restrict__ view_valid,
+                                                 double* __restrict__ per_map, int64_t n_maps, int V, int J, int hh,
+                                                 int wh, double sigma) {
   const int lane = threadIdx.x & 63;
   const int64_t map = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (map >= n_maps) return;
   const int j = (int)(map % J);
   const int v = (int)((map / J) % V);
   const int64_t b = map / ((int64_t)V * J);
+  if (MASKED && !view_valid[b * V + v]) return;
   const double* P = proj + (b * V + v) * 12;
   const double* X = kp3d + (b * J + j) * 3;
   double u = X[0] * P[0] + X[1] * P[1] + X[2] * P[2] + P[3];
@@ -378,24 +476,51 @@ __global__ __launch_bounds__(256) void xe_kernel(const double* __restrict__ kp3d
   if (lane == 0) per_map[map] = acc / (double)(hh * wh);
 }
 
-__global__ void xe_sum_kernel(const double* __restrict__ per_map, double* __restrict__ out, int B, int VJ) {
+template <bool MASKED>
+__global__ void xe_sum_kernel(const double* __restrict__ per_map, const uint8_t* __restrict__ view_valid,
+                              double* __restrict__ out, int B, int V, int J) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   double s = 0.0;  // the reference accumulates view-major, joint-minor, left to right
-  for (int i = 0; i < VJ; i++) s += per_map[(int64_t)b * VJ + i];
+  if (MASKED) {
+    for (int v = 0; v < V; v++)
+      if (view_valid[(int64_t)b * V + v])
+        for (int j = 0; j < J; j++) s += per_map[((int64_t)b * V + v) * J + j];
+  } else {
+    const int VJ = V * J;
+    for (int i = 0; i < VJ; i++) s += per_map[(int64_t)b * VJ + i];
+  }
   out[b] = s;
+}
+
+template <bool MASKED>
+static int launch_xe(const char* name, const char* sum_name, const double* kp3d, const double* proj, const float* heatmaps,
+                     const uint8_t* view_valid, double* out, double* ws, int B, int V, int J, int hh, int wh, double sigma,
+                     void* stream) {
+  int64_t n_maps = (int64_t)B * V * J;
+  hipLaunchKernelGGL(xe_kernel<MASKED>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, mval_stream(stream), kp3d, proj,
+                     heatmaps, view_valid, ws, n_maps, V, J, hh, wh, sigma);
+  MVAL_CHECK_LAUNCH(name);
+  hipLaunchKernelGGL(xe_sum_kernel<MASKED>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), ws, view_valid, out, B, V,
+                     J);
+  MVAL_CHECK_LAUNCH(sum_name);
+  return 0;
 }
 
 extern "C" int mval_reprojection_xe(const double* kp3d, const double* proj, const float* heatmaps, double* out,
                                     double* ws, int B, int V, int J, int hh, int wh, double sigma, void* stream) {
   MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && sigma > 0, "mval_reprojection_xe: bad dims");
   if (B == 0) return 0;
-  int64_t n_maps = (int64_t)B * V * J;
-  double* g_xe_ws = ws;
-  hipLaunchKernelGGL(xe_kernel, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, mval_stream(stream), kp3d, proj,
-                     heatmaps, g_xe_ws, n_maps, V, J, hh, wh, sigma);
-  MVAL_CHECK_LAUNCH("mval_reprojection_xe");
-  hipLaunchKernelGGL(xe_sum_kernel, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), g_xe_ws, out, B, V * J);
-  MVAL_CHECK_LAUNCH("mval_reprojection_xe/sum");
-  return 0;
+  return launch_xe<false>("mval_reprojection_xe", "mval_reprojection_xe/sum", kp3d, proj, heatmaps, nullptr, out, ws, B, V, J,
+                          hh, wh, sigma, stream);
+}
+
+extern "C" int mval_reprojection_xe_views(const double* kp3d, const double* proj, const float* heatmaps,
+                                          const uint8_t* view_valid, double* out, double* ws, int B, int V, int J, int hh,
+                                          int wh, double sigma, void* stream) {
+  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && sigma > 0, "mval_reprojection_xe_views: bad dims");
+  MVAL_REQUIRE(view_valid, "mval_reprojection_xe_views: view_valid is NULL (use mval_reprojection_xe)");
+  if (B == 0) return 0;
+  return launch_xe<true>("mval_reprojection_xe_views", "mval_reprojection_xe_views/sum", kp3d, proj, heatmaps, view_valid, out,
+                         ws, B, V, J, hh, wh, sigma, stream);
 }

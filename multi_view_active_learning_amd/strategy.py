@@ -40,12 +40,15 @@ def _reduce_mode(kind: str, config: str) -> int:
     raise NotImplementedError("AL.%s_CONFIG should be either AVG or STD." % kind)
 
 
-def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_quirk=True, decode=False):
+def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_quirk=True, decode=False, view_valid=None):
     """The heat-map scorer behind the three public functions below.  ``configs`` maps "HP" / "MPE" / "BSB" to "AVG" / "STD";
     heatmaps (B,V,J,Hh,Wh) f32 HIP, joint_valid (B,J).  ONE launch reads the heat-maps -- one kind without ``decode``:
     mval_score_maps; one kind with it: mval_score_decode_maps; several kinds: mval_score_decode_maps_all (csrc/scoring.hip builds
     them from the same stages: a statistic has the same bits whichever computes it) --, then ``mval_score_reduce`` per kind.
-    Returns an OrderedDict kind -> (out (B,) float64, per_map (B,V,J), n_peaks (B,V,J), valid, keypoints_2d or None)."""
+    Returns an OrderedDict kind -> (out (B,) float64, per_map (B,V,J), n_peaks (B,V,J), valid, keypoints_2d or None).
+    ``view_valid`` (B,V), nonzero = present: ``out`` is reduced over the present views of each frame alone
+    (``mval_score_reduce_views``).  The map launch is unchanged -- per_map, n_peaks and keypoints_2d still hold entries for
+    the maps of absent views, which every consumer ignores."""
     modes = OrderedDict((kind, _reduce_mode(kind, configs[kind])) for kind in configs)
     for kind in modes:
         if kind not in _KIND:
@@ -54,6 +57,11 @@ def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_q
     hm = heatmaps.to(torch.float32).contiguous()
     valid = (torch.as_tensor(joint_valid) != 0).to(torch.uint8).reshape(b, j).to(hm.device).contiguous()
     split_width = hh if mirror_nonsquare_quirk else wh
+    if view_valid is None:
+        reduce = lambda stat, mode: _lib.score_reduce(stat, valid, b, v, j, mode)  # noqa: E731
+    else:
+        vv = (torch.as_tensor(view_valid) != 0).to(torch.uint8).reshape(b, v).to(hm.device).contiguous()
+        reduce = lambda stat, mode: _lib.score_reduce_views(stat, valid, vv, b, v, j, mode)  # noqa: E731
     if len(modes) == 1:
         (kind,) = modes
         if decode:
@@ -65,29 +73,30 @@ def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_q
         stat, n_peaks, kp2d = _lib.score_decode_maps_all(hm, valid, b, v, j, hh, wh, int(stride), split_width, decode=decode)
         stats = {kind: stat[_KIND[kind]] for kind in modes}
         counts = {"HP": torch.zeros_like(n_peaks[0]) if "HP" in modes else None, "MPE": n_peaks[0], "BSB": n_peaks[1]}
-    return OrderedDict((kind, (_lib.score_reduce(stats[kind], valid, b, v, j, mode), stats[kind].reshape(b, v, j),
+    return OrderedDict((kind, (reduce(stats[kind], mode), stats[kind].reshape(b, v, j),
                                counts[kind].reshape(b, v, j), valid, kp2d)) for kind, mode in modes.items())
 
 
-def score_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid):
+def score_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid, view_valid=None):
     """heatmaps (B,V,J,Hh,Wh) f32 HIP, joint_valid (B,J) -> (B,) float64 HIP tensor holding
     the value the reference's ``_compute_{hp,mpe,bsb}`` returns for each frame (exactly
-    representable float32 where the reference's result is float32); then per_map, n_peaks, valid."""
-    return _score_heatmaps({kind: config}, heatmaps, joint_valid)[kind][:4]
+    representable float32 where the reference's result is float32); then per_map, n_peaks, valid.
+    ``view_valid`` (B,V): the value over each frame's present views alone (``_score_heatmaps``)."""
+    return _score_heatmaps({kind: config}, heatmaps, joint_valid, view_valid=view_valid)[kind][:4]
 
 
-def score_decode_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True):
+def score_decode_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True, view_valid=None):
     """``score_heatmaps_batch`` + the hard arg-max decode of ``triangulate_batch`` from ONE read of the heat-maps
     (csrc/scoring.hip, DECODE): what a pool-scoring pass needs per map (strategy.py:1027-1090 reads every heat-map in
     get_scaled_pred_corrdinates AND in _compute_{hp,mpe,bsb}).  Returns (out, per_map, n_peaks, valid, keypoints_2d)."""
-    return _score_heatmaps({kind: config}, heatmaps, joint_valid, stride, mirror_nonsquare_quirk, decode=True)[kind]
+    return _score_heatmaps({kind: config}, heatmaps, joint_valid, stride, mirror_nonsquare_quirk, decode=True, view_valid=view_valid)[kind]
 
 
-def score_decode_heatmaps_all(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True, decode=True):
+def score_decode_heatmaps_all(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True, decode=True, view_valid=None):
     """``score_decode_heatmaps_batch`` for several kinds from ONE read of the heat-maps: ``configs`` maps "HP" / "MPE" / "BSB"
     to "AVG" / "STD".  Returns an OrderedDict kind -> (out, per_map, n_peaks, valid, keypoints_2d), each entry what
     ``score_decode_heatmaps_batch(kind, config, ...)`` returns (keypoints_2d None without ``decode``)."""
-    return _score_heatmaps(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk, decode)
+    return _score_heatmaps(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk, decode, view_valid)
 
 
 AL_STRATEGIES = ("HP", "MPE", "BSB", "TRIANGULATION", "CORESET", "RANDOM")
@@ -163,7 +172,7 @@ def tables_to_sal_dict(per_rank, batch_sizes, sal_dict=None):
     return sal_dict
 
 
-_SMALL_KEYS = ("proj_matrices", "joint_valid", "3d_keypoints", "pose", "frame_id")
+_SMALL_KEYS = ("proj_matrices", "joint_valid", "3d_keypoints", "pose", "frame_id", "view_valid")
 
 
 def _stage_batch(dp):
@@ -173,7 +182,8 @@ def _stage_batch(dp):
     host until the side stream -- which has just waited for this batch's network -- drains, so the NEXT batch's network could not be
     enqueued meanwhile.  A ``joint_valid`` that arrives on the host also stays there as ``joint_valid_host``: the
     view-pair draw of a rig with more than 11 views (utils.triangulation.draw_view_pairs) reads it, and copying the staged mask back
-    would be such a blocking copy.  Returns a shallow copy of ``dp``; host-only runs (no HIP device) get ``dp`` back."""
+    would be such a blocking copy; a ``view_valid`` (frames with missing views) likewise stays as ``view_valid_host``, which that
+    draw reads too.  Returns a shallow copy of ``dp``; host-only runs (no HIP device) get ``dp`` back."""
     if not torch.cuda.is_available() or not isinstance(dp, dict):
         return dp
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -183,8 +193,8 @@ def _stage_batch(dp):
             continue
         t = torch.as_tensor(dp[k])
         if not t.is_cuda:
-            if k == "joint_valid":
-                out["joint_valid_host"] = t
+            if k in ("joint_valid", "view_valid"):
+                out[k + "_host"] = t
             t = t.contiguous()
             t = (t if t.is_pinned() else t.pin_memory()).to(dev, non_blocking=True)
         out[k] = t
@@ -349,7 +359,9 @@ class ActiveLearningStrategy:
         """Everything the reference does per sample inside _compute_sal_dict (strategy.py:1036-1094,1134), for a whole
         batch, on device, for each of ``strategies``: one heat-map launch (when HP, MPE or BSB is among them; with the hard
         arg-max decode unless AL.USE_SOFTARGMAX), one triangulation.  heatmaps (B*V,J,h,w).  Returns float64 HIP columns
-        (ids [pose, frame_id], rest [sal_metric, inlier_count, mkpe, keypoints_3d(3J)], al_metric per strategy)."""
+        (ids [pose, frame_id], rest [sal_metric, inlier_count, mkpe, keypoints_3d(3J)], al_metric per strategy).
+        A batch with ``view_valid`` (B, V) -- frames with missing views -- is scored and triangulated over each frame's
+        present views alone."""
         cfg = self.al_cfg
         dev = heatmaps.device
         pose = torch.as_tensor(dp["pose"]).reshape(-1)
@@ -357,11 +369,13 @@ class ActiveLearningStrategy:
         _, j, hh, wh = heatmaps.shape
         hm = heatmaps.reshape(b, -1, j, hh, wh)
         joint_valid = torch.as_tensor(dp["joint_valid"]).reshape(b, j)
+        view_valid = dp.get("view_valid")
         configs = OrderedDict((s, getattr(cfg.AL, s + "_CONFIG")) for s in strategies if s in _KIND)
         scored, kp2d = {}, None
         if configs:
             # one read of every heat-map for the uncertainty statistics and the key-point decode
-            scored = _score_heatmaps(configs, hm, joint_valid, cfg.POSE_ESTIMATOR.STRIDE, decode=not cfg.AL.USE_SOFTARGMAX)
+            scored = _score_heatmaps(configs, hm, joint_valid, cfg.POSE_ESTIMATOR.STRIDE, decode=not cfg.AL.USE_SOFTARGMAX,
+                                     view_valid=view_valid)
             kp2d = next(iter(scored.values()))[4]
         r = triangulation.triangulate_batch(
             hm, dp["proj_matrices"], cfg.POSE_ESTIMATOR.STRIDE, joint_valid,
@@ -369,9 +383,12 @@ class ActiveLearningStrategy:
             keypoints_2d=kp2d,
             pair_rng=random,  # more than n_iters view pairs (12 views on): the reference's draws, frames in batch order
             valid_joints_host=dp.get("joint_valid_host"),
+            view_valid=view_valid, view_valid_host=dp.get("view_valid_host"),
         )
         pred32 = r["keypoints_3d"].to(torch.float32)  # torch.Tensor(results["keypoints_3d"]) (:1046)
         sal_metric = r["metric"].to(torch.float32).to(torch.float64)  # torch.Tensor([metric]) (:1061)
+        # frames with missing views: an absent view has no peak list to run short, the deferred peak checks count it as fine
+        absent = None if view_valid is None or not configs else (torch.as_tensor(view_valid).reshape(b, -1) == 0).to(dev)[:, :, None]
         als = []
         for s in strategies:
             if s == "RANDOM":
@@ -380,6 +397,8 @@ class ActiveLearningStrategy:
                 al = r["metric"].to(torch.float64)  # torch.tensor([np.float64]) keeps float64 (:1075)
             elif s in _KIND:
                 al, _, n_peaks, valid = scored[s][:4]
+                if absent is not None:
+                    n_peaks = torch.where(absent, torch.full_like(n_peaks, 2), n_peaks)
                 self._pending_checks.append((s, n_peaks, valid))
                 if configs[s] == "AVG" or s != "HP":
                     al = al.to(torch.float32).to(torch.float64)  # torch.tensor(python float) is float32
@@ -481,7 +500,10 @@ class ActiveLearningStrategy:
         """Error behaviour of the reference's per-sample loop, checked once per pass."""
         for kind, t, valid in self._pending_checks:
             if kind == "INLIER":
-                if bool((t < 0).any().item()):
+                bad = t[t < 0]
+                if bad.numel():  # the reference stops at its first bad frame
+                    if int(bad[0].item()) == -2:  # fewer than two present views (view_valid)
+                        raise AssertionError("need at least two views")
                     raise ValueError("zero-size array to reduction operation minimum which has no identity")
             else:
                 if bool((t < 0).any().item()):
@@ -666,7 +688,8 @@ class ActiveLearningStrategy:
             (b, j), (hh, wh) = jv.shape, hm.shape[2:]
             r = triangulation.triangulate_batch(hm.reshape(b, -1, j, hh, wh), dp["proj_matrices"],
                                                 self.al_cfg.POSE_ESTIMATOR.STRIDE, jv, pair_rng=random,
-                                                valid_joints_host=dp.get("joint_valid_host"))
+                                                valid_joints_host=dp.get("joint_valid_host"),
+                                                view_valid=dp.get("view_valid"), view_valid_host=dp.get("view_valid_host"))
             return (r["keypoints_3d"].to(torch.float32), torch.as_tensor(dp["3d_keypoints"]).to(hm.device, torch.float32),
                     jv.to(hm.device, torch.float32))
 
@@ -722,13 +745,20 @@ class ActiveLearningStrategy:
     @staticmethod
     def _stage_pckh_targets(dp):
         """``_stage_batch`` plus what the 2-D PCKh pass reads -- ``square_box`` and ``2d_after_crop`` -- on the device, uploaded
-        like the small tensors: pinned, non-blocking, on the caller's stream before the network."""
+        like the small tensors: pinned, non-blocking, on the caller's stream before the network.  With ``view_valid`` also
+        ``view_rows``, the row numbers of the present images."""
         out = _stage_batch(dp)
         if torch.cuda.is_available() and isinstance(dp, dict):
             out = dict(out)
             for key in ("square_box", "2d_after_crop"):
                 if key in dp:
                     out[key] = _stage_small(torch.as_tensor(dp[key]))
+            if dp.get("view_valid") is not None:
+                # frames with missing views: the rows of the present images, listed on the host from the loader's mask
+                # (``view_valid_host``, or the caller's own host copy under that key) and uploaded with the rest.  Only a mask
+                # that exists on the device alone is read back, which blocks the host on the current stream (INTEGRATION.md)
+                host = out.get("view_valid_host", dp["view_valid"])
+                out["view_rows"] = _stage_small(torch.nonzero(torch.as_tensor(host).reshape(-1) != 0).reshape(-1))
         return out
 
     def evaluate_2d_pckh(self, data_loader, pose_estimator, thresholds=None):
@@ -737,7 +767,7 @@ class ActiveLearningStrategy:
         next batch's network; per pass ONE packed gather of [pred 2J | gt 2J] float32 rows (the reference: two all_gathers
         per batch) and one counter launch for all thresholds.  The ground truth is ``2d_after_crop`` reshaped to
         (-1, J, 2) with J = DATA.NUM_JOINTS, where the reference hard-codes 19 (strategy.py:567).  The gathered tables stay
-        in ``self._eval2d_tables``."""
+        in ``self._eval2d_tables``.  A batch with ``view_valid`` (B, V) contributes the rows of its present images only."""
         j = self.num_joints
 
         def decode(hm, _keys, dp):
@@ -745,7 +775,10 @@ class ActiveLearningStrategy:
             gt = torch.as_tensor(dp["2d_after_crop"]).to(hm.device, torch.float32).reshape(-1, j, 2)
             if pred.shape != gt.shape:
                 raise ValueError("2-D PCKh: %s predictions for %s ground-truth key-points" % (tuple(pred.shape), tuple(gt.shape)))
-            return torch.cat([pred.reshape(-1, 2 * j), gt.reshape(-1, 2 * j)], dim=1)
+            rows = torch.cat([pred.reshape(-1, 2 * j), gt.reshape(-1, 2 * j)], dim=1)
+            if dp.get("view_rows") is not None:  # the images of absent views are not scored: S counts present images
+                rows = rows.index_select(0, dp["view_rows"])
+            return rows
 
         rows = self._pool_loop(data_loader, pose_estimator, decode, stage=self._stage_pckh_targets)
         from .parallel import all_gather_reference_order as gather

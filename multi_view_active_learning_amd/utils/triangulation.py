@@ -11,6 +11,10 @@ Rigs with more view pairs than ``n_iters`` (from 12 views on at the default 64):
 shuffles the pair list of every valid joint with python's ``random`` and keeps the first
 ``n_iters`` (utils/triangulation.py:279-282).  ``draw_view_pairs`` makes those draws on the host,
 in the reference's order, and the device triangulates the drawn pairs (up to 32 views).
+
+Frames with missing views: ``view_valid`` (B, V) makes every frame's result what these functions give on that frame's
+present views alone -- what the per-sample reference computes when it is handed the views that exist -- with all frames
+of a batch in one triangulation launch.
 """
 from __future__ import annotations
 
@@ -36,7 +40,31 @@ def _as_valid_u8(valid, shape, device):
     return v.to(device).contiguous()
 
 
-def draw_view_pairs(valid, V, n_iters, rng):
+PAIR_PAD = 255  # a view index no rig has (at most 32 views): an entry naming it takes no part in the vote
+
+
+def _draw_view_pairs_masked(valid, V, n_iters, rng, view_valid):
+    b, j = valid.shape
+    present = [np.flatnonzero(view_valid[bi]) for bi in range(b)]
+    n_pairs = [len(p) * (len(p) - 1) // 2 for p in present]
+    out = np.full((b, j, max([1] + [min(n, n_iters) for n in n_pairs]), 2), PAIR_PAD, dtype=np.uint8)
+    for bi in range(b):
+        n = n_pairs[bi]
+        if n == 0:  # fewer than two present views: nothing to triangulate, nothing drawn
+            continue
+        lex = np.array(list(itertools.combinations(present[bi].tolist(), 2)), dtype=np.uint8).reshape(-1, 2)
+        if n <= n_iters:
+            out[bi, :, :n] = lex
+            continue
+        out[bi] = 0  # (a frame that draws fills all P = n_iters entries; the rows of its invalid joints stay zero)
+        for ji in np.flatnonzero(valid[bi]):
+            order = list(range(n))
+            rng.shuffle(order)
+            out[bi, ji] = lex[order[:n_iters]]
+    return out
+
+
+def draw_view_pairs(valid, V, n_iters, rng, view_valid=None):
     """The view pairs the reference samples for every joint of a batch (utils/triangulation.py:279-282):
     valid (B, J) -> uint8 ndarray (B, J, P, 2), P = min(n_iters, C(V,2)).
 
@@ -44,8 +72,18 @@ def draw_view_pairs(valid, V, n_iters, rng):
     :210-211), ``rng.shuffle`` permutes a list as long as ``itertools.combinations(range(V), 2)`` and the first
     ``n_iters`` pairs are kept: ``rng`` (the ``random`` module or a ``random.Random``) is left in the state the
     reference leaves it in.  The rows of an invalid joint stay zero.  With C(V,2) <= n_iters the reference draws
-    nothing: neither does this, and every row is the lexicographic list."""
+    nothing: neither does this, and every row is the lexicographic list.
+
+    ``view_valid`` (B, V), nonzero = present: what the reference draws when it is handed each frame's present views
+    alone, in ORIGINAL view indices.  Frame b with n_b present views: C(n_b, 2) <= n_iters -> the lexicographic pairs of
+    its present views, nothing drawn; otherwise per valid joint a shuffle of a list of length C(n_b, 2), first
+    ``n_iters`` kept.  Frames in batch order, valid joints ascending: ``rng`` ends in the reference's state.
+    P = max over frames of min(C(n_b, 2), n_iters), at least 1; shorter rows, and those of a frame with n_b < 2 (which
+    draws nothing), are padded with ``PAIR_PAD`` = 255.  The rows of an invalid joint stay zero in a frame that draws."""
     valid = torch.as_tensor(valid).cpu().numpy() != 0
+    if view_valid is not None:
+        vv = torch.as_tensor(view_valid).cpu().numpy().reshape(valid.shape[0], V) != 0
+        return _draw_view_pairs_masked(valid, V, n_iters, rng, vv)
     b, j = valid.shape
     lex = np.array(list(itertools.combinations(range(V), 2)), dtype=np.uint8).reshape(-1, 2)
     n = len(lex)
@@ -84,6 +122,8 @@ def triangulate_batch(
     keypoints_2d=None,
     pair_rng=None,
     valid_joints_host=None,
+    view_valid=None,
+    view_valid_host=None,
 ):
     """heatmaps (B,V,J,Hh,Wh) f32 HIP tensor, proj (B,V,3,4), valid (B,J) ->
     dict of HIP tensors: keypoints_3d (B,J,3) f64, keypoints_2d (B,V,J,2) i64|f32,
@@ -104,7 +144,16 @@ def triangulate_batch(
 
     ``valid_joints_host``: ``valid_joints`` once more, on the host, for callers that hand the mask in as a device
     tensor: the draw reads the mask on the host, and copying a device mask back blocks the host on the current
-    stream.  The drawn table goes up through pinned memory without blocking."""
+    stream.  The drawn table goes up through pinned memory without blocking.
+
+    ``view_valid`` (B, V), nonzero = the view is present in that frame (None: every view is, today's path call for
+    call).  Each frame's result is what this function gives on that frame's present views alone, bit for bit; all frames
+    go through ONE triangulation launch, however their present sets differ.  Nothing of an absent view is used (its
+    heat-maps and matrix may hold NaN); ``keypoints_2d`` comes back dense with the rows of absent views zero.  A frame
+    with fewer than two present views and a valid joint gets inlier_count -2, metric NaN and keypoints_3d 0 (the
+    reference asserts two views); without a valid joint it is -1 as ever.  Up to 11 views nothing of the mask is needed
+    on the host; beyond, the pair tables are built per frame from its present views (``draw_view_pairs``), from
+    ``view_valid_host`` -- the mask once more on the host, as ``valid_joints_host`` -- where given."""
     dev = _device_of(heatmaps)
     if heatmaps.dim() != 5:
         raise ValueError("heatmaps must be (B, V, J, Hh, Wh)")
@@ -113,34 +162,47 @@ def triangulate_batch(
         raise AssertionError("need at least two views")  # reference: assert len(points) >= 2
     if v > _lib.PAIRS_MAX_VIEWS:
         raise NotImplementedError("at most %d views (got %d): the device's inlier mask is 32 bits wide" % (_lib.PAIRS_MAX_VIEWS, v))
-    sampled = v * (v - 1) // 2 > n_iters
+    masked = view_valid is not None
+    sampled = not masked and v * (v - 1) // 2 > n_iters  # (under a mask the frames decide one by one: _masked_pair_tables)
     if sampled and pair_rng is None:
-        raise NotImplementedError(
-            "more view pairs than n_iters: the reference samples pairs from python's global RNG there "
-            "(pass pair_rng=random to draw them in its order)"
-        )
-    if sampled and n_iters < 1:
+        raise NotImplementedError(_NEEDS_RNG)
+    if (sampled or (masked and v > 11)) and n_iters < 1:
         raise ValueError("n_iters must be at least 1")
     hm = heatmaps.to(torch.float32).contiguous()
     proj = torch.as_tensor(proj_matricies).to(device=dev, dtype=torch.float64).reshape(b, v, 3, 4).contiguous()
     valid = _as_valid_u8(valid_joints, (b, j), dev)
+    vv = _as_valid_u8(view_valid, (b, v), dev)
     if keypoints_2d is not None:
         kp2d = keypoints_2d
     elif use_soft_argmax:
         kp2d = _lib.soft_argmax(hm, b * v * j, hh, wh, float(stride)).reshape(b, v, j, 2)
     else:
         kp2d = _lib.argmax_decode(hm, valid, b, v, j, hh, wh, int(stride), hh if mirror_nonsquare_quirk else wh)
+    if masked:
+        # (the map kernels still decode the maps of absent views; a select, not a product: such a row may be NaN)
+        kp2d = torch.where(vv.bool()[:, :, None, None], kp2d, torch.zeros((), dtype=kp2d.dtype, device=dev))
     eps = float(reprojection_error_epsilon)
-    if sampled:
+    if sampled or (masked and v > 11):
         host_valid = valid_joints_host if valid_joints_host is not None else valid_joints
         host_valid = torch.ones((b, j)) if host_valid is None else torch.as_tensor(host_valid).reshape(b, j)
+    if masked and v <= 11:  # lane p keeps its pair and sits out if a view is absent: no host knowledge of the mask
+        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_views(kp2d, proj, valid, vv, b, v, j, eps)
+    elif masked:
+        host_vv = view_valid_host if view_valid_host is not None else view_valid
+        pairs = _masked_pair_tables(host_valid, torch.as_tensor(host_vv).reshape(b, v), v, n_iters, pair_rng)
+        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs_views(kp2d, proj, valid, vv, pairs.pin_memory().to(dev, non_blocking=True),
+                                                                            b, v, j, eps)
+    elif sampled:
         pairs = torch.from_numpy(draw_view_pairs(host_valid, v, n_iters, pair_rng)).pin_memory().to(dev, non_blocking=True)
         kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs(kp2d, proj, valid, pairs, b, v, j, eps)
     elif v > 11:  # all pairs, more than the 64 the one-lane-per-pair entry holds
         kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs(kp2d, proj, valid, _lexicographic_pairs(v, dev), b, v, j, eps)
     else:
         kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac(kp2d, proj, valid, b, v, j, eps)
-    if use_reprojection_xe:
+    if use_reprojection_xe and masked:
+        xe = _lib.reprojection_xe_views(kp3d, proj, hm, vv, b, v, j, hh, wh, float(sigma))
+        metric = torch.where(inl == -2, metric, xe)  # (fewer than two views: NaN, the reference never reaches _compute_xe)
+    elif use_reprojection_xe:
         metric = _lib.reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, float(sigma))
     return {
         "keypoints_3d": kp3d,
@@ -150,6 +212,20 @@ def triangulate_batch(
         "joint_error": jerr,
         "joint_inliers": jinl,
     }
+
+
+_NEEDS_RNG = ("more view pairs than n_iters: the reference samples pairs from python's global RNG there "
+              "(pass pair_rng=random to draw them in its order)")
+
+
+def _masked_pair_tables(host_valid, host_view_valid, v, n_iters, pair_rng):
+    """The per-problem pair tables of a masked batch with more than 11 views, as a host tensor (``draw_view_pairs``); without
+    ``pair_rng`` only where no frame has more present pairs than ``n_iters``."""
+    host_vv = (host_view_valid != 0).cpu().numpy()
+    n_present = host_vv.sum(axis=1)
+    if bool((n_present * (n_present - 1) // 2 > n_iters).any()) and pair_rng is None:
+        raise NotImplementedError(_NEEDS_RNG)
+    return torch.from_numpy(draw_view_pairs(host_valid, v, n_iters, pair_rng, host_vv))
 
 
 def triangulation(
@@ -163,10 +239,13 @@ def triangulation(
     n_iters=64,
     reprojection_error_epsilon=5,
     direct_optimization=False,
+    view_valid=None,
 ):
     """One frame, reference signature and return types (utils/triangulation.py:168-233):
     heatmaps (V,J,Hh,Wh), proj (V,3,4), valid (J,) -> {"keypoints_3d": ndarray (J,3) f64,
-    "keypoints_2d": ndarray (V,J,2) int64|f32, "metric": float, "inlier_count": int}."""
+    "keypoints_2d": ndarray (V,J,2) int64|f32, "metric": float, "inlier_count": int}.
+    ``view_valid`` (V,): the views present in this frame (``triangulate_batch``); fewer than two of them with a valid
+    joint raise the reference's AssertionError."""
     if direct_optimization:
         raise NotImplementedError(
             "direct_optimization (scipy Huber least-squares, off in every reference call site): its result is where "
@@ -184,8 +263,11 @@ def triangulation(
         n_iters,
         reprojection_error_epsilon,
         pair_rng=random,
+        view_valid=None if view_valid is None else torch.as_tensor(view_valid).reshape(1, -1),
     )
     inl = int(r["inlier_count"][0].item())
+    if inl == -2:
+        raise AssertionError("need at least two views")  # reference: assert len(points) >= 2
     if inl < 0:
         raise ValueError("zero-size array to reduction operation minimum which has no identity")  # np.min([])
     return {

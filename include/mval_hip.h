@@ -601,6 +601,13 @@ typedef struct mval_p2_form {
   int32_t smem_bytes, threads;
 } mval_p2_form;
 int mval_conv_p2_form(int use, const mval_op* op, int n_images, mval_p2_form* form);
+/* The tiling of the four fused P2 launches as mval_op_launch runs them -- MVAL_OP_BLOCK (csrc/conv_block_p2.hip), MVAL_OP_BNECK
+ * (conv_bneck_p2.hip), MVAL_OP_STEM_P2 (conv_stem_p2.hip), MVAL_OP_FUSE_UP (conv_fuse_up_p2.hip) --, read from each launcher's own dry run: host
+ * arithmetic only, no GPU needed.  Fills th, tile_w (the output tile: 8 x 16 for the block and the Bottleneck, 2 x 16 for the stem, what the
+ * fuse-up launcher picks for the channel count and width -- its six instances differ in (cout, th, tile_w)), tiles_x, tiles_y, tiles_total,
+ * groups = 1, parities = 1, smem_bytes (the dynamic LDS of the launch) and threads; every other field is 0.  Returns 1, or 0 where
+ * mval_op_algo_supported(op, n_images, MVAL_ALGO_MFMA_P2) does not hold or the op is of another kind. */
+int mval_fused_p2_form(const mval_op* op, int n_images, mval_p2_form* form);
 
 int mval_op_launch(const mval_op* op, int n_images, float* workspace, const float* params,
                    const float* net_input, float* net_output, void* stream);

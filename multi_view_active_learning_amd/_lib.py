@@ -647,6 +647,14 @@ def conv_p2_form(use, op, n_images):
     return form if ok else None
 
 
+def fused_p2_form(op, n_images):
+    """mval_fused_p2_form: the tiling (P2Form: th, tile_w, tiles_*, groups, parities, smem_bytes, threads) of the fused P2 launch -- BasicBlock,
+    Bottleneck, stem, fuse-up -- mval_op_launch runs for the MvalOp ``op``, or None where it has no such kernel for it."""
+    form = P2Form()
+    ok = lib().mval_fused_p2_form(C.byref(op), C.c_int(n_images), C.byref(form))
+    return form if ok else None
+
+
 # --------------------------------------------------------------------------
 # core-set (k-center greedy)
 # --------------------------------------------------------------------------

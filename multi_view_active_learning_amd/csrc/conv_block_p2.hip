@@ -383,6 +383,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
 }
 
 static thread_local int g_bp_dry = 0;
+static thread_local mval_p2_form* g_bp_form = nullptr;  // dry runs leave the tiling they end on here (mval_fused_p2_form)
 
 template <int C>
 static int launch_block_p2(P2BlockArgs a, hipStream_t s) {
@@ -391,7 +392,14 @@ static int launch_block_p2(P2BlockArgs a, hipStream_t s) {
   constexpr size_t smem = (C > 32 ? XB : XB + MB) + 16;
   p2_walk_fill(a.walk, a.H, a.W, 8, 16, a.N);
   const int tiles_img = a.walk.tiles_x * a.walk.tiles_y;
-  if (g_bp_dry) return 0;
+  if (g_bp_dry) {
+    if (mval_p2_form* f = g_bp_form) {
+      f->th = 8; f->tile_w = 16; f->groups = 1; f->parities = 1;
+      f->tiles_x = a.walk.tiles_x; f->tiles_y = a.walk.tiles_y; f->tiles_total = a.walk.tiles_total;
+      f->smem_bytes = (int)smem; f->threads = 256;
+    }
+    return 0;
+  }
 #ifdef P2_STAMP
   a.dbg = g_p2_dbg_shared;
 #endif
@@ -429,4 +437,15 @@ int mval_launch_conv_block_p2(int C, const void* in, void* out, const float* w1,
   a.N = N; a.H = H; a.W = W;
   if (C == 32) return launch_block_p2<32>(a, s);
   return launch_block_p2<64>(a, s);
+}
+
+int mval_conv_block_p2_form(int C, int N, int H, int W, mval_p2_form* form) {  // net.hip mval_fused_p2_form: no launch, no HIP call
+  *form = {};
+  g_bp_form = form;
+  g_bp_dry = 1;
+  const int rc = mval_launch_conv_block_p2(C, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr, nullptr, N, H, W, nullptr);
+  g_bp_dry = 0;
+  g_bp_form = nullptr;
+  return rc == 0;
 }

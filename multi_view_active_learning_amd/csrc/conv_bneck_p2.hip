@@ -472,13 +472,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
 }
 
 static thread_local int g_bn_dry = 0;
+static thread_local mval_p2_form* g_bn_form = nullptr;  // dry runs leave the tiling they end on here (mval_fused_p2_form)
 
 template <int CIN>
 static int launch_bneck_p2(P2BneckArgs a, hipStream_t s) {
   constexpr size_t smem = 2 * 8 * 180 * 16 + 2 * 8 * 128 * 16 + 2048 + 16;
   p2_walk_fill(a.walk, a.H, a.W, 8, 16, a.N);
   const int tiles_img = a.walk.tiles_x * a.walk.tiles_y;
-  if (g_bn_dry) return 0;
+  if (g_bn_dry) {
+    if (mval_p2_form* f = g_bn_form) {
+      f->th = 8; f->tile_w = 16; f->groups = 1; f->parities = 1;
+      f->tiles_x = a.walk.tiles_x; f->tiles_y = a.walk.tiles_y; f->tiles_total = a.walk.tiles_total;
+      f->smem_bytes = (int)smem; f->threads = 256;
+    }
+    return 0;
+  }
 #ifdef P2_STAMP
   a.dbg = g_p2_dbg_shared;
 #endif
@@ -520,4 +528,15 @@ int mval_launch_conv_bneck_p2(int cin, const void* in, const void* res, void* ou
   a.N = N; a.H = H; a.W = W;
   if (cin == 64) return launch_bneck_p2<64>(a, s);
   return launch_bneck_p2<256>(a, s);
+}
+
+int mval_conv_bneck_p2_form(int cin, int N, int H, int W, mval_p2_form* form) {  // net.hip mval_fused_p2_form: no launch, no HIP call
+  static const int64_t zero[3] = {0, 0, 0};
+  *form = {};
+  g_bn_form = form;
+  g_bn_dry = 1;
+  const int rc = mval_launch_conv_bneck_p2(cin, nullptr, nullptr, nullptr, nullptr, zero, zero, zero, zero, zero, nullptr, nullptr, nullptr, N, H, W, nullptr);
+  g_bn_dry = 0;
+  g_bn_form = nullptr;
+  return rc == 0;
 }

@@ -184,6 +184,9 @@ static void fuse_up_tile(int cout, int W, int* th, int* tw) {
   if (cout == 96 && W % 36 == 0 && W % 32 != 0) *tw = 36;
 }
 
+static thread_local int g_fu_dry = 0;
+static thread_local mval_p2_form* g_fu_form = nullptr;  // dry runs leave the tiling they end on here (mval_fused_p2_form)
+
 int mval_conv_fuse_up_p2_supported(int cout, int n_terms, const int* cin, const int* up, int N, int H, int W) {
   if ((cout != 32 && cout != 64 && cout != 48 && cout != 96) || n_terms < 2 || n_terms > FU_MAX_TERMS) return 0;
   int th, tw;
@@ -224,6 +227,14 @@ int mval_launch_conv_fuse_up_p2(int cout, int n_terms, int relu, const void* res
   a.tiles_x = (W + tw - 1) / tw;
   a.tiles_y = (H + th - 1) / th;
   const int tiles_img = a.tiles_x * a.tiles_y;
+  if (g_fu_dry) {
+    if (mval_p2_form* f = g_fu_form) {
+      f->th = th; f->tile_w = tw; f->groups = 1; f->parities = 1;
+      f->tiles_x = a.tiles_x; f->tiles_y = a.tiles_y; f->tiles_total = tiles_img * N;
+      f->smem_bytes = (int)lds; f->threads = 256;
+    }
+    return 0;
+  }
   if (tiles_img > P2_SLOTS) mval_launch_zero_rows(out_row, (int64_t)N * P2_ROW, s);
   const dim3 grid((unsigned)(tiles_img * N));
   if (cout == 32) hipLaunchKernelGGL((conv_fuse_up_p2_kernel<32>), grid, dim3(256), lds, s, a);
@@ -233,4 +244,18 @@ int mval_launch_conv_fuse_up_p2(int cout, int n_terms, int relu, const void* res
   else if (tw == 36) hipLaunchKernelGGL((conv_fuse_up_p2_kernel<96, 4, 36>), grid, dim3(256), lds, s, a);
   else hipLaunchKernelGGL((conv_fuse_up_p2_kernel<96, 4, 32>), grid, dim3(256), lds, s, a);
   return 0;
+}
+
+int mval_conv_fuse_up_p2_form(int cout, int n_terms, const int* cin, const int* up, int N, int H, int W, mval_p2_form* form) {  // net.hip mval_fused_p2_form
+  static const int64_t zero[FU_MAX_TERMS] = {};
+  static const void* const no_in[FU_MAX_TERMS] = {};
+  static const unsigned* const no_row[FU_MAX_TERMS] = {};
+  *form = {};
+  g_fu_form = form;
+  g_fu_dry = 1;
+  const int rc = mval_launch_conv_fuse_up_p2(cout, n_terms, 0, nullptr, nullptr, nullptr, nullptr, nullptr, no_in, no_row, cin, up, zero, zero, zero, zero, zero, N, H,
+                                             W, nullptr);
+  g_fu_dry = 0;
+  g_fu_form = nullptr;
+  return rc == 0;
 }

@@ -332,6 +332,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   P2F_FLUSH;
 }
 
+static thread_local int g_st_dry = 0;
+static thread_local mval_p2_form* g_st_form = nullptr;  // dry runs leave the tiling they end on here (mval_fused_p2_form)
+
 int mval_conv_stem_p2_supported(int N, int H, int W) {
   if (H < 16 || W < 64 || (H & 3) || (W & 3)) return 0;
   if ((int64_t)N * 3 * H * W * 4 >= ((int64_t)1 << 31)) return 0;  // byte offsets into the image below 2^31
@@ -352,9 +355,17 @@ int mval_launch_conv_stem_p2(const float* in, void* out, const float* w1, const 
   a.H2 = (a.H1 - 1) / 2 + 1; a.W2 = (a.W1 - 1) / 2 + 1;
   p2_walk_fill(a.walk, a.H2, a.W2, 2, 16, N);
   const int tiles_img = a.walk.tiles_x * a.walk.tiles_y;
+  constexpr size_t smem = 2 * 8 * 170 * 16 + 3 * 11 * 68 * 4 + 16 + 512;
+  if (g_st_dry) {
+    if (mval_p2_form* f = g_st_form) {
+      f->th = 2; f->tile_w = 16; f->groups = 1; f->parities = 1;
+      f->tiles_x = a.walk.tiles_x; f->tiles_y = a.walk.tiles_y; f->tiles_total = a.walk.tiles_total;
+      f->smem_bytes = (int)smem; f->threads = 256;
+    }
+    return 0;
+  }
   // max |x| per image: 64 partial slots of the input's rows
   hipLaunchKernelGGL(image_amax_rows_kernel, dim3(64, (unsigned)N), dim3(256), 0, s, in, (int64_t)3 * H * W, in_row);
-  constexpr size_t smem = 2 * 8 * 170 * 16 + 3 * 11 * 68 * 4 + 16 + 512;
   static std::atomic<int> occ{0};
   int per_cu = p2_resident_wgs(&conv_stem_p2_kernel, occ, smem, 4);
 #ifdef P2_TUNE  // (measurement builds only: workgroups per CU)
@@ -369,4 +380,15 @@ int mval_launch_conv_stem_p2(const float* in, void* out, const float* w1, const 
   if (tiles_img > P2_SLOTS) mval_launch_zero_rows(out_row, (int64_t)N * P2_ROW, s);
   hipLaunchKernelGGL(conv_stem_p2_kernel, dim3((unsigned)wgs), dim3(256), smem, s, a);
   return 0;
+}
+
+int mval_conv_stem_p2_form(int N, int H, int W, mval_p2_form* form) {  // net.hip mval_fused_p2_form: no launch, no HIP call
+  *form = {};
+  g_st_form = form;
+  g_st_dry = 1;
+  const int rc = mval_launch_conv_stem_p2(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, H,
+                                          W, nullptr);
+  g_st_dry = 0;
+  g_st_form = nullptr;
+  return rc == 0;
 }

@@ -634,6 +634,23 @@ extern "C" int mval_conv_p2_form(int use, const mval_op* op, int n_images, mval_
   return mval_conv_p2_form_of(p, form);
 }
 
+// The same for the four fused P2 launches (include/mval_hip.h): each launcher's dry run (conv_block_p2.hip, conv_bneck_p2.hip,
+// conv_stem_p2.hip, conv_fuse_up_p2.hip) called with the arguments mval_op_launch passes it.  No HIP call.
+int mval_conv_block_p2_form(int C, int N, int H, int W, mval_p2_form* form);
+int mval_conv_bneck_p2_form(int cin, int N, int H, int W, mval_p2_form* form);
+int mval_conv_stem_p2_form(int N, int H, int W, mval_p2_form* form);
+int mval_conv_fuse_up_p2_form(int cout, int n_terms, const int* cin, const int* up, int N, int H, int W, mval_p2_form* form);
+extern "C" int mval_fused_p2_form(const mval_op* op, int n_images, mval_p2_form* form) {
+  if (!op || !form || n_images <= 0) return 0;
+  if (op->kind != MVAL_OP_BLOCK && op->kind != MVAL_OP_BNECK && op->kind != MVAL_OP_STEM_P2 && op->kind != MVAL_OP_FUSE_UP) return 0;
+  if (!mval_op_algo_supported(op, n_images, MVAL_ALGO_MFMA_P2)) return 0;
+  *form = {};
+  if (op->kind == MVAL_OP_BLOCK) return mval_conv_block_p2_form(op->cin, n_images, op->hin, op->win, form);
+  if (op->kind == MVAL_OP_BNECK) return mval_conv_bneck_p2_form(op->cin, n_images, op->hin, op->win, form);
+  if (op->kind == MVAL_OP_STEM_P2) return mval_conv_stem_p2_form(n_images, op->hin, op->win, form);
+  return mval_conv_fuse_up_p2_form(op->cout, op->n_terms, op->t_cin, op->t_up, n_images, op->hout, op->wout, form);
+}
+
 #define MVAL_MAX_DEVICES 16
 static MvalLanes g_lanes[MVAL_MAX_DEVICES];
 

@@ -478,6 +478,7 @@ def test_form_struct_mirrors_match_the_header():
         assert fields == [name for name, _ in mirror._fields_], struct
         assert all(t is C.c_int32 for _, t in mirror._fields_) and C.sizeof(mirror) == 4 * len(fields), struct
         assert hasattr(lib, struct.replace("mval_", "mval_conv_")), struct
+    assert hasattr(lib, "mval_fused_p2_form") and re.search(r"int mval_fused_p2_form\(const mval_op\* op, int n_images, mval_p2_form\* form\);", text)
     uses = [int(re.search(r"\bMVAL_SPLIT_USE_%s\s*=\s*(\d+)" % n, text).group(1)) for n in ("OP", "TRAIN_FWD", "DGRAD", "DGRAD_PARITY")]
     assert uses == [_lib.SPLIT_USE_OP, _lib.SPLIT_USE_TRAIN_FWD, _lib.SPLIT_USE_DGRAD, _lib.SPLIT_USE_DGRAD_PARITY]
 

@@ -64,6 +64,11 @@ int mval_pred_coordinates_from_keys(const uint64_t* keys, const float* boxes, fl
  * * stride): softmax over hh*wh, expectation of the pixel grid; kp2d [n_maps,2] f32 (x,y)*scale. */
 int mval_soft_argmax(const float* heatmaps, float* kp2d, int64_t n_maps, int hh, int wh, float scale, void* stream);
 
+/* Peak gate: out[m] = 1 iff some element of map m is >= min_peak, else 0 (a comparison: a map of NaNs gives 0; exact, no
+ * tolerance).  heatmaps [n_maps,hh,wh] f32 ; out [n_maps] u8.  One read of the maps.  With n_maps = B*V*J in the maps' own
+ * order the result is a view_joint_valid [B,V,J] for the `_vj` entries below. */
+int mval_peak_mask(const float* heatmaps, float min_peak, uint8_t* out, int64_t n_maps, int hh, int wh, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Triangulation
  * ---------------------------------------------------------------------------------- */
@@ -136,6 +141,30 @@ int mval_triangulate_ransac_pairs_views(const void* kp2d, int kp_is_f32, const d
 int mval_reprojection_xe_views(const double* kp3d, const double* proj, const float* heatmaps, const uint8_t* view_valid,
                                double* out, double* ws, int B, int V, int J, int hh, int wh, double sigma, void* stream);
 
+/* Joints missing from single views.  view_joint_valid [B,V,J] u8, nonzero = joint j is usable in view v of frame b (never
+ * NULL: a NULL mask is an error and nothing is launched).  The present views are a property of the PROBLEM (frame, joint):
+ * for a valid joint with two or more present views the result is what the entry without `_vj` gives on that joint's present
+ * views alone (B = 1, J = 1), bit for bit.  Nothing of an absent entry is used: it never votes, is never an inlier or part
+ * of a walked pair, is skipped by the final DLT, and its key-point row may hold anything, NaN included.  All problems of a
+ * batch go through one launch however their sets differ.  Same V / J / P limits and pair-table rules as the `_views` entries
+ * (a per-problem table names original view indices; entries naming an absent view or a view >= V take no part).
+ *   A valid joint with fewer than two present views is written like an invalid joint: kp3d, joint_err, joint_inliers 0.
+ *   metric (mean) and inlier_count (min) of a frame run over its USED joints: valid and two or more present views.  A used
+ *   joint has joint_inliers >= 2 (the winning pair is in its own set), so joint_inliers > 0 is the used mask.
+ *   No valid joint -> inlier_count -1; a valid joint but no used joint -> -2; metric NaN in both. */
+int mval_triangulate_ransac_vj(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                               const uint8_t* view_joint_valid, double* kp3d, double* joint_err, int32_t* joint_inliers,
+                               double* metric, int32_t* inlier_count, int B, int V, int J, double eps, void* stream);
+int mval_triangulate_ransac_pairs_vj(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                     const uint8_t* view_joint_valid, const uint8_t* pairs, int P, int pairs_shared,
+                                     double* kp3d, double* joint_err, int32_t* joint_inliers, double* metric,
+                                     int32_t* inlier_count, int B, int V, int J, double eps, void* stream);
+
+/* mval_reprojection_xe over the present entries: the map of an absent (view, joint) entry is not read, its ws slot is not
+ * written, and the serial view-major, joint-minor sum skips it.  A frame without a present entry gives 0. */
+int mval_reprojection_xe_vj(const double* kp3d, const double* proj, const float* heatmaps, const uint8_t* view_joint_valid,
+                            double* out, double* ws, int B, int V, int J, int hh, int wh, double sigma, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Uncertainty scorers (strategy.py:1149-1215)
  * ---------------------------------------------------------------------------------- */
@@ -184,6 +213,12 @@ int mval_score_reduce(const float* per_map, const uint8_t* valid, double* out, i
  * per mode, so a frame gives what mval_score_reduce gives on its present views alone.  n = 0 -> NaN. */
 int mval_score_reduce_views(const float* per_map, const uint8_t* valid, const uint8_t* view_valid, double* out, int B,
                             int V, int J, int mode, void* stream);
+
+/* mval_score_reduce over the present entries of each frame (view_joint_valid [B,V,J] u8, never NULL): a map counts when its
+ * joint is valid and its own entry is nonzero; n = the entries left; same loop order and precision per mode, so a frame gives
+ * what mval_score_reduce gives on the compacted list (V = 1, J = n).  n = 0 -> NaN. */
+int mval_score_reduce_vj(const float* per_map, const uint8_t* valid, const uint8_t* view_joint_valid, double* out, int B,
+                         int V, int J, int mode, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Loss / metric

@@ -258,6 +258,12 @@ _VIEWS_ARGTYPES = {
     "mval_triangulate_ransac_pairs_views": [_VOIDP, _INT] + [_VOIDP] * 4 + [_INT] * 2 + [_VOIDP] * 5 + [_INT] * 3 + [_DOUBLE, _VOIDP],
     "mval_reprojection_xe_views": [_VOIDP] * 6 + [_INT] * 5 + [_DOUBLE, _VOIDP],
     "mval_score_reduce_views": [_VOIDP] * 4 + [_INT] * 4 + [_VOIDP],
+    # joints missing from single views: the `_vj` twins take view_joint_valid (B, V, J) where those take view_valid (B, V)
+    "mval_triangulate_ransac_vj": [_VOIDP, _INT] + [_VOIDP] * 8 + [_INT] * 3 + [_DOUBLE, _VOIDP],
+    "mval_triangulate_ransac_pairs_vj": [_VOIDP, _INT] + [_VOIDP] * 4 + [_INT] * 2 + [_VOIDP] * 5 + [_INT] * 3 + [_DOUBLE, _VOIDP],
+    "mval_reprojection_xe_vj": [_VOIDP] * 6 + [_INT] * 5 + [_DOUBLE, _VOIDP],
+    "mval_score_reduce_vj": [_VOIDP] * 4 + [_INT] * 4 + [_VOIDP],
+    "mval_peak_mask": [_VOIDP, C.c_float, _VOIDP, C.c_longlong, _INT, _INT, _VOIDP],
 }
 
 
@@ -304,6 +310,59 @@ def reprojection_xe_views(kp3d, proj, hm, view_valid, b, v, j, hh, wh, sigma):
             b, v, j, hh, wh, sigma, _stream(),
         ),
         "mval_reprojection_xe_views",
+    )
+    return out
+
+
+# Joints missing from single views (include/mval_hip.h, the `_vj` entries): view_joint_valid (B, V, J) uint8 on the device,
+# nonzero = joint j is usable in view v of frame b.
+def _req_view_joint_valid(view_joint_valid, b, v, j):
+    _req(view_joint_valid, torch.uint8, "view_joint_valid")
+    if tuple(view_joint_valid.shape) != (b, v, j):
+        raise MvalError(f"view_joint_valid: expected ({b}, {v}, {j}), got {tuple(view_joint_valid.shape)}")
+    return view_joint_valid
+
+
+def triangulate_ransac_vj(kp2d, proj, valid, view_joint_valid, b, v, j, eps):
+    """mval_triangulate_ransac_vj: ``triangulate_ransac`` over the present views of each (frame, joint) problem (V <= 11)."""
+    _views_entry("mval_triangulate_ransac_vj")
+    return _triangulate("mval_triangulate_ransac_vj", kp2d, proj, valid, b, v, j, eps,
+                        table=(_p(_req_view_joint_valid(view_joint_valid, b, v, j)),))
+
+
+def triangulate_ransac_pairs_vj(kp2d, proj, valid, view_joint_valid, pairs, b, v, j, eps):
+    """mval_triangulate_ransac_pairs_vj: ``triangulate_ransac_pairs`` over the present views of each problem; the table names
+    original view indices, entries >= V (255: padding) or naming a view the joint is absent from take no part."""
+    _req(pairs, torch.uint8, "pairs")
+    shared = pairs.dim() == 3
+    if pairs.shape[-1] != 2 or (tuple(pairs.shape[:-2]) != (1,) if shared else tuple(pairs.shape[:-2]) != (b, j)):
+        raise MvalError(f"pairs: expected (1, P, 2) or ({b}, {j}, P, 2), got {tuple(pairs.shape)}")
+    _views_entry("mval_triangulate_ransac_pairs_vj")
+    return _triangulate("mval_triangulate_ransac_pairs_vj", kp2d, proj, valid, b, v, j, eps,
+                        table=(_p(_req_view_joint_valid(view_joint_valid, b, v, j)), _p(pairs), C.c_int(pairs.shape[-2]),
+                               C.c_int(int(shared))))
+
+
+def reprojection_xe_vj(kp3d, proj, hm, view_joint_valid, b, v, j, hh, wh, sigma):
+    out = torch.empty((b,), dtype=torch.float64, device=hm.device)
+    ws = torch.empty((b * v * j,), dtype=torch.float64, device=hm.device)
+    _check(
+        _views_entry("mval_reprojection_xe_vj")(
+            _p(_req(kp3d, torch.float64, "keypoints_3d")), _p(_req(proj, torch.float64, "proj")),
+            _p(_req(hm, torch.float32, "heatmaps")), _p(_req_view_joint_valid(view_joint_valid, b, v, j)), _p(out), _p(ws),
+            b, v, j, hh, wh, sigma, _stream(),
+        ),
+        "mval_reprojection_xe_vj",
+    )
+    return out
+
+
+def peak_mask(hm, min_peak, n_maps, hh, wh):
+    """mval_peak_mask: (n_maps,) uint8, 1 where some element of the map is >= min_peak."""
+    out = torch.empty((n_maps,), dtype=torch.uint8, device=hm.device)
+    _check(
+        _views_entry("mval_peak_mask")(_p(_req(hm, torch.float32, "heatmaps")), float(min_peak), _p(out), n_maps, hh, wh, _stream()),
+        "mval_peak_mask",
     )
     return out
 
@@ -397,6 +456,19 @@ def score_reduce_views(per_map, valid, view_valid, b, v, j, mode):
             b, v, j, mode, _stream(),
         ),
         "mval_score_reduce_views",
+    )
+    return out
+
+
+def score_reduce_vj(per_map, valid, view_joint_valid, b, v, j, mode):
+    """mval_score_reduce_vj: ``score_reduce`` over the present (view, joint) entries of each frame."""
+    out = torch.empty((b,), dtype=torch.float64, device=per_map.device)
+    _check(
+        _views_entry("mval_score_reduce_vj")(
+            _p(_req(per_map, torch.float32, "per_map")), _p(valid), _p(_req_view_joint_valid(view_joint_valid, b, v, j)), _p(out),
+            b, v, j, mode, _stream(),
+        ),
+        "mval_score_reduce_vj",
     )
     return out
 

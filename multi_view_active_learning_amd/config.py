@@ -54,6 +54,10 @@ def get_default_configs():
     c.AL.BSB_CONFIG = "AVG"
     c.AL.HP_CONFIG = "AVG"
     c.AL.CORESET_METRIC = "euclidean"  # not in the reference (it never passes another): the names of _lib.KC_METRIC_IDS
+    # not in the reference (which has no per-(view, joint) visibility in its post stage): check_view_joint_valid below.  With both at
+    # their defaults only a batch's own "view_joint_valid" key masks anything
+    c.AL.VIEW_JOINT_VALID_KEY = ""  # a batch key whose (B, V, J) tensor is the visibility mask, e.g. "per_view_joint_valid"
+    c.AL.MIN_PEAK = 0.0  # > 0: a (view, joint) entry also needs a heat-map value >= this (utils.triangulation.peak_mask)
     c.AL.CLUSTER = CN()  # EXPR_TYPE "CLUSTER" (strategy.py:137-191): what ActiveLearningStrategy.cluster writes
     c.AL.CLUSTER.TYPE = "LOSS"  # LOSS | POSE (cluster_type below)
     c.AL.CLUSTER.SAVE_PATH = ""
@@ -108,3 +112,13 @@ def check_rotate_targets(value):
     if value not in ROTATE_TARGETS:
         raise ValueError("DATA.ROTATE_TARGETS %r: accepted are %s" % (value, ", ".join(repr(m) for m in ROTATE_TARGETS)))
     return value
+
+
+def check_view_joint_valid(key, min_peak):
+    """Valid AL.VIEW_JOINT_VALID_KEY (a string; "" = no named key) and AL.MIN_PEAK (a finite number >= 0; 0 = no peak gate), or
+    ValueError saying what is accepted.  Returns (key, float(min_peak))."""
+    if not isinstance(key, str):
+        raise ValueError("AL.VIEW_JOINT_VALID_KEY %r: accepted is a string, the name of a batch key (\"\" for none)" % (key,))
+    if isinstance(min_peak, bool) or not isinstance(min_peak, (int, float)) or not 0.0 <= float(min_peak) < float("inf"):
+        raise ValueError("AL.MIN_PEAK %r: accepted is a finite number >= 0 (0 switches the peak gate off)" % (min_peak,))
+    return key, float(min_peak)

@@ -201,3 +201,37 @@ extern "C" int mval_soft_argmax(const float* heatmaps, float* kp2d, int64_t n_ma
   MVAL_CHECK_LAUNCH("mval_soft_argmax");
   return 0;
 }
+
+// ---- peak gate: which maps have a peak of at least min_peak (utils.triangulation.peak_mask) ---------------------------------
+// One streaming read of the maps, one wave per map like the decode above.  `x >= min_peak` is false for a NaN, so a map
+// of NaNs is absent; the wave-wide OR is a ballot.
+__global__ __launch_bounds__(256) void peak_mask_kernel(const float* __restrict__ hm, uint8_t* __restrict__ out, int64_t n_maps,
+                                                        int npix, float min_peak) {
+  const int lane = threadIdx.x & 63;
+  const int64_t map = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (map >= n_maps) return;
+  const float* p = hm + map * (int64_t)npix;
+  bool hit = false;
+  if ((npix & 3) == 0 && ((uintptr_t)p & 15) == 0) {
+    const float4* p4 = reinterpret_cast<const float4*>(p);
+    for (int i = lane; i < (npix >> 2); i += 64) {
+      const float4 q = p4[i];
+      hit |= (q.x >= min_peak) | (q.y >= min_peak) | (q.z >= min_peak) | (q.w >= min_peak);
+    }
+  } else {
+    for (int i = lane; i < npix; i += 64) hit |= p[i] >= min_peak;
+  }
+  const bool any = __ballot(hit) != 0ull;
+  if (lane == 0) out[map] = any ? 1 : 0;
+}
+
+extern "C" int mval_peak_mask(const float* heatmaps, float min_peak, uint8_t* out, int64_t n_maps, int hh, int wh, void* stream) {
+  MVAL_REQUIRE(n_maps >= 0 && hh > 0 && wh > 0 && (int64_t)hh * wh <= 0x7fffffff, "mval_peak_mask: bad dims");
+  if (n_maps == 0) return 0;
+  MVAL_REQUIRE(heatmaps && out, "mval_peak_mask: heatmaps and out must not be NULL");
+  MVAL_REQUIRE((n_maps + 3) / 4 <= 0x7fffffff, "mval_peak_mask: too many maps");
+  hipLaunchKernelGGL(peak_mask_kernel, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, mval_stream(stream), heatmaps, out,
+                     n_maps, hh * wh, min_peak);
+  MVAL_CHECK_LAUNCH("mval_peak_mask");
+  return 0;
+}

@@ -30,6 +30,10 @@ void mval_set_error(const char* fmt, ...);
 
 static inline hipStream_t mval_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// What the mask argument of a post-stage kernel is (template parameter of the triangulation, XE and score-reduce kernels):
+// nothing, view_valid [B,V] (frames with missing views) or view_joint_valid [B,V,J] (joints missing from single views).
+enum { MASK_NONE = 0, MASK_VIEWS = 1, MASK_VIEW_JOINT = 2 };
+
 // ---- wave-level reductions (64 lanes) ------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -597,16 +597,27 @@ extern "C" int mval_score_decode_maps_all(const float* heatmaps, const uint8_t* 
 
 // MASKED: the maps of the views whose view_valid is 0 are left out (and not read): n = valid joints x present views, the same
 // loops over what is left -- what the unmasked kernel computes on the frame's present views alone.
-template <bool MASKED>
+// MASK_VIEW_JOINT: `view_valid` is view_joint_valid [B,V,J]; a map counts when its joint is valid and its own entry is set:
+// n = the entries left, the same loops over them -- the unmasked kernel on the compacted list (V = 1, J = n).
+template <int MASK>
 __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uint8_t* __restrict__ valid,
                                     const uint8_t* __restrict__ view_valid, double* __restrict__ out, int B, int V, int J,
                                     int mode) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const float* pm = per_map + (int64_t)b * V * J;
+  constexpr bool MASKED = MASK == MASK_VIEWS;
   const uint8_t* vv = MASKED ? view_valid + (int64_t)b * V : nullptr;
+  const uint8_t* vj = MASK == MASK_VIEW_JOINT ? view_valid + (int64_t)b * V * J : nullptr;
+  const auto used = [&](int v, int j) { return (!valid || valid[(int64_t)b * J + j]) && (MASK != MASK_VIEW_JOINT || vj[v * J + j]); };
   int n = 0, nv = V;
-  for (int j = 0; j < J; j++) n += (!valid || valid[(int64_t)b * J + j]) ? 1 : 0;
+  if (MASK == MASK_VIEW_JOINT) {
+    for (int v = 0; v < V; v++)
+      for (int j = 0; j < J; j++) n += used(v, j) ? 1 : 0;
+    nv = 1;
+  } else {
+    for (int j = 0; j < J; j++) n += (!valid || valid[(int64_t)b * J + j]) ? 1 : 0;
+  }
   if (MASKED) {
     nv = 0;
     for (int v = 0; v < V; v++) nv += vv[v] ? 1 : 0;
@@ -618,7 +629,7 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
     for (int v = 0; v < V; v++) {
       if (MASKED && !vv[v]) continue;
       for (int j = 0; j < J; j++)
-        if (!valid || valid[(int64_t)b * J + j]) s += (double)pm[v * J + j];
+        if (used(v, j)) s += (double)pm[v * J + j];
     }
     out[b] = s / (double)n;
   } else if (mode == MVAL_REDUCE_AVG_F32) {  // sum(np.float32) / len  (float32 throughout)
@@ -626,7 +637,7 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
     for (int v = 0; v < V; v++) {
       if (MASKED && !vv[v]) continue;
       for (int j = 0; j < J; j++)
-        if (!valid || valid[(int64_t)b * J + j]) s += pm[v * J + j];
+        if (used(v, j)) s += pm[v * J + j];
     }
     out[b] = (double)(s / (float)n);
   } else if (mode == MVAL_REDUCE_STD_F64) {  // np.std(float64 array)
@@ -635,7 +646,7 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
     for (int v = 0; v < V; v++) {
       if (MASKED && !vv[v]) continue;
       for (int j = 0; j < J; j++)
-        if (!valid || valid[(int64_t)b * J + j]) buf[k++] = (double)pm[v * J + j];
+        if (used(v, j)) buf[k++] = (double)pm[v * J + j];
     }
     double mean = np_pairwise_sum<double>(buf, n) / (double)n;
     for (int i = 0; i < n; i++) { double d = buf[i] - mean; buf[i] = d * d; }
@@ -646,7 +657,7 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
     for (int v = 0; v < V; v++) {
       if (MASKED && !vv[v]) continue;
       for (int j = 0; j < J; j++)
-        if (!valid || valid[(int64_t)b * J + j]) buf[k++] = pm[v * J + j];
+        if (used(v, j)) buf[k++] = pm[v * J + j];
     }
     float mean = (float)((double)np_pairwise_sum<float>(buf, n) / (double)n);
     for (int i = 0; i < n; i++) { float d = buf[i] - mean; buf[i] = d * d; }
@@ -660,7 +671,7 @@ extern "C" int mval_score_reduce(const float* per_map, const uint8_t* valid, dou
   MVAL_REQUIRE(mode >= 0 && mode <= 3, "mval_score_reduce: unknown mode %d", mode);
   if (B == 0) return 0;
   const uint8_t* const no_mask = nullptr;
-  hipLaunchKernelGGL(score_reduce_kernel<false>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map, valid,
+  hipLaunchKernelGGL(score_reduce_kernel<MASK_NONE>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map, valid,
                      no_mask, out, B, V, J, mode);
   MVAL_CHECK_LAUNCH("mval_score_reduce");
   return 0;
@@ -672,8 +683,20 @@ extern "C" int mval_score_reduce_views(const float* per_map, const uint8_t* vali
   MVAL_REQUIRE(mode >= 0 && mode <= 3, "mval_score_reduce_views: unknown mode %d", mode);
   MVAL_REQUIRE(view_valid, "mval_score_reduce_views: view_valid is NULL (use mval_score_reduce)");
   if (B == 0) return 0;
-  hipLaunchKernelGGL(score_reduce_kernel<true>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map, valid,
+  hipLaunchKernelGGL(score_reduce_kernel<MASK_VIEWS>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map, valid,
                      view_valid, out, B, V, J, mode);
   MVAL_CHECK_LAUNCH("mval_score_reduce_views");
+  return 0;
+}
+
+extern "C" int mval_score_reduce_vj(const float* per_map, const uint8_t* valid, const uint8_t* view_joint_valid, double* out,
+                                    int B, int V, int J, int mode, void* stream) {
+  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && V * J <= SR_MAX, "mval_score_reduce_vj: bad dims (V*J must be <= %d)", SR_MAX);
+  MVAL_REQUIRE(mode >= 0 && mode <= 3, "mval_score_reduce_vj: unknown mode %d", mode);
+  MVAL_REQUIRE(view_joint_valid, "mval_score_reduce_vj: view_joint_valid is NULL (use mval_score_reduce)");
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(score_reduce_kernel<MASK_VIEW_JOINT>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map, valid,
+                     view_joint_valid, out, B, V, J, mode);
+  MVAL_CHECK_LAUNCH("mval_score_reduce_vj");
   return 0;
 }

@@ -28,6 +28,12 @@
 // kernels.  A frame's present views are the bits of `present`; a pair with an absent view sits out, the vote and the
 // "no usable pair" fallback run over present views only, and nothing of an absent view (key-point row, matrix) is read.
 // MASKED is a template parameter: the unmasked instantiations compile to the code they were without it.
+//
+// Joints missing from single views: the `_vj` entries take view_joint_valid [B,V,J] u8 and run the MASK_VIEW_JOINT
+// instantiations.  `present` is then a property of the problem (frame, joint), folded from the joint's column of the mask;
+// everything a lane does with it is what it does with a frame's word.  A valid joint with fewer than two present views is
+// written like an invalid one, and frame_reduce_kernel runs over the USED joints (valid, two or more views) -- which are
+// the joints with joint_inliers > 0, a winning pair being part of its own inlier set.
 #include "mval_common.h"
 #include "numeric_order.h"  // np_pairwise_sum: np.mean's order
 
@@ -147,8 +153,8 @@ __device__ __forceinline__ double reproj_err(const double* __restrict__ P, const
 }
 
 // stage 1 of one lane: triangulate the view pair (a, c) and vote over all V views -> inlier mask (a and c always in it)
-// (MASKED: over the views of `present` only)
-template <bool MASKED = false, typename KP>
+// (MASK != MASK_NONE: over the views of `present` only)
+template <int MASK = MASK_NONE, typename KP>
 __device__ __forceinline__ unsigned vote_pair(const double* __restrict__ Pb, const KP* __restrict__ kb, int V, int J,
                                               int a, int c, double eps, unsigned present = 0u) {
   R4 m;
@@ -160,7 +166,7 @@ __device__ __forceinline__ unsigned vote_pair(const double* __restrict__ Pb, con
   dehomogenise(h, X);
   unsigned mask = (1u << a) | (1u << c);
   for (int v = 0; v < V; v++) {
-    if (MASKED && !(present >> v & 1)) continue;
+    if (MASK != MASK_NONE && !(present >> v & 1)) continue;
     double e = reproj_err(Pb + v * 12, X, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
     if (e < eps) mask |= 1u << v;
   }
@@ -206,12 +212,24 @@ __device__ __forceinline__ unsigned present_views(const uint8_t* __restrict__ vv
   return m;
 }
 
+// the present views of one problem as bits: of its frame (MASK_VIEWS, mask [B,V]) or of its joint in that frame
+// (MASK_VIEW_JOINT, mask [B,V,J])
+template <int MASK>
+__device__ __forceinline__ unsigned present_of(const uint8_t* __restrict__ mask, int64_t b, int j, int V, int J) {
+  if (MASK == MASK_VIEWS) return present_views(mask + b * V, V);
+  unsigned m = 0;
+  if (MASK == MASK_VIEW_JOINT)
+    for (int v = 0; v < V; v++)
+      if (mask[(b * V + v) * J + j]) m |= 1u << v;
+  return m;
+}
+
 // All C(V,2) pairs in lexicographic order, pair p on lane p of the problem's group (V <= MAXV: n_pairs <= 64).
 // MASKED: lane p keeps its pair and sits out when one of its views is absent; the pairs that take part are the
 // lexicographic pairs of the present views in the same relative order, so the key picks the winner the unmasked
 // kernel picks on the frame's present views alone.  Fewer than two present views: the problem is written as an
-// invalid joint's (frame_reduce_kernel marks the frame).
-template <bool MASKED, typename KP>
+// invalid joint's (frame_reduce_kernel marks the frame).  MASK_VIEW_JOINT: the same with the problem's own `present`.
+template <int MASK, typename KP>
 __global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ kp2d, const double* __restrict__ proj,
                                                          const uint8_t* __restrict__ valid,
                                                          const uint8_t* __restrict__ view_valid,
@@ -229,7 +247,8 @@ __global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ k
   const double* Pb = proj + b * V * 12;
   const KP* kb = kp2d + (b * V * (int64_t)J + j) * 2;  // + v * J * 2
 
-  const unsigned present = MASKED ? present_views(view_valid + b * V, V) : 0u;
+  constexpr bool MASKED = MASK != MASK_NONE;
+  const unsigned present = present_of<MASK>(view_valid, b, j, V, J);
 
   unsigned mask = 0;
   bool voted = false;
@@ -238,7 +257,7 @@ __global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ k
     while (rem >= V - 1 - a) { rem -= V - 1 - a; a++; }
     const int c = a + 1 + rem;
     voted = !MASKED || ((present >> a & 1) && (present >> c & 1));
-    if (voted) mask = vote_pair<MASKED>(Pb, kb, V, J, a, c, eps, present);
+    if (voted) mask = vote_pair<MASK>(Pb, kb, V, J, a, c, eps, present);
   }
   // first pair with the strictly largest set: key = count * 64 + (63 - p), maximise
   int key = voted ? __popc(mask) * 64 + (63 - p) : -1;
@@ -258,7 +277,7 @@ __global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ k
 // lowest position among equal counts: the winner is the first position with the largest set (utils/triangulation.py
 // :299-300).  key = count * 512 + (511 - position) <= 32 * 512 + 511.  An entry that names a view >= V takes no part.
 // MASKED: neither does one that names an absent view, and the fallback is all PRESENT views.
-template <bool MASKED, typename KP>
+template <int MASK, typename KP>
 __global__ __launch_bounds__(64) void ransac_pairs_kernel(const KP* __restrict__ kp2d, const double* __restrict__ proj,
                                                            const uint8_t* __restrict__ valid,
                                                            const uint8_t* __restrict__ view_valid,
@@ -277,7 +296,8 @@ __global__ __launch_bounds__(64) void ransac_pairs_kernel(const KP* __restrict__
   const double* Pb = proj + b * V * 12;
   const KP* kb = kp2d + (b * V * (int64_t)J + j) * 2;  // + v * J * 2
   const uint8_t* tab = pairs + pr * pairs_stride;
-  const unsigned present = MASKED ? present_views(view_valid + b * V, V) : 0u;
+  constexpr bool MASKED = MASK != MASK_NONE;
+  const unsigned present = present_of<MASK>(view_valid, b, j, V, J);
 
   int key = -1;
   unsigned mask = 0;
@@ -286,7 +306,7 @@ __global__ __launch_bounds__(64) void ransac_pairs_kernel(const KP* __restrict__
       int a = tab[p * 2], c = tab[p * 2 + 1];
       if (a >= V || c >= V) continue;
       if (MASKED && !((present >> a & 1) && (present >> c & 1))) continue;
-      unsigned m = vote_pair<MASKED>(Pb, kb, V, J, a, c, eps, present);
+      unsigned m = vote_pair<MASK>(Pb, kb, V, J, a, c, eps, present);
       int k = __popc(m) * 512 + (511 - p);
       if ((k >> 9) > (key >> 9)) { key = k; mask = m; }  // key = -1 >> 9 = -1: any set beats none
     }
@@ -305,13 +325,15 @@ __global__ __launch_bounds__(64) void ransac_pairs_kernel(const KP* __restrict__
 // MASKED: a frame with a valid joint and fewer than two present views gets metric NaN and inlier_count -2 (the reference
 // asserts len(points) >= 2 inside the first valid joint, :268); without a valid joint it stays -1 (np.min([]) comes
 // without any assert).
-template <bool MASKED>
+// MASK_VIEW_JOINT: mean and min run over the used joints, those with joint_inliers > 0 (a valid joint with fewer than two
+// present views was written with 0, as an invalid one); a valid joint but no used one: metric NaN, inlier_count -2.
+template <int MASK>
 __global__ void frame_reduce_kernel(const double* __restrict__ joint_err, const int32_t* __restrict__ joint_inliers,
                                     const uint8_t* __restrict__ valid, const uint8_t* __restrict__ view_valid,
                                     double* __restrict__ metric, int32_t* __restrict__ inlier_count, int B, int V, int J) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  if (MASKED && __popc(present_views(view_valid + (int64_t)b * V, V)) < 2) {
+  if (MASK == MASK_VIEWS && __popc(present_views(view_valid + (int64_t)b * V, V)) < 2) {
     bool any = false;
     for (int j = 0; j < J; j++) any |= !valid || valid[(int64_t)b * J + j];
     metric[b] = NAN;
@@ -320,13 +342,16 @@ __global__ void frame_reduce_kernel(const double* __restrict__ joint_err, const 
   }
   double buf[512];
   int n = 0, mn = 0x7fffffff;
+  bool any = false;
   for (int j = 0; j < J; j++) {
     if (valid && !valid[(int64_t)b * J + j]) continue;
+    any = true;
+    if (MASK == MASK_VIEW_JOINT && joint_inliers[(int64_t)b * J + j] <= 0) continue;
     buf[n++] = joint_err[(int64_t)b * J + j];
     mn = min(mn, joint_inliers[(int64_t)b * J + j]);
   }
   metric[b] = n ? np_pairwise_sum(buf, n) / (double)n : NAN;
-  inlier_count[b] = n ? mn : -1;
+  inlier_count[b] = n ? mn : (MASK == MASK_VIEW_JOINT && any) ? -2 : -1;
 }
 
 // What the two entries share behind their argument checks: the grid of PG-lane groups, `launch(kp, grid, n_prob)` -- the
@@ -334,18 +359,22 @@ __global__ void frame_reduce_kernel(const double* __restrict__ joint_err, const 
 template <typename Launch>
 static int launch_ransac(const char* name, const void* kp2d, int kp_is_f32, int PG, const uint8_t* valid,
                          const double* joint_err, const int32_t* joint_inliers, double* metric, int32_t* inlier_count,
-                         int B, int J, hipStream_t s, Launch launch, const uint8_t* view_valid = nullptr, int V = 0) {
+                         int B, int J, hipStream_t s, Launch launch, const uint8_t* view_valid = nullptr, int V = 0,
+                         int mask = MASK_VIEWS) {
   const int64_t n_prob = (int64_t)B * J;
   const int per_block = 64 / PG;
   const dim3 grid((unsigned)((n_prob + per_block - 1) / per_block));
   if (kp_is_f32) launch((const float*)kp2d, grid, n_prob);
   else launch((const int64_t*)kp2d, grid, n_prob);
   MVAL_CHECK_LAUNCH(name);
-  if (view_valid)
-    hipLaunchKernelGGL(frame_reduce_kernel<true>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers, valid,
+  if (view_valid && mask == MASK_VIEW_JOINT)
+    hipLaunchKernelGGL(frame_reduce_kernel<MASK_VIEW_JOINT>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers,
+                       valid, view_valid, metric, inlier_count, B, V, J);
+  else if (view_valid)
+    hipLaunchKernelGGL(frame_reduce_kernel<MASK_VIEWS>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers, valid,
                        view_valid, metric, inlier_count, B, V, J);
   else
-    hipLaunchKernelGGL(frame_reduce_kernel<false>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers, valid,
+    hipLaunchKernelGGL(frame_reduce_kernel<MASK_NONE>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers, valid,
                        view_valid, metric, inlier_count, B, V, J);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -369,7 +398,7 @@ extern "C" int mval_triangulate_ransac(const void* kp2d, int kp_is_f32, const do
   const uint8_t* const no_mask = nullptr;
   return launch_ransac("mval_triangulate_ransac", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric, inlier_count,
                        B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<false>), grid, dim3(64), 0, s, kp, proj, valid,
+                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<MASK_NONE>), grid, dim3(64), 0, s, kp, proj, valid,
                                             no_mask, kp3d, joint_err, joint_inliers, n_prob, V, J, n_pairs, PG, eps);
                        });
 }
@@ -389,7 +418,7 @@ extern "C" int mval_triangulate_ransac_views(const void* kp2d, int kp_is_f32, co
   const hipStream_t s = mval_stream(stream);
   return launch_ransac("mval_triangulate_ransac_views", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
                        inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<true>), grid, dim3(64), 0, s, kp, proj, valid,
+                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<MASK_VIEWS>), grid, dim3(64), 0, s, kp, proj, valid,
                                             view_valid, kp3d, joint_err, joint_inliers, n_prob, V, J, n_pairs, PG, eps);
                        }, view_valid, V);
 }
@@ -410,7 +439,7 @@ extern "C" int mval_triangulate_ransac_pairs(const void* kp2d, int kp_is_f32, co
   const uint8_t* const no_mask = nullptr;
   return launch_ransac("mval_triangulate_ransac_pairs", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
                        inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<false>), grid, dim3(64), 0, s, kp, proj,
+                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<MASK_NONE>), grid, dim3(64), 0, s, kp, proj,
                                             valid, no_mask, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V, J, P,
                                             PG, eps);
                        });
@@ -433,17 +462,62 @@ extern "C" int mval_triangulate_ransac_pairs_views(const void* kp2d, int kp_is_f
   const hipStream_t s = mval_stream(stream);
   return launch_ransac("mval_triangulate_ransac_pairs_views", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
                        inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<true>), grid, dim3(64), 0, s, kp, proj,
+                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<MASK_VIEWS>), grid, dim3(64), 0, s, kp, proj,
                                             valid, view_valid, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V, J,
                                             P, PG, eps);
                        }, view_valid, V);
 }
 
+extern "C" int mval_triangulate_ransac_vj(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                          const uint8_t* view_joint_valid, double* kp3d, double* joint_err,
+                                          int32_t* joint_inliers, double* metric, int32_t* inlier_count, int B, int V,
+                                          int J, double eps, void* stream) {
+  MVAL_REQUIRE(V >= 2, "mval_triangulate_ransac_vj: need >= 2 views in the rig (a joint may have fewer present)");
+  MVAL_REQUIRE(V <= MAXV, "mval_triangulate_ransac_vj: V > 11 takes a pair table (mval_triangulate_ransac_pairs_vj)");
+  MVAL_REQUIRE(view_joint_valid, "mval_triangulate_ransac_vj: view_joint_valid is NULL (use mval_triangulate_ransac)");
+  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac_vj: bad dims");
+  if (B == 0) return 0;
+  const int n_pairs = V * (V - 1) / 2;
+  int PG = 1;
+  while (PG < n_pairs) PG <<= 1;
+  const hipStream_t s = mval_stream(stream);
+  return launch_ransac("mval_triangulate_ransac_vj", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
+                       inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
+                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<MASK_VIEW_JOINT>), grid, dim3(64), 0, s, kp, proj,
+                                            valid, view_joint_valid, kp3d, joint_err, joint_inliers, n_prob, V, J, n_pairs, PG,
+                                            eps);
+                       }, view_joint_valid, V, MASK_VIEW_JOINT);
+}
+
+extern "C" int mval_triangulate_ransac_pairs_vj(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                                const uint8_t* view_joint_valid, const uint8_t* pairs, int P,
+                                                int pairs_shared, double* kp3d, double* joint_err, int32_t* joint_inliers,
+                                                double* metric, int32_t* inlier_count, int B, int V, int J, double eps,
+                                                void* stream) {
+  MVAL_REQUIRE(V >= 2, "mval_triangulate_ransac_pairs_vj: need >= 2 views in the rig (a joint may have fewer present)");
+  MVAL_REQUIRE(V <= MVAL_PAIRS_MAX_VIEWS, "mval_triangulate_ransac_pairs_vj: at most %d views (the inlier mask is 32 bits wide)", MVAL_PAIRS_MAX_VIEWS);
+  MVAL_REQUIRE(view_joint_valid, "mval_triangulate_ransac_pairs_vj: view_joint_valid is NULL (use mval_triangulate_ransac_pairs)");
+  MVAL_REQUIRE(pairs && P >= 1 && P <= MVAL_PAIRS_MAX_PAIRS, "mval_triangulate_ransac_pairs_vj: need a pair table of 1..%d pairs", MVAL_PAIRS_MAX_PAIRS);
+  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac_pairs_vj: bad dims");
+  if (B == 0) return 0;
+  int PG = 1;
+  while (PG < P && PG < 64) PG <<= 1;
+  const int64_t stride = pairs_shared ? 0 : (int64_t)P * 2;
+  const hipStream_t s = mval_stream(stream);
+  return launch_ransac("mval_triangulate_ransac_pairs_vj", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
+                       inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
+                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<MASK_VIEW_JOINT>), grid, dim3(64), 0, s, kp, proj,
+                                            valid, view_joint_valid, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V,
+                                            J, P, PG, eps);
+                       }, view_joint_valid, V, MASK_VIEW_JOINT);
+}
+
 // ---- XE metric (utils/triangulation.py:236-257) ---------------------------------------
 // one wave per (frame, view, joint) map; float64 like the reference's rendered target.
 // MASKED: the maps of an absent view are neither read nor written, and xe_sum_kernel leaves them out of its serial sum --
-// the sum the unmasked entry makes over the frame's present views alone.
-template <bool MASKED>
+// the sum the unmasked entry makes over the frame's present views alone.  MASK_VIEW_JOINT: the same per map, the mask
+// [B,V,J] being laid out like the maps.
+template <int MASK>
 __global__ __launch_bounds__(256) void xe_kernel(const double* __restrict__ kp3d, const double* __restrict__ proj,
                                                  const float* __restrict__ hm, const uint8_t* __restrict__ view_valid,
                                                  double* __restrict__ per_map, int64_t n_maps, int V, int J, int hh,
@@ -454,7 +528,8 @@ __global__ __launch_bounds__(256) void xe_kernel(const double* __restrict__ kp3d
   const int j = (int)(map % J);
   const int v = (int)((map / J) % V);
   const int64_t b = map / ((int64_t)V * J);
-  if (MASKED && !view_valid[b * V + v]) return;
+  if (MASK == MASK_VIEWS && !view_valid[b * V + v]) return;
+  if (MASK == MASK_VIEW_JOINT && !view_valid[map]) return;
   const double* P = proj + (b * V + v) * 12;
   const double* X = kp3d + (b * J + j) * 3;
   double u = X[0] * P[0] + X[1] * P[1] + X[2] * P[2] + P[3];
@@ -476,16 +551,20 @@ __global__ __launch_bounds__(256) void xe_kernel(const double* __restrict__ kp3d
   if (lane == 0) per_map[map] = acc / (double)(hh * wh);
 }
 
-template <bool MASKED>
+template <int MASK>
 __global__ void xe_sum_kernel(const double* __restrict__ per_map, const uint8_t* __restrict__ view_valid,
                               double* __restrict__ out, int B, int V, int J) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   double s = 0.0;  // the reference accumulates view-major, joint-minor, left to right
-  if (MASKED) {
+  if (MASK == MASK_VIEWS) {
     for (int v = 0; v < V; v++)
       if (view_valid[(int64_t)b * V + v])
         for (int j = 0; j < J; j++) s += per_map[((int64_t)b * V + v) * J + j];
+  } else if (MASK == MASK_VIEW_JOINT) {
+    const int VJ = V * J;
+    for (int i = 0; i < VJ; i++)
+      if (view_valid[(int64_t)b * VJ + i]) s += per_map[(int64_t)b * VJ + i];
   } else {
     const int VJ = V * J;
     for (int i = 0; i < VJ; i++) s += per_map[(int64_t)b * VJ + i];
@@ -493,15 +572,15 @@ __global__ void xe_sum_kernel(const double* __restrict__ per_map, const uint8_t*
   out[b] = s;
 }
 
-template <bool MASKED>
+template <int MASK>
 static int launch_xe(const char* name, const char* sum_name, const double* kp3d, const double* proj, const float* heatmaps,
                      const uint8_t* view_valid, double* out, double* ws, int B, int V, int J, int hh, int wh, double sigma,
                      void* stream) {
   int64_t n_maps = (int64_t)B * V * J;
-  hipLaunchKernelGGL(xe_kernel<MASKED>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, mval_stream(stream), kp3d, proj,
+  hipLaunchKernelGGL(xe_kernel<MASK>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, mval_stream(stream), kp3d, proj,
                      heatmaps, view_valid, ws, n_maps, V, J, hh, wh, sigma);
   MVAL_CHECK_LAUNCH(name);
-  hipLaunchKernelGGL(xe_sum_kernel<MASKED>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), ws, view_valid, out, B, V,
+  hipLaunchKernelGGL(xe_sum_kernel<MASK>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), ws, view_valid, out, B, V,
                      J);
   MVAL_CHECK_LAUNCH(sum_name);
   return 0;
@@ -511,7 +590,7 @@ extern "C" int mval_reprojection_xe(const double* kp3d, const double* proj, cons
                                     double* ws, int B, int V, int J, int hh, int wh, double sigma, void* stream) {
   MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && sigma > 0, "mval_reprojection_xe: bad dims");
   if (B == 0) return 0;
-  return launch_xe<false>("mval_reprojection_xe", "mval_reprojection_xe/sum", kp3d, proj, heatmaps, nullptr, out, ws, B, V, J,
+  return launch_xe<MASK_NONE>("mval_reprojection_xe", "mval_reprojection_xe/sum", kp3d, proj, heatmaps, nullptr, out, ws, B, V, J,
                           hh, wh, sigma, stream);
 }
 
@@ -521,6 +600,16 @@ extern "C" int mval_reprojection_xe_views(const double* kp3d, const double* proj
   MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && sigma > 0, "mval_reprojection_xe_views: bad dims");
   MVAL_REQUIRE(view_valid, "mval_reprojection_xe_views: view_valid is NULL (use mval_reprojection_xe)");
   if (B == 0) return 0;
-  return launch_xe<true>("mval_reprojection_xe_views", "mval_reprojection_xe_views/sum", kp3d, proj, heatmaps, view_valid, out,
+  return launch_xe<MASK_VIEWS>("mval_reprojection_xe_views", "mval_reprojection_xe_views/sum", kp3d, proj, heatmaps, view_valid, out,
                          ws, B, V, J, hh, wh, sigma, stream);
+}
+
+extern "C" int mval_reprojection_xe_vj(const double* kp3d, const double* proj, const float* heatmaps,
+                                       const uint8_t* view_joint_valid, double* out, double* ws, int B, int V, int J, int hh,
+                                       int wh, double sigma, void* stream) {
+  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && sigma > 0, "mval_reprojection_xe_vj: bad dims");
+  MVAL_REQUIRE(view_joint_valid, "mval_reprojection_xe_vj: view_joint_valid is NULL (use mval_reprojection_xe)");
+  if (B == 0) return 0;
+  return launch_xe<MASK_VIEW_JOINT>("mval_reprojection_xe_vj", "mval_reprojection_xe_vj/sum", kp3d, proj, heatmaps,
+                                    view_joint_valid, out, ws, B, V, J, hh, wh, sigma, stream);
 }

@@ -40,7 +40,8 @@ def _reduce_mode(kind: str, config: str) -> int:
     raise NotImplementedError("AL.%s_CONFIG should be either AVG or STD." % kind)
 
 
-def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_quirk=True, decode=False, view_valid=None):
+def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_quirk=True, decode=False, view_valid=None,
+                    view_joint_valid=None):
     """The heat-map scorer behind the three public functions below.  ``configs`` maps "HP" / "MPE" / "BSB" to "AVG" / "STD";
     heatmaps (B,V,J,Hh,Wh) f32 HIP, joint_valid (B,J).  ONE launch reads the heat-maps -- one kind without ``decode``:
     mval_score_maps; one kind with it: mval_score_decode_maps; several kinds: mval_score_decode_maps_all (csrc/scoring.hip builds
@@ -48,7 +49,10 @@ def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_q
     Returns an OrderedDict kind -> (out (B,) float64, per_map (B,V,J), n_peaks (B,V,J), valid, keypoints_2d or None).
     ``view_valid`` (B,V), nonzero = present: ``out`` is reduced over the present views of each frame alone
     (``mval_score_reduce_views``).  The map launch is unchanged -- per_map, n_peaks and keypoints_2d still hold entries for
-    the maps of absent views, which every consumer ignores."""
+    the maps of absent views, which every consumer ignores.
+    ``view_joint_valid`` (B,V,J), nonzero = the joint is usable in that view (ANDed with ``view_valid`` where both are given):
+    ``out`` is the reference's list of per-map values with the absent entries deleted -- same order, same arithmetic, n the
+    entries left (``mval_score_reduce_vj``)."""
     modes = OrderedDict((kind, _reduce_mode(kind, configs[kind])) for kind in configs)
     for kind in modes:
         if kind not in _KIND:
@@ -57,7 +61,13 @@ def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_q
     hm = heatmaps.to(torch.float32).contiguous()
     valid = (torch.as_tensor(joint_valid) != 0).to(torch.uint8).reshape(b, j).to(hm.device).contiguous()
     split_width = hh if mirror_nonsquare_quirk else wh
-    if view_valid is None:
+    if view_joint_valid is not None:
+        vj = (torch.as_tensor(view_joint_valid) != 0).to(torch.uint8).reshape(b, v, j).to(hm.device)
+        if view_valid is not None:
+            vj = vj & (torch.as_tensor(view_valid) != 0).to(torch.uint8).reshape(b, v, 1).to(hm.device)
+        vj = vj.contiguous()
+        reduce = lambda stat, mode: _lib.score_reduce_vj(stat, valid, vj, b, v, j, mode)  # noqa: E731
+    elif view_valid is None:
         reduce = lambda stat, mode: _lib.score_reduce(stat, valid, b, v, j, mode)  # noqa: E731
     else:
         vv = (torch.as_tensor(view_valid) != 0).to(torch.uint8).reshape(b, v).to(hm.device).contiguous()
@@ -77,26 +87,30 @@ def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_q
                                counts[kind].reshape(b, v, j), valid, kp2d)) for kind, mode in modes.items())
 
 
-def score_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid, view_valid=None):
+def score_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid, view_valid=None, view_joint_valid=None):
     """heatmaps (B,V,J,Hh,Wh) f32 HIP, joint_valid (B,J) -> (B,) float64 HIP tensor holding
     the value the reference's ``_compute_{hp,mpe,bsb}`` returns for each frame (exactly
     representable float32 where the reference's result is float32); then per_map, n_peaks, valid.
-    ``view_valid`` (B,V): the value over each frame's present views alone (``_score_heatmaps``)."""
-    return _score_heatmaps({kind: config}, heatmaps, joint_valid, view_valid=view_valid)[kind][:4]
+    ``view_valid`` (B,V): the value over each frame's present views alone; ``view_joint_valid`` (B,V,J): over its present
+    (view, joint) entries (``_score_heatmaps``)."""
+    return _score_heatmaps({kind: config}, heatmaps, joint_valid, view_valid=view_valid, view_joint_valid=view_joint_valid)[kind][:4]
 
 
-def score_decode_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True, view_valid=None):
+def score_decode_heatmaps_batch(kind: str, config: str, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True, view_valid=None,
+                                view_joint_valid=None):
     """``score_heatmaps_batch`` + the hard arg-max decode of ``triangulate_batch`` from ONE read of the heat-maps
     (csrc/scoring.hip, DECODE): what a pool-scoring pass needs per map (strategy.py:1027-1090 reads every heat-map in
     get_scaled_pred_corrdinates AND in _compute_{hp,mpe,bsb}).  Returns (out, per_map, n_peaks, valid, keypoints_2d)."""
-    return _score_heatmaps({kind: config}, heatmaps, joint_valid, stride, mirror_nonsquare_quirk, decode=True, view_valid=view_valid)[kind]
+    return _score_heatmaps({kind: config}, heatmaps, joint_valid, stride, mirror_nonsquare_quirk, decode=True, view_valid=view_valid,
+                           view_joint_valid=view_joint_valid)[kind]
 
 
-def score_decode_heatmaps_all(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True, decode=True, view_valid=None):
+def score_decode_heatmaps_all(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk=True, decode=True, view_valid=None,
+                              view_joint_valid=None):
     """``score_decode_heatmaps_batch`` for several kinds from ONE read of the heat-maps: ``configs`` maps "HP" / "MPE" / "BSB"
     to "AVG" / "STD".  Returns an OrderedDict kind -> (out, per_map, n_peaks, valid, keypoints_2d), each entry what
     ``score_decode_heatmaps_batch(kind, config, ...)`` returns (keypoints_2d None without ``decode``)."""
-    return _score_heatmaps(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk, decode, view_valid)
+    return _score_heatmaps(configs, heatmaps, joint_valid, stride, mirror_nonsquare_quirk, decode, view_valid, view_joint_valid)
 
 
 AL_STRATEGIES = ("HP", "MPE", "BSB", "TRIANGULATION", "CORESET", "RANDOM")
@@ -172,10 +186,10 @@ def tables_to_sal_dict(per_rank, batch_sizes, sal_dict=None):
     return sal_dict
 
 
-_SMALL_KEYS = ("proj_matrices", "joint_valid", "3d_keypoints", "pose", "frame_id", "view_valid")
+_SMALL_KEYS = ("proj_matrices", "joint_valid", "3d_keypoints", "pose", "frame_id", "view_valid", "view_joint_valid")
 
 
-def _stage_batch(dp):
+def _stage_batch(dp, mask_keys=()):
     """The batch's SMALL tensors (cameras, validity, ground truth, ids) as device tensors, uploaded on the caller's stream BEFORE the
     network is launched, through pinned staging (torch's caching host allocator) with non_blocking copies.  Why: score_batch /
     evaluate_mkpe run inside the side-stream context (parallel.PostStream), and a pageable host -> device copy issued there blocks the
@@ -183,17 +197,19 @@ def _stage_batch(dp):
     enqueued meanwhile.  A ``joint_valid`` that arrives on the host also stays there as ``joint_valid_host``: the
     view-pair draw of a rig with more than 11 views (utils.triangulation.draw_view_pairs) reads it, and copying the staged mask back
     would be such a blocking copy; a ``view_valid`` (frames with missing views) likewise stays as ``view_valid_host``, which that
-    draw reads too.  Returns a shallow copy of ``dp``; host-only runs (no HIP device) get ``dp`` back."""
+    draw reads too, and so does a ``view_joint_valid`` (joints missing from single views) as ``view_joint_valid_host``.
+    ``mask_keys``: further batch keys to stage like ``view_joint_valid`` (the key AL.VIEW_JOINT_VALID_KEY names).  Returns a shallow
+    copy of ``dp``; host-only runs (no HIP device) get ``dp`` back."""
     if not torch.cuda.is_available() or not isinstance(dp, dict):
         return dp
     dev = torch.device("cuda", torch.cuda.current_device())
     out = dict(dp)
-    for k in _SMALL_KEYS:
+    for k in _SMALL_KEYS + tuple(k for k in mask_keys if k not in _SMALL_KEYS):
         if k not in dp:
             continue
         t = torch.as_tensor(dp[k])
         if not t.is_cuda:
-            if k in ("joint_valid", "view_valid"):
+            if k in ("joint_valid", "view_valid", "view_joint_valid") or k in mask_keys:
                 out[k + "_host"] = t
             t = t.contiguous()
             t = (t if t.is_pinned() else t.pin_memory()).to(dev, non_blocking=True)
@@ -354,6 +370,55 @@ class ActiveLearningStrategy:
     def _compute_bsb(self, heatmaps, joint_valid):
         return self._score_one("BSB", self.al_cfg.AL.BSB_CONFIG, heatmaps, joint_valid)
 
+    # ---- joints missing from single views ------------------------------------------------
+    def _mask_keys(self):
+        """The batch keys that hold a per-(view, joint) visibility mask: ``view_joint_valid`` itself and the key that
+        AL.VIEW_JOINT_VALID_KEY names."""
+        from .config import check_view_joint_valid
+
+        key, _ = check_view_joint_valid(self.al_cfg.AL.VIEW_JOINT_VALID_KEY, self.al_cfg.AL.MIN_PEAK)
+        return ("view_joint_valid",) + ((key,) if key not in ("", "view_joint_valid") else ())
+
+    def _stage_masked(self, dp):
+        """``_stage_batch`` that also stages the key AL.VIEW_JOINT_VALID_KEY names (and keeps its host copy)."""
+        return _stage_batch(dp, self._mask_keys()[1:])
+
+    def _view_joint_valid(self, hm, dp):
+        """The ONE place where a batch's per-(view, joint) mask is resolved.  hm (B,V,J,h,w) on the device.  Sources, ANDed:
+        the batch's own ``view_joint_valid``; the batch key AL.VIEW_JOINT_VALID_KEY names (KeyError when the batch lacks it);
+        with AL.MIN_PEAK > 0 the peak gate ``triangulation.peak_mask(hm, AL.MIN_PEAK)``, computed on the device without a host
+        sync.  Returns (mask (B,V,J) uint8 on the device, host copy or None) -- (None, None) when nothing is given, which is
+        every batch under the default config that has no ``view_joint_valid`` key.  The host copy (read by the pair draw of
+        rigs with more than 11 views) exists when every source has one: ``<key>_host`` from ``_stage_batch``, or a tensor that
+        is on the host anyway; the peak gate has none, and triangulate_batch then copies the device mask back (one blocking
+        copy per batch, V > 11 only: DESIGN.md 6.3).  ``view_valid`` is not folded in here: the callees AND it."""
+        from .config import check_view_joint_valid
+
+        key, min_peak = check_view_joint_valid(self.al_cfg.AL.VIEW_JOINT_VALID_KEY, self.al_cfg.AL.MIN_PEAK)
+        b, v, j = hm.shape[:3]
+        mask, host, host_ok = None, None, True
+        for name in self._mask_keys():
+            if name != "view_joint_valid" and name not in dp:
+                raise KeyError("AL.VIEW_JOINT_VALID_KEY %r: the batch has no such key" % (name,))
+            if dp.get(name) is None:
+                continue
+            m = torch.as_tensor(dp[name])
+            h = dp.get(name + "_host", None if m.is_cuda else m)
+            m = (m.reshape(b, v, j) != 0).to(hm.device)
+            mask = m if mask is None else mask & m
+            if h is None:
+                host_ok = False
+            else:
+                h = torch.as_tensor(h).reshape(b, v, j) != 0
+                host = h if host is None else host & h
+        if min_peak > 0.0:
+            gate = triangulation.peak_mask(hm, min_peak).bool()
+            mask = gate if mask is None else mask & gate
+            host_ok = False
+        if mask is None:
+            return None, None
+        return mask.to(torch.uint8).contiguous(), host if host_ok else None
+
     # ---- pool scoring ---------------------------------------------------------------
     def _score_columns(self, heatmaps, dp, strategies):
         """Everything the reference does per sample inside _compute_sal_dict (strategy.py:1036-1094,1134), for a whole
@@ -361,7 +426,8 @@ class ActiveLearningStrategy:
         arg-max decode unless AL.USE_SOFTARGMAX), one triangulation.  heatmaps (B*V,J,h,w).  Returns float64 HIP columns
         (ids [pose, frame_id], rest [sal_metric, inlier_count, mkpe, keypoints_3d(3J)], al_metric per strategy).
         A batch with ``view_valid`` (B, V) -- frames with missing views -- is scored and triangulated over each frame's
-        present views alone."""
+        present views alone; one with a per-(view, joint) mask (``_view_joint_valid``) over each joint's present views, and
+        its per-sample MKPE leaves out the joints nobody triangulated (``joint_valid & joint_used``)."""
         cfg = self.al_cfg
         dev = heatmaps.device
         pose = torch.as_tensor(dp["pose"]).reshape(-1)
@@ -370,12 +436,13 @@ class ActiveLearningStrategy:
         hm = heatmaps.reshape(b, -1, j, hh, wh)
         joint_valid = torch.as_tensor(dp["joint_valid"]).reshape(b, j)
         view_valid = dp.get("view_valid")
+        vj, vj_host = self._view_joint_valid(hm, dp)
         configs = OrderedDict((s, getattr(cfg.AL, s + "_CONFIG")) for s in strategies if s in _KIND)
         scored, kp2d = {}, None
         if configs:
             # one read of every heat-map for the uncertainty statistics and the key-point decode
             scored = _score_heatmaps(configs, hm, joint_valid, cfg.POSE_ESTIMATOR.STRIDE, decode=not cfg.AL.USE_SOFTARGMAX,
-                                     view_valid=view_valid)
+                                     view_valid=view_valid, view_joint_valid=vj)
             kp2d = next(iter(scored.values()))[4]
         r = triangulation.triangulate_batch(
             hm, dp["proj_matrices"], cfg.POSE_ESTIMATOR.STRIDE, joint_valid,
@@ -384,11 +451,14 @@ class ActiveLearningStrategy:
             pair_rng=random,  # more than n_iters view pairs (12 views on): the reference's draws, frames in batch order
             valid_joints_host=dp.get("joint_valid_host"),
             view_valid=view_valid, view_valid_host=dp.get("view_valid_host"),
+            view_joint_valid=vj, view_joint_valid_host=vj_host,
         )
         pred32 = r["keypoints_3d"].to(torch.float32)  # torch.Tensor(results["keypoints_3d"]) (:1046)
         sal_metric = r["metric"].to(torch.float32).to(torch.float64)  # torch.Tensor([metric]) (:1061)
         # frames with missing views: an absent view has no peak list to run short, the deferred peak checks count it as fine
         absent = None if view_valid is None or not configs else (torch.as_tensor(view_valid).reshape(b, -1) == 0).to(dev)[:, :, None]
+        if vj is not None and configs:  # likewise an absent (view, joint) entry
+            absent = (vj == 0) if absent is None else absent | (vj == 0)
         als = []
         for s in strategies:
             if s == "RANDOM":
@@ -408,7 +478,10 @@ class ActiveLearningStrategy:
                 raise NotImplementedError()
             als.append(al[:, None])
         gt = torch.as_tensor(dp["3d_keypoints"]).to(dev)
-        mk = evaluation.mkpe_per_sample(pred32, gt, joint_valid.to(dev))
+        scored_joints = joint_valid.to(dev)
+        if vj is not None:  # a joint nobody triangulated is not scored as a prediction at the origin
+            scored_joints = ((scored_joints != 0) & r["joint_used"].bool()).to(scored_joints.dtype)
+        mk = evaluation.mkpe_per_sample(pred32, gt, scored_joints)
         self._pending_checks.append(("INLIER", r["inlier_count"], None))
         ids = [pose.to(dev, torch.float64)[:, None], torch.as_tensor(dp["frame_id"]).reshape(b).to(dev, torch.float64)[:, None]]
         rest = [sal_metric[:, None], r["inlier_count"].to(torch.float64)[:, None], mk.to(torch.float64)[:, None],
@@ -477,7 +550,7 @@ class ActiveLearningStrategy:
         the reference's gather order (batch -> sample -> rank), but with one device->host
         copy and (when torch.distributed is initialised) one all_gather for the whole pass."""
         self._pending_checks = []
-        tables = self._pool_loop(data_loader, pose_estimator, lambda hm, _keys, dp: self.score_batch(hm, dp))
+        tables = self._pool_loop(data_loader, pose_estimator, lambda hm, _keys, dp: self.score_batch(hm, dp), stage=self._stage_masked)
         gathered = self._gather_score_tables(tables, 6 + 3 * self.num_joints)
         return _empty_sal_dict() if gathered is None else tables_to_sal_dict(*gathered)
 
@@ -488,7 +561,8 @@ class ActiveLearningStrategy:
         (the table is E columns wider).  Errors of a strategy that was not asked for are not raised."""
         strategies = check_strategies(strategies)
         self._pending_checks = []
-        tables = self._pool_loop(data_loader, pose_estimator, lambda hm, _keys, dp: self.score_batch_all(hm, dp, strategies))
+        tables = self._pool_loop(data_loader, pose_estimator, lambda hm, _keys, dp: self.score_batch_all(hm, dp, strategies),
+                                 stage=self._stage_masked)
         gathered = self._gather_score_tables(tables, 6 + 3 * self.num_joints + len(strategies))
         if gathered is None:
             return OrderedDict((s, _empty_sal_dict()) for s in strategies)
@@ -502,7 +576,7 @@ class ActiveLearningStrategy:
             if kind == "INLIER":
                 bad = t[t < 0]
                 if bad.numel():  # the reference stops at its first bad frame
-                    if int(bad[0].item()) == -2:  # fewer than two present views (view_valid)
+                    if int(bad[0].item()) == -2:  # fewer than two present views (view_valid), or no used joint (view_joint_valid)
                         raise AssertionError("need at least two views")
                     raise ValueError("zero-size array to reduction operation minimum which has no identity")
             else:
@@ -678,7 +752,9 @@ class ActiveLearningStrategy:
     # ---- evaluation core (strategy.py:597-636) ----------------------------------------
     def evaluate_mkpe(self, data_loader, pose_estimator):
         """_evaluate_all's MKPE path: heat-maps -> hard arg-max triangulation -> MPJPE over the
-        whole loader (one size exchange + one packed data gather instead of 3 all_gathers per sample)."""
+        whole loader (one size exchange + one packed data gather instead of 3 all_gathers per sample).  A batch with a
+        per-(view, joint) mask (``_view_joint_valid``) is triangulated joint by joint from the views that have the joint, and the
+        validity column it contributes is ``joint_valid & joint_used``: a joint nobody triangulated is left out."""
         def inputs(hm, dp):
             b = torch.as_tensor(dp["pose"]).reshape(-1).shape[0] if "pose" in dp else dp["images"].shape[0]
             jv = torch.as_tensor(dp["joint_valid"]).reshape(b, hm.shape[1])
@@ -686,14 +762,19 @@ class ActiveLearningStrategy:
 
         def triangulate(hm, _keys, dp, jv):  # (decode + triangulation of a batch beside the next batch's network)
             (b, j), (hh, wh) = jv.shape, hm.shape[2:]
-            r = triangulation.triangulate_batch(hm.reshape(b, -1, j, hh, wh), dp["proj_matrices"],
+            hm5 = hm.reshape(b, -1, j, hh, wh)
+            vj, vj_host = self._view_joint_valid(hm5, dp)
+            r = triangulation.triangulate_batch(hm5, dp["proj_matrices"],
                                                 self.al_cfg.POSE_ESTIMATOR.STRIDE, jv, pair_rng=random,
                                                 valid_joints_host=dp.get("joint_valid_host"),
-                                                view_valid=dp.get("view_valid"), view_valid_host=dp.get("view_valid_host"))
-            return (r["keypoints_3d"].to(torch.float32), torch.as_tensor(dp["3d_keypoints"]).to(hm.device, torch.float32),
-                    jv.to(hm.device, torch.float32))
+                                                view_valid=dp.get("view_valid"), view_valid_host=dp.get("view_valid_host"),
+                                                view_joint_valid=vj, view_joint_valid_host=vj_host)
+            scored = jv.to(hm.device, torch.float32)
+            if vj is not None:
+                scored = ((scored != 0) & r["joint_used"].bool()).to(torch.float32)
+            return (r["keypoints_3d"].to(torch.float32), torch.as_tensor(dp["3d_keypoints"]).to(hm.device, torch.float32), scored)
 
-        rows = self._pool_loop(data_loader, pose_estimator, triangulate, inputs)
+        rows = self._pool_loop(data_loader, pose_estimator, triangulate, inputs, stage=self._stage_masked)
         preds, gts, valids = ([r[k] for r in rows] for k in range(3))
         sizes = [p.shape[0] for p in preds]
         from .parallel import all_gather_reference_order as gather

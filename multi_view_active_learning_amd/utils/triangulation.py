@@ -15,6 +15,11 @@ in the reference's order, and the device triangulates the drawn pairs (up to 32 
 Frames with missing views: ``view_valid`` (B, V) makes every frame's result what these functions give on that frame's
 present views alone -- what the per-sample reference computes when it is handed the views that exist -- with all frames
 of a batch in one triangulation launch.
+
+Joints missing from single views: ``view_joint_valid`` (B, V, J) makes the present views a property of the problem (frame,
+joint): every joint is triangulated from the views that have it, a joint with fewer than two of them is left out of the
+frame's metric and inlier count, and ``peak_mask`` builds such a mask on the device from the heat-maps' own peak heights
+(DESIGN.md 6.3).
 """
 from __future__ import annotations
 
@@ -64,7 +69,34 @@ def _draw_view_pairs_masked(valid, V, n_iters, rng, view_valid):
     return out
 
 
-def draw_view_pairs(valid, V, n_iters, rng, view_valid=None):
+def _draw_view_pairs_vj(valid, V, n_iters, rng, vj):
+    """``vj`` (B, V, J) bool: the tables of ``_draw_view_pairs_masked`` with one present set per problem."""
+    b, j = valid.shape
+    n_present = vj.sum(axis=1)  # (B, J)
+    n_pairs = n_present * (n_present - 1) // 2
+    out = np.full((b, j, max(1, int(np.minimum(n_pairs, n_iters).max(initial=0))), 2), PAIR_PAD, dtype=np.uint8)
+    lex_of = {}  # present set -> its lexicographic pairs (the joints of a frame mostly share a few sets)
+    for bi in range(b):
+        for ji in range(j):
+            n = int(n_pairs[bi, ji])
+            if n == 0:  # fewer than two present views: nothing to triangulate, nothing drawn
+                continue
+            key = vj[bi, :, ji].tobytes()
+            if key not in lex_of:
+                lex_of[key] = np.array(list(itertools.combinations(np.flatnonzero(vj[bi, :, ji]).tolist(), 2)), dtype=np.uint8).reshape(-1, 2)
+            lex = lex_of[key]
+            if n <= n_iters:
+                out[bi, ji, :n] = lex
+                continue
+            out[bi, ji] = 0  # (a problem that draws fills all P = n_iters entries; the row of an invalid joint stays zero)
+            if valid[bi, ji]:
+                order = list(range(n))
+                rng.shuffle(order)
+                out[bi, ji] = lex[order[:n_iters]]
+    return out
+
+
+def draw_view_pairs(valid, V, n_iters, rng, view_valid=None, view_joint_valid=None):
     """The view pairs the reference samples for every joint of a batch (utils/triangulation.py:279-282):
     valid (B, J) -> uint8 ndarray (B, J, P, 2), P = min(n_iters, C(V,2)).
 
@@ -79,8 +111,21 @@ def draw_view_pairs(valid, V, n_iters, rng, view_valid=None):
     its present views, nothing drawn; otherwise per valid joint a shuffle of a list of length C(n_b, 2), first
     ``n_iters`` kept.  Frames in batch order, valid joints ascending: ``rng`` ends in the reference's state.
     P = max over frames of min(C(n_b, 2), n_iters), at least 1; shorter rows, and those of a frame with n_b < 2 (which
-    draws nothing), are padded with ``PAIR_PAD`` = 255.  The rows of an invalid joint stay zero in a frame that draws."""
+    draws nothing), are padded with ``PAIR_PAD`` = 255.  The rows of an invalid joint stay zero in a frame that draws.
+
+    ``view_joint_valid`` (B, V, J), nonzero = joint j is usable in view v (ANDed with ``view_valid`` where both are given):
+    one table per problem, as the reference would draw for that joint's slice of the views.  Problem (b, j) with n_bj
+    present views: C(n_bj, 2) <= n_iters -> the lexicographic pairs of its present views, nothing drawn; otherwise, for a
+    valid joint, one shuffle of a list of length C(n_bj, 2), first ``n_iters`` kept.  Frames in batch order, valid joints
+    ascending, joints with n_bj < 2 drawing nothing: ``rng`` ends in the state the reference's per-joint calls, made in
+    that order, leave it in.  P = max over problems of min(C(n_bj, 2), n_iters), at least 1; padding and invalid joints as
+    above, so a mask that is the same for every joint of a frame gives the ``view_valid`` tables."""
     valid = torch.as_tensor(valid).cpu().numpy() != 0
+    if view_joint_valid is not None:
+        vj = torch.as_tensor(view_joint_valid).cpu().numpy().reshape(valid.shape[0], V, valid.shape[1]) != 0
+        if view_valid is not None:
+            vj = vj & (torch.as_tensor(view_valid).cpu().numpy().reshape(valid.shape[0], V, 1) != 0)
+        return _draw_view_pairs_vj(valid, V, n_iters, rng, vj)
     if view_valid is not None:
         vv = torch.as_tensor(view_valid).cpu().numpy().reshape(valid.shape[0], V) != 0
         return _draw_view_pairs_masked(valid, V, n_iters, rng, vv)
@@ -124,6 +169,8 @@ def triangulate_batch(
     valid_joints_host=None,
     view_valid=None,
     view_valid_host=None,
+    view_joint_valid=None,
+    view_joint_valid_host=None,
 ):
     """heatmaps (B,V,J,Hh,Wh) f32 HIP tensor, proj (B,V,3,4), valid (B,J) ->
     dict of HIP tensors: keypoints_3d (B,J,3) f64, keypoints_2d (B,V,J,2) i64|f32,
@@ -153,7 +200,18 @@ def triangulate_batch(
     with fewer than two present views and a valid joint gets inlier_count -2, metric NaN and keypoints_3d 0 (the
     reference asserts two views); without a valid joint it is -1 as ever.  Up to 11 views nothing of the mask is needed
     on the host; beyond, the pair tables are built per frame from its present views (``draw_view_pairs``), from
-    ``view_valid_host`` -- the mask once more on the host, as ``valid_joints_host`` -- where given."""
+    ``view_valid_host`` -- the mask once more on the host, as ``valid_joints_host`` -- where given.
+
+    ``view_joint_valid`` (B, V, J), nonzero = joint j is usable in view v of frame b; ANDed with ``view_valid[:, :, None]``
+    where that is given too.  Per joint the result is what this function gives on that joint's present views alone (B = 1,
+    J = 1), bit for bit for a valid joint with two or more of them; all problems go through ONE triangulation launch.
+    Nothing of an absent entry is used (its heat-map may hold NaN); ``keypoints_2d`` comes back dense with absent entries
+    zero.  A valid joint with fewer than two present views is written like an invalid one (keypoints_3d, joint_error,
+    joint_inliers 0); ``metric`` and ``inlier_count`` run over the USED joints (valid, two or more present views), and the
+    result carries ``joint_used`` (B, J) uint8 = joint_inliers > 0.  No valid joint: inlier_count -1; a valid joint but no
+    used one: -2, metric NaN.  Up to 11 views nothing of the mask is needed on the host; beyond, the per-problem pair
+    tables are drawn from ``view_joint_valid_host`` where given -- a mask that exists on the device alone is copied back,
+    which blocks the host on the current stream."""
     dev = _device_of(heatmaps)
     if heatmaps.dim() != 5:
         raise ValueError("heatmaps must be (B, V, J, Hh, Wh)")
@@ -162,7 +220,8 @@ def triangulate_batch(
         raise AssertionError("need at least two views")  # reference: assert len(points) >= 2
     if v > _lib.PAIRS_MAX_VIEWS:
         raise NotImplementedError("at most %d views (got %d): the device's inlier mask is 32 bits wide" % (_lib.PAIRS_MAX_VIEWS, v))
-    masked = view_valid is not None
+    per_joint = view_joint_valid is not None
+    masked = view_valid is not None or per_joint
     sampled = not masked and v * (v - 1) // 2 > n_iters  # (under a mask the frames decide one by one: _masked_pair_tables)
     if sampled and pair_rng is None:
         raise NotImplementedError(_NEEDS_RNG)
@@ -172,6 +231,9 @@ def triangulate_batch(
     proj = torch.as_tensor(proj_matricies).to(device=dev, dtype=torch.float64).reshape(b, v, 3, 4).contiguous()
     valid = _as_valid_u8(valid_joints, (b, j), dev)
     vv = _as_valid_u8(view_valid, (b, v), dev)
+    vj = _as_valid_u8(view_joint_valid, (b, v, j), dev)
+    if per_joint and vv is not None:
+        vj = vj & vv[:, :, None]
     if keypoints_2d is not None:
         kp2d = keypoints_2d
     elif use_soft_argmax:
@@ -180,12 +242,23 @@ def triangulate_batch(
         kp2d = _lib.argmax_decode(hm, valid, b, v, j, hh, wh, int(stride), hh if mirror_nonsquare_quirk else wh)
     if masked:
         # (the map kernels still decode the maps of absent views; a select, not a product: such a row may be NaN)
-        kp2d = torch.where(vv.bool()[:, :, None, None], kp2d, torch.zeros((), dtype=kp2d.dtype, device=dev))
+        present = vj.bool()[:, :, :, None] if per_joint else vv.bool()[:, :, None, None]
+        kp2d = torch.where(present, kp2d, torch.zeros((), dtype=kp2d.dtype, device=dev))
     eps = float(reprojection_error_epsilon)
     if sampled or (masked and v > 11):
         host_valid = valid_joints_host if valid_joints_host is not None else valid_joints
         host_valid = torch.ones((b, j)) if host_valid is None else torch.as_tensor(host_valid).reshape(b, j)
-    if masked and v <= 11:  # lane p keeps its pair and sits out if a view is absent: no host knowledge of the mask
+    if per_joint and v <= 11:
+        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_vj(kp2d, proj, valid, vj, b, v, j, eps)
+    elif per_joint:
+        host_vj = torch.as_tensor(view_joint_valid_host if view_joint_valid_host is not None else view_joint_valid).reshape(b, v, j)
+        if view_valid is not None:
+            host_vv = view_valid_host if view_valid_host is not None else view_valid
+            host_vj = (host_vj.cpu() != 0) & (torch.as_tensor(host_vv).reshape(b, v, 1).cpu() != 0)
+        pairs = _masked_pair_tables(host_valid, host_vj, v, n_iters, pair_rng)
+        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs_vj(kp2d, proj, valid, vj, pairs.pin_memory().to(dev, non_blocking=True),
+                                                                         b, v, j, eps)
+    elif masked and v <= 11:  # lane p keeps its pair and sits out if a view is absent: no host knowledge of the mask
         kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_views(kp2d, proj, valid, vv, b, v, j, eps)
     elif masked:
         host_vv = view_valid_host if view_valid_host is not None else view_valid
@@ -199,12 +272,15 @@ def triangulate_batch(
         kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs(kp2d, proj, valid, _lexicographic_pairs(v, dev), b, v, j, eps)
     else:
         kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac(kp2d, proj, valid, b, v, j, eps)
-    if use_reprojection_xe and masked:
+    if use_reprojection_xe and per_joint:
+        xe = _lib.reprojection_xe_vj(kp3d, proj, hm, vj, b, v, j, hh, wh, float(sigma))
+        metric = torch.where(inl == -2, metric, xe)  # (no used joint: NaN)
+    elif use_reprojection_xe and masked:
         xe = _lib.reprojection_xe_views(kp3d, proj, hm, vv, b, v, j, hh, wh, float(sigma))
         metric = torch.where(inl == -2, metric, xe)  # (fewer than two views: NaN, the reference never reaches _compute_xe)
     elif use_reprojection_xe:
         metric = _lib.reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, float(sigma))
-    return {
+    out = {
         "keypoints_3d": kp3d,
         "keypoints_2d": kp2d,
         "metric": metric,
@@ -212,6 +288,9 @@ def triangulate_batch(
         "joint_error": jerr,
         "joint_inliers": jinl,
     }
+    if per_joint:
+        out["joint_used"] = (jinl > 0).to(torch.uint8)  # a used joint's winning pair is in its own inlier set: >= 2
+    return out
 
 
 _NEEDS_RNG = ("more view pairs than n_iters: the reference samples pairs from python's global RNG there "
@@ -220,12 +299,28 @@ _NEEDS_RNG = ("more view pairs than n_iters: the reference samples pairs from py
 
 def _masked_pair_tables(host_valid, host_view_valid, v, n_iters, pair_rng):
     """The per-problem pair tables of a masked batch with more than 11 views, as a host tensor (``draw_view_pairs``); without
-    ``pair_rng`` only where no frame has more present pairs than ``n_iters``."""
+    ``pair_rng`` only where no frame (no problem) has more present pairs than ``n_iters``.  ``host_view_valid``: (B, V), or
+    the effective (B, V, J) mask of a batch with ``view_joint_valid``."""
     host_vv = (host_view_valid != 0).cpu().numpy()
     n_present = host_vv.sum(axis=1)
     if bool((n_present * (n_present - 1) // 2 > n_iters).any()) and pair_rng is None:
         raise NotImplementedError(_NEEDS_RNG)
+    if host_vv.ndim == 3:
+        return torch.from_numpy(draw_view_pairs(host_valid, v, n_iters, pair_rng, view_joint_valid=host_vv))
     return torch.from_numpy(draw_view_pairs(host_valid, v, n_iters, pair_rng, host_vv))
+
+
+def peak_mask(heatmaps, min_peak):
+    """The peak gate: heatmaps (B, V, J, h, w) f32 HIP tensor -> (B, V, J) uint8 on the device, 1 where some element of the
+    map is ``>= min_peak``.  A comparison, so a map of NaNs is absent; exact, equal to
+    ``(heatmaps >= min_peak).flatten(-2).any(-1)``.  One read of the maps (``mval_peak_mask``), no host sync: a mask for
+    ``view_joint_valid`` where no annotation says which joints a view sees."""
+    _device_of(heatmaps)
+    if heatmaps.dim() != 5:
+        raise ValueError("heatmaps must be (B, V, J, Hh, Wh)")
+    b, v, j, hh, wh = heatmaps.shape
+    hm = heatmaps.to(torch.float32).contiguous()
+    return _lib.peak_mask(hm, float(min_peak), b * v * j, hh, wh).reshape(b, v, j)
 
 
 def triangulation(
@@ -240,12 +335,14 @@ def triangulation(
     reprojection_error_epsilon=5,
     direct_optimization=False,
     view_valid=None,
+    view_joint_valid=None,
 ):
     """One frame, reference signature and return types (utils/triangulation.py:168-233):
     heatmaps (V,J,Hh,Wh), proj (V,3,4), valid (J,) -> {"keypoints_3d": ndarray (J,3) f64,
     "keypoints_2d": ndarray (V,J,2) int64|f32, "metric": float, "inlier_count": int}.
     ``view_valid`` (V,): the views present in this frame (``triangulate_batch``); fewer than two of them with a valid
-    joint raise the reference's AssertionError."""
+    joint raise the reference's AssertionError.  ``view_joint_valid`` (V, J): the views each joint is usable in; a valid joint
+    but none with two such views raises the same AssertionError."""
     if direct_optimization:
         raise NotImplementedError(
             "direct_optimization (scipy Huber least-squares, off in every reference call site): its result is where "
@@ -264,6 +361,7 @@ def triangulation(
         reprojection_error_epsilon,
         pair_rng=random,
         view_valid=None if view_valid is None else torch.as_tensor(view_valid).reshape(1, -1),
+        view_joint_valid=None if view_joint_valid is None else torch.as_tensor(view_joint_valid).unsqueeze(0),
     )
     inl = int(r["inlier_count"][0].item())
     if inl == -2:

@@ -1,0 +1,213 @@
+"""Host tests (no GPU) of the per-(view, joint) visibility support: the new entries in the header and the library, the pair
+tables ``draw_view_pairs(..., view_joint_valid=)`` builds per problem -- against the tables and RNG digests the real reference
+left when its ``_triangulate_ransac`` was handed each joint's present views (tests/golden/view_joint_mask.npz,
+make_view_joint_mask_golden.py) --, the two config fields, and how a batch's mask is resolved from them."""
+import ctypes
+import inspect
+import itertools
+import os
+import random
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import view_joint_mask_cases as vjc
+import view_mask_cases as vm
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NPZ = os.path.join(os.path.dirname(__file__), "golden", "view_joint_mask.npz")
+VIEWS_NPZ = os.path.join(os.path.dirname(__file__), "golden", "view_mask.npz")
+NEW_ENTRIES = ("mval_triangulate_ransac_vj", "mval_triangulate_ransac_pairs_vj", "mval_reprojection_xe_vj", "mval_score_reduce_vj",
+               "mval_peak_mask")
+
+
+def test_new_entries_are_declared_and_exported():
+    from multi_view_active_learning_amd import _lib, build
+
+    if not os.path.exists(_lib.LIB_PATH):
+        build.build(verbose=False)
+    hdr = open(os.path.join(REPO, "include", "mval_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    names = set(re.findall(r"\b(mval_[a-z0-9_]+)\s*\(", hdr))
+    for n in NEW_ENTRIES:
+        assert n in names, n + " is not declared in include/mval_hip.h"
+        assert hasattr(_lib.lib(), n), n + " is not exported"
+        f = _lib._views_entry(n)
+        assert f.restype is ctypes.c_int and len(f.argtypes) == len(_lib._VIEWS_ARGTYPES[n])
+        decl = re.search(r"\b%s\s*\(([^)]*)\)" % n, hdr).group(1)
+        assert len(decl.split(",")) == len(f.argtypes), n
+    # a `_vj` entry takes what its `_views` sibling takes
+    for n in NEW_ENTRIES[:4]:
+        assert _lib._VIEWS_ARGTYPES[n] == _lib._VIEWS_ARGTYPES[n[:-3] + "_views"], n
+
+
+@pytest.mark.parametrize("name", list(vjc.view_joint_mask_cases()))
+def test_view_joint_draw_reproduces_the_reference_tables(name):
+    """The whole batch at once and frame by frame (the digest after EVERY frame is the reference's): the same tables, the same
+    RNG states.  A case that draws nothing leaves the generator alone."""
+    from multi_view_active_learning_amd.utils.triangulation import draw_view_pairs
+
+    c = vjc.view_joint_mask_cases()[name]
+    z = vjc.load_golden(NPZ, name)
+    valid, mask = vjc.valid_joints(c), vjc.view_joint_valid(c)
+    random.seed(int(z["rseed"]))
+    before = random.getstate()
+    tab = draw_view_pairs(valid, c["v"], c["n_iters"], random, view_joint_valid=mask)
+    assert tab.dtype == np.uint8 and tab.shape == z["pairs"].shape == (c["b"], c["j"], vjc.n_pairs(c), 2)
+    np.testing.assert_array_equal(tab, z["pairs"])
+    assert vjc.state_digest(random.getstate()) == str(z["frame_digests"][-1])
+    if not vjc.draws(c).any():
+        assert random.getstate() == before
+    random.seed(int(z["rseed"]))
+    for b in range(c["b"]):
+        before = random.getstate()
+        one = draw_view_pairs(valid[b : b + 1], c["v"], c["n_iters"], random, view_joint_valid=torch.from_numpy(mask[b : b + 1]).float())
+        assert vjc.state_digest(random.getstate()) == str(z["frame_digests"][b])
+        if not vjc.draws(c)[b].any():
+            assert random.getstate() == before
+        np.testing.assert_array_equal(one[0], z["pairs"][b, :, : one.shape[2]])
+        assert (z["pairs"][b, :, one.shape[2] :] == 255).all()
+
+
+def test_mixed_frame_table_layout():
+    """j12_mixed, ONE frame: a joint with 12 present views has 64 drawn pairs, one with 11 the 55 lexicographic pairs of its
+    views then padding, one with 10 its 45; only the 12-view joints moved the generator (one shuffle of 66 each)."""
+    from multi_view_active_learning_amd.utils.triangulation import draw_view_pairs
+
+    c = vjc.view_joint_mask_cases()["j12_mixed"]
+    valid, mask = vjc.valid_joints(c), vjc.view_joint_valid(c)
+    n = mask.sum(axis=1)[0]
+    assert set(n.tolist()) == {10, 11, 12}
+    rng, ref = random.Random(8), random.Random(8)
+    tab = draw_view_pairs(valid, 12, 64, rng, view_joint_valid=mask)
+    assert tab.shape == (1, 19, 64, 2)
+    for j in range(19):
+        views = np.flatnonzero(mask[0, :, j]).tolist()
+        lex = list(itertools.combinations(views, 2))
+        if not valid[0, j]:
+            assert n[j] == 12 and not tab[0, j].any()  # (a drawing problem's row stays zero for an invalid joint)
+        elif n[j] == 12:
+            order = list(range(66))
+            ref.shuffle(order)
+            np.testing.assert_array_equal(tab[0, j], [lex[k] for k in order[:64]])
+        else:
+            np.testing.assert_array_equal(tab[0, j, : len(lex)], lex)
+            assert (tab[0, j, len(lex) :] == 255).all()
+    assert rng.getstate() == ref.getstate()
+
+
+@pytest.mark.parametrize("name", list(vm.view_mask_cases()))
+def test_broadcast_mask_gives_the_view_valid_tables(name):
+    """view_joint_valid = view_valid[:, :, None] expanded: the tables and the final RNG state of the ``view_valid`` draw (which
+    the missing-view goldens pin), also when the frame mask is given beside an all-ones joint mask (the two are ANDed)."""
+    from multi_view_active_learning_amd.utils.triangulation import draw_view_pairs
+
+    c = vm.view_mask_cases()[name]
+    z = vm.load_golden(VIEWS_NPZ, name)
+    valid = np.ones((c["b"], c["j"]), dtype=bool)
+    valid[:, list(c["invalid"])] = False
+    valid[list(c["no_valid_joint"])] = False
+    vv = vm.view_valid(c)
+    wide = np.broadcast_to(vv[:, :, None], (c["b"], c["v"], c["j"])).copy()
+    for kw in (dict(view_joint_valid=wide), dict(view_valid=vv, view_joint_valid=np.ones_like(wide))):
+        random.seed(int(z["rseed"]))
+        tab = draw_view_pairs(valid, c["v"], c["n_iters"], random, **kw)
+        np.testing.assert_array_equal(tab, z["pairs"])
+        assert vm.state_digest(random.getstate()) == str(z["frame_digests"][-1])
+    random.seed(int(z["rseed"]))
+    np.testing.assert_array_equal(draw_view_pairs(valid, c["v"], c["n_iters"], random, view_valid=vv), z["pairs"])
+
+
+def test_nothing_is_drawn_where_all_pairs_fit():
+    """Up to n_iters pairs per problem: no shuffle at all, the global generator keeps its state; a joint with one view or none
+    is all padding; P is at least 1."""
+    from multi_view_active_learning_amd.utils.triangulation import draw_view_pairs
+
+    class NoDraw:
+        def shuffle(self, x):
+            raise AssertionError("nothing is drawn when all pairs fit")
+
+    mask = np.ones((2, 5, 3), dtype=np.uint8)
+    mask[0, [0, 2], 1] = 0
+    mask[0, 1:, 2] = 0
+    mask[1] = 0
+    mask[1, 3, 0] = 1
+    state = random.getstate()
+    tab = draw_view_pairs(np.ones((2, 3)), 5, 64, NoDraw(), view_joint_valid=mask)
+    assert random.getstate() == state
+    assert tab.shape == (2, 3, 10, 2)
+    np.testing.assert_array_equal(tab[0, 0], list(itertools.combinations(range(5), 2)))
+    np.testing.assert_array_equal(tab[0, 1, :3], [(1, 3), (1, 4), (3, 4)])
+    assert (tab[0, 1, 3:] == 255).all() and (tab[0, 2] == 255).all() and (tab[1] == 255).all()
+    assert draw_view_pairs(np.ones((1, 3)), 5, 64, NoDraw(), view_joint_valid=mask[1:]).shape == (1, 3, 1, 2)
+
+
+def test_config_fields_and_their_validator():
+    from multi_view_active_learning_amd.config import check_view_joint_valid, get_default_configs
+
+    cfg = get_default_configs()
+    assert cfg.AL.VIEW_JOINT_VALID_KEY == "" and cfg.AL.MIN_PEAK == 0.0
+    assert check_view_joint_valid(cfg.AL.VIEW_JOINT_VALID_KEY, cfg.AL.MIN_PEAK) == ("", 0.0)
+    cfg.merge_from_list(["AL.VIEW_JOINT_VALID_KEY", "per_view_joint_valid", "AL.MIN_PEAK", 0.25])
+    assert check_view_joint_valid(cfg.AL.VIEW_JOINT_VALID_KEY, cfg.AL.MIN_PEAK) == ("per_view_joint_valid", 0.25)
+    assert check_view_joint_valid("view_joint_valid", 1) == ("view_joint_valid", 1.0)
+    for bad in (None, 3, ["per_view_joint_valid"], b"key"):
+        with pytest.raises(ValueError, match="VIEW_JOINT_VALID_KEY"):
+            check_view_joint_valid(bad, 0.0)
+    for bad in (-0.1, float("nan"), float("inf"), "0.5", None, True):
+        with pytest.raises(ValueError, match="MIN_PEAK"):
+            check_view_joint_valid("", bad)
+
+
+def test_stage_batch_and_wrappers_know_the_mask():
+    from multi_view_active_learning_amd import strategy
+    from multi_view_active_learning_amd.utils import triangulation
+
+    assert "view_joint_valid" in strategy._SMALL_KEYS
+    for fn, kws in ((triangulation.triangulate_batch, ("view_joint_valid", "view_joint_valid_host")),
+                    (triangulation.triangulation, ("view_joint_valid",)), (triangulation.draw_view_pairs, ("view_valid", "view_joint_valid")),
+                    (strategy.score_heatmaps_batch, ("view_joint_valid",)), (strategy.score_decode_heatmaps_batch, ("view_joint_valid",)),
+                    (strategy.score_decode_heatmaps_all, ("view_joint_valid",))):
+        params = inspect.signature(fn).parameters
+        for kw in kws:
+            assert kw in params and params[kw].default is None, (fn.__name__, kw)
+    assert list(inspect.signature(triangulation.peak_mask).parameters) == ["heatmaps", "min_peak"]
+    if not torch.cuda.is_available():  # (host-only: the batch comes back as it is)
+        dp = dict(view_joint_valid=torch.ones((1, 2, 3)))
+        assert strategy._stage_batch(dp) is dp
+
+
+def test_mask_resolution_from_the_config():
+    """Both fields off and no ``view_joint_valid`` in the batch: no mask, whatever else the batch carries.  A named key, the
+    batch's own key, both (ANDed), a missing named key, a bad config value."""
+    from multi_view_active_learning_amd.config import get_default_configs
+    from multi_view_active_learning_amd.strategy import ActiveLearningStrategy
+
+    b, v, j = 2, 3, 4
+    hm = torch.zeros((b, v, j, 1, 1))
+    rng = np.random.default_rng(3)
+    per = torch.from_numpy((rng.random((b, v, j)) < 0.7).astype(np.float32))
+    own = torch.from_numpy((rng.random((b, v, j)) < 0.7).astype(np.float32))
+    cfg = get_default_configs()
+    st = ActiveLearningStrategy(cfg)
+    assert st._mask_keys() == ("view_joint_valid",)
+    assert st._view_joint_valid(hm, dict(per_view_joint_valid=per, view_valid=torch.ones((b, v)))) == (None, None)
+    mask, host = st._view_joint_valid(hm, dict(view_joint_valid=own))
+    assert mask.dtype == torch.uint8 and torch.equal(mask, (own != 0).to(torch.uint8)) and torch.equal(host, own != 0)
+    cfg.AL.VIEW_JOINT_VALID_KEY = "per_view_joint_valid"
+    assert st._mask_keys() == ("view_joint_valid", "per_view_joint_valid")
+    mask, host = st._view_joint_valid(hm, dict(per_view_joint_valid=per.reshape(b, v * j)))
+    assert torch.equal(mask, (per != 0).to(torch.uint8)) and torch.equal(host, per != 0)
+    mask, host = st._view_joint_valid(hm, dict(per_view_joint_valid=per, view_joint_valid=own))
+    assert torch.equal(mask.bool(), (per != 0) & (own != 0)) and torch.equal(host, mask.bool())
+    with pytest.raises(KeyError, match="per_view_joint_valid"):
+        st._view_joint_valid(hm, dict(view_joint_valid=own))
+    cfg.AL.VIEW_JOINT_VALID_KEY = 7
+    with pytest.raises(ValueError, match="VIEW_JOINT_VALID_KEY"):
+        st._view_joint_valid(hm, dict())
+    cfg.AL.VIEW_JOINT_VALID_KEY = ""
+    cfg.AL.MIN_PEAK = -1.0
+    with pytest.raises(ValueError, match="MIN_PEAK"):
+        st._view_joint_valid(hm, dict())

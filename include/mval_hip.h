@@ -552,6 +552,11 @@ int mval_p2_to_nhwc(const void* planes, const uint32_t* rows, float* out, int n_
 int mval_op_mfma_supported(const mval_op* op, int n_images);
 /* Same question for a given MVAL_ALGO_* (MFMA, MFMA_BF3 or MFMA_H2). */
 int mval_op_algo_supported(const mval_op* op, int n_images, int algo);
+/* Which kernel mval_op_launch runs an MVAL_OP_CONV with MVAL_ALGO_DIRECT on: 3 or 7 = the stem kernel of that size (csrc/conv_stem.hip:
+ * 3 NCHW input channels, k 3 or 7, stride 2, pad k / 2, cout % 4 == 0, no up-sampling, residual or NCHW output, weights and input
+ * patch within 64 KB of LDS), 0 = the generic direct kernel (also when op->no_stem is set, or for any other kind or algo).  Host
+ * arithmetic: the predicate the launcher itself asks; no HIP call. */
+int mval_conv_stem_covers(const mval_op* op);
 
 /* Which kernel of the split-MFMA conv family (csrc/conv_mfma_split.hip: MVAL_ALGO_MFMA_BF3 / _H2) a launch of the library runs on: the
  * launcher's own dispatch up to, but without, the launch.  Host arithmetic only (no GPU needed, nothing is launched).
@@ -761,6 +766,14 @@ int mval_conv_wgrad(const float* x, const float* dz, float* dw, float* ws, int N
 int mval_conv_wgrad_scaled(const float* x, const float* dz, float* dw, float* ws, int N, int Hin, int Win, int Cin,
                            int Hout, int Wout, int Cout, int k, int stride, int pad, int x_nchw,
                            const uint32_t* x_amax_row, const uint32_t* dz_amax_row, void* stream);
+/* Which kernel those two entries run the weight gradient on -- the decision of the launcher itself, host arithmetic, no HIP call:
+ *   SPLIT    the split-bf16 / fp16 kernel (csrc/conv_wgrad_bf3.hip; NHWC x, pad k / 2, mval_conv_wgrad_split_covers)
+ *   STEM     the stem kernel (NCHW x of 3 channels, k 3 or 7, stride 2, pad k / 2, cout a multiple of 16 up to 64)
+ *   MFMA     the exact-fp32 kernel (NHWC x, cin % 4 == 0 and >= 16; 1x1 / 3x3 at stride 1 or 2 with pad k / 2, or k4 s2 p1)
+ *   DIRECT   the generic kernel for whatever is left, up to 64 * 2048 outputs k * k * cin * cout
+ *   REFUSED  more outputs than that (or bad dimensions): the entries return -1 */
+enum { MVAL_WGRAD_REFUSED = 0, MVAL_WGRAD_SPLIT = 1, MVAL_WGRAD_STEM = 2, MVAL_WGRAD_MFMA = 3, MVAL_WGRAD_DIRECT = 4 };
+int mval_conv_wgrad_path(int cin, int cout, int k, int stride, int pad, int x_nchw);
 int mval_slab_reduce(const float* slabs, int S, int64_t n, float* out, int accumulate, void* stream);
 /* Backward of MaxPool2d(k, stride, pad) (pose_resnet.py:35 under autograd): gin (+)= gout routed to the
  * first maximum of each window in ATen's scan order (NaN wins); x / gin NHWC [N,Hin,Win,C], gout

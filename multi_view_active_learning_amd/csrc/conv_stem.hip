@@ -99,15 +99,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   if (a.out_amax) conv_amax_commit(a.out_amax + (int64_t)n * MVAL_AMAX_ROW, (int)(blockIdx.x % (unsigned)a.amax_tiles), a.amax_tiles, amax);
 }
 
+static size_t stem_smem_bytes(int k, int cout) {
+  const int PH = (ST_TH - 1) * 2 + k, PW = ((ST_TW - 1) * 2 + k) | 1;
+  return (size_t)(k * k * 3 * cout + 3 * PH * PW) * sizeof(float);
+}
+
+// The stem kernel's shape: 3 NCHW channels, k 3 or 7, stride 2, pad k / 2, cout % 4 == 0, a plain NHWC store, weights + patch within 64 KB
+// of LDS.  Returns the kernel's k (3 or 7), or 0 when the op is not such a stem.
+static int stem_covers(int in_nchw, int cin, int stride, int k, int pad, int cout, int up, bool residual, int out_nchw) {
+  if (!in_nchw || cin != 3 || stride != 2 || up || residual || out_nchw || (cout & 3)) return 0;
+  if (k != 3 && k != 7) return 0;
+  if (pad != k / 2) return 0;
+  if (stem_smem_bytes(k, cout) > 64 * 1024) return 0;
+  return k;
+}
+
+// Which stem kernel mval_op_launch runs the op on (include/mval_hip.h).  No HIP call.
+extern "C" int mval_conv_stem_covers(const mval_op* op) {
+  if (!op || op->kind != MVAL_OP_CONV || op->algo != MVAL_ALGO_DIRECT || op->no_stem) return 0;
+  return stem_covers(op->in_nchw, op->cin, op->stride, op->k, op->pad, op->cout, op->up, op->res1_off >= 0 || op->res2_off >= 0, op->out_nchw);
+}
+
 // returns 1 when the op is not a stem of the supported shape
 int mval_launch_conv_stem(const ConvArgs& a0, hipStream_t s) {
   ConvArgs a = a0;
-  if (!a.in_nchw || a.Cin != 3 || a.stride != 2 || a.up || a.res1 || a.res2 || a.out_nchw || (a.Cout & 3)) return 1;
-  if (a.k != 3 && a.k != 7) return 1;
-  if (a.pad != a.k / 2) return 1;
-  const int PH = (ST_TH - 1) * 2 + a.k, PW = ((ST_TW - 1) * 2 + a.k) | 1;
-  size_t smem = (size_t)(a.k * a.k * 3 * a.Cout + 3 * PH * PW) * sizeof(float);
-  if (smem > 64 * 1024) return 1;
+  if (!stem_covers(a.in_nchw, a.Cin, a.stride, a.k, a.pad, a.Cout, a.up, a.res1 || a.res2, a.out_nchw)) return 1;
+  const size_t smem = stem_smem_bytes(a.k, a.Cout);
   const int tiles = ((a.Wout + ST_TW - 1) / ST_TW) * ((a.Hout + ST_TH - 1) / ST_TH) * a.N;
   conv_amax_prepare(a, tiles / a.N, 1, s);
   if (a.k == 3)

@@ -358,6 +358,25 @@ static int wg_splits(int cin, int cout, int target) {
 int mval_conv_wgrad_on(const float* x, const float* dz, float* dw, float* ws, int N, int Hin, int Win, int Cin, int Hout, int Wout, int Cout,
                        int k, int stride, int pad, int x_nchw, bool split, const uint32_t* x_amax_row, const uint32_t* dz_amax_row, hipStream_t s);
 
+// Which kernel mval_conv_wgrad_on runs a conv's weight gradient on (MVAL_WGRAD_* of include/mval_hip.h); split = false: the caller
+// asked for the exact-fp32 kernels.
+static int wgrad_path(int Cin, int Cout, int k, int stride, int pad, int x_nchw, bool split) {
+  if (split && !x_nchw && pad == k / 2 && mval_wgrad_bf3_covers(Cin, Cout, k, stride)) return MVAL_WGRAD_SPLIT;  // (conv_wgrad_bf3.hip)
+  if (x_nchw && Cin == 3 && (k == 3 || k == 7) && stride == 2 && pad == k / 2 && (Cout & 15) == 0 && Cout <= 64) return MVAL_WGRAD_STEM;
+  // k = 4, stride 2, pad 1: the weight gradient of ConvTranspose2d(k4, s2, p1) with the roles of the
+  // activations swapped (x := dz of the transposed conv, dz := its input)
+  if (!x_nchw && (Cin & 3) == 0 && Cin >= 16 &&
+      (((k == 1 || k == 3) && (stride == 1 || stride == 2) && pad == k / 2) || (k == 4 && stride == 2 && pad == 1)))
+    return MVAL_WGRAD_MFMA;
+  return (int64_t)k * k * Cin * Cout <= 64 * 256 * WD_EPT ? MVAL_WGRAD_DIRECT : MVAL_WGRAD_REFUSED;
+}
+
+// The same for mval_conv_wgrad / mval_conv_wgrad_scaled (which always allow the split kernel).  No HIP call.
+extern "C" int mval_conv_wgrad_path(int cin, int cout, int k, int stride, int pad, int x_nchw) {
+  if (cin <= 0 || cout <= 0 || k <= 0 || stride <= 0) return MVAL_WGRAD_REFUSED;
+  return wgrad_path(cin, cout, k, stride, pad, x_nchw, true);
+}
+
 extern "C" size_t mval_conv_wgrad_workspace_floats(int cin, int cout, int k) {
   return (size_t)wg_splits(cin, cout, 1024) * k * k * cin * cout;  // PS slabs of [tap][cin][cout]
 }
@@ -383,11 +402,7 @@ int mval_conv_wgrad_on(const float* x, const float* dz, float* dw, float* ws, in
   MVAL_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && k > 0 && stride > 0, "mval_conv_wgrad: bad dims");
   const int T = k * k;
   const int64_t n_out = (int64_t)T * Cin * Cout;
-  // k = 4, stride 2, pad 1: the weight gradient of ConvTranspose2d(k4, s2, p1) with the roles of the
-  // activations swapped (x := dz of the transposed conv, dz := its input)
-  const bool mfma = !x_nchw && (Cin & 3) == 0 && Cin >= 16 &&
-                    (((k == 1 || k == 3) && (stride == 1 || stride == 2) && pad == k / 2) || (k == 4 && stride == 2 && pad == 1));
-  const bool stem = x_nchw && Cin == 3 && (k == 3 || k == 7) && stride == 2 && pad == k / 2 && (Cout & 15) == 0 && Cout <= 64;
+  const int path = wgrad_path(Cin, Cout, k, stride, pad, x_nchw, split);
   int PS = 0;
   const void* xp2 = g_wgrad_x_p2;
   const unsigned* xp2_rows = g_wgrad_x_p2_rows;
@@ -402,9 +417,10 @@ int mval_conv_wgrad_on(const float* x, const float* dz, float* dw, float* ws, in
                                   x_amax_row, dz_amax_row, s, zp2, zp2_rows, split);
   MVAL_REQUIRE(PS >= 0, "mval_conv_wgrad: x given as its producer's raw z (mval_conv_wgrad_set_z_x) needs the split kernel's 3x3 stride-1 form with dz as planes (k%d s%d cin%d cout%d)", k, stride, Cin, Cout);
   MVAL_REQUIRE(!(xp2 || zp2) || PS > 0, "mval_conv_wgrad: the P2 form of x needs the split kernel (k%d s%d cin%d cout%d) and dz's magnitude row", k, stride, Cin, Cout);
+  MVAL_REQUIRE((PS > 0) == (path == MVAL_WGRAD_SPLIT), "mval_conv_wgrad: the split kernel and mval_conv_wgrad_path disagree (k%d s%d cin%d cout%d)", k, stride, Cin, Cout);
   if (PS > 0) {
     MVAL_CHECK_LAUNCH("mval_conv_wgrad/bf3");
-  } else if (stem) {
+  } else if (path == MVAL_WGRAD_STEM) {
     WgradArgs a;
     a.x = x; a.dz = dz; a.slabs = ws;
     a.N = N; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.Cout = Cout; a.pad = pad;
@@ -422,7 +438,7 @@ int mval_conv_wgrad_on(const float* x, const float* dz, float* dw, float* ws, in
     else
       hipLaunchKernelGGL((conv_wgrad_stem_kernel<7, 128>), dim3(PS), dim3(256), smem, s, a);
     MVAL_CHECK_LAUNCH("mval_conv_wgrad/stem");
-  } else if (mfma) {
+  } else if (path == MVAL_WGRAD_MFMA) {
     WgradArgs a;
     a.x = x; a.dz = dz; a.slabs = ws;
     a.N = N; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.Cout = Cout; a.pad = pad;
@@ -465,7 +481,7 @@ int mval_conv_wgrad_on(const float* x, const float* dz, float* dw, float* ws, in
 #undef WG_LAUNCH
     MVAL_CHECK_LAUNCH("mval_conv_wgrad/mfma");
   } else {
-    MVAL_REQUIRE(n_out <= 64 * 256 * WD_EPT, "mval_conv_wgrad: operator too large for the direct kernel (%lld outputs)",
+    MVAL_REQUIRE(path == MVAL_WGRAD_DIRECT, "mval_conv_wgrad: operator too large for the direct kernel (%lld outputs)",
                  (long long)n_out);
     WgradDirectArgs a;
     a.x = x; a.dz = dz; a.slabs = ws;

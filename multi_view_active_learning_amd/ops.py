@@ -34,9 +34,10 @@ def pack_weights(weight, algo, transposed=False):
 
 
 def fused_conv(x, weight, scale, shift, stride=1, pad=None, relu=False, res1=None, res2=None, up=0,
-               algo=ALGO_MFMA, in_nchw=False, out_nchw=False, kind=OP_CONV):
+               algo=ALGO_MFMA, in_nchw=False, out_nchw=False, kind=OP_CONV, no_stem=False):
     """out = act(((conv(x, w) * scale + shift + res1) + res2)), nearest-upsampled by 2^up.
-    x NHWC (N,H,W,Cin) unless in_nchw; returns NHWC (N,Ho,Wo,Cout) unless out_nchw."""
+    x NHWC (N,H,W,Cin) unless in_nchw; returns NHWC (N,Ho,Wo,Cout) unless out_nchw.  no_stem: a 3-channel NCHW stem with
+    ALGO_DIRECT runs on the generic direct kernel (MvalOp.no_stem, the all-direct plans)."""
     dev = x.device
     transposed = kind == OP_DECONV
     if kind == OP_MAXPOOL:
@@ -85,6 +86,7 @@ def fused_conv(x, weight, scale, shift, stride=1, pad=None, relu=False, res1=Non
     m.k, m.stride, m.pad, m.cin, m.cout = k, stride, pad, cin, cout
     m.hin, m.win, m.hout, m.wout = hin, win, hout, wout
     m.up, m.relu, m.in_nchw, m.out_nchw = up, int(relu), int(in_nchw), int(out_nchw)
+    m.no_stem = int(no_stem)
     m.in_off, m.out_off = 0, out_off
     it = iter(offs[1:])
     m.res1_off = next(it) if res1 is not None else -1

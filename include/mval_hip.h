@@ -64,6 +64,27 @@ int mval_pred_coordinates_from_keys(const uint64_t* keys, const float* boxes, fl
  * * stride): softmax over hh*wh, expectation of the pixel grid; kp2d [n_maps,2] f32 (x,y)*scale. */
 int mval_soft_argmax(const float* heatmaps, float* kp2d, int64_t n_maps, int hh, int wh, float scale, void* stream);
 
+/* Sub-pixel refinement of the hard arg-max (not in the reference; DESIGN.md 6.4 holds the definition).  The peak of a map is
+ * (px, py) = kp2d / stride; with the peak interior (1 <= px <= wh-2, 1 <= py <= hh-2) and its 3x3 neighbourhood n finite, in
+ * float64:
+ *   MVAL_REFINE_QUARTER: ox = 0.25 sgn(n[1][2] - n[1][0]), oy = 0.25 sgn(n[2][1] - n[0][1])   (HRNet's evaluation shift)
+ *   MVAL_REFINE_TAYLOR:  with L = log(max(n, 1e-10)), g and H the central first and second differences of L at the peak,
+ *                        (ox, oy) = -H^-1 g, taken iff n[1][1] > 0, dxx < 0, det H > 0, |ox| <= 1 and |oy| <= 1
+ *                        (DARK's Taylor step without its Gaussian pre-blur)
+ * and (0, 0) otherwise.  out = f32((px + ox) * stride), f32((py + oy) * stride), rounded once; conf = the map's value at the
+ * peak.  No FMA contraction: a float64 evaluation on the host takes the same sgn and accept decisions.
+ *   heatmaps [B,V,J,hh,wh] f32 ; kp2d [B,V,J,2] i64, the hard decode (px*stride, py*stride) as mval_argmax_decode,
+ *   mval_argmax_from_keys and the scoring kernels write it WITH split_width = wh ; valid [B,J] u8 or NULL (invalid joints ->
+ *   (0, 0), conf 0) ; out [B,V,J,2] f32 (x,y) ; conf [B,V,J] f32 or NULL.
+ * One thread per map, nine loads, no second read of the maps.  A kp2d entry that is no point of its map (negative, px >= wh or
+ * py >= hh: a decode split by hh on a non-square map can give one) is checked BEFORE any load and handed through as
+ * (f32(kp2d.x), f32(kp2d.y)) with conf NaN.  method outside {1, 2}, stride <= 0 or bad dimensions return an error and launch
+ * nothing; B = 0 returns 0. */
+#define MVAL_REFINE_QUARTER 1
+#define MVAL_REFINE_TAYLOR 2
+int mval_refine_keypoints(int method, const float* heatmaps, const int64_t* kp2d, const uint8_t* valid,
+                          float* out, float* conf, int B, int V, int J, int hh, int wh, int stride, void* stream);
+
 /* Peak gate: out[m] = 1 iff some element of map m is >= min_peak, else 0 (a comparison: a map of NaNs gives 0; exact, no
  * tolerance).  heatmaps [n_maps,hh,wh] f32 ; out [n_maps] u8.  One read of the maps.  With n_maps = B*V*J in the maps' own
  * order the result is a view_joint_valid [B,V,J] for the `_vj` entries below. */

@@ -207,6 +207,31 @@ def soft_argmax(hm, n_maps, hh, wh, scale):
     return out
 
 
+# MVAL_REFINE_* (include/mval_hip.h): the sub-pixel refinements of mval_refine_keypoints, under the names the config uses
+REFINE_QUARTER, REFINE_TAYLOR = 1, 2
+REFINE_IDS = {"quarter": REFINE_QUARTER, "taylor": REFINE_TAYLOR}
+
+
+def refine_keypoints(hm, kp2d, valid, b, v, j, hh, wh, stride, method):
+    """mval_refine_keypoints: hm (b,v,j,hh,wh) f32, kp2d (b,v,j,2) int64 -- the hard decode made with split_width = wh --,
+    valid (b,j) uint8 or None, method a name of REFINE_IDS -> (kp f32 (b,v,j,2), conf f32 (b,v,j))."""
+    if not isinstance(method, str) or method not in REFINE_IDS:
+        raise MvalError(f"refine_keypoints: method {method!r}: accepted are " + ", ".join(repr(k) for k in REFINE_IDS))
+    if tuple(kp2d.shape) != (b, v, j, 2) or hm.numel() != b * v * j * hh * wh:
+        raise MvalError(f"refine_keypoints: heat-maps of {b * v * j * hh * wh} elements and kp2d ({b}, {v}, {j}, 2), got "
+                        f"{hm.numel()} and {tuple(kp2d.shape)}")
+    out = torch.empty((b, v, j, 2), dtype=torch.float32, device=hm.device)
+    conf = torch.empty((b, v, j), dtype=torch.float32, device=hm.device)
+    _check(
+        lib().mval_refine_keypoints(
+            C.c_int(REFINE_IDS[method]), _p(_req(hm, torch.float32, "heatmaps")), _p(_req(kp2d, torch.int64, "keypoints_2d")), _p(valid),
+            _p(out), _p(conf), C.c_int(b), C.c_int(v), C.c_int(j), C.c_int(hh), C.c_int(wh), C.c_int(int(stride)), _stream(),
+        ),
+        "mval_refine_keypoints",
+    )
+    return out, conf
+
+
 def _triangulate(entry, kp2d, proj, valid, b, v, j, eps, table=()):
     """What the two triangulation entries share: key-points float32 or int64, the five outputs, the call.  ``table``: the
     arguments an entry takes between ``valid`` and the outputs."""

@@ -58,6 +58,9 @@ def get_default_configs():
     # their defaults only a batch's own "view_joint_valid" key masks anything
     c.AL.VIEW_JOINT_VALID_KEY = ""  # a batch key whose (B, V, J) tensor is the visibility mask, e.g. "per_view_joint_valid"
     c.AL.MIN_PEAK = 0.0  # > 0: a (view, joint) entry also needs a heat-map value >= this (utils.triangulation.peak_mask)
+    # not in the reference (which decodes to whole heat-map pixels): the sub-pixel decode of the pool-scoring passes, "none" |
+    # "quarter" | "taylor" (check_decode_refine below); not together with USE_SOFTARGMAX
+    c.AL.DECODE_REFINE = "none"
     c.AL.CLUSTER = CN()  # EXPR_TYPE "CLUSTER" (strategy.py:137-191): what ActiveLearningStrategy.cluster writes
     c.AL.CLUSTER.TYPE = "LOSS"  # LOSS | POSE (cluster_type below)
     c.AL.CLUSTER.SAVE_PATH = ""
@@ -78,6 +81,7 @@ def get_default_configs():
 
     c.EVAL = CN()
     c.EVAL.METRIC = "3DPCK"
+    c.EVAL.DECODE_REFINE = "none"  # not in the reference: AL.DECODE_REFINE for evaluate_mkpe / evaluate_all
 
     c.POSE_ESTIMATOR = _pose_defaults()
     c.DATA = _data_defaults()
@@ -122,3 +126,18 @@ def check_view_joint_valid(key, min_peak):
     if isinstance(min_peak, bool) or not isinstance(min_peak, (int, float)) or not 0.0 <= float(min_peak) < float("inf"):
         raise ValueError("AL.MIN_PEAK %r: accepted is a finite number >= 0 (0 switches the peak gate off)" % (min_peak,))
     return key, float(min_peak)
+
+
+DECODE_REFINES = ("none", "quarter", "taylor")  # "none": the reference's hard arg-max; the others: the names of _lib.REFINE_IDS
+
+
+def check_decode_refine(value, use_softargmax=False):
+    """A valid AL.DECODE_REFINE / EVAL.DECODE_REFINE / ``refine=`` of utils.triangulation, or ValueError naming the accepted ones --
+    also for a refinement together with the soft-arg-max (AL.USE_SOFTARGMAX, ``use_soft_argmax``): the refinements start from the
+    hard arg-max, the soft-arg-max has none."""
+    if not isinstance(value, str) or value not in DECODE_REFINES:
+        raise ValueError("decode refinement %r: accepted are %s" % (value, ", ".join(repr(m) for m in DECODE_REFINES)))
+    if value != "none" and use_softargmax:
+        raise ValueError("decode refinement %r together with the soft-arg-max (AL.USE_SOFTARGMAX / use_soft_argmax): a refinement "
+                         "(accepted are %s) starts from the hard arg-max, use one or the other" % (value, ", ".join(repr(m) for m in DECODE_REFINES)))
+    return value

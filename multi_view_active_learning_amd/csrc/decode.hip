@@ -235,3 +235,85 @@ extern "C" int mval_peak_mask(const float* heatmaps, float min_peak, uint8_t* ou
   MVAL_CHECK_LAUNCH("mval_peak_mask");
   return 0;
 }
+
+// ---- sub-pixel refinement of the hard arg-max ----------------------------------------------------------------
+// One THREAD per map: the arg-max is known (kp2d), what is left is nine loads around it and a few dozen float64 operations, so
+// the launch is latency-bound on B*V*J independent small problems and a wave per map would idle 63 lanes.  The point is checked
+// against the map before any load; every decision (sgn, accept) is taken on float64 values computed without FMA contraction, in
+// the order the definition writes them, so that a host float64 evaluation takes the same decisions.
+struct refine_offset { double ox, oy; };
+
+__device__ __forceinline__ refine_offset refine_quarter(const double (&n)[3][3]) {
+  const double dx = n[1][2] - n[1][0], dy = n[2][1] - n[0][1];  // (float32 values in float64: exact)
+  return {dx > 0.0 ? 0.25 : dx < 0.0 ? -0.25 : 0.0, dy > 0.0 ? 0.25 : dy < 0.0 ? -0.25 : 0.0};
+}
+
+__device__ __forceinline__ refine_offset refine_taylor(const double (&n)[3][3]) {
+#pragma clang fp contract(off)
+  if (!(n[1][1] > 0.0)) return {0.0, 0.0};
+  double L[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) L[r][c] = log(fmax(n[r][c], 1e-10));
+  const double gx = 0.5 * (L[1][2] - L[1][0]), gy = 0.5 * (L[2][1] - L[0][1]);
+  const double dxx = L[1][2] - 2.0 * L[1][1] + L[1][0], dyy = L[2][1] - 2.0 * L[1][1] + L[0][1];
+  const double dxy = 0.25 * (L[2][2] - L[2][0] - L[0][2] + L[0][0]);
+  const double det = dxx * dyy - dxy * dxy;
+  const double ox = -(dyy * gx - dxy * gy) / det, oy = -(dxx * gy - dxy * gx) / det;
+  const bool ok = dxx < 0.0 && det > 0.0 && fabs(ox) <= 1.0 && fabs(oy) <= 1.0;  // (every comparison is false for a NaN)
+  return ok ? refine_offset{ox, oy} : refine_offset{0.0, 0.0};
+}
+
+__global__ __launch_bounds__(256) void refine_keypoints_kernel(int method, const float* __restrict__ hm, const int64_t* __restrict__ kp2d,
+                                                               const uint8_t* __restrict__ valid, float* __restrict__ out,
+                                                               float* __restrict__ conf, int64_t n_maps, int V, int J, int hh, int wh,
+                                                               int stride) {
+#pragma clang fp contract(off)
+  const int64_t map = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (map >= n_maps) return;
+  float2 xy = make_float2(0.f, 0.f);
+  float peak = 0.f;
+  if (!valid || valid[(map / ((int64_t)V * J)) * J + map % J]) {
+    const int64_t kx = kp2d[map * 2], ky = kp2d[map * 2 + 1];
+    const int64_t px = kx / stride, py = ky / stride;
+    if (kx < 0 || ky < 0 || px >= wh || py >= hh) {  // not a point of this map (a decode split by another width): handed through, nothing loaded
+      xy = make_float2((float)kx, (float)ky);
+      peak = __builtin_nanf("");
+    } else {
+      const float* p = hm + map * ((int64_t)hh * wh) + py * wh + px;
+      peak = p[0];
+      refine_offset o = {0.0, 0.0};
+      if (px >= 1 && px <= wh - 2 && py >= 1 && py <= hh - 2) {
+        double n[3][3];
+        bool finite = true;
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            n[r][c] = (double)p[(r - 1) * wh + (c - 1)];
+            finite = finite && fabs(n[r][c]) < INFINITY;  // (false for a NaN)
+          }
+        if (finite) o = method == MVAL_REFINE_QUARTER ? refine_quarter(n) : refine_taylor(n);
+      }
+      xy = make_float2((float)(((double)px + o.ox) * (double)stride), (float)(((double)py + o.oy) * (double)stride));
+    }
+  }
+  reinterpret_cast<float2*>(out)[map] = xy;
+  if (conf) conf[map] = peak;
+}
+
+extern "C" int mval_refine_keypoints(int method, const float* heatmaps, const int64_t* kp2d, const uint8_t* valid, float* out,
+                                     float* conf, int B, int V, int J, int hh, int wh, int stride, void* stream) {
+  MVAL_REQUIRE(method == MVAL_REFINE_QUARTER || method == MVAL_REFINE_TAYLOR, "mval_refine_keypoints: method %d is neither MVAL_REFINE_QUARTER nor MVAL_REFINE_TAYLOR", method);
+  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && (int64_t)hh * wh <= 0x7fffffff && stride > 0, "mval_refine_keypoints: bad dims");
+  const int64_t n_maps = (int64_t)B * V * J;
+  if (n_maps == 0) return 0;
+  MVAL_REQUIRE(heatmaps && kp2d && out, "mval_refine_keypoints: heatmaps, kp2d and out must not be NULL");
+  MVAL_REQUIRE(((uintptr_t)out & 7) == 0, "mval_refine_keypoints: out must be 8-byte aligned");
+  MVAL_REQUIRE((n_maps + 255) / 256 <= 0x7fffffff, "mval_refine_keypoints: too many maps");
+  hipLaunchKernelGGL(refine_keypoints_kernel, dim3((unsigned)((n_maps + 255) / 256)), dim3(256), 0, mval_stream(stream), method, heatmaps,
+                     kp2d, valid, out, conf, n_maps, V, J, hh, wh, stride);
+  MVAL_CHECK_LAUNCH("mval_refine_keypoints");
+  return 0;
+}

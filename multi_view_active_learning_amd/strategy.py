@@ -427,8 +427,13 @@ class ActiveLearningStrategy:
         (ids [pose, frame_id], rest [sal_metric, inlier_count, mkpe, keypoints_3d(3J)], al_metric per strategy).
         A batch with ``view_valid`` (B, V) -- frames with missing views -- is scored and triangulated over each frame's
         present views alone; one with a per-(view, joint) mask (``_view_joint_valid``) over each joint's present views, and
-        its per-sample MKPE leaves out the joints nobody triangulated (``joint_valid & joint_used``)."""
+        its per-sample MKPE leaves out the joints nobody triangulated (``joint_valid & joint_used``).
+        AL.DECODE_REFINE "quarter" | "taylor": the decode of the heat-map launch is split by the width and refined before
+        the triangulation (``triangulate_batch(refine=...)``); "none" is the path above call for call."""
+        from .config import check_decode_refine
+
         cfg = self.al_cfg
+        refine = check_decode_refine(cfg.AL.DECODE_REFINE if "DECODE_REFINE" in cfg.AL else "none", cfg.AL.USE_SOFTARGMAX)
         dev = heatmaps.device
         pose = torch.as_tensor(dp["pose"]).reshape(-1)
         b = pose.shape[0]
@@ -441,9 +446,14 @@ class ActiveLearningStrategy:
         scored, kp2d = {}, None
         if configs:
             # one read of every heat-map for the uncertainty statistics and the key-point decode
-            scored = _score_heatmaps(configs, hm, joint_valid, cfg.POSE_ESTIMATOR.STRIDE, decode=not cfg.AL.USE_SOFTARGMAX,
-                                     view_valid=view_valid, view_joint_valid=vj)
+            if refine == "none":
+                scored = _score_heatmaps(configs, hm, joint_valid, cfg.POSE_ESTIMATOR.STRIDE, decode=not cfg.AL.USE_SOFTARGMAX,
+                                         view_valid=view_valid, view_joint_valid=vj)
+            else:  # (the refinement works in the neighbourhood of the geometric peak: no split by the height)
+                scored = _score_heatmaps(configs, hm, joint_valid, cfg.POSE_ESTIMATOR.STRIDE, mirror_nonsquare_quirk=False, decode=True,
+                                         view_valid=view_valid, view_joint_valid=vj)
             kp2d = next(iter(scored.values()))[4]
+        refined = {} if refine == "none" else {"refine": refine}
         r = triangulation.triangulate_batch(
             hm, dp["proj_matrices"], cfg.POSE_ESTIMATOR.STRIDE, joint_valid,
             cfg.AL.USE_SOFTARGMAX, cfg.AL.USE_REPROJECTION_XE, cfg.AL.REPROJECTION_SIGMA,
@@ -451,7 +461,7 @@ class ActiveLearningStrategy:
             pair_rng=random,  # more than n_iters view pairs (12 views on): the reference's draws, frames in batch order
             valid_joints_host=dp.get("joint_valid_host"),
             view_valid=view_valid, view_valid_host=dp.get("view_valid_host"),
-            view_joint_valid=vj, view_joint_valid_host=vj_host,
+            view_joint_valid=vj, view_joint_valid_host=vj_host, **refined,
         )
         pred32 = r["keypoints_3d"].to(torch.float32)  # torch.Tensor(results["keypoints_3d"]) (:1046)
         sal_metric = r["metric"].to(torch.float32).to(torch.float64)  # torch.Tensor([metric]) (:1061)
@@ -754,7 +764,13 @@ class ActiveLearningStrategy:
         """_evaluate_all's MKPE path: heat-maps -> hard arg-max triangulation -> MPJPE over the
         whole loader (one size exchange + one packed data gather instead of 3 all_gathers per sample).  A batch with a
         per-(view, joint) mask (``_view_joint_valid``) is triangulated joint by joint from the views that have the joint, and the
-        validity column it contributes is ``joint_valid & joint_used``: a joint nobody triangulated is left out."""
+        validity column it contributes is ``joint_valid & joint_used``: a joint nobody triangulated is left out.
+        EVAL.DECODE_REFINE "quarter" | "taylor": the sub-pixel decode of ``triangulate_batch(refine=...)``."""
+        from .config import check_decode_refine
+
+        refine = check_decode_refine(self.al_cfg.EVAL.DECODE_REFINE if "DECODE_REFINE" in self.al_cfg.EVAL else "none")
+        refined = {} if refine == "none" else {"refine": refine}
+
         def inputs(hm, dp):
             b = torch.as_tensor(dp["pose"]).reshape(-1).shape[0] if "pose" in dp else dp["images"].shape[0]
             jv = torch.as_tensor(dp["joint_valid"]).reshape(b, hm.shape[1])
@@ -768,7 +784,7 @@ class ActiveLearningStrategy:
                                                 self.al_cfg.POSE_ESTIMATOR.STRIDE, jv, pair_rng=random,
                                                 valid_joints_host=dp.get("joint_valid_host"),
                                                 view_valid=dp.get("view_valid"), view_valid_host=dp.get("view_valid_host"),
-                                                view_joint_valid=vj, view_joint_valid_host=vj_host)
+                                                view_joint_valid=vj, view_joint_valid_host=vj_host, **refined)
             scored = jv.to(hm.device, torch.float32)
             if vj is not None:
                 scored = ((scored != 0) & r["joint_used"].bool()).to(torch.float32)

@@ -20,6 +20,9 @@ Joints missing from single views: ``view_joint_valid`` (B, V, J) makes the prese
 joint): every joint is triangulated from the views that have it, a joint with fewer than two of them is left out of the
 frame's metric and inlier count, and ``peak_mask`` builds such a mask on the device from the heat-maps' own peak heights
 (DESIGN.md 6.3).
+
+Sub-pixel decode: ``refine`` = "quarter" | "taylor" refines the hard arg-max inside its 3x3 neighbourhood (``mval_refine_keypoints``,
+DESIGN.md 6.4) and hands float32 key-points to the unchanged triangulation entries; "none", the default, is the reference's decode.
 """
 from __future__ import annotations
 
@@ -29,6 +32,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..config import check_decode_refine
 
 
 def _device_of(heatmaps):
@@ -171,6 +175,7 @@ def triangulate_batch(
     view_valid_host=None,
     view_joint_valid=None,
     view_joint_valid_host=None,
+    refine="none",
 ):
     """heatmaps (B,V,J,Hh,Wh) f32 HIP tensor, proj (B,V,3,4), valid (B,J) ->
     dict of HIP tensors: keypoints_3d (B,J,3) f64, keypoints_2d (B,V,J,2) i64|f32,
@@ -211,8 +216,15 @@ def triangulate_batch(
     result carries ``joint_used`` (B, J) uint8 = joint_inliers > 0.  No valid joint: inlier_count -1; a valid joint but no
     used one: -2, metric NaN.  Up to 11 views nothing of the mask is needed on the host; beyond, the per-problem pair
     tables are drawn from ``view_joint_valid_host`` where given -- a mask that exists on the device alone is copied back,
-    which blocks the host on the current stream."""
+    which blocks the host on the current stream.
+
+    ``refine``: "none" (today's path call for call) | "quarter" | "taylor", the sub-pixel refinement of the hard arg-max
+    (``config.check_decode_refine``).  The hard decode is then made with ``split_width = wh`` whatever ``mirror_nonsquare_quirk`` says -- the
+    reference's split by the height has no neighbourhood to refine in --, a ``keypoints_2d`` handed in must be that int64 decode,
+    and the result carries the refined ``keypoints_2d`` (float32) and ``keypoints_conf`` (B, V, J) float32, the maps' values at
+    their peaks (0 for absent entries and invalid joints).  Not together with ``use_soft_argmax``: ValueError."""
     dev = _device_of(heatmaps)
+    check_decode_refine(refine, use_soft_argmax)
     if heatmaps.dim() != 5:
         raise ValueError("heatmaps must be (B, V, J, Hh, Wh)")
     b, v, j, hh, wh = heatmaps.shape
@@ -234,7 +246,11 @@ def triangulate_batch(
     vj = _as_valid_u8(view_joint_valid, (b, v, j), dev)
     if per_joint and vv is not None:
         vj = vj & vv[:, :, None]
-    if keypoints_2d is not None:
+    conf = None
+    if refine != "none":
+        kp2d = keypoints_2d if keypoints_2d is not None else _lib.argmax_decode(hm, valid, b, v, j, hh, wh, int(stride), wh)
+        kp2d, conf = _lib.refine_keypoints(hm, kp2d, valid, b, v, j, hh, wh, int(stride), refine)
+    elif keypoints_2d is not None:
         kp2d = keypoints_2d
     elif use_soft_argmax:
         kp2d = _lib.soft_argmax(hm, b * v * j, hh, wh, float(stride)).reshape(b, v, j, 2)
@@ -244,6 +260,8 @@ def triangulate_batch(
         # (the map kernels still decode the maps of absent views; a select, not a product: such a row may be NaN)
         present = vj.bool()[:, :, :, None] if per_joint else vv.bool()[:, :, None, None]
         kp2d = torch.where(present, kp2d, torch.zeros((), dtype=kp2d.dtype, device=dev))
+        if conf is not None:
+            conf = torch.where(present[..., 0], conf, torch.zeros((), dtype=conf.dtype, device=dev))
     eps = float(reprojection_error_epsilon)
     if sampled or (masked and v > 11):
         host_valid = valid_joints_host if valid_joints_host is not None else valid_joints
@@ -288,9 +306,28 @@ def triangulate_batch(
         "joint_error": jerr,
         "joint_inliers": jinl,
     }
+    if conf is not None:
+        out["keypoints_conf"] = conf
     if per_joint:
         out["joint_used"] = (jinl > 0).to(torch.uint8)  # a used joint's winning pair is in its own inlier set: >= 2
     return out
+
+
+def decode_keypoints(heatmaps, stride, valid_joints=None, refine="none"):
+    """The 2-D key-points alone: heatmaps (B, V, J, Hh, Wh) f32 HIP tensor, valid_joints (B, J) or None -> (keypoints_2d, conf).
+    "none": the hard arg-max (B, V, J, 2) int64 as ``triangulate_batch`` decodes it by default (the reference's split), conf None.
+    "quarter" | "taylor": the refined key-points float32, split by the width, and conf (B, V, J) float32, the peak values."""
+    _device_of(heatmaps)
+    check_decode_refine(refine)
+    if heatmaps.dim() != 5:
+        raise ValueError("heatmaps must be (B, V, J, Hh, Wh)")
+    b, v, j, hh, wh = heatmaps.shape
+    hm = heatmaps.to(torch.float32).contiguous()
+    valid = _as_valid_u8(valid_joints, (b, j), hm.device)
+    if refine == "none":
+        return _lib.argmax_decode(hm, valid, b, v, j, hh, wh, int(stride), hh), None
+    kp2d = _lib.argmax_decode(hm, valid, b, v, j, hh, wh, int(stride), wh)
+    return _lib.refine_keypoints(hm, kp2d, valid, b, v, j, hh, wh, int(stride), refine)
 
 
 _NEEDS_RNG = ("more view pairs than n_iters: the reference samples pairs from python's global RNG there "
@@ -336,13 +373,15 @@ def triangulation(
     direct_optimization=False,
     view_valid=None,
     view_joint_valid=None,
+    refine="none",
 ):
     """One frame, reference signature and return types (utils/triangulation.py:168-233):
     heatmaps (V,J,Hh,Wh), proj (V,3,4), valid (J,) -> {"keypoints_3d": ndarray (J,3) f64,
     "keypoints_2d": ndarray (V,J,2) int64|f32, "metric": float, "inlier_count": int}.
     ``view_valid`` (V,): the views present in this frame (``triangulate_batch``); fewer than two of them with a valid
     joint raise the reference's AssertionError.  ``view_joint_valid`` (V, J): the views each joint is usable in; a valid joint
-    but none with two such views raises the same AssertionError."""
+    but none with two such views raises the same AssertionError.  ``refine``: the sub-pixel decode of ``triangulate_batch``; the
+    result then also holds "keypoints_conf": ndarray (V, J) f32."""
     if direct_optimization:
         raise NotImplementedError(
             "direct_optimization (scipy Huber least-squares, off in every reference call site): its result is where "
@@ -362,15 +401,19 @@ def triangulation(
         pair_rng=random,
         view_valid=None if view_valid is None else torch.as_tensor(view_valid).reshape(1, -1),
         view_joint_valid=None if view_joint_valid is None else torch.as_tensor(view_joint_valid).unsqueeze(0),
+        refine=refine,
     )
     inl = int(r["inlier_count"][0].item())
     if inl == -2:
         raise AssertionError("need at least two views")  # reference: assert len(points) >= 2
     if inl < 0:
         raise ValueError("zero-size array to reduction operation minimum which has no identity")  # np.min([])
-    return {
+    out = {
         "keypoints_3d": r["keypoints_3d"][0].cpu().numpy(),
         "keypoints_2d": r["keypoints_2d"][0].cpu().numpy(),
         "metric": float(r["metric"][0].item()),
         "inlier_count": inl,
     }
+    if "keypoints_conf" in r:
+        out["keypoints_conf"] = r["keypoints_conf"][0].cpu().numpy()
+    return out

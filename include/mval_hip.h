@@ -186,6 +186,43 @@ int mval_triangulate_ransac_pairs_vj(const void* kp2d, int kp_is_f32, const doub
 int mval_reprojection_xe_vj(const double* kp3d, const double* proj, const float* heatmaps, const uint8_t* view_joint_valid,
                             double* out, double* ws, int B, int V, int J, int hh, int wh, double sigma, void* stream);
 
+/* 3-D refinement of the triangulated joints (not in the reference, whose direct_optimization has no defined result;
+ * DESIGN.md 6.5 holds the definition).  One extra launch between a triangulation entry and the metrics.  Per problem (frame,
+ * joint), with X0 = kp3d the triangulation's point:
+ *   S = the present views v whose half-distance error at X0, 1/2 |p_v - pi(P_v [X0; 1])| -- the vote's own -- is finite and
+ *       < eps, and, with weights, whose w_v is finite and > 0.  Presence is read as the triangulation entries read it: valid
+ *       [B,J] u8 or NULL, and mask = NULL (MVAL_MASK_NONE), view_valid [B,V] u8 (MVAL_MASK_VIEWS) or view_joint_valid [B,V,J]
+ *       u8 (MVAL_MASK_VIEW_JOINT); nothing of an absent view or entry is read.
+ *   Not refined -- kp3d_out = X0 bit for bit, joint_err_out = joint_err, joint_status 0 -- when the joint is invalid, X0 is
+ *       non-finite or |S| < 2.
+ *   Otherwise kp3d_out = the minimiser of E(X) = 1/2 sum_{v in S} w_v |p_v - pi(P_v [X; 1])|^2 (w_v = 1 without weights) by
+ *       Levenberg-Marquardt in float64, views ascending: lam = 1e-3; an iteration solves (A + lam diag A) d = g and tries
+ *       X + d, accepted iff E does not rise and every view of S has depth > 0 there; accepted: lam = max(lam / 10, 1e-9),
+ *       and converged when |d| <= 1e-8 (1 + |X|); rejected: lam *= 10, and converged when lam > 1e12 (no damping lowers the
+ *       cost).  joint_status = k > 0: converged in iteration k; -MVAL_REFINE3D_MAX_ITERS: the cap was reached, the point
+ *       found so far is kept.  joint_err_out = the mean over S of the half-distance error at kp3d_out.
+ *   joint_support [B,J] i32 = |S| (0 for an invalid joint).
+ *   metric [B] f64, inlier_count [B] i32: the frame reduction of the triangulation entries over joint_err_out and the
+ *       unchanged joint_inliers [B,J] i32 -- inlier_count comes out as the triangulation wrote it.
+ *   kp2d [B,V,J,2] i64 | f32 (kp_is_f32) ; proj [B,V,3,4] f64 ; weights [B,V,J] f32 or NULL ; kp3d, kp3d_out [B,J,3] f64 ;
+ *   joint_err, joint_err_out [B,J] f64.  The outputs must not alias the inputs.
+ *   The accept test is decided by the last bit of E once two points are closer than about 1e-6 mm, so the solver's arithmetic
+ *   is part of the definition: per view h_i = P_i0 X0 + P_i1 X1 + P_i2 X2 + P_i3 (left to right), u = h0 / h2, v = h1 / h2,
+ *   r = (px - u, py - v), jx_k = (P_0k - u P_2k) / h2, jy_k = (P_1k - v P_2k) / h2; a_kl += w (jx_k jx_l + jy_k jy_l),
+ *   g_k += w (jx_k rx + jy_k ry), E += w (rx rx + ry ry), E halved at the end; LDL^T without pivoting; one IEEE float64
+ *   operation each, no FMA contraction (csrc/triangulate.hip: refine_normal, refine_solve).
+ * One lane per problem; a problem's bits do not depend on the rest of the batch.  V outside 2..32, a mask_kind outside 0..2
+ * or not matching `mask`, NULL or misaligned arrays return an error and launch nothing; B = 0 returns 0. */
+#define MVAL_REFINE3D_MAX_ITERS 32
+#define MVAL_MASK_NONE 0
+#define MVAL_MASK_VIEWS 1
+#define MVAL_MASK_VIEW_JOINT 2
+int mval_refine_points_3d(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid, const uint8_t* mask,
+                          int mask_kind, const float* weights, const double* kp3d, const double* joint_err,
+                          const int32_t* joint_inliers, double* kp3d_out, double* joint_err_out, int32_t* joint_support,
+                          int32_t* joint_status, double* metric, int32_t* inlier_count, int B, int V, int J, double eps,
+                          void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Uncertainty scorers (strategy.py:1149-1215)
  * ---------------------------------------------------------------------------------- */

@@ -392,6 +392,52 @@ def peak_mask(hm, min_peak, n_maps, hh, wh):
     return out
 
 
+# MVAL_MASK_* (include/mval_hip.h): what the mask argument of mval_refine_points_3d is
+MASK_NONE, MASK_VIEWS, MASK_VIEW_JOINT = 0, 1, 2
+REFINE3D_MAX_ITERS = 32  # MVAL_REFINE3D_MAX_ITERS
+_VIEWS_ARGTYPES["mval_refine_points_3d"] = [_VOIDP, _INT] + [_VOIDP] * 3 + [_INT] + [_VOIDP] * 10 + [_INT] * 3 + [_DOUBLE, _VOIDP]
+
+
+def refine_points_3d(kp2d, proj, valid, kp3d, joint_err, joint_inliers, b, v, j, eps, view_valid=None, view_joint_valid=None,
+                     weights=None):
+    """mval_refine_points_3d: the triangulation's kp3d (b,j,3) f64, joint_err (b,j) f64 and joint_inliers (b,j) i32 with the
+    inputs it had -- kp2d (b,v,j,2) int64|float32, proj (b,v,3,4) f64, valid (b,j) uint8 or None, at most one of view_valid
+    (b,v) / view_joint_valid (b,v,j) uint8 -- and optional weights (b,v,j) float32 ->
+    (kp3d refined (b,j,3) f64, joint_err (b,j) f64, joint_support (b,j) i32, joint_status (b,j) i32, metric (b,) f64)."""
+    if view_valid is not None and view_joint_valid is not None:
+        raise MvalError("refine_points_3d: view_valid or view_joint_valid, not both (AND them into view_joint_valid)")
+    kp_is_f32 = 1 if kp2d.dtype == torch.float32 else 0
+    if not kp_is_f32:
+        _req(kp2d, torch.int64, "keypoints_2d")
+    if tuple(kp2d.shape) != (b, v, j, 2) or tuple(kp3d.shape) != (b, j, 3) or tuple(joint_err.shape) != (b, j) or tuple(joint_inliers.shape) != (b, j):
+        raise MvalError(f"refine_points_3d: kp2d ({b}, {v}, {j}, 2), kp3d ({b}, {j}, 3), joint_err and joint_inliers ({b}, {j}), got "
+                        f"{tuple(kp2d.shape)}, {tuple(kp3d.shape)}, {tuple(joint_err.shape)} and {tuple(joint_inliers.shape)}")
+    if weights is not None and tuple(_req(weights, torch.float32, "weights").shape) != (b, v, j):
+        raise MvalError(f"refine_points_3d: weights ({b}, {v}, {j}), got {tuple(weights.shape)}")
+    mask, kind = None, MASK_NONE
+    if view_joint_valid is not None:
+        mask, kind = _req_view_joint_valid(view_joint_valid, b, v, j), MASK_VIEW_JOINT
+    elif view_valid is not None:
+        mask, kind = _req_view_valid(view_valid, b, v), MASK_VIEWS
+    dev = proj.device
+    out = torch.empty((b, j, 3), dtype=torch.float64, device=dev)
+    jerr = torch.empty((b, j), dtype=torch.float64, device=dev)
+    support = torch.empty((b, j), dtype=torch.int32, device=dev)
+    status = torch.empty((b, j), dtype=torch.int32, device=dev)
+    metric = torch.empty((b,), dtype=torch.float64, device=dev)
+    inl = torch.empty((b,), dtype=torch.int32, device=dev)  # (rewritten with the triangulation's own values)
+    _check(
+        _views_entry("mval_refine_points_3d")(
+            _p(kp2d), kp_is_f32, _p(_req(proj, torch.float64, "proj_matricies")), _p(valid), _p(mask), kind, _p(weights),
+            _p(_req(kp3d, torch.float64, "keypoints_3d")), _p(_req(joint_err, torch.float64, "joint_error")),
+            _p(_req(joint_inliers, torch.int32, "joint_inliers")), _p(out), _p(jerr), _p(support), _p(status), _p(metric), _p(inl),
+            b, v, j, float(eps), _stream(),
+        ),
+        "mval_refine_points_3d",
+    )
+    return out, jerr, support, status, metric
+
+
 def reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, sigma):
     out = torch.empty((b,), dtype=torch.float64, device=hm.device)
     ws = torch.empty((b * v * j,), dtype=torch.float64, device=hm.device)

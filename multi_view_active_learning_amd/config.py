@@ -61,6 +61,11 @@ def get_default_configs():
     # not in the reference (which decodes to whole heat-map pixels): the sub-pixel decode of the pool-scoring passes, "none" |
     # "quarter" | "taylor" (check_decode_refine below); not together with USE_SOFTARGMAX
     c.AL.DECODE_REFINE = "none"
+    # not in the reference (whose direct_optimization has no defined result): the 3-D refinement of every triangulated joint in the
+    # pool-scoring passes, "none" | "lm", and its weights, "none" | "conf" (the peak heights of DECODE_REFINE); check_refine_3d
+    # below, DESIGN.md 6.5
+    c.AL.REFINE_3D = "none"
+    c.AL.REFINE_3D_WEIGHTS = "none"
     c.AL.CLUSTER = CN()  # EXPR_TYPE "CLUSTER" (strategy.py:137-191): what ActiveLearningStrategy.cluster writes
     c.AL.CLUSTER.TYPE = "LOSS"  # LOSS | POSE (cluster_type below)
     c.AL.CLUSTER.SAVE_PATH = ""
@@ -82,6 +87,8 @@ def get_default_configs():
     c.EVAL = CN()
     c.EVAL.METRIC = "3DPCK"
     c.EVAL.DECODE_REFINE = "none"  # not in the reference: AL.DECODE_REFINE for evaluate_mkpe / evaluate_all
+    c.EVAL.REFINE_3D = "none"  # not in the reference: AL.REFINE_3D / AL.REFINE_3D_WEIGHTS for evaluate_mkpe / evaluate_all
+    c.EVAL.REFINE_3D_WEIGHTS = "none"
 
     c.POSE_ESTIMATOR = _pose_defaults()
     c.DATA = _data_defaults()
@@ -141,3 +148,29 @@ def check_decode_refine(value, use_softargmax=False):
         raise ValueError("decode refinement %r together with the soft-arg-max (AL.USE_SOFTARGMAX / use_soft_argmax): a refinement "
                          "(accepted are %s) starts from the hard arg-max, use one or the other" % (value, ", ".join(repr(m) for m in DECODE_REFINES)))
     return value
+
+
+REFINE_3DS = ("none", "lm")  # "none": the DLT point of the inlier views; "lm": its reprojection-error minimiser (mval_refine_points_3d)
+REFINE_3D_WEIGHTS = ("none", "conf")  # "conf": the peak heights a decode refinement returns (keypoints_conf)
+
+
+def check_refine_3d(value, weights="none", decode_refine="none"):
+    """A valid (AL|EVAL).REFINE_3D / ``refine_3d=`` of utils.triangulation with its (AL|EVAL).REFINE_3D_WEIGHTS / ``refine_3d_weights=``
+    (None reads as "none"; a tensor is the caller's own weights and is checked where it is used), or ValueError naming the
+    accepted ones -- also for weights without a refinement, and for "conf" without a decode refinement (``decode_refine``
+    "none"): only a refined decode returns the confidences.  Returns (value, weights)."""
+    if not isinstance(value, str) or value not in REFINE_3DS:
+        raise ValueError("3-D refinement %r: accepted are %s" % (value, ", ".join(repr(m) for m in REFINE_3DS)))
+    if weights is None:
+        weights = "none"
+    named = isinstance(weights, str)
+    if (named and weights not in REFINE_3D_WEIGHTS) or not (named or hasattr(weights, "shape")):
+        raise ValueError("3-D refinement weights %r: accepted are %s (or a (B, V, J) tensor handed to triangulate_batch)"
+                         % (weights, ", ".join(repr(m) for m in REFINE_3D_WEIGHTS)))
+    if value == "none" and not (named and weights == "none"):
+        raise ValueError("3-D refinement weights without a 3-D refinement (accepted are %s): set REFINE_3D / refine_3d to 'lm'"
+                         % ", ".join(repr(m) for m in REFINE_3DS))
+    if named and weights == "conf" and decode_refine == "none":
+        raise ValueError("3-D refinement weights 'conf' need a decode refinement (DECODE_REFINE / refine = 'quarter' | 'taylor'): "
+                         "the hard arg-max returns no confidences")
+    return value, weights

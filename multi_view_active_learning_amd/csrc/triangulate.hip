@@ -512,6 +512,224 @@ extern "C" int mval_triangulate_ransac_pairs_vj(const void* kp2d, int kp_is_f32,
                        }, view_joint_valid, V, MASK_VIEW_JOINT);
 }
 
+// ---- 3-D refinement (not in the reference) ---------------------------------------------------------------
+// Every triangulated joint is moved from its DLT point X0 to the minimiser of the reprojection error over its support set S:
+// the present views whose reproj_err at X0 is finite and < eps (with weights: and whose weight is finite and > 0) -- the
+// vote's test, taken again at the final point, since the RANSAC kernels do not hand their winning mask on.
+//   E(X) = 1/2 sum_{v in S} w_v |p_v - pi(P_v [X; 1])|^2,  two smooth residuals per view.
+// One lane per problem, like mval_refine_keypoints: no LDS, no atomics, nothing indexed by a loaded value; the loops run over
+// v < V <= 32 in ascending order, so a problem's bits do not depend on its place in the batch.  Levenberg-Marquardt in float64
+// with the analytic 2x3 Jacobian, the 3x3 system (A + lam diag A) d = g solved in registers (LDL^T; a pivot that is not > 0
+// counts as a rejected step).  One iteration = one trial point = one pass over S that gives E, A and g there.
+// The accept test E(X + d) <= E(X) cannot tell two points apart that are closer than about 1e-6 mm (the cost moves by less
+// than its own rounding there), so near the minimum the decisions are taken by the last bit of E.  The solver's arithmetic
+// is therefore part of the definition: the operations below in the order written, one IEEE operation each, no FMA
+// contraction (refine_normal, refine_solve and the loop), with the correctly rounded float64 division and square root.  The
+// float64 oracle on the host (tests/refine3d_oracle.py) follows the same order and takes the same decisions.
+struct Normal3 {
+  double E, a00, a01, a02, a11, a12, a22, g0, g1, g2;
+  bool front;  // every support view has depth > 0
+};
+
+template <typename KP>
+__device__ __forceinline__ void refine_normal(const double* __restrict__ Pb, const KP* __restrict__ kb,
+                                              const float* __restrict__ wb, int V, int J, unsigned S, const double X[3],
+                                              Normal3& n) {
+#pragma clang fp contract(off)
+  n.E = n.a00 = n.a01 = n.a02 = n.a11 = n.a12 = n.a22 = n.g0 = n.g1 = n.g2 = 0.0;
+  n.front = true;
+  for (int v = 0; v < V; v++) {
+    if (!(S >> v & 1)) continue;
+    const double* P = Pb + v * 12;
+    const double px = (double)kb[(int64_t)v * J * 2], py = (double)kb[(int64_t)v * J * 2 + 1];
+    const double wt = wb ? (double)wb[(int64_t)v * J] : 1.0;
+    const double h0 = P[0] * X[0] + P[1] * X[1] + P[2] * X[2] + P[3];
+    const double h1 = P[4] * X[0] + P[5] * X[1] + P[6] * X[2] + P[7];
+    const double h2 = P[8] * X[0] + P[9] * X[1] + P[10] * X[2] + P[11];
+    n.front = n.front && h2 > 0.0;
+    const double u = h0 / h2, w = h1 / h2;
+    const double rx = px - u, ry = py - w;
+    const double x0 = (P[0] - u * P[8]) / h2, x1 = (P[1] - u * P[9]) / h2, x2 = (P[2] - u * P[10]) / h2;
+    const double y0 = (P[4] - w * P[8]) / h2, y1 = (P[5] - w * P[9]) / h2, y2 = (P[6] - w * P[10]) / h2;
+    n.a00 += wt * (x0 * x0 + y0 * y0);
+    n.a01 += wt * (x0 * x1 + y0 * y1);
+    n.a02 += wt * (x0 * x2 + y0 * y2);
+    n.a11 += wt * (x1 * x1 + y1 * y1);
+    n.a12 += wt * (x1 * x2 + y1 * y2);
+    n.a22 += wt * (x2 * x2 + y2 * y2);
+    n.g0 += wt * (x0 * rx + y0 * ry);
+    n.g1 += wt * (x1 * rx + y1 * ry);
+    n.g2 += wt * (x2 * rx + y2 * ry);
+    n.E += wt * (rx * rx + ry * ry);
+  }
+  n.E *= 0.5;
+}
+
+// (A + lam diag A) d = g by LDL^T; false when a pivot is not > 0 or the step is not finite
+__device__ __forceinline__ bool refine_solve(const Normal3& n, double lam, double d[3]) {
+#pragma clang fp contract(off)
+  const double m00 = n.a00 + lam * n.a00, m11 = n.a11 + lam * n.a11, m22 = n.a22 + lam * n.a22;
+  const double d0 = m00;
+  if (!(d0 > 0.0)) return false;
+  const double l10 = n.a01 / d0, l20 = n.a02 / d0;
+  const double d1 = m11 - l10 * n.a01;
+  if (!(d1 > 0.0)) return false;
+  const double l21 = (n.a12 - l20 * n.a01) / d1;
+  const double d2 = m22 - l20 * n.a02 - l21 * l21 * d1;
+  if (!(d2 > 0.0)) return false;
+  const double y0 = n.g0, y1 = n.g1 - l10 * y0, y2 = n.g2 - l20 * y0 - l21 * y1;
+  d[2] = y2 / d2;
+  d[1] = y1 / d1 - l21 * d[2];
+  d[0] = y0 / d0 - l10 * d[1] - l20 * d[2];
+  return isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]);
+}
+
+template <int MASK, typename KP>
+__global__ __launch_bounds__(64) void refine_points_3d_kernel(
+    const KP* __restrict__ kp2d, const double* __restrict__ proj, const uint8_t* __restrict__ valid,
+    const uint8_t* __restrict__ mask, const float* __restrict__ weights, const double* __restrict__ kp3d,
+    const double* __restrict__ joint_err, double* __restrict__ kp3d_out, double* __restrict__ joint_err_out,
+    int32_t* __restrict__ joint_support, int32_t* __restrict__ joint_status, int64_t n_prob, int V, int J, double eps) {
+  const int64_t pr = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (pr >= n_prob) return;
+  const int64_t b = pr / J;
+  const int j = (int)(pr % J);
+  const double* Pb = proj + b * V * 12;
+  const KP* kb = kp2d + (b * V * (int64_t)J + j) * 2;                        // + v * J * 2
+  const float* wb = weights ? weights + b * V * (int64_t)J + j : nullptr;  // + v * J
+  double X[3] = {kp3d[pr * 3], kp3d[pr * 3 + 1], kp3d[pr * 3 + 2]};
+  double err = joint_err[pr];
+  int status = 0;
+
+  unsigned S = 0;
+  if ((!valid || valid[pr]) && isfinite(X[0]) && isfinite(X[1]) && isfinite(X[2])) {
+    const unsigned present = MASK == MASK_NONE ? ((V >= 32) ? 0xffffffffu : ((1u << V) - 1u)) : present_of<MASK>(mask, b, j, V, J);
+    for (int v = 0; v < V; v++) {
+      if (!(present >> v & 1)) continue;
+      const double e = reproj_err(Pb + v * 12, X, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
+      bool in = isfinite(e) && e < eps;
+      if (in && wb) {
+        const float w = wb[(int64_t)v * J];
+        in = isfinite(w) && w > 0.f;
+      }
+      if (in) S |= 1u << v;
+    }
+  }
+  const int n = __popc(S);
+
+  if (n >= 2) {
+#pragma clang fp contract(off)
+    double lam = 1e-3;
+    Normal3 cur;
+    refine_normal(Pb, kb, wb, V, J, S, X, cur);
+    status = -MVAL_REFINE3D_MAX_ITERS;
+    for (int k = 1; k <= MVAL_REFINE3D_MAX_ITERS; k++) {
+      double d[3], Xt[3];
+      Normal3 t;
+      bool ok = refine_solve(cur, lam, d);
+      if (ok) {
+        Xt[0] = X[0] + d[0];
+        Xt[1] = X[1] + d[1];
+        Xt[2] = X[2] + d[2];
+        refine_normal(Pb, kb, wb, V, J, S, Xt, t);
+        ok = t.front && t.E <= cur.E;  // (a NaN cost compares false)
+      }
+      if (ok) {
+        X[0] = Xt[0];
+        X[1] = Xt[1];
+        X[2] = Xt[2];
+        cur = t;
+        lam = fmax(lam / 10.0, 1e-9);
+        if (sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) <= 1e-8 * (1.0 + sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]))) {
+          status = k;
+          break;
+        }
+      } else {
+        lam *= 10.0;
+        if (lam > 1e12) {  // no damping lowers the cost: the iterate is at the float64 floor
+          status = k;
+          break;
+        }
+      }
+    }
+    double errs[MVAL_PAIRS_MAX_VIEWS];
+    int m = 0;
+    for (int v = 0; v < V; v++)
+      if (S >> v & 1)
+        errs[m++] = reproj_err(Pb + v * 12, X, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
+    err = np_pairwise_sum(errs, m) / (double)m;
+  }
+  kp3d_out[pr * 3] = X[0];
+  kp3d_out[pr * 3 + 1] = X[1];
+  kp3d_out[pr * 3 + 2] = X[2];
+  joint_err_out[pr] = err;
+  joint_support[pr] = n;
+  joint_status[pr] = status;
+}
+
+static_assert(MVAL_MASK_NONE == MASK_NONE && MVAL_MASK_VIEWS == MASK_VIEWS && MVAL_MASK_VIEW_JOINT == MASK_VIEW_JOINT,
+              "the mask kinds of the C-ABI are the kernels' template values");
+
+template <int MASK>
+static void launch_refine_3d(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid, const uint8_t* mask,
+                             const float* weights, const double* kp3d, const double* joint_err, double* kp3d_out,
+                             double* joint_err_out, int32_t* joint_support, int32_t* joint_status, int64_t n_prob, int V,
+                             int J, double eps, hipStream_t s) {
+  const dim3 grid((unsigned)((n_prob + 63) / 64));
+  if (kp_is_f32)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_points_3d_kernel<MASK, float>), grid, dim3(64), 0, s, (const float*)kp2d, proj,
+                       valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out, joint_support, joint_status, n_prob, V,
+                       J, eps);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_points_3d_kernel<MASK, int64_t>), grid, dim3(64), 0, s, (const int64_t*)kp2d,
+                       proj, valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out, joint_support, joint_status,
+                       n_prob, V, J, eps);
+}
+
+extern "C" int mval_refine_points_3d(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                     const uint8_t* mask, int mask_kind, const float* weights, const double* kp3d,
+                                     const double* joint_err, const int32_t* joint_inliers, double* kp3d_out,
+                                     double* joint_err_out, int32_t* joint_support, int32_t* joint_status, double* metric,
+                                     int32_t* inlier_count, int B, int V, int J, double eps, void* stream) {
+  MVAL_REQUIRE(V >= 2 && V <= MVAL_PAIRS_MAX_VIEWS, "mval_refine_points_3d: 2..%d views (the support set is 32 bits wide)", MVAL_PAIRS_MAX_VIEWS);
+  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_refine_points_3d: bad dims");
+  MVAL_REQUIRE(mask_kind == MASK_NONE || mask_kind == MASK_VIEWS || mask_kind == MASK_VIEW_JOINT,
+               "mval_refine_points_3d: mask_kind %d (0 none, 1 view_valid [B,V], 2 view_joint_valid [B,V,J])", mask_kind);
+  MVAL_REQUIRE((mask_kind == MASK_NONE) == (mask == nullptr), "mval_refine_points_3d: a mask goes with mask_kind 1 or 2, NULL with 0");
+  if (B == 0) return 0;
+  MVAL_REQUIRE(kp2d && proj && kp3d && joint_err && joint_inliers, "mval_refine_points_3d: an input is NULL");
+  MVAL_REQUIRE(kp3d_out && joint_err_out && joint_support && joint_status && metric && inlier_count, "mval_refine_points_3d: an output is NULL");
+  MVAL_REQUIRE(kp3d_out != kp3d && joint_err_out != joint_err, "mval_refine_points_3d: the outputs must not alias the inputs");
+  MVAL_REQUIRE(((uintptr_t)proj | (uintptr_t)kp3d | (uintptr_t)joint_err | (uintptr_t)kp3d_out | (uintptr_t)joint_err_out | (uintptr_t)metric) % 8 == 0,
+               "mval_refine_points_3d: a float64 array is not 8-byte aligned");
+  MVAL_REQUIRE(((uintptr_t)kp2d % (kp_is_f32 ? 4 : 8)) == 0 && ((uintptr_t)weights | (uintptr_t)joint_inliers | (uintptr_t)joint_support | (uintptr_t)joint_status | (uintptr_t)inlier_count) % 4 == 0,
+               "mval_refine_points_3d: a 4-byte array is not aligned");
+  const hipStream_t s = mval_stream(stream);
+  const int64_t n_prob = (int64_t)B * J;
+  if (mask_kind == MASK_VIEW_JOINT)
+    launch_refine_3d<MASK_VIEW_JOINT>(kp2d, kp_is_f32, proj, valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out,
+                                      joint_support, joint_status, n_prob, V, J, eps, s);
+  else if (mask_kind == MASK_VIEWS)
+    launch_refine_3d<MASK_VIEWS>(kp2d, kp_is_f32, proj, valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out,
+                                 joint_support, joint_status, n_prob, V, J, eps, s);
+  else
+    launch_refine_3d<MASK_NONE>(kp2d, kp_is_f32, proj, valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out,
+                                joint_support, joint_status, n_prob, V, J, eps, s);
+  MVAL_CHECK_LAUNCH("mval_refine_points_3d");
+  // the frame's metric over the new joint errors; joint_inliers are RANSAC's, so inlier_count comes out as it was
+  if (mask_kind == MASK_VIEW_JOINT)
+    hipLaunchKernelGGL(frame_reduce_kernel<MASK_VIEW_JOINT>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err_out, joint_inliers,
+                       valid, mask, metric, inlier_count, B, V, J);
+  else if (mask_kind == MASK_VIEWS)
+    hipLaunchKernelGGL(frame_reduce_kernel<MASK_VIEWS>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err_out, joint_inliers, valid,
+                       mask, metric, inlier_count, B, V, J);
+  else
+    hipLaunchKernelGGL(frame_reduce_kernel<MASK_NONE>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err_out, joint_inliers, valid,
+                       mask, metric, inlier_count, B, V, J);
+  MVAL_CHECK_LAUNCH("mval_refine_points_3d/reduce");
+  return 0;
+}
+
 // ---- XE metric (utils/triangulation.py:236-257) ---------------------------------------
 // one wave per (frame, view, joint) map; float64 like the reference's rendered target.
 // MASKED: the maps of an absent view are neither read nor written, and xe_sum_kernel leaves them out of its serial sum --

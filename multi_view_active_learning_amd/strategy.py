@@ -429,11 +429,16 @@ class ActiveLearningStrategy:
         present views alone; one with a per-(view, joint) mask (``_view_joint_valid``) over each joint's present views, and
         its per-sample MKPE leaves out the joints nobody triangulated (``joint_valid & joint_used``).
         AL.DECODE_REFINE "quarter" | "taylor": the decode of the heat-map launch is split by the width and refined before
-        the triangulation (``triangulate_batch(refine=...)``); "none" is the path above call for call."""
-        from .config import check_decode_refine
+        the triangulation (``triangulate_batch(refine=...)``); "none" is the path above call for call.
+        AL.REFINE_3D "lm" (with AL.REFINE_3D_WEIGHTS "none" | "conf"): every triangulated joint is refined by
+        ``triangulate_batch(refine_3d=...)``, and sal_metric, the TRIANGULATION metric, the per-sample MKPE and
+        the key-point columns come from the refined points; "none" adds no launch."""
+        from .config import check_decode_refine, check_refine_3d
 
         cfg = self.al_cfg
         refine = check_decode_refine(cfg.AL.DECODE_REFINE if "DECODE_REFINE" in cfg.AL else "none", cfg.AL.USE_SOFTARGMAX)
+        refine_3d, weights_3d = check_refine_3d(cfg.AL.REFINE_3D if "REFINE_3D" in cfg.AL else "none",
+                                                cfg.AL.REFINE_3D_WEIGHTS if "REFINE_3D_WEIGHTS" in cfg.AL else "none", refine)
         dev = heatmaps.device
         pose = torch.as_tensor(dp["pose"]).reshape(-1)
         b = pose.shape[0]
@@ -454,6 +459,8 @@ class ActiveLearningStrategy:
                                          view_valid=view_valid, view_joint_valid=vj)
             kp2d = next(iter(scored.values()))[4]
         refined = {} if refine == "none" else {"refine": refine}
+        if refine_3d != "none":
+            refined.update(refine_3d=refine_3d, refine_3d_weights=None if weights_3d == "none" else weights_3d)
         r = triangulation.triangulate_batch(
             hm, dp["proj_matrices"], cfg.POSE_ESTIMATOR.STRIDE, joint_valid,
             cfg.AL.USE_SOFTARGMAX, cfg.AL.USE_REPROJECTION_XE, cfg.AL.REPROJECTION_SIGMA,
@@ -765,11 +772,18 @@ class ActiveLearningStrategy:
         whole loader (one size exchange + one packed data gather instead of 3 all_gathers per sample).  A batch with a
         per-(view, joint) mask (``_view_joint_valid``) is triangulated joint by joint from the views that have the joint, and the
         validity column it contributes is ``joint_valid & joint_used``: a joint nobody triangulated is left out.
-        EVAL.DECODE_REFINE "quarter" | "taylor": the sub-pixel decode of ``triangulate_batch(refine=...)``."""
-        from .config import check_decode_refine
+        EVAL.DECODE_REFINE "quarter" | "taylor": the sub-pixel decode of ``triangulate_batch(refine=...)``.
+        EVAL.REFINE_3D "lm" (with EVAL.REFINE_3D_WEIGHTS "none" | "conf"): the 3-D refinement of ``triangulate_batch(refine_3d=...)``
+        (DESIGN.md 6.5); MKPE and the 3-D PCK(h) figures of ``evaluate_all`` then come from the refined points."""
+        from .config import check_decode_refine, check_refine_3d
 
-        refine = check_decode_refine(self.al_cfg.EVAL.DECODE_REFINE if "DECODE_REFINE" in self.al_cfg.EVAL else "none")
+        ev = self.al_cfg.EVAL
+        refine = check_decode_refine(ev.DECODE_REFINE if "DECODE_REFINE" in ev else "none")
+        refine_3d, weights_3d = check_refine_3d(ev.REFINE_3D if "REFINE_3D" in ev else "none",
+                                                ev.REFINE_3D_WEIGHTS if "REFINE_3D_WEIGHTS" in ev else "none", refine)
         refined = {} if refine == "none" else {"refine": refine}
+        if refine_3d != "none":
+            refined.update(refine_3d=refine_3d, refine_3d_weights=None if weights_3d == "none" else weights_3d)
 
         def inputs(hm, dp):
             b = torch.as_tensor(dp["pose"]).reshape(-1).shape[0] if "pose" in dp else dp["images"].shape[0]

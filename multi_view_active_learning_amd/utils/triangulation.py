@@ -23,6 +23,10 @@ frame's metric and inlier count, and ``peak_mask`` builds such a mask on the dev
 
 Sub-pixel decode: ``refine`` = "quarter" | "taylor" refines the hard arg-max inside its 3x3 neighbourhood (``mval_refine_keypoints``,
 DESIGN.md 6.4) and hands float32 key-points to the unchanged triangulation entries; "none", the default, is the reference's decode.
+
+3-D refinement: ``refine_3d`` = "lm" moves every triangulated joint from the DLT point of its inlier views to the minimiser of the
+reprojection error over the views within eps of that point (``mval_refine_points_3d``, one launch after the triangulation,
+DESIGN.md 6.5).  It is a defined stand-in for the reference's ``direct_optimization``, which itself keeps raising.
 """
 from __future__ import annotations
 
@@ -32,7 +36,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..config import check_decode_refine
+from ..config import check_decode_refine, check_refine_3d
 
 
 def _device_of(heatmaps):
@@ -176,6 +180,9 @@ def triangulate_batch(
     view_joint_valid=None,
     view_joint_valid_host=None,
     refine="none",
+    refine_3d="none",
+    refine_3d_weights=None,
+    refine_3d_epsilon=None,
 ):
     """heatmaps (B,V,J,Hh,Wh) f32 HIP tensor, proj (B,V,3,4), valid (B,J) ->
     dict of HIP tensors: keypoints_3d (B,J,3) f64, keypoints_2d (B,V,J,2) i64|f32,
@@ -222,9 +229,20 @@ def triangulate_batch(
     (``config.check_decode_refine``).  The hard decode is then made with ``split_width = wh`` whatever ``mirror_nonsquare_quirk`` says -- the
     reference's split by the height has no neighbourhood to refine in --, a ``keypoints_2d`` handed in must be that int64 decode,
     and the result carries the refined ``keypoints_2d`` (float32) and ``keypoints_conf`` (B, V, J) float32, the maps' values at
-    their peaks (0 for absent entries and invalid joints).  Not together with ``use_soft_argmax``: ValueError."""
+    their peaks (0 for absent entries and invalid joints).  Not together with ``use_soft_argmax``: ValueError.
+
+    ``refine_3d``: "none" (today's path call for call: no new launch, no new keys) | "lm": one more launch
+    (``mval_refine_points_3d``) moves every triangulated joint from its DLT point to the minimiser of the
+    reprojection error over its support set -- the present views within ``refine_3d_epsilon`` (None: ``reprojection_error_epsilon``)
+    of the DLT point.  The result's ``keypoints_3d`` are then the refined points, ``keypoints_3d_dlt`` the points before,
+    ``joint_error`` and ``metric`` are recomputed from the refined points (the XE metric too), and ``joint_support`` (B, J) int32
+    = the size of the support set and ``joint_status`` (B, J) int32 (0 not refined, k > 0 converged after k iterations, < 0
+    the iteration cap was reached) are added; ``joint_inliers`` and ``inlier_count`` stay RANSAC's.  ``refine_3d_weights``:
+    None | "conf" (``keypoints_conf``: needs ``refine`` != "none", else ValueError) | a (B, V, J) tensor; a view whose weight is
+    non-finite or <= 0 leaves the support set.  The launch runs on the current stream and adds no host sync."""
     dev = _device_of(heatmaps)
     check_decode_refine(refine, use_soft_argmax)
+    check_refine_3d(refine_3d, refine_3d_weights, refine)
     if heatmaps.dim() != 5:
         raise ValueError("heatmaps must be (B, V, J, Hh, Wh)")
     b, v, j, hh, wh = heatmaps.shape
@@ -290,6 +308,18 @@ def triangulate_batch(
         kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs(kp2d, proj, valid, _lexicographic_pairs(v, dev), b, v, j, eps)
     else:
         kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac(kp2d, proj, valid, b, v, j, eps)
+    refined = None
+    if refine_3d != "none":
+        weights = refine_3d_weights
+        if isinstance(weights, str):  # "conf" (check_refine_3d): the peak heights, absent entries already 0
+            weights = conf
+        elif weights is not None:
+            weights = torch.as_tensor(weights).to(device=dev, dtype=torch.float32).reshape(b, v, j).contiguous()
+        kp3d_dlt = kp3d
+        kp3d, jerr, support, status, metric = _lib.refine_points_3d(
+            kp2d, proj, valid, kp3d, jerr, jinl, b, v, j, eps if refine_3d_epsilon is None else float(refine_3d_epsilon),
+            view_valid=None if per_joint else vv, view_joint_valid=vj if per_joint else None, weights=weights)
+        refined = {"keypoints_3d_dlt": kp3d_dlt, "joint_support": support, "joint_status": status}
     if use_reprojection_xe and per_joint:
         xe = _lib.reprojection_xe_vj(kp3d, proj, hm, vj, b, v, j, hh, wh, float(sigma))
         metric = torch.where(inl == -2, metric, xe)  # (no used joint: NaN)
@@ -308,6 +338,8 @@ def triangulate_batch(
     }
     if conf is not None:
         out["keypoints_conf"] = conf
+    if refined is not None:
+        out.update(refined)
     if per_joint:
         out["joint_used"] = (jinl > 0).to(torch.uint8)  # a used joint's winning pair is in its own inlier set: >= 2
     return out
@@ -374,6 +406,8 @@ def triangulation(
     view_valid=None,
     view_joint_valid=None,
     refine="none",
+    refine_3d="none",
+    refine_3d_weights=None,
 ):
     """One frame, reference signature and return types (utils/triangulation.py:168-233):
     heatmaps (V,J,Hh,Wh), proj (V,3,4), valid (J,) -> {"keypoints_3d": ndarray (J,3) f64,
@@ -381,7 +415,9 @@ def triangulation(
     ``view_valid`` (V,): the views present in this frame (``triangulate_batch``); fewer than two of them with a valid
     joint raise the reference's AssertionError.  ``view_joint_valid`` (V, J): the views each joint is usable in; a valid joint
     but none with two such views raises the same AssertionError.  ``refine``: the sub-pixel decode of ``triangulate_batch``; the
-    result then also holds "keypoints_conf": ndarray (V, J) f32."""
+    result then also holds "keypoints_conf": ndarray (V, J) f32.  ``refine_3d`` = "lm" (with ``refine_3d_weights`` None | "conf" |
+    (V, J)): the 3-D refinement of ``triangulate_batch``; "keypoints_3d" are then the refined points and the result also holds
+    "keypoints_3d_dlt" (J, 3) f64, "joint_error" (J,) f64, "joint_support" and "joint_status" (J,) int32."""
     if direct_optimization:
         raise NotImplementedError(
             "direct_optimization (scipy Huber least-squares, off in every reference call site): its result is where "
@@ -402,6 +438,10 @@ def triangulation(
         view_valid=None if view_valid is None else torch.as_tensor(view_valid).reshape(1, -1),
         view_joint_valid=None if view_joint_valid is None else torch.as_tensor(view_joint_valid).unsqueeze(0),
         refine=refine,
+        **({} if refine_3d == "none" and refine_3d_weights is None else dict(
+            refine_3d=refine_3d,
+            refine_3d_weights=refine_3d_weights if refine_3d_weights is None or isinstance(refine_3d_weights, str)
+            else torch.as_tensor(refine_3d_weights).unsqueeze(0))),
     )
     inl = int(r["inlier_count"][0].item())
     if inl == -2:
@@ -416,4 +456,7 @@ def triangulation(
     }
     if "keypoints_conf" in r:
         out["keypoints_conf"] = r["keypoints_conf"][0].cpu().numpy()
+    if "joint_status" in r:
+        for key in ("keypoints_3d_dlt", "joint_error", "joint_support", "joint_status"):
+            out[key] = r[key][0].cpu().numpy()
     return out

@@ -87,7 +87,7 @@ int mval_refine_keypoints(int method, const float* heatmaps, const int64_t* kp2d
 
 /* Peak gate: out[m] = 1 iff some element of map m is >= min_peak, else 0 (a comparison: a map of NaNs gives 0; exact, no
  * tolerance).  heatmaps [n_maps,hh,wh] f32 ; out [n_maps] u8.  One read of the maps.  With n_maps = B*V*J in the maps' own
- * order the result is a view_joint_valid [B,V,J] for the `_vj` entries below. */
+ * order the result is a view_joint_valid [B,V,J] for the `_masked` entries below (MVAL_MASK_VIEW_JOINT). */
 int mval_peak_mask(const float* heatmaps, float min_peak, uint8_t* out, int64_t n_maps, int hh, int wh, void* stream);
 
 /* ------------------------------------------------------------------------------------
@@ -134,65 +134,61 @@ int mval_triangulate_ransac_pairs(const void* kp2d, int kp_is_f32, const double*
 int mval_reprojection_xe(const double* kp3d, const double* proj, const float* heatmaps, double* out, double* ws,
                          int B, int V, int J, int hh, int wh, double sigma, void* stream);
 
-/* Frames with missing views.  view_valid [B,V] u8, nonzero = the view is present in that frame (never NULL: a NULL mask is
- * an error and nothing is launched -- call the entry without `_views`).  For every frame the result is what the entry without
- * `_views` gives on that frame's present views alone, bit for bit: nothing of an absent view enters arithmetic, its
- * key-point row, projection matrix and heat-maps are not read and may hold anything, NaN included.  All frames of a batch
- * go through one launch, however their present sets differ.
+/* Presence masks.  The four `_masked` entries below -- and mval_refine_points_3d -- take `const uint8_t* mask, int mask_kind`
+ * and compute what their unmasked sibling computes on the views that are present.  mask_kind must be one of the three values
+ * and (mask_kind == MVAL_MASK_NONE) == (mask == NULL); anything else is an error and nothing is launched.
  *
- * mval_triangulate_ransac_views (2 <= V <= 11): lane p keeps its lexicographic pair and sits out when one of its views is
- *   absent; the vote runs over present views.
- * mval_triangulate_ransac_pairs_views (2 <= V <= 32): the table names ORIGINAL view indices; an entry naming an absent
- *   view, or a view >= V (the host pads the shorter rows of a per-problem table with 255), takes no part; with no usable
- *   pair all PRESENT views are inliers.
- * Both, per frame with n present views: n < 2 and at least one valid joint -> inlier_count -2, metric NaN, kp3d /
- *   joint_err / joint_inliers 0 (the reference asserts len(points) >= 2 inside the first valid joint; the host wrapper
- *   raises AssertionError); no valid joint -> inlier_count -1 and metric NaN whatever n is.  joint_inliers counts present
- *   views only.  Every other argument and output as the entry without `_views`. */
-int mval_triangulate_ransac_views(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
-                                  const uint8_t* view_valid, double* kp3d, double* joint_err, int32_t* joint_inliers,
-                                  double* metric, int32_t* inlier_count, int B, int V, int J, double eps, void* stream);
-int mval_triangulate_ransac_pairs_views(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
-                                        const uint8_t* view_valid, const uint8_t* pairs, int P, int pairs_shared,
-                                        double* kp3d, double* joint_err, int32_t* joint_inliers, double* metric,
-                                        int32_t* inlier_count, int B, int V, int J, double eps, void* stream);
+ * MVAL_MASK_NONE: no mask.  The entry runs what its unmasked sibling runs (which forwards here), bit for bit.
+ *
+ * MVAL_MASK_VIEWS: mask = view_valid [B,V] u8, nonzero = the view is present in that frame.  For every frame the result is
+ *   what the unmasked entry gives on that frame's present views alone, bit for bit.  All frames of a batch go through one
+ *   launch, however their present sets differ.  Per frame with n present views: n < 2 and at least one valid joint ->
+ *   inlier_count -2, metric NaN, kp3d / joint_err / joint_inliers 0 (the reference asserts len(points) >= 2 inside the first
+ *   valid joint; the host wrapper raises AssertionError); no valid joint -> inlier_count -1 and metric NaN whatever n is.
+ *   joint_inliers counts present views only.
+ *
+ * MVAL_MASK_VIEW_JOINT: mask = view_joint_valid [B,V,J] u8, nonzero = joint j is usable in view v of frame b.  The present
+ *   views are a property of the PROBLEM (frame, joint): for a valid joint with two or more present views the result is what
+ *   the unmasked entry gives on that joint's present views alone (B = 1, J = 1), bit for bit.  All problems of a batch go
+ *   through one launch however their sets differ.  A valid joint with fewer than two present views is written like an invalid
+ *   joint: kp3d, joint_err, joint_inliers 0.  metric (mean) and inlier_count (min) of a frame run over its USED joints: valid
+ *   and two or more present views.  A used joint has joint_inliers >= 2 (the winning pair is in its own set), so
+ *   joint_inliers > 0 is the used mask.  No valid joint -> inlier_count -1; a valid joint but no used joint -> -2; metric NaN
+ *   in both.
+ *
+ * Nothing of an absent view / entry is read: it never votes, is never an inlier or part of a walked pair, is skipped by the
+ * final DLT, and its key-point row, projection matrix (MVAL_MASK_VIEWS) and heat-maps may hold anything, NaN included. */
+#define MVAL_MASK_NONE 0
+#define MVAL_MASK_VIEWS 1
+#define MVAL_MASK_VIEW_JOINT 2
 
-/* mval_reprojection_xe over the present views of each frame: the maps of an absent view are not read, their ws slots are
- * not written, and the serial (view, joint) sum skips them.  A frame without a present view gives 0. */
-int mval_reprojection_xe_views(const double* kp3d, const double* proj, const float* heatmaps, const uint8_t* view_valid,
-                               double* out, double* ws, int B, int V, int J, int hh, int wh, double sigma, void* stream);
+/* mval_triangulate_ransac under a mask (2 <= V <= 11): lane p keeps its lexicographic pair and sits out when one of its views
+ * is absent; the vote runs over present views.  Every other argument and output as mval_triangulate_ransac. */
+int mval_triangulate_ransac_masked(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                   const uint8_t* mask, int mask_kind, double* kp3d, double* joint_err,
+                                   int32_t* joint_inliers, double* metric, int32_t* inlier_count, int B, int V, int J,
+                                   double eps, void* stream);
 
-/* Joints missing from single views.  view_joint_valid [B,V,J] u8, nonzero = joint j is usable in view v of frame b (never
- * NULL: a NULL mask is an error and nothing is launched).  The present views are a property of the PROBLEM (frame, joint):
- * for a valid joint with two or more present views the result is what the entry without `_vj` gives on that joint's present
- * views alone (B = 1, J = 1), bit for bit.  Nothing of an absent entry is used: it never votes, is never an inlier or part
- * of a walked pair, is skipped by the final DLT, and its key-point row may hold anything, NaN included.  All problems of a
- * batch go through one launch however their sets differ.  Same V / J / P limits and pair-table rules as the `_views` entries
- * (a per-problem table names original view indices; entries naming an absent view or a view >= V take no part).
- *   A valid joint with fewer than two present views is written like an invalid joint: kp3d, joint_err, joint_inliers 0.
- *   metric (mean) and inlier_count (min) of a frame run over its USED joints: valid and two or more present views.  A used
- *   joint has joint_inliers >= 2 (the winning pair is in its own set), so joint_inliers > 0 is the used mask.
- *   No valid joint -> inlier_count -1; a valid joint but no used joint -> -2; metric NaN in both. */
-int mval_triangulate_ransac_vj(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
-                               const uint8_t* view_joint_valid, double* kp3d, double* joint_err, int32_t* joint_inliers,
-                               double* metric, int32_t* inlier_count, int B, int V, int J, double eps, void* stream);
-int mval_triangulate_ransac_pairs_vj(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
-                                     const uint8_t* view_joint_valid, const uint8_t* pairs, int P, int pairs_shared,
-                                     double* kp3d, double* joint_err, int32_t* joint_inliers, double* metric,
-                                     int32_t* inlier_count, int B, int V, int J, double eps, void* stream);
+/* mval_triangulate_ransac_pairs under a mask (2 <= V <= 32): the table names ORIGINAL view indices; an entry naming an absent
+ * view, or a view >= V (the host pads the shorter rows of a per-problem table with 255), takes no part; with no usable pair
+ * all PRESENT views are inliers.  Every other argument and output as mval_triangulate_ransac_pairs. */
+int mval_triangulate_ransac_pairs_masked(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                         const uint8_t* mask, int mask_kind, const uint8_t* pairs, int P, int pairs_shared,
+                                         double* kp3d, double* joint_err, int32_t* joint_inliers, double* metric,
+                                         int32_t* inlier_count, int B, int V, int J, double eps, void* stream);
 
-/* mval_reprojection_xe over the present entries: the map of an absent (view, joint) entry is not read, its ws slot is not
- * written, and the serial view-major, joint-minor sum skips it.  A frame without a present entry gives 0. */
-int mval_reprojection_xe_vj(const double* kp3d, const double* proj, const float* heatmaps, const uint8_t* view_joint_valid,
-                            double* out, double* ws, int B, int V, int J, int hh, int wh, double sigma, void* stream);
+/* mval_reprojection_xe under a mask: the maps of an absent view / entry are not read, their ws slots are not written, and the
+ * serial view-major, joint-minor sum skips them.  A frame without a present view / entry gives 0. */
+int mval_reprojection_xe_masked(const double* kp3d, const double* proj, const float* heatmaps, const uint8_t* mask,
+                                int mask_kind, double* out, double* ws, int B, int V, int J, int hh, int wh, double sigma,
+                                void* stream);
 
 /* 3-D refinement of the triangulated joints (not in the reference, whose direct_optimization has no defined result;
  * DESIGN.md 6.5 holds the definition).  One extra launch between a triangulation entry and the metrics.  Per problem (frame,
  * joint), with X0 = kp3d the triangulation's point:
  *   S = the present views v whose half-distance error at X0, 1/2 |p_v - pi(P_v [X0; 1])| -- the vote's own -- is finite and
  *       < eps, and, with weights, whose w_v is finite and > 0.  Presence is read as the triangulation entries read it: valid
- *       [B,J] u8 or NULL, and mask = NULL (MVAL_MASK_NONE), view_valid [B,V] u8 (MVAL_MASK_VIEWS) or view_joint_valid [B,V,J]
- *       u8 (MVAL_MASK_VIEW_JOINT); nothing of an absent view or entry is read.
+ *       [B,J] u8 or NULL, and (mask, mask_kind) as under "Presence masks" above; nothing of an absent view or entry is read.
  *   Not refined -- kp3d_out = X0 bit for bit, joint_err_out = joint_err, joint_status 0 -- when the joint is invalid, X0 is
  *       non-finite or |S| < 2.
  *   Otherwise kp3d_out = the minimiser of E(X) = 1/2 sum_{v in S} w_v |p_v - pi(P_v [X; 1])|^2 (w_v = 1 without weights) by
@@ -214,9 +210,6 @@ int mval_reprojection_xe_vj(const double* kp3d, const double* proj, const float*
  * One lane per problem; a problem's bits do not depend on the rest of the batch.  V outside 2..32, a mask_kind outside 0..2
  * or not matching `mask`, NULL or misaligned arrays return an error and launch nothing; B = 0 returns 0. */
 #define MVAL_REFINE3D_MAX_ITERS 32
-#define MVAL_MASK_NONE 0
-#define MVAL_MASK_VIEWS 1
-#define MVAL_MASK_VIEW_JOINT 2
 int mval_refine_points_3d(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid, const uint8_t* mask,
                           int mask_kind, const float* weights, const double* kp3d, const double* joint_err,
                           const int32_t* joint_inliers, double* kp3d_out, double* joint_err_out, int32_t* joint_support,
@@ -266,17 +259,13 @@ int mval_score_decode_maps_all(const float* heatmaps, const uint8_t* valid, floa
 int mval_score_reduce(const float* per_map, const uint8_t* valid, double* out, int B, int V, int J,
                       int mode, void* stream);
 
-/* mval_score_reduce over the present views of each frame (view_valid [B,V] u8, never NULL): the statistics of an absent
- * view's maps are not read; n = valid joints x present views; same loop order (views outer, joints inner) and precision
- * per mode, so a frame gives what mval_score_reduce gives on its present views alone.  n = 0 -> NaN. */
-int mval_score_reduce_views(const float* per_map, const uint8_t* valid, const uint8_t* view_valid, double* out, int B,
-                            int V, int J, int mode, void* stream);
-
-/* mval_score_reduce over the present entries of each frame (view_joint_valid [B,V,J] u8, never NULL): a map counts when its
- * joint is valid and its own entry is nonzero; n = the entries left; same loop order and precision per mode, so a frame gives
- * what mval_score_reduce gives on the compacted list (V = 1, J = n).  n = 0 -> NaN. */
-int mval_score_reduce_vj(const float* per_map, const uint8_t* valid, const uint8_t* view_joint_valid, double* out, int B,
-                         int V, int J, int mode, void* stream);
+/* mval_score_reduce under a mask ("Presence masks" above): the statistics of absent maps are not read; same loop order
+ * (views outer, joints inner) and precision per mode.  MVAL_MASK_VIEWS: n = valid joints x present views, and a frame gives
+ * what mval_score_reduce gives on its present views alone.  MVAL_MASK_VIEW_JOINT: a map counts when its joint is valid and
+ * its own entry is nonzero, n = the entries left, and a frame gives what mval_score_reduce gives on the compacted list
+ * (V = 1, J = n).  n = 0 -> NaN. */
+int mval_score_reduce_masked(const float* per_map, const uint8_t* valid, const uint8_t* mask, int mask_kind, double* out,
+                             int B, int V, int J, int mode, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Loss / metric

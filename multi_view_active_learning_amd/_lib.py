@@ -232,62 +232,21 @@ def refine_keypoints(hm, kp2d, valid, b, v, j, hh, wh, stride, method):
     return out, conf
 
 
-def _triangulate(entry, kp2d, proj, valid, b, v, j, eps, table=()):
-    """What the two triangulation entries share: key-points float32 or int64, the five outputs, the call.  ``table``: the
-    arguments an entry takes between ``valid`` and the outputs."""
-    kp_is_f32 = 1 if kp2d.dtype == torch.float32 else 0
-    if not kp_is_f32:
-        _req(kp2d, torch.int64, "keypoints_2d")
-    dev = proj.device
-    kp3d = torch.empty((b, j, 3), dtype=torch.float64, device=dev)
-    jerr = torch.empty((b, j), dtype=torch.float64, device=dev)
-    jinl = torch.empty((b, j), dtype=torch.int32, device=dev)
-    metric = torch.empty((b,), dtype=torch.float64, device=dev)
-    inl = torch.empty((b,), dtype=torch.int32, device=dev)
-    _check(
-        getattr(lib(), entry)(
-            _p(kp2d), C.c_int(kp_is_f32), _p(_req(proj, torch.float64, "proj_matricies")), _p(valid), *table,
-            _p(kp3d), _p(jerr), _p(jinl), _p(metric), _p(inl),
-            C.c_int(b), C.c_int(v), C.c_int(j), C.c_double(eps), _stream(),
-        ),
-        entry,
-    )
-    return kp3d, jerr, jinl, metric, inl
+# Presence masks (include/mval_hip.h): the `_masked` entries take (mask, mask_kind) -- nothing, view_valid (B, V) uint8 on the
+# device, nonzero = the view is present in that frame, or view_joint_valid (B, V, J) uint8, nonzero = joint j is usable in view
+# v of frame b.  The wrappers below take them as keyword arguments and always call the `_masked` entry.
+MASK_NONE, MASK_VIEWS, MASK_VIEW_JOINT = 0, 1, 2  # MVAL_MASK_*
 
-
-PAIRS_MAX_VIEWS = 32  # MVAL_PAIRS_MAX_VIEWS (include/mval_hip.h): views mval_triangulate_ransac_pairs accepts
-
-
-def triangulate_ransac_pairs(kp2d, proj, valid, pairs, b, v, j, eps):
-    """mval_triangulate_ransac_pairs: pairs (B, J, P, 2) uint8, one table per problem, or (1, P, 2), one shared by all."""
-    _req(pairs, torch.uint8, "pairs")
-    shared = pairs.dim() == 3
-    if pairs.shape[-1] != 2 or (tuple(pairs.shape[:-2]) != (1,) if shared else tuple(pairs.shape[:-2]) != (b, j)):
-        raise MvalError(f"pairs: expected (1, P, 2) or ({b}, {j}, P, 2), got {tuple(pairs.shape)}")
-    return _triangulate("mval_triangulate_ransac_pairs", kp2d, proj, valid, b, v, j, eps,
-                        table=(_p(pairs), C.c_int(pairs.shape[-2]), C.c_int(int(shared))))
-
-
-def triangulate_ransac(kp2d, proj, valid, b, v, j, eps):
-    return _triangulate("mval_triangulate_ransac", kp2d, proj, valid, b, v, j, eps)
-
-
-# Frames with missing views (include/mval_hip.h, the `_views` entries): view_valid (B, V) uint8 on the device, nonzero = present.
-# These four entries carry ctypes argtypes, set on first use, where the older wrappers convert every argument by hand
-# (C.c_int(b), ...): the masked entries differ from their unmasked twins by ONE pointer in the middle of a long list, and with
-# argtypes a call that leaves it out fails in ctypes with an argument-count error instead of shifting every later argument.
+# The entries below carry ctypes argtypes, set on first use, where the older wrappers convert every argument by hand
+# (C.c_int(b), ...): a masked entry differs from its unmasked sibling by two arguments in the middle of a long list, and with
+# argtypes a call that leaves one out fails in ctypes with an argument-count error instead of shifting every later argument.
 # The older entries are left as they are.
 _VOIDP, _INT, _DOUBLE = C.c_void_p, C.c_int, C.c_double
 _VIEWS_ARGTYPES = {
-    "mval_triangulate_ransac_views": [_VOIDP, _INT] + [_VOIDP] * 8 + [_INT] * 3 + [_DOUBLE, _VOIDP],
-    "mval_triangulate_ransac_pairs_views": [_VOIDP, _INT] + [_VOIDP] * 4 + [_INT] * 2 + [_VOIDP] * 5 + [_INT] * 3 + [_DOUBLE, _VOIDP],
-    "mval_reprojection_xe_views": [_VOIDP] * 6 + [_INT] * 5 + [_DOUBLE, _VOIDP],
-    "mval_score_reduce_views": [_VOIDP] * 4 + [_INT] * 4 + [_VOIDP],
-    # joints missing from single views: the `_vj` twins take view_joint_valid (B, V, J) where those take view_valid (B, V)
-    "mval_triangulate_ransac_vj": [_VOIDP, _INT] + [_VOIDP] * 8 + [_INT] * 3 + [_DOUBLE, _VOIDP],
-    "mval_triangulate_ransac_pairs_vj": [_VOIDP, _INT] + [_VOIDP] * 4 + [_INT] * 2 + [_VOIDP] * 5 + [_INT] * 3 + [_DOUBLE, _VOIDP],
-    "mval_reprojection_xe_vj": [_VOIDP] * 6 + [_INT] * 5 + [_DOUBLE, _VOIDP],
-    "mval_score_reduce_vj": [_VOIDP] * 4 + [_INT] * 4 + [_VOIDP],
+    "mval_triangulate_ransac_masked": [_VOIDP, _INT] + [_VOIDP] * 3 + [_INT] + [_VOIDP] * 5 + [_INT] * 3 + [_DOUBLE, _VOIDP],
+    "mval_triangulate_ransac_pairs_masked": [_VOIDP, _INT] + [_VOIDP] * 3 + [_INT, _VOIDP] + [_INT] * 2 + [_VOIDP] * 5 + [_INT] * 3 + [_DOUBLE, _VOIDP],
+    "mval_reprojection_xe_masked": [_VOIDP] * 4 + [_INT] + [_VOIDP] * 2 + [_INT] * 5 + [_DOUBLE, _VOIDP],
+    "mval_score_reduce_masked": [_VOIDP] * 3 + [_INT, _VOIDP] + [_INT] * 4 + [_VOIDP],
     "mval_peak_mask": [_VOIDP, C.c_float, _VOIDP, C.c_longlong, _INT, _INT, _VOIDP],
 }
 
@@ -299,87 +258,65 @@ def _views_entry(name):
     return f
 
 
-def _req_view_valid(view_valid, b, v):
-    _req(view_valid, torch.uint8, "view_valid")
-    if tuple(view_valid.shape) != (b, v):
-        raise MvalError(f"view_valid: expected ({b}, {v}), got {tuple(view_valid.shape)}")
-    return view_valid
+def _mask_arg(view_valid, view_joint_valid, b, v, j):
+    """(mask, mask_kind) of a `_masked` entry from the wrappers' two keywords, at most one of which is given."""
+    if view_valid is not None and view_joint_valid is not None:
+        raise MvalError("view_valid or view_joint_valid, not both (AND them into view_joint_valid)")
+    if view_joint_valid is not None:
+        _req(view_joint_valid, torch.uint8, "view_joint_valid")
+        if tuple(view_joint_valid.shape) != (b, v, j):
+            raise MvalError(f"view_joint_valid: expected ({b}, {v}, {j}), got {tuple(view_joint_valid.shape)}")
+        return view_joint_valid, MASK_VIEW_JOINT
+    if view_valid is not None:
+        _req(view_valid, torch.uint8, "view_valid")
+        if tuple(view_valid.shape) != (b, v):
+            raise MvalError(f"view_valid: expected ({b}, {v}), got {tuple(view_valid.shape)}")
+        return view_valid, MASK_VIEWS
+    return None, MASK_NONE
 
 
-def triangulate_ransac_views(kp2d, proj, valid, view_valid, b, v, j, eps):
-    """mval_triangulate_ransac_views: ``triangulate_ransac`` over the present views of each frame (V <= 11)."""
-    _views_entry("mval_triangulate_ransac_views")
-    return _triangulate("mval_triangulate_ransac_views", kp2d, proj, valid, b, v, j, eps,
-                        table=(_p(_req_view_valid(view_valid, b, v)),))
+def _triangulate(entry, kp2d, proj, valid, mask, kind, b, v, j, eps, table=()):
+    """What the two triangulation entries share: key-points float32 or int64, the five outputs, the call.  ``table``: the
+    arguments an entry takes between the mask and the outputs."""
+    kp_is_f32 = 1 if kp2d.dtype == torch.float32 else 0
+    if not kp_is_f32:
+        _req(kp2d, torch.int64, "keypoints_2d")
+    dev = proj.device
+    kp3d = torch.empty((b, j, 3), dtype=torch.float64, device=dev)
+    jerr = torch.empty((b, j), dtype=torch.float64, device=dev)
+    jinl = torch.empty((b, j), dtype=torch.int32, device=dev)
+    metric = torch.empty((b,), dtype=torch.float64, device=dev)
+    inl = torch.empty((b,), dtype=torch.int32, device=dev)
+    _check(
+        _views_entry(entry)(
+            _p(kp2d), kp_is_f32, _p(_req(proj, torch.float64, "proj_matricies")), _p(valid), _p(mask), kind, *table,
+            _p(kp3d), _p(jerr), _p(jinl), _p(metric), _p(inl), b, v, j, eps, _stream(),
+        ),
+        entry,
+    )
+    return kp3d, jerr, jinl, metric, inl
 
 
-def triangulate_ransac_pairs_views(kp2d, proj, valid, view_valid, pairs, b, v, j, eps):
-    """mval_triangulate_ransac_pairs_views: ``triangulate_ransac_pairs`` over the present views of each frame; the table
-    names original view indices, entries >= V (255: padding) or naming an absent view take no part."""
+PAIRS_MAX_VIEWS = 32  # MVAL_PAIRS_MAX_VIEWS (include/mval_hip.h): views mval_triangulate_ransac_pairs accepts
+
+
+def triangulate_ransac_pairs(kp2d, proj, valid, pairs, b, v, j, eps, *, view_valid=None, view_joint_valid=None):
+    """mval_triangulate_ransac_pairs_masked: pairs (B, J, P, 2) uint8, one table per problem, or (1, P, 2), one shared by all.
+    Under a mask the result is over the present views of each frame / problem; the table names original view indices, entries
+    >= V (255: padding) or naming an absent view take no part."""
     _req(pairs, torch.uint8, "pairs")
     shared = pairs.dim() == 3
     if pairs.shape[-1] != 2 or (tuple(pairs.shape[:-2]) != (1,) if shared else tuple(pairs.shape[:-2]) != (b, j)):
         raise MvalError(f"pairs: expected (1, P, 2) or ({b}, {j}, P, 2), got {tuple(pairs.shape)}")
-    _views_entry("mval_triangulate_ransac_pairs_views")
-    return _triangulate("mval_triangulate_ransac_pairs_views", kp2d, proj, valid, b, v, j, eps,
-                        table=(_p(_req_view_valid(view_valid, b, v)), _p(pairs), C.c_int(pairs.shape[-2]), C.c_int(int(shared))))
+    mask, kind = _mask_arg(view_valid, view_joint_valid, b, v, j)
+    return _triangulate("mval_triangulate_ransac_pairs_masked", kp2d, proj, valid, mask, kind, b, v, j, eps,
+                        table=(_p(pairs), pairs.shape[-2], int(shared)))
 
 
-def reprojection_xe_views(kp3d, proj, hm, view_valid, b, v, j, hh, wh, sigma):
-    out = torch.empty((b,), dtype=torch.float64, device=hm.device)
-    ws = torch.empty((b * v * j,), dtype=torch.float64, device=hm.device)
-    _check(
-        _views_entry("mval_reprojection_xe_views")(
-            _p(_req(kp3d, torch.float64, "keypoints_3d")), _p(_req(proj, torch.float64, "proj")),
-            _p(_req(hm, torch.float32, "heatmaps")), _p(_req_view_valid(view_valid, b, v)), _p(out), _p(ws),
-            b, v, j, hh, wh, sigma, _stream(),
-        ),
-        "mval_reprojection_xe_views",
-    )
-    return out
-
-
-# Joints missing from single views (include/mval_hip.h, the `_vj` entries): view_joint_valid (B, V, J) uint8 on the device,
-# nonzero = joint j is usable in view v of frame b.
-def _req_view_joint_valid(view_joint_valid, b, v, j):
-    _req(view_joint_valid, torch.uint8, "view_joint_valid")
-    if tuple(view_joint_valid.shape) != (b, v, j):
-        raise MvalError(f"view_joint_valid: expected ({b}, {v}, {j}), got {tuple(view_joint_valid.shape)}")
-    return view_joint_valid
-
-
-def triangulate_ransac_vj(kp2d, proj, valid, view_joint_valid, b, v, j, eps):
-    """mval_triangulate_ransac_vj: ``triangulate_ransac`` over the present views of each (frame, joint) problem (V <= 11)."""
-    _views_entry("mval_triangulate_ransac_vj")
-    return _triangulate("mval_triangulate_ransac_vj", kp2d, proj, valid, b, v, j, eps,
-                        table=(_p(_req_view_joint_valid(view_joint_valid, b, v, j)),))
-
-
-def triangulate_ransac_pairs_vj(kp2d, proj, valid, view_joint_valid, pairs, b, v, j, eps):
-    """mval_triangulate_ransac_pairs_vj: ``triangulate_ransac_pairs`` over the present views of each problem; the table names
-    original view indices, entries >= V (255: padding) or naming a view the joint is absent from take no part."""
-    _req(pairs, torch.uint8, "pairs")
-    shared = pairs.dim() == 3
-    if pairs.shape[-1] != 2 or (tuple(pairs.shape[:-2]) != (1,) if shared else tuple(pairs.shape[:-2]) != (b, j)):
-        raise MvalError(f"pairs: expected (1, P, 2) or ({b}, {j}, P, 2), got {tuple(pairs.shape)}")
-    _views_entry("mval_triangulate_ransac_pairs_vj")
-    return _triangulate("mval_triangulate_ransac_pairs_vj", kp2d, proj, valid, b, v, j, eps,
-                        table=(_p(_req_view_joint_valid(view_joint_valid, b, v, j)), _p(pairs), C.c_int(pairs.shape[-2]),
-                               C.c_int(int(shared))))
-
-
-def reprojection_xe_vj(kp3d, proj, hm, view_joint_valid, b, v, j, hh, wh, sigma):
-    out = torch.empty((b,), dtype=torch.float64, device=hm.device)
-    ws = torch.empty((b * v * j,), dtype=torch.float64, device=hm.device)
-    _check(
-        _views_entry("mval_reprojection_xe_vj")(
-            _p(_req(kp3d, torch.float64, "keypoints_3d")), _p(_req(proj, torch.float64, "proj")),
-            _p(_req(hm, torch.float32, "heatmaps")), _p(_req_view_joint_valid(view_joint_valid, b, v, j)), _p(out), _p(ws),
-            b, v, j, hh, wh, sigma, _stream(),
-        ),
-        "mval_reprojection_xe_vj",
-    )
-    return out
+def triangulate_ransac(kp2d, proj, valid, b, v, j, eps, *, view_valid=None, view_joint_valid=None):
+    """mval_triangulate_ransac_masked (V <= 11); under a mask over the present views of each frame / (frame, joint) problem."""
+    mask, kind = _mask_arg(view_valid, view_joint_valid, b, v, j)
+    return _triangulate("mval_triangulate_ransac_masked", kp2d, proj, valid, mask, kind, b, v, j, eps)
 
 
 def peak_mask(hm, min_peak, n_maps, hh, wh):
@@ -392,8 +329,6 @@ def peak_mask(hm, min_peak, n_maps, hh, wh):
     return out
 
 
-# MVAL_MASK_* (include/mval_hip.h): what the mask argument of mval_refine_points_3d is
-MASK_NONE, MASK_VIEWS, MASK_VIEW_JOINT = 0, 1, 2
 REFINE3D_MAX_ITERS = 32  # MVAL_REFINE3D_MAX_ITERS
 _VIEWS_ARGTYPES["mval_refine_points_3d"] = [_VOIDP, _INT] + [_VOIDP] * 3 + [_INT] + [_VOIDP] * 10 + [_INT] * 3 + [_DOUBLE, _VOIDP]
 
@@ -404,8 +339,7 @@ def refine_points_3d(kp2d, proj, valid, kp3d, joint_err, joint_inliers, b, v, j,
     inputs it had -- kp2d (b,v,j,2) int64|float32, proj (b,v,3,4) f64, valid (b,j) uint8 or None, at most one of view_valid
     (b,v) / view_joint_valid (b,v,j) uint8 -- and optional weights (b,v,j) float32 ->
     (kp3d refined (b,j,3) f64, joint_err (b,j) f64, joint_support (b,j) i32, joint_status (b,j) i32, metric (b,) f64)."""
-    if view_valid is not None and view_joint_valid is not None:
-        raise MvalError("refine_points_3d: view_valid or view_joint_valid, not both (AND them into view_joint_valid)")
+    mask, kind = _mask_arg(view_valid, view_joint_valid, b, v, j)
     kp_is_f32 = 1 if kp2d.dtype == torch.float32 else 0
     if not kp_is_f32:
         _req(kp2d, torch.int64, "keypoints_2d")
@@ -414,11 +348,6 @@ def refine_points_3d(kp2d, proj, valid, kp3d, joint_err, joint_inliers, b, v, j,
                         f"{tuple(kp2d.shape)}, {tuple(kp3d.shape)}, {tuple(joint_err.shape)} and {tuple(joint_inliers.shape)}")
     if weights is not None and tuple(_req(weights, torch.float32, "weights").shape) != (b, v, j):
         raise MvalError(f"refine_points_3d: weights ({b}, {v}, {j}), got {tuple(weights.shape)}")
-    mask, kind = None, MASK_NONE
-    if view_joint_valid is not None:
-        mask, kind = _req_view_joint_valid(view_joint_valid, b, v, j), MASK_VIEW_JOINT
-    elif view_valid is not None:
-        mask, kind = _req_view_valid(view_valid, b, v), MASK_VIEWS
     dev = proj.device
     out = torch.empty((b, j, 3), dtype=torch.float64, device=dev)
     jerr = torch.empty((b, j), dtype=torch.float64, device=dev)
@@ -438,16 +367,17 @@ def refine_points_3d(kp2d, proj, valid, kp3d, joint_err, joint_inliers, b, v, j,
     return out, jerr, support, status, metric
 
 
-def reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, sigma):
+def reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, sigma, *, view_valid=None, view_joint_valid=None):
+    """mval_reprojection_xe_masked: (b,) float64; under a mask the sum over the present views / entries of each frame."""
+    mask, kind = _mask_arg(view_valid, view_joint_valid, b, v, j)
     out = torch.empty((b,), dtype=torch.float64, device=hm.device)
     ws = torch.empty((b * v * j,), dtype=torch.float64, device=hm.device)
     _check(
-        lib().mval_reprojection_xe(
+        _views_entry("mval_reprojection_xe_masked")(
             _p(_req(kp3d, torch.float64, "keypoints_3d")), _p(_req(proj, torch.float64, "proj")),
-            _p(_req(hm, torch.float32, "heatmaps")), _p(out), _p(ws),
-            C.c_int(b), C.c_int(v), C.c_int(j), C.c_int(hh), C.c_int(wh), C.c_double(sigma), _stream(),
+            _p(_req(hm, torch.float32, "heatmaps")), _p(mask), kind, _p(out), _p(ws), b, v, j, hh, wh, sigma, _stream(),
         ),
-        "mval_reprojection_xe",
+        "mval_reprojection_xe_masked",
     )
     return out
 
@@ -506,40 +436,15 @@ def score_decode_maps_all(hm, valid, b, v, j, hh, wh, stride, split_width, decod
     return out, cnt, kp
 
 
-def score_reduce(per_map, valid, b, v, j, mode):
+def score_reduce(per_map, valid, b, v, j, mode, *, view_valid=None, view_joint_valid=None):
+    """mval_score_reduce_masked: (b,) float64; under a mask over the present views / (view, joint) entries of each frame."""
+    mask, kind = _mask_arg(view_valid, view_joint_valid, b, v, j)
     out = torch.empty((b,), dtype=torch.float64, device=per_map.device)
     _check(
-        lib().mval_score_reduce(
-            _p(_req(per_map, torch.float32, "per_map")), _p(valid), _p(out),
-            C.c_int(b), C.c_int(v), C.c_int(j), C.c_int(mode), _stream(),
+        _views_entry("mval_score_reduce_masked")(
+            _p(_req(per_map, torch.float32, "per_map")), _p(valid), _p(mask), kind, _p(out), b, v, j, mode, _stream(),
         ),
-        "mval_score_reduce",
-    )
-    return out
-
-
-def score_reduce_views(per_map, valid, view_valid, b, v, j, mode):
-    """mval_score_reduce_views: ``score_reduce`` over the present views of each frame."""
-    out = torch.empty((b,), dtype=torch.float64, device=per_map.device)
-    _check(
-        _views_entry("mval_score_reduce_views")(
-            _p(_req(per_map, torch.float32, "per_map")), _p(valid), _p(_req_view_valid(view_valid, b, v)), _p(out),
-            b, v, j, mode, _stream(),
-        ),
-        "mval_score_reduce_views",
-    )
-    return out
-
-
-def score_reduce_vj(per_map, valid, view_joint_valid, b, v, j, mode):
-    """mval_score_reduce_vj: ``score_reduce`` over the present (view, joint) entries of each frame."""
-    out = torch.empty((b,), dtype=torch.float64, device=per_map.device)
-    _check(
-        _views_entry("mval_score_reduce_vj")(
-            _p(_req(per_map, torch.float32, "per_map")), _p(valid), _p(_req_view_joint_valid(view_joint_valid, b, v, j)), _p(out),
-            b, v, j, mode, _stream(),
-        ),
-        "mval_score_reduce_vj",
+        "mval_score_reduce_masked",
     )
     return out
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 
 #include "../../include/mval_hip.h"
 
@@ -11,14 +12,16 @@
 
 void mval_set_error(const char* fmt, ...);
 
-#define MVAL_CHECK_LAUNCH(name)                                                        \
+// (stage: "" or the launch of an entry that makes several, as "/reduce")
+#define MVAL_CHECK_LAUNCH_STAGE(name, stage)                                           \
   do {                                                                                 \
     hipError_t e__ = hipGetLastError();                                                \
     if (e__ != hipSuccess) {                                                           \
-      mval_set_error("%s: launch failed: %s", name, hipGetErrorString(e__));           \
+      mval_set_error("%s%s: launch failed: %s", name, stage, hipGetErrorString(e__));  \
       return -2;                                                                       \
     }                                                                                  \
   } while (0)
+#define MVAL_CHECK_LAUNCH(name) MVAL_CHECK_LAUNCH_STAGE(name, "")
 
 #define MVAL_REQUIRE(cond, ...)                                                        \
   do {                                                                                 \
@@ -33,6 +36,26 @@ static inline hipStream_t mval_stream(void* s) { return reinterpret_cast<hipStre
 // What the mask argument of a post-stage kernel is (template parameter of the triangulation, XE and score-reduce kernels):
 // nothing, view_valid [B,V] (frames with missing views) or view_joint_valid [B,V,J] (joints missing from single views).
 enum { MASK_NONE = 0, MASK_VIEWS = 1, MASK_VIEW_JOINT = 2 };
+static_assert(MVAL_MASK_NONE == MASK_NONE && MVAL_MASK_VIEWS == MASK_VIEWS && MVAL_MASK_VIEW_JOINT == MASK_VIEW_JOINT,
+              "the mask kinds of the C-ABI are the kernels' template values");
+
+// The argument check of every entry that takes (mask, mask_kind): include/mval_hip.h, "Presence masks".
+#define MVAL_REQUIRE_MASK(name, mask, mask_kind)                                                                        \
+  do {                                                                                                                  \
+    MVAL_REQUIRE((mask_kind) == MASK_NONE || (mask_kind) == MASK_VIEWS || (mask_kind) == MASK_VIEW_JOINT,               \
+                 "%s: mask_kind %d (0 none, 1 view_valid [B,V], 2 view_joint_valid [B,V,J])", name, mask_kind);         \
+    MVAL_REQUIRE(((mask_kind) == MASK_NONE) == ((mask) == nullptr),                                                     \
+                 "%s: a mask goes with mask_kind 1 or 2, NULL with 0", name);                                           \
+  } while (0)
+
+// The one place where a runtime mask kind (checked: MVAL_REQUIRE_MASK) picks an instantiation: f is a generic lambda and gets
+// the kind as a std::integral_constant -- with_mask_kind(kind, [&](auto K) { constexpr int MASK = decltype(K)::value; ... }).
+template <typename F>
+static inline auto with_mask_kind(int mask_kind, F&& f) {
+  if (mask_kind == MASK_VIEW_JOINT) return f(std::integral_constant<int, MASK_VIEW_JOINT>{});
+  if (mask_kind == MASK_VIEWS) return f(std::integral_constant<int, MASK_VIEWS>{});
+  return f(std::integral_constant<int, MASK_NONE>{});
+}
 
 // ---- wave-level reductions (64 lanes) ------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

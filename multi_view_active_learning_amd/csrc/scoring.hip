@@ -595,7 +595,7 @@ extern "C" int mval_score_decode_maps_all(const float* heatmaps, const uint8_t* 
 // ---- AVG / STD over the valid maps of a frame, in python / numpy order -----------------
 #define SR_MAX 1024
 
-// MASKED: the maps of the views whose view_valid is 0 are left out (and not read): n = valid joints x present views, the same
+// MASK_VIEWS: the maps of the views whose view_valid is 0 are left out (and not read): n = valid joints x present views, the same
 // loops over what is left -- what the unmasked kernel computes on the frame's present views alone.
 // MASK_VIEW_JOINT: `view_valid` is view_joint_valid [B,V,J]; a map counts when its joint is valid and its own entry is set:
 // n = the entries left, the same loops over them -- the unmasked kernel on the compacted list (V = 1, J = n).
@@ -606,8 +606,8 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const float* pm = per_map + (int64_t)b * V * J;
-  constexpr bool MASKED = MASK == MASK_VIEWS;
-  const uint8_t* vv = MASKED ? view_valid + (int64_t)b * V : nullptr;
+  constexpr bool BY_VIEW = MASK == MASK_VIEWS;  // the mask is per view: whole views sit out
+  const uint8_t* vv = BY_VIEW ? view_valid + (int64_t)b * V : nullptr;
   const uint8_t* vj = MASK == MASK_VIEW_JOINT ? view_valid + (int64_t)b * V * J : nullptr;
   const auto used = [&](int v, int j) { return (!valid || valid[(int64_t)b * J + j]) && (MASK != MASK_VIEW_JOINT || vj[v * J + j]); };
   int n = 0, nv = V;
@@ -618,7 +618,7 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
   } else {
     for (int j = 0; j < J; j++) n += (!valid || valid[(int64_t)b * J + j]) ? 1 : 0;
   }
-  if (MASKED) {
+  if (BY_VIEW) {
     nv = 0;
     for (int v = 0; v < V; v++) nv += vv[v] ? 1 : 0;
   }
@@ -627,7 +627,7 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
   if (mode == MVAL_REDUCE_AVG_F64) {  // sum(python floats) / len
     double s = 0.0;
     for (int v = 0; v < V; v++) {
-      if (MASKED && !vv[v]) continue;
+      if (BY_VIEW && !vv[v]) continue;
       for (int j = 0; j < J; j++)
         if (used(v, j)) s += (double)pm[v * J + j];
     }
@@ -635,7 +635,7 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
   } else if (mode == MVAL_REDUCE_AVG_F32) {  // sum(np.float32) / len  (float32 throughout)
     float s = 0.f;
     for (int v = 0; v < V; v++) {
-      if (MASKED && !vv[v]) continue;
+      if (BY_VIEW && !vv[v]) continue;
       for (int j = 0; j < J; j++)
         if (used(v, j)) s += pm[v * J + j];
     }
@@ -644,7 +644,7 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
     double buf[SR_MAX];
     int k = 0;
     for (int v = 0; v < V; v++) {
-      if (MASKED && !vv[v]) continue;
+      if (BY_VIEW && !vv[v]) continue;
       for (int j = 0; j < J; j++)
         if (used(v, j)) buf[k++] = (double)pm[v * J + j];
     }
@@ -655,7 +655,7 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
     float buf[SR_MAX];
     int k = 0;
     for (int v = 0; v < V; v++) {
-      if (MASKED && !vv[v]) continue;
+      if (BY_VIEW && !vv[v]) continue;
       for (int j = 0; j < J; j++)
         if (used(v, j)) buf[k++] = pm[v * J + j];
     }
@@ -665,38 +665,27 @@ __global__ void score_reduce_kernel(const float* __restrict__ per_map, const uin
   }
 }
 
+// The two reduce entries: `name` is the one that was called.
+static int score_reduce(const char* name, const float* per_map, const uint8_t* valid, const uint8_t* mask, int mask_kind,
+                        double* out, int B, int V, int J, int mode, void* stream) {
+  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && V * J <= SR_MAX, "%s: bad dims (V*J must be <= %d)", name, SR_MAX);
+  MVAL_REQUIRE(mode >= 0 && mode <= 3, "%s: unknown mode %d", name, mode);
+  MVAL_REQUIRE_MASK(name, mask, mask_kind);
+  if (B == 0) return 0;
+  with_mask_kind(mask_kind, [&](auto K) {
+    hipLaunchKernelGGL(score_reduce_kernel<decltype(K)::value>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map,
+                       valid, mask, out, B, V, J, mode);
+  });
+  MVAL_CHECK_LAUNCH(name);
+  return 0;
+}
+
 extern "C" int mval_score_reduce(const float* per_map, const uint8_t* valid, double* out, int B, int V, int J, int mode,
                                  void* stream) {
-  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && V * J <= SR_MAX, "mval_score_reduce: bad dims (V*J must be <= %d)", SR_MAX);
-  MVAL_REQUIRE(mode >= 0 && mode <= 3, "mval_score_reduce: unknown mode %d", mode);
-  if (B == 0) return 0;
-  const uint8_t* const no_mask = nullptr;
-  hipLaunchKernelGGL(score_reduce_kernel<MASK_NONE>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map, valid,
-                     no_mask, out, B, V, J, mode);
-  MVAL_CHECK_LAUNCH("mval_score_reduce");
-  return 0;
+  return score_reduce("mval_score_reduce", per_map, valid, nullptr, MASK_NONE, out, B, V, J, mode, stream);
 }
 
-extern "C" int mval_score_reduce_views(const float* per_map, const uint8_t* valid, const uint8_t* view_valid, double* out,
-                                       int B, int V, int J, int mode, void* stream) {
-  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && V * J <= SR_MAX, "mval_score_reduce_views: bad dims (V*J must be <= %d)", SR_MAX);
-  MVAL_REQUIRE(mode >= 0 && mode <= 3, "mval_score_reduce_views: unknown mode %d", mode);
-  MVAL_REQUIRE(view_valid, "mval_score_reduce_views: view_valid is NULL (use mval_score_reduce)");
-  if (B == 0) return 0;
-  hipLaunchKernelGGL(score_reduce_kernel<MASK_VIEWS>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map, valid,
-                     view_valid, out, B, V, J, mode);
-  MVAL_CHECK_LAUNCH("mval_score_reduce_views");
-  return 0;
-}
-
-extern "C" int mval_score_reduce_vj(const float* per_map, const uint8_t* valid, const uint8_t* view_joint_valid, double* out,
-                                    int B, int V, int J, int mode, void* stream) {
-  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && V * J <= SR_MAX, "mval_score_reduce_vj: bad dims (V*J must be <= %d)", SR_MAX);
-  MVAL_REQUIRE(mode >= 0 && mode <= 3, "mval_score_reduce_vj: unknown mode %d", mode);
-  MVAL_REQUIRE(view_joint_valid, "mval_score_reduce_vj: view_joint_valid is NULL (use mval_score_reduce)");
-  if (B == 0) return 0;
-  hipLaunchKernelGGL(score_reduce_kernel<MASK_VIEW_JOINT>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), per_map, valid,
-                     view_joint_valid, out, B, V, J, mode);
-  MVAL_CHECK_LAUNCH("mval_score_reduce_vj");
-  return 0;
+extern "C" int mval_score_reduce_masked(const float* per_map, const uint8_t* valid, const uint8_t* mask, int mask_kind,
+                                        double* out, int B, int V, int J, int mode, void* stream) {
+  return score_reduce("mval_score_reduce_masked", per_map, valid, mask, mask_kind, out, B, V, J, mode, stream);
 }

@@ -22,15 +22,19 @@
 // n_iters.  Up to 64 pairs keep the grouping above; beyond, one wave per problem and lane p takes pairs p, p + 64, ...
 // Both kernels are built from the same two stages, vote_pair (a lane triangulates one pair and votes) and
 // finish_problem (final DLT over the winner's inlier views), and differ only in where a lane's pairs come from and in
-// the width of the reduction key; the host entries share launch_ransac (key-point dtype dispatch, frame_reduce_kernel).
+// the width of the reduction key; the host entries share `triangulate` (argument checks, mask kind and key-point dtype
+// dispatch, frame_reduce_kernel).
 //
-// Frames with missing views: the `_views` entries take view_valid [B,V] u8 and run the MASKED instantiations of the same
-// kernels.  A frame's present views are the bits of `present`; a pair with an absent view sits out, the vote and the
-// "no usable pair" fallback run over present views only, and nothing of an absent view (key-point row, matrix) is read.
-// MASKED is a template parameter: the unmasked instantiations compile to the code they were without it.
+// Presence masks (include/mval_hip.h): the `_masked` entries take (mask, mask_kind) and run the MASK instantiation of the same
+// kernels; MASKED in a kernel means MASK != MASK_NONE.  MASK is a template parameter: the MASK_NONE instantiations, which the
+// unmasked entries and the `_masked` ones with MVAL_MASK_NONE run, compile to the code they were without it.
 //
-// Joints missing from single views: the `_vj` entries take view_joint_valid [B,V,J] u8 and run the MASK_VIEW_JOINT
-// instantiations.  `present` is then a property of the problem (frame, joint), folded from the joint's column of the mask;
+// Frames with missing views: MASK_VIEWS, mask = view_valid [B,V] u8.  A frame's present views are the bits of `present`; a
+// pair with an absent view sits out, the vote and the "no usable pair" fallback run over present views only, and nothing of
+// an absent view (key-point row, matrix) is read.
+//
+// Joints missing from single views: MASK_VIEW_JOINT, mask = view_joint_valid [B,V,J] u8.  `present` is then a property of the
+// problem (frame, joint), folded from the joint's column of the mask;
 // everything a lane does with it is what it does with a frame's word.  A valid joint with fewer than two present views is
 // written like an invalid one, and frame_reduce_kernel runs over the USED joints (valid, two or more views) -- which are
 // the joints with joint_inliers > 0, a winning pair being part of its own inlier set.
@@ -354,162 +358,93 @@ __global__ void frame_reduce_kernel(const double* __restrict__ joint_err, const 
   inlier_count[b] = n ? mn : (MASK == MASK_VIEW_JOINT && any) ? -2 : -1;
 }
 
-// What the two entries share behind their argument checks: the grid of PG-lane groups, `launch(kp, grid, n_prob)` -- the
-// entry's kernel for the key-point type of `kp` --, its launch check, and frame_reduce_kernel with its check.
-template <typename Launch>
-static int launch_ransac(const char* name, const void* kp2d, int kp_is_f32, int PG, const uint8_t* valid,
-                         const double* joint_err, const int32_t* joint_inliers, double* metric, int32_t* inlier_count,
-                         int B, int J, hipStream_t s, Launch launch, const uint8_t* view_valid = nullptr, int V = 0,
-                         int mask = MASK_VIEWS) {
+// frame_reduce_kernel of the mask kind: the last launch of the triangulation entries and of mval_refine_points_3d
+static void launch_frame_reduce(const double* joint_err, const int32_t* joint_inliers, const uint8_t* valid,
+                                const uint8_t* mask, int mask_kind, double* metric, int32_t* inlier_count, int B, int V, int J,
+                                hipStream_t s) {
+  with_mask_kind(mask_kind, [&](auto K) {
+    hipLaunchKernelGGL(frame_reduce_kernel<decltype(K)::value>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers,
+                       valid, mask, metric, inlier_count, B, V, J);
+  });
+}
+
+// The four triangulation entries: `name` is the one that was called, `pairs` its table or nullptr for the lexicographic
+// kernel.  Argument checks, the grid of PG-lane groups, the entry's kernel for the mask kind and the key-point type, and
+// frame_reduce_kernel.
+static int triangulate(const char* name, const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                       const uint8_t* mask, int mask_kind, const uint8_t* pairs, int P, int pairs_shared, double* kp3d,
+                       double* joint_err, int32_t* joint_inliers, double* metric, int32_t* inlier_count, int B, int V, int J,
+                       double eps, void* stream) {
+  MVAL_REQUIRE(V >= 2, "%s: need >= 2 views in the rig (the reference asserts len(points) >= 2)", name);
+  if (pairs) {
+    MVAL_REQUIRE(V <= MVAL_PAIRS_MAX_VIEWS, "%s: at most %d views (the inlier mask is 32 bits wide)", name, MVAL_PAIRS_MAX_VIEWS);
+    MVAL_REQUIRE(P >= 1 && P <= MVAL_PAIRS_MAX_PAIRS, "%s: need a pair table of 1..%d pairs", name, MVAL_PAIRS_MAX_PAIRS);
+  } else {
+    MVAL_REQUIRE(V <= MAXV, "%s: V > 11 takes a pair table (the reference samples pairs from python's RNG there)", name);
+  }
+  MVAL_REQUIRE_MASK(name, mask, mask_kind);
+  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "%s: bad dims", name);
+  if (B == 0) return 0;
+  const int n_pairs = pairs ? P : V * (V - 1) / 2;
+  int PG = 1;  // lanes per problem: pow2 >= n_pairs, one wave beyond 64 pairs
+  while (PG < n_pairs && PG < 64) PG <<= 1;
+  const int64_t stride = pairs_shared ? 0 : (int64_t)P * 2;
   const int64_t n_prob = (int64_t)B * J;
   const int per_block = 64 / PG;
   const dim3 grid((unsigned)((n_prob + per_block - 1) / per_block));
-  if (kp_is_f32) launch((const float*)kp2d, grid, n_prob);
-  else launch((const int64_t*)kp2d, grid, n_prob);
+  const hipStream_t s = mval_stream(stream);
+  with_mask_kind(mask_kind, [&](auto K) {
+    constexpr int MASK = decltype(K)::value;
+    const auto launch = [&](auto* kp) {
+      if (pairs)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<MASK>), grid, dim3(64), 0, s, kp, proj, valid, mask, pairs, stride,
+                           kp3d, joint_err, joint_inliers, n_prob, V, J, P, PG, eps);
+      else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<MASK>), grid, dim3(64), 0, s, kp, proj, valid, mask, kp3d, joint_err,
+                           joint_inliers, n_prob, V, J, n_pairs, PG, eps);
+    };
+    if (kp_is_f32) launch((const float*)kp2d);
+    else launch((const int64_t*)kp2d);
+  });
   MVAL_CHECK_LAUNCH(name);
-  if (view_valid && mask == MASK_VIEW_JOINT)
-    hipLaunchKernelGGL(frame_reduce_kernel<MASK_VIEW_JOINT>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers,
-                       valid, view_valid, metric, inlier_count, B, V, J);
-  else if (view_valid)
-    hipLaunchKernelGGL(frame_reduce_kernel<MASK_VIEWS>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers, valid,
-                       view_valid, metric, inlier_count, B, V, J);
-  else
-    hipLaunchKernelGGL(frame_reduce_kernel<MASK_NONE>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err, joint_inliers, valid,
-                       view_valid, metric, inlier_count, B, V, J);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    mval_set_error("%s/reduce: launch failed: %s", name, hipGetErrorString(e));
-    return -2;
-  }
+  launch_frame_reduce(joint_err, joint_inliers, valid, mask, mask_kind, metric, inlier_count, B, V, J, s);
+  MVAL_CHECK_LAUNCH_STAGE(name, "/reduce");
   return 0;
 }
 
 extern "C" int mval_triangulate_ransac(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
                                        double* kp3d, double* joint_err, int32_t* joint_inliers, double* metric,
                                        int32_t* inlier_count, int B, int V, int J, double eps, void* stream) {
-  MVAL_REQUIRE(V >= 2, "mval_triangulate_ransac: need >= 2 views (reference asserts len(points) >= 2)");
-  MVAL_REQUIRE(V <= MAXV, "mval_triangulate_ransac: V > 11 makes the reference sample pairs from python's RNG (unsupported)");
-  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac: bad dims");
-  if (B == 0) return 0;
-  const int n_pairs = V * (V - 1) / 2;
-  int PG = 1;
-  while (PG < n_pairs) PG <<= 1;
-  const hipStream_t s = mval_stream(stream);
-  const uint8_t* const no_mask = nullptr;
-  return launch_ransac("mval_triangulate_ransac", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric, inlier_count,
-                       B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<MASK_NONE>), grid, dim3(64), 0, s, kp, proj, valid,
-                                            no_mask, kp3d, joint_err, joint_inliers, n_prob, V, J, n_pairs, PG, eps);
-                       });
+  return triangulate("mval_triangulate_ransac", kp2d, kp_is_f32, proj, valid, nullptr, MASK_NONE, nullptr, 0, 0, kp3d, joint_err,
+                     joint_inliers, metric, inlier_count, B, V, J, eps, stream);
 }
 
-extern "C" int mval_triangulate_ransac_views(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
-                                             const uint8_t* view_valid, double* kp3d, double* joint_err,
-                                             int32_t* joint_inliers, double* metric, int32_t* inlier_count, int B, int V,
-                                             int J, double eps, void* stream) {
-  MVAL_REQUIRE(V >= 2, "mval_triangulate_ransac_views: need >= 2 views in the rig (a frame may have fewer present)");
-  MVAL_REQUIRE(V <= MAXV, "mval_triangulate_ransac_views: V > 11 takes a pair table (mval_triangulate_ransac_pairs_views)");
-  MVAL_REQUIRE(view_valid, "mval_triangulate_ransac_views: view_valid is NULL (use mval_triangulate_ransac)");
-  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac_views: bad dims");
-  if (B == 0) return 0;
-  const int n_pairs = V * (V - 1) / 2;
-  int PG = 1;
-  while (PG < n_pairs) PG <<= 1;
-  const hipStream_t s = mval_stream(stream);
-  return launch_ransac("mval_triangulate_ransac_views", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
-                       inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<MASK_VIEWS>), grid, dim3(64), 0, s, kp, proj, valid,
-                                            view_valid, kp3d, joint_err, joint_inliers, n_prob, V, J, n_pairs, PG, eps);
-                       }, view_valid, V);
+extern "C" int mval_triangulate_ransac_masked(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                              const uint8_t* mask, int mask_kind, double* kp3d, double* joint_err,
+                                              int32_t* joint_inliers, double* metric, int32_t* inlier_count, int B, int V,
+                                              int J, double eps, void* stream) {
+  return triangulate("mval_triangulate_ransac_masked", kp2d, kp_is_f32, proj, valid, mask, mask_kind, nullptr, 0, 0, kp3d,
+                     joint_err, joint_inliers, metric, inlier_count, B, V, J, eps, stream);
 }
 
+// (a NULL table is the pairs entries' own fault: `triangulate` would take it for the lexicographic kernel)
 extern "C" int mval_triangulate_ransac_pairs(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
                                              const uint8_t* pairs, int P, int pairs_shared, double* kp3d,
                                              double* joint_err, int32_t* joint_inliers, double* metric,
                                              int32_t* inlier_count, int B, int V, int J, double eps, void* stream) {
-  MVAL_REQUIRE(V >= 2, "mval_triangulate_ransac_pairs: need >= 2 views (reference asserts len(points) >= 2)");
-  MVAL_REQUIRE(V <= MVAL_PAIRS_MAX_VIEWS, "mval_triangulate_ransac_pairs: at most %d views (the inlier mask is 32 bits wide)", MVAL_PAIRS_MAX_VIEWS);
-  MVAL_REQUIRE(pairs && P >= 1 && P <= MVAL_PAIRS_MAX_PAIRS, "mval_triangulate_ransac_pairs: need a pair table of 1..%d pairs", MVAL_PAIRS_MAX_PAIRS);
-  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac_pairs: bad dims");
-  if (B == 0) return 0;
-  int PG = 1;
-  while (PG < P && PG < 64) PG <<= 1;
-  const int64_t stride = pairs_shared ? 0 : (int64_t)P * 2;
-  const hipStream_t s = mval_stream(stream);
-  const uint8_t* const no_mask = nullptr;
-  return launch_ransac("mval_triangulate_ransac_pairs", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
-                       inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<MASK_NONE>), grid, dim3(64), 0, s, kp, proj,
-                                            valid, no_mask, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V, J, P,
-                                            PG, eps);
-                       });
+  MVAL_REQUIRE(pairs, "mval_triangulate_ransac_pairs: need a pair table (pairs is NULL)");
+  return triangulate("mval_triangulate_ransac_pairs", kp2d, kp_is_f32, proj, valid, nullptr, MASK_NONE, pairs, P, pairs_shared,
+                     kp3d, joint_err, joint_inliers, metric, inlier_count, B, V, J, eps, stream);
 }
 
-extern "C" int mval_triangulate_ransac_pairs_views(const void* kp2d, int kp_is_f32, const double* proj,
-                                                   const uint8_t* valid, const uint8_t* view_valid, const uint8_t* pairs,
-                                                   int P, int pairs_shared, double* kp3d, double* joint_err,
-                                                   int32_t* joint_inliers, double* metric, int32_t* inlier_count, int B,
-                                                   int V, int J, double eps, void* stream) {
-  MVAL_REQUIRE(V >= 2, "mval_triangulate_ransac_pairs_views: need >= 2 views in the rig (a frame may have fewer present)");
-  MVAL_REQUIRE(V <= MVAL_PAIRS_MAX_VIEWS, "mval_triangulate_ransac_pairs_views: at most %d views (the inlier mask is 32 bits wide)", MVAL_PAIRS_MAX_VIEWS);
-  MVAL_REQUIRE(view_valid, "mval_triangulate_ransac_pairs_views: view_valid is NULL (use mval_triangulate_ransac_pairs)");
-  MVAL_REQUIRE(pairs && P >= 1 && P <= MVAL_PAIRS_MAX_PAIRS, "mval_triangulate_ransac_pairs_views: need a pair table of 1..%d pairs", MVAL_PAIRS_MAX_PAIRS);
-  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac_pairs_views: bad dims");
-  if (B == 0) return 0;
-  int PG = 1;
-  while (PG < P && PG < 64) PG <<= 1;
-  const int64_t stride = pairs_shared ? 0 : (int64_t)P * 2;
-  const hipStream_t s = mval_stream(stream);
-  return launch_ransac("mval_triangulate_ransac_pairs_views", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
-                       inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<MASK_VIEWS>), grid, dim3(64), 0, s, kp, proj,
-                                            valid, view_valid, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V, J,
-                                            P, PG, eps);
-                       }, view_valid, V);
-}
-
-extern "C" int mval_triangulate_ransac_vj(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
-                                          const uint8_t* view_joint_valid, double* kp3d, double* joint_err,
-                                          int32_t* joint_inliers, double* metric, int32_t* inlier_count, int B, int V,
-                                          int J, double eps, void* stream) {
-  MVAL_REQUIRE(V >= 2, "mval_triangulate_ransac_vj: need >= 2 views in the rig (a joint may have fewer present)");
-  MVAL_REQUIRE(V <= MAXV, "mval_triangulate_ransac_vj: V > 11 takes a pair table (mval_triangulate_ransac_pairs_vj)");
-  MVAL_REQUIRE(view_joint_valid, "mval_triangulate_ransac_vj: view_joint_valid is NULL (use mval_triangulate_ransac)");
-  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac_vj: bad dims");
-  if (B == 0) return 0;
-  const int n_pairs = V * (V - 1) / 2;
-  int PG = 1;
-  while (PG < n_pairs) PG <<= 1;
-  const hipStream_t s = mval_stream(stream);
-  return launch_ransac("mval_triangulate_ransac_vj", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
-                       inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<MASK_VIEW_JOINT>), grid, dim3(64), 0, s, kp, proj,
-                                            valid, view_joint_valid, kp3d, joint_err, joint_inliers, n_prob, V, J, n_pairs, PG,
-                                            eps);
-                       }, view_joint_valid, V, MASK_VIEW_JOINT);
-}
-
-extern "C" int mval_triangulate_ransac_pairs_vj(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
-                                                const uint8_t* view_joint_valid, const uint8_t* pairs, int P,
-                                                int pairs_shared, double* kp3d, double* joint_err, int32_t* joint_inliers,
-                                                double* metric, int32_t* inlier_count, int B, int V, int J, double eps,
-                                                void* stream) {
-  MVAL_REQUIRE(V >= 2, "mval_triangulate_ransac_pairs_vj: need >= 2 views in the rig (a joint may have fewer present)");
-  MVAL_REQUIRE(V <= MVAL_PAIRS_MAX_VIEWS, "mval_triangulate_ransac_pairs_vj: at most %d views (the inlier mask is 32 bits wide)", MVAL_PAIRS_MAX_VIEWS);
-  MVAL_REQUIRE(view_joint_valid, "mval_triangulate_ransac_pairs_vj: view_joint_valid is NULL (use mval_triangulate_ransac_pairs)");
-  MVAL_REQUIRE(pairs && P >= 1 && P <= MVAL_PAIRS_MAX_PAIRS, "mval_triangulate_ransac_pairs_vj: need a pair table of 1..%d pairs", MVAL_PAIRS_MAX_PAIRS);
-  MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_triangulate_ransac_pairs_vj: bad dims");
-  if (B == 0) return 0;
-  int PG = 1;
-  while (PG < P && PG < 64) PG <<= 1;
-  const int64_t stride = pairs_shared ? 0 : (int64_t)P * 2;
-  const hipStream_t s = mval_stream(stream);
-  return launch_ransac("mval_triangulate_ransac_pairs_vj", kp2d, kp_is_f32, PG, valid, joint_err, joint_inliers, metric,
-                       inlier_count, B, J, s, [&](auto* kp, dim3 grid, int64_t n_prob) {
-                         hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<MASK_VIEW_JOINT>), grid, dim3(64), 0, s, kp, proj,
-                                            valid, view_joint_valid, pairs, stride, kp3d, joint_err, joint_inliers, n_prob, V,
-                                            J, P, PG, eps);
-                       }, view_joint_valid, V, MASK_VIEW_JOINT);
+extern "C" int mval_triangulate_ransac_pairs_masked(const void* kp2d, int kp_is_f32, const double* proj,
+                                                    const uint8_t* valid, const uint8_t* mask, int mask_kind,
+                                                    const uint8_t* pairs, int P, int pairs_shared, double* kp3d,
+                                                    double* joint_err, int32_t* joint_inliers, double* metric,
+                                                    int32_t* inlier_count, int B, int V, int J, double eps, void* stream) {
+  MVAL_REQUIRE(pairs, "mval_triangulate_ransac_pairs_masked: need a pair table (pairs is NULL)");
+  return triangulate("mval_triangulate_ransac_pairs_masked", kp2d, kp_is_f32, proj, valid, mask, mask_kind, pairs, P,
+                     pairs_shared, kp3d, joint_err, joint_inliers, metric, inlier_count, B, V, J, eps, stream);
 }
 
 // ---- 3-D refinement (not in the reference) ---------------------------------------------------------------
@@ -667,25 +602,6 @@ __global__ __launch_bounds__(64) void refine_points_3d_kernel(
   joint_status[pr] = status;
 }
 
-static_assert(MVAL_MASK_NONE == MASK_NONE && MVAL_MASK_VIEWS == MASK_VIEWS && MVAL_MASK_VIEW_JOINT == MASK_VIEW_JOINT,
-              "the mask kinds of the C-ABI are the kernels' template values");
-
-template <int MASK>
-static void launch_refine_3d(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid, const uint8_t* mask,
-                             const float* weights, const double* kp3d, const double* joint_err, double* kp3d_out,
-                             double* joint_err_out, int32_t* joint_support, int32_t* joint_status, int64_t n_prob, int V,
-                             int J, double eps, hipStream_t s) {
-  const dim3 grid((unsigned)((n_prob + 63) / 64));
-  if (kp_is_f32)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_points_3d_kernel<MASK, float>), grid, dim3(64), 0, s, (const float*)kp2d, proj,
-                       valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out, joint_support, joint_status, n_prob, V,
-                       J, eps);
-  else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_points_3d_kernel<MASK, int64_t>), grid, dim3(64), 0, s, (const int64_t*)kp2d,
-                       proj, valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out, joint_support, joint_status,
-                       n_prob, V, J, eps);
-}
-
 extern "C" int mval_refine_points_3d(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
                                      const uint8_t* mask, int mask_kind, const float* weights, const double* kp3d,
                                      const double* joint_err, const int32_t* joint_inliers, double* kp3d_out,
@@ -693,9 +609,7 @@ extern "C" int mval_refine_points_3d(const void* kp2d, int kp_is_f32, const doub
                                      int32_t* inlier_count, int B, int V, int J, double eps, void* stream) {
   MVAL_REQUIRE(V >= 2 && V <= MVAL_PAIRS_MAX_VIEWS, "mval_refine_points_3d: 2..%d views (the support set is 32 bits wide)", MVAL_PAIRS_MAX_VIEWS);
   MVAL_REQUIRE(J >= 1 && J <= 512 && B >= 0, "mval_refine_points_3d: bad dims");
-  MVAL_REQUIRE(mask_kind == MASK_NONE || mask_kind == MASK_VIEWS || mask_kind == MASK_VIEW_JOINT,
-               "mval_refine_points_3d: mask_kind %d (0 none, 1 view_valid [B,V], 2 view_joint_valid [B,V,J])", mask_kind);
-  MVAL_REQUIRE((mask_kind == MASK_NONE) == (mask == nullptr), "mval_refine_points_3d: a mask goes with mask_kind 1 or 2, NULL with 0");
+  MVAL_REQUIRE_MASK("mval_refine_points_3d", mask, mask_kind);
   if (B == 0) return 0;
   MVAL_REQUIRE(kp2d && proj && kp3d && joint_err && joint_inliers, "mval_refine_points_3d: an input is NULL");
   MVAL_REQUIRE(kp3d_out && joint_err_out && joint_support && joint_status && metric && inlier_count, "mval_refine_points_3d: an output is NULL");
@@ -706,26 +620,21 @@ extern "C" int mval_refine_points_3d(const void* kp2d, int kp_is_f32, const doub
                "mval_refine_points_3d: a 4-byte array is not aligned");
   const hipStream_t s = mval_stream(stream);
   const int64_t n_prob = (int64_t)B * J;
-  if (mask_kind == MASK_VIEW_JOINT)
-    launch_refine_3d<MASK_VIEW_JOINT>(kp2d, kp_is_f32, proj, valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out,
-                                      joint_support, joint_status, n_prob, V, J, eps, s);
-  else if (mask_kind == MASK_VIEWS)
-    launch_refine_3d<MASK_VIEWS>(kp2d, kp_is_f32, proj, valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out,
-                                 joint_support, joint_status, n_prob, V, J, eps, s);
-  else
-    launch_refine_3d<MASK_NONE>(kp2d, kp_is_f32, proj, valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out,
-                                joint_support, joint_status, n_prob, V, J, eps, s);
+  const dim3 grid((unsigned)((n_prob + 63) / 64));
+  with_mask_kind(mask_kind, [&](auto K) {
+    constexpr int MASK = decltype(K)::value;
+    if (kp_is_f32)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_points_3d_kernel<MASK, float>), grid, dim3(64), 0, s, (const float*)kp2d, proj,
+                         valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out, joint_support, joint_status, n_prob, V,
+                         J, eps);
+    else
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_points_3d_kernel<MASK, int64_t>), grid, dim3(64), 0, s, (const int64_t*)kp2d,
+                         proj, valid, mask, weights, kp3d, joint_err, kp3d_out, joint_err_out, joint_support, joint_status,
+                         n_prob, V, J, eps);
+  });
   MVAL_CHECK_LAUNCH("mval_refine_points_3d");
   // the frame's metric over the new joint errors; joint_inliers are RANSAC's, so inlier_count comes out as it was
-  if (mask_kind == MASK_VIEW_JOINT)
-    hipLaunchKernelGGL(frame_reduce_kernel<MASK_VIEW_JOINT>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err_out, joint_inliers,
-                       valid, mask, metric, inlier_count, B, V, J);
-  else if (mask_kind == MASK_VIEWS)
-    hipLaunchKernelGGL(frame_reduce_kernel<MASK_VIEWS>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err_out, joint_inliers, valid,
-                       mask, metric, inlier_count, B, V, J);
-  else
-    hipLaunchKernelGGL(frame_reduce_kernel<MASK_NONE>, dim3((B + 63) / 64), dim3(64), 0, s, joint_err_out, joint_inliers, valid,
-                       mask, metric, inlier_count, B, V, J);
+  launch_frame_reduce(joint_err_out, joint_inliers, valid, mask, mask_kind, metric, inlier_count, B, V, J, s);
   MVAL_CHECK_LAUNCH("mval_refine_points_3d/reduce");
   return 0;
 }
@@ -790,44 +699,33 @@ __global__ void xe_sum_kernel(const double* __restrict__ per_map, const uint8_t*
   out[b] = s;
 }
 
-template <int MASK>
-static int launch_xe(const char* name, const char* sum_name, const double* kp3d, const double* proj, const float* heatmaps,
-                     const uint8_t* view_valid, double* out, double* ws, int B, int V, int J, int hh, int wh, double sigma,
-                     void* stream) {
-  int64_t n_maps = (int64_t)B * V * J;
-  hipLaunchKernelGGL(xe_kernel<MASK>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, mval_stream(stream), kp3d, proj,
-                     heatmaps, view_valid, ws, n_maps, V, J, hh, wh, sigma);
-  MVAL_CHECK_LAUNCH(name);
-  hipLaunchKernelGGL(xe_sum_kernel<MASK>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), ws, view_valid, out, B, V,
-                     J);
-  MVAL_CHECK_LAUNCH(sum_name);
-  return 0;
+// The two XE entries: `name` is the one that was called.
+static int reprojection_xe(const char* name, const double* kp3d, const double* proj, const float* heatmaps, const uint8_t* mask,
+                           int mask_kind, double* out, double* ws, int B, int V, int J, int hh, int wh, double sigma,
+                           void* stream) {
+  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && sigma > 0, "%s: bad dims", name);
+  MVAL_REQUIRE_MASK(name, mask, mask_kind);
+  if (B == 0) return 0;
+  const int64_t n_maps = (int64_t)B * V * J;
+  return with_mask_kind(mask_kind, [&](auto K) {
+    constexpr int MASK = decltype(K)::value;
+    hipLaunchKernelGGL(xe_kernel<MASK>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, mval_stream(stream), kp3d, proj,
+                       heatmaps, mask, ws, n_maps, V, J, hh, wh, sigma);
+    MVAL_CHECK_LAUNCH(name);
+    hipLaunchKernelGGL(xe_sum_kernel<MASK>, dim3((B + 63) / 64), dim3(64), 0, mval_stream(stream), ws, mask, out, B, V, J);
+    MVAL_CHECK_LAUNCH_STAGE(name, "/sum");
+    return 0;
+  });
 }
 
 extern "C" int mval_reprojection_xe(const double* kp3d, const double* proj, const float* heatmaps, double* out,
                                     double* ws, int B, int V, int J, int hh, int wh, double sigma, void* stream) {
-  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && sigma > 0, "mval_reprojection_xe: bad dims");
-  if (B == 0) return 0;
-  return launch_xe<MASK_NONE>("mval_reprojection_xe", "mval_reprojection_xe/sum", kp3d, proj, heatmaps, nullptr, out, ws, B, V, J,
-                          hh, wh, sigma, stream);
+  return reprojection_xe("mval_reprojection_xe", kp3d, proj, heatmaps, nullptr, MASK_NONE, out, ws, B, V, J, hh, wh, sigma, stream);
 }
 
-extern "C" int mval_reprojection_xe_views(const double* kp3d, const double* proj, const float* heatmaps,
-                                          const uint8_t* view_valid, double* out, double* ws, int B, int V, int J, int hh,
-                                          int wh, double sigma, void* stream) {
-  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && sigma > 0, "mval_reprojection_xe_views: bad dims");
-  MVAL_REQUIRE(view_valid, "mval_reprojection_xe_views: view_valid is NULL (use mval_reprojection_xe)");
-  if (B == 0) return 0;
-  return launch_xe<MASK_VIEWS>("mval_reprojection_xe_views", "mval_reprojection_xe_views/sum", kp3d, proj, heatmaps, view_valid, out,
-                         ws, B, V, J, hh, wh, sigma, stream);
-}
-
-extern "C" int mval_reprojection_xe_vj(const double* kp3d, const double* proj, const float* heatmaps,
-                                       const uint8_t* view_joint_valid, double* out, double* ws, int B, int V, int J, int hh,
-                                       int wh, double sigma, void* stream) {
-  MVAL_REQUIRE(B >= 0 && V > 0 && J > 0 && hh > 0 && wh > 0 && sigma > 0, "mval_reprojection_xe_vj: bad dims");
-  MVAL_REQUIRE(view_joint_valid, "mval_reprojection_xe_vj: view_joint_valid is NULL (use mval_reprojection_xe)");
-  if (B == 0) return 0;
-  return launch_xe<MASK_VIEW_JOINT>("mval_reprojection_xe_vj", "mval_reprojection_xe_vj/sum", kp3d, proj, heatmaps,
-                                    view_joint_valid, out, ws, B, V, J, hh, wh, sigma, stream);
+extern "C" int mval_reprojection_xe_masked(const double* kp3d, const double* proj, const float* heatmaps, const uint8_t* mask,
+                                           int mask_kind, double* out, double* ws, int B, int V, int J, int hh, int wh,
+                                           double sigma, void* stream) {
+  return reprojection_xe("mval_reprojection_xe_masked", kp3d, proj, heatmaps, mask, mask_kind, out, ws, B, V, J, hh, wh, sigma,
+                         stream);
 }

@@ -45,14 +45,14 @@ def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_q
     """The heat-map scorer behind the three public functions below.  ``configs`` maps "HP" / "MPE" / "BSB" to "AVG" / "STD";
     heatmaps (B,V,J,Hh,Wh) f32 HIP, joint_valid (B,J).  ONE launch reads the heat-maps -- one kind without ``decode``:
     mval_score_maps; one kind with it: mval_score_decode_maps; several kinds: mval_score_decode_maps_all (csrc/scoring.hip builds
-    them from the same stages: a statistic has the same bits whichever computes it) --, then ``mval_score_reduce`` per kind.
+    them from the same stages: a statistic has the same bits whichever computes it) --, then ``mval_score_reduce_masked`` per kind.
     Returns an OrderedDict kind -> (out (B,) float64, per_map (B,V,J), n_peaks (B,V,J), valid, keypoints_2d or None).
     ``view_valid`` (B,V), nonzero = present: ``out`` is reduced over the present views of each frame alone
-    (``mval_score_reduce_views``).  The map launch is unchanged -- per_map, n_peaks and keypoints_2d still hold entries for
+    (MVAL_MASK_VIEWS).  The map launch is unchanged -- per_map, n_peaks and keypoints_2d still hold entries for
     the maps of absent views, which every consumer ignores.
     ``view_joint_valid`` (B,V,J), nonzero = the joint is usable in that view (ANDed with ``view_valid`` where both are given):
     ``out`` is the reference's list of per-map values with the absent entries deleted -- same order, same arithmetic, n the
-    entries left (``mval_score_reduce_vj``)."""
+    entries left (MVAL_MASK_VIEW_JOINT)."""
     modes = OrderedDict((kind, _reduce_mode(kind, configs[kind])) for kind in configs)
     for kind in modes:
         if kind not in _KIND:
@@ -61,17 +61,13 @@ def _score_heatmaps(configs, heatmaps, joint_valid, stride=0, mirror_nonsquare_q
     hm = heatmaps.to(torch.float32).contiguous()
     valid = (torch.as_tensor(joint_valid) != 0).to(torch.uint8).reshape(b, j).to(hm.device).contiguous()
     split_width = hh if mirror_nonsquare_quirk else wh
+    vv = vj = None  # the effective mask: one or none
+    if view_valid is not None:
+        vv = (torch.as_tensor(view_valid) != 0).to(torch.uint8).reshape(b, v).to(hm.device).contiguous()
     if view_joint_valid is not None:
         vj = (torch.as_tensor(view_joint_valid) != 0).to(torch.uint8).reshape(b, v, j).to(hm.device)
-        if view_valid is not None:
-            vj = vj & (torch.as_tensor(view_valid) != 0).to(torch.uint8).reshape(b, v, 1).to(hm.device)
-        vj = vj.contiguous()
-        reduce = lambda stat, mode: _lib.score_reduce_vj(stat, valid, vj, b, v, j, mode)  # noqa: E731
-    elif view_valid is None:
-        reduce = lambda stat, mode: _lib.score_reduce(stat, valid, b, v, j, mode)  # noqa: E731
-    else:
-        vv = (torch.as_tensor(view_valid) != 0).to(torch.uint8).reshape(b, v).to(hm.device).contiguous()
-        reduce = lambda stat, mode: _lib.score_reduce_views(stat, valid, vv, b, v, j, mode)  # noqa: E731
+        vj, vv = (vj if vv is None else vj & vv[:, :, None]).contiguous(), None
+    reduce = lambda stat, mode: _lib.score_reduce(stat, valid, b, v, j, mode, view_valid=vv, view_joint_valid=vj)  # noqa: E731
     if len(modes) == 1:
         (kind,) = modes
         if decode:

@@ -56,29 +56,9 @@ def _as_valid_u8(valid, shape, device):
 PAIR_PAD = 255  # a view index no rig has (at most 32 views): an entry naming it takes no part in the vote
 
 
-def _draw_view_pairs_masked(valid, V, n_iters, rng, view_valid):
-    b, j = valid.shape
-    present = [np.flatnonzero(view_valid[bi]) for bi in range(b)]
-    n_pairs = [len(p) * (len(p) - 1) // 2 for p in present]
-    out = np.full((b, j, max([1] + [min(n, n_iters) for n in n_pairs]), 2), PAIR_PAD, dtype=np.uint8)
-    for bi in range(b):
-        n = n_pairs[bi]
-        if n == 0:  # fewer than two present views: nothing to triangulate, nothing drawn
-            continue
-        lex = np.array(list(itertools.combinations(present[bi].tolist(), 2)), dtype=np.uint8).reshape(-1, 2)
-        if n <= n_iters:
-            out[bi, :, :n] = lex
-            continue
-        out[bi] = 0  # (a frame that draws fills all P = n_iters entries; the rows of its invalid joints stay zero)
-        for ji in np.flatnonzero(valid[bi]):
-            order = list(range(n))
-            rng.shuffle(order)
-            out[bi, ji] = lex[order[:n_iters]]
-    return out
-
-
 def _draw_view_pairs_vj(valid, V, n_iters, rng, vj):
-    """``vj`` (B, V, J) bool: the tables of ``_draw_view_pairs_masked`` with one present set per problem."""
+    """``vj`` (B, V, J) bool (a ``view_valid`` broadcast over the joints): the masked tables of ``draw_view_pairs``, one present
+    set per problem."""
     b, j = valid.shape
     n_present = vj.sum(axis=1)  # (B, J)
     n_pairs = n_present * (n_present - 1) // 2
@@ -129,15 +109,15 @@ def draw_view_pairs(valid, V, n_iters, rng, view_valid=None, view_joint_valid=No
     that order, leave it in.  P = max over problems of min(C(n_bj, 2), n_iters), at least 1; padding and invalid joints as
     above, so a mask that is the same for every joint of a frame gives the ``view_valid`` tables."""
     valid = torch.as_tensor(valid).cpu().numpy() != 0
-    if view_joint_valid is not None:
-        vj = torch.as_tensor(view_joint_valid).cpu().numpy().reshape(valid.shape[0], V, valid.shape[1]) != 0
-        if view_valid is not None:
-            vj = vj & (torch.as_tensor(view_valid).cpu().numpy().reshape(valid.shape[0], V, 1) != 0)
-        return _draw_view_pairs_vj(valid, V, n_iters, rng, vj)
-    if view_valid is not None:
-        vv = torch.as_tensor(view_valid).cpu().numpy().reshape(valid.shape[0], V) != 0
-        return _draw_view_pairs_masked(valid, V, n_iters, rng, vv)
     b, j = valid.shape
+    if view_valid is not None or view_joint_valid is not None:
+        vj = np.ones((b, V, j), dtype=bool)
+        if view_joint_valid is not None:
+            vj = torch.as_tensor(view_joint_valid).cpu().numpy().reshape(b, V, j) != 0
+        if view_valid is not None:
+            vj = vj & (torch.as_tensor(view_valid).cpu().numpy().reshape(b, V, 1) != 0)
+        return _draw_view_pairs_vj(valid, V, n_iters, rng, vj)
+    # (unmasked: what the masked body gives with an all-ones mask, without its B x J python loop on the sampled hot path)
     lex = np.array(list(itertools.combinations(range(V), 2)), dtype=np.uint8).reshape(-1, 2)
     n = len(lex)
     if n <= n_iters:
@@ -281,33 +261,27 @@ def triangulate_batch(
         if conf is not None:
             conf = torch.where(present[..., 0], conf, torch.zeros((), dtype=conf.dtype, device=dev))
     eps = float(reprojection_error_epsilon)
+    mask = dict(view_valid=None if per_joint else vv, view_joint_valid=vj if per_joint else None)  # the effective mask: one or none
     if sampled or (masked and v > 11):
         host_valid = valid_joints_host if valid_joints_host is not None else valid_joints
         host_valid = torch.ones((b, j)) if host_valid is None else torch.as_tensor(host_valid).reshape(b, j)
-    if per_joint and v <= 11:
-        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_vj(kp2d, proj, valid, vj, b, v, j, eps)
-    elif per_joint:
-        host_vj = torch.as_tensor(view_joint_valid_host if view_joint_valid_host is not None else view_joint_valid).reshape(b, v, j)
+    pairs = None  # up to 11 views: lane p takes lexicographic pair p and sits out if a view is absent, no host knowledge of a mask
+    if masked and v > 11:
+        host_mask = None  # the effective mask once more, on the host
         if view_valid is not None:
-            host_vv = view_valid_host if view_valid_host is not None else view_valid
-            host_vj = (host_vj.cpu() != 0) & (torch.as_tensor(host_vv).reshape(b, v, 1).cpu() != 0)
-        pairs = _masked_pair_tables(host_valid, host_vj, v, n_iters, pair_rng)
-        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs_vj(kp2d, proj, valid, vj, pairs.pin_memory().to(dev, non_blocking=True),
-                                                                         b, v, j, eps)
-    elif masked and v <= 11:  # lane p keeps its pair and sits out if a view is absent: no host knowledge of the mask
-        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_views(kp2d, proj, valid, vv, b, v, j, eps)
-    elif masked:
-        host_vv = view_valid_host if view_valid_host is not None else view_valid
-        pairs = _masked_pair_tables(host_valid, torch.as_tensor(host_vv).reshape(b, v), v, n_iters, pair_rng)
-        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs_views(kp2d, proj, valid, vv, pairs.pin_memory().to(dev, non_blocking=True),
-                                                                            b, v, j, eps)
+            host_mask = torch.as_tensor(view_valid_host if view_valid_host is not None else view_valid).reshape(b, v)
+        if per_joint:
+            host_vj = torch.as_tensor(view_joint_valid_host if view_joint_valid_host is not None else view_joint_valid).reshape(b, v, j)
+            host_mask = host_vj if host_mask is None else (host_vj.cpu() != 0) & (host_mask.reshape(b, v, 1).cpu() != 0)
+        pairs = _masked_pair_tables(host_valid, host_mask, v, n_iters, pair_rng).pin_memory().to(dev, non_blocking=True)
     elif sampled:
         pairs = torch.from_numpy(draw_view_pairs(host_valid, v, n_iters, pair_rng)).pin_memory().to(dev, non_blocking=True)
-        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs(kp2d, proj, valid, pairs, b, v, j, eps)
     elif v > 11:  # all pairs, more than the 64 the one-lane-per-pair entry holds
-        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs(kp2d, proj, valid, _lexicographic_pairs(v, dev), b, v, j, eps)
+        pairs = _lexicographic_pairs(v, dev)
+    if pairs is None:
+        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac(kp2d, proj, valid, b, v, j, eps, **mask)
     else:
-        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac(kp2d, proj, valid, b, v, j, eps)
+        kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs(kp2d, proj, valid, pairs, b, v, j, eps, **mask)
     refined = None
     if refine_3d != "none":
         weights = refine_3d_weights
@@ -320,14 +294,10 @@ def triangulate_batch(
             kp2d, proj, valid, kp3d, jerr, jinl, b, v, j, eps if refine_3d_epsilon is None else float(refine_3d_epsilon),
             view_valid=None if per_joint else vv, view_joint_valid=vj if per_joint else None, weights=weights)
         refined = {"keypoints_3d_dlt": kp3d_dlt, "joint_support": support, "joint_status": status}
-    if use_reprojection_xe and per_joint:
-        xe = _lib.reprojection_xe_vj(kp3d, proj, hm, vj, b, v, j, hh, wh, float(sigma))
-        metric = torch.where(inl == -2, metric, xe)  # (no used joint: NaN)
-    elif use_reprojection_xe and masked:
-        xe = _lib.reprojection_xe_views(kp3d, proj, hm, vv, b, v, j, hh, wh, float(sigma))
-        metric = torch.where(inl == -2, metric, xe)  # (fewer than two views: NaN, the reference never reaches _compute_xe)
-    elif use_reprojection_xe:
-        metric = _lib.reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, float(sigma))
+    if use_reprojection_xe:
+        xe = _lib.reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, float(sigma), **mask)
+        # (-2: fewer than two views / no used joint: NaN, the reference never reaches _compute_xe)
+        metric = torch.where(inl == -2, metric, xe) if masked else xe
     out = {
         "keypoints_3d": kp3d,
         "keypoints_2d": kp2d,

@@ -1,5 +1,5 @@
-"""GPU tests of per-(view, joint) visibility (``view_joint_valid``): the `_vj` triangulation entries, mval_score_reduce_vj,
-mval_reprojection_xe_vj, mval_peak_mask, and the calls that carry the mask (triangulate_batch, triangulation, the heat-map
+"""GPU tests of per-(view, joint) visibility (``view_joint_valid``, MVAL_MASK_VIEW_JOINT): the `_masked` triangulation entries,
+mval_score_reduce_masked, mval_reprojection_xe_masked, mval_peak_mask, and the calls that carry the mask (triangulate_batch, triangulation, the heat-map
 scorers, the scoring and evaluation passes, the two config fields).
 
 Two oracles.  (1) The real reference's ``_triangulate_ransac`` handed each joint's present views (tests/golden/
@@ -161,7 +161,7 @@ def test_broadcast_mask_equals_the_view_valid_call(dev, name):
 
 
 def test_all_ones_mask_equals_no_mask(dev):
-    """Check 3b.  Through mval_triangulate_ransac_vj (V = 4) and mval_triangulate_ransac_pairs_vj with drawn pairs (V = 12, 64
+    """Check 3b.  Through mval_triangulate_ransac_masked (V = 4) and mval_triangulate_ransac_pairs_masked with drawn pairs (V = 12, 64
     of 66) and with all pairs (V = 12, n_iters 128): bit for bit, key-points and RNG state included; the scorers and the XE
     metric likewise."""
     from multi_view_active_learning_amd.strategy import score_heatmaps_batch
@@ -227,10 +227,10 @@ def test_absent_entries_may_hold_nan(dev, name):
     pt = torch.from_numpy(proj).to(dev)
     vt, mt = torch.from_numpy(valid.astype(np.uint8)).to(dev), torch.from_numpy(mask.astype(np.uint8)).to(dev)
     if v <= 11:
-        call = lambda k: _lib.triangulate_ransac_vj(k, pt, vt, mt, b_, v, j, vjc.EPS)  # noqa: E731
+        call = lambda k: _lib.triangulate_ransac(k, pt, vt, b_, v, j, vjc.EPS, view_joint_valid=mt)  # noqa: E731
     else:
         pairs = torch.from_numpy(draw_view_pairs(valid, v, c["n_iters"], random.Random(1), view_joint_valid=mask)).to(dev)
-        call = lambda k: _lib.triangulate_ransac_pairs_vj(k, pt, vt, mt, pairs, b_, v, j, vjc.EPS)  # noqa: E731
+        call = lambda k: _lib.triangulate_ransac_pairs(k, pt, vt, pairs, b_, v, j, vjc.EPS, view_joint_valid=mt)  # noqa: E731
     clean, poisoned = call(kp), call(kp_bad.contiguous())
     for x, y in zip(clean, poisoned):
         assert _same_bits(x, y)
@@ -254,7 +254,7 @@ def test_score_reduce_vj_equals_score_reduce_on_the_compacted_list(dev):
     mask[3, 4, 18] = True  # (n = 1)
     vt, mt = torch.from_numpy(valid.astype(np.uint8)).to(dev), torch.from_numpy(mask.astype(np.uint8)).to(dev)
     for mode in (_lib.REDUCE_AVG_F64, _lib.REDUCE_AVG_F32, _lib.REDUCE_STD_F64, _lib.REDUCE_STD_F32):
-        got = _lib.score_reduce_vj(per_map.reshape(-1), vt, mt, b, v, j, mode)
+        got = _lib.score_reduce(per_map.reshape(-1), vt, b, v, j, mode, view_joint_valid=mt)
         for f in range(b):
             keep = torch.from_numpy(mask[f] & valid[f][None, :]).to(dev)
             vals = per_map[f][keep].contiguous()  # (row-major: views outer, joints inner)
@@ -282,7 +282,7 @@ def test_reprojection_xe_vj_equals_the_serial_sum_over_present_entries(dev):
     assert r["inlier_count"].tolist() == [2, -2, -1]
     t, pt, mt = torch.from_numpy(hm).to(dev), torch.from_numpy(proj).to(dev), torch.from_numpy(mask.astype(np.uint8)).to(dev)
     kp3d = plain["keypoints_3d"]
-    got = _lib.reprojection_xe_vj(kp3d, pt, t, mt, b, v, j, hh, wh, sigma).cpu().numpy()
+    got = _lib.reprojection_xe(kp3d, pt, t, b, v, j, hh, wh, sigma, view_joint_valid=mt).cpu().numpy()
     for f in range(b):
         s = 0.0
         for vi in range(v):
@@ -540,18 +540,20 @@ def test_entries_refuse_bad_arguments_and_launch_nothing(dev):
     gate = torch.full((b * v * j,), 7, dtype=torch.uint8, device=dev)
     P, N = _lib._p, _lib._p(None)
     outs = (P(k3), P(jerr), P(jinl), P(metric), P(cnt))
-    one, table = _lib._views_entry("mval_triangulate_ransac_vj"), _lib._views_entry("mval_triangulate_ransac_pairs_vj")
-    xe, red, peak = (_lib._views_entry(n) for n in ("mval_reprojection_xe_vj", "mval_score_reduce_vj", "mval_peak_mask"))
-    for v_, mask, word in ((33, P(mt), "32"), (1, P(mt), "2 views"), (12, N, "view_joint_valid is NULL")):
-        assert table(P(kp), 0, P(proj), N, mask, P(pairs), p, 0, *outs, b, v_, j, 5.0, _lib._stream()) != 0
+    K, NULL_MASK = _lib.MASK_VIEW_JOINT, "a mask goes with mask_kind 1 or 2, NULL with 0"
+    one, table = _lib._views_entry("mval_triangulate_ransac_masked"), _lib._views_entry("mval_triangulate_ransac_pairs_masked")
+    xe, red, peak = (_lib._views_entry(n) for n in ("mval_reprojection_xe_masked", "mval_score_reduce_masked", "mval_peak_mask"))
+    for v_, mask, word in ((33, P(mt), "32"), (1, P(mt), "2 views"), (12, N, NULL_MASK)):
+        assert table(P(kp), 0, P(proj), N, mask, K, P(pairs), p, 0, *outs, b, v_, j, 5.0, _lib._stream()) != 0
         assert word in _lib.lib().mval_last_error().decode(), (v_, word)
-    for v_, mask, word in ((33, P(mt), "V > 11"), (12, P(mt), "V > 11"), (1, P(mt), "2 views"), (4, N, "view_joint_valid is NULL")):
-        assert one(P(kp), 0, P(proj), N, mask, *outs, b, v_, j, 5.0, _lib._stream()) != 0
+    for v_, mask, word in ((33, P(mt), "V > 11"), (12, P(mt), "V > 11"), (1, P(mt), "2 views"), (4, N, NULL_MASK)):
+        assert one(P(kp), 0, P(proj), N, mask, K, *outs, b, v_, j, 5.0, _lib._stream()) != 0
         assert word in _lib.lib().mval_last_error().decode(), (v_, word)
-    assert xe(P(k3), P(proj), P(hm), N, P(metric), P(ws), b, 4, j, 8, 8, 1.0, _lib._stream()) != 0
-    assert "view_joint_valid is NULL" in _lib.lib().mval_last_error().decode()
-    assert red(P(per_map), N, N, P(metric), b, 4, j, 0, _lib._stream()) != 0
-    assert "view_joint_valid is NULL" in _lib.lib().mval_last_error().decode()
+    assert xe(P(k3), P(proj), P(hm), N, K, P(metric), P(ws), b, 4, j, 8, 8, 1.0, _lib._stream()) != 0
+    assert NULL_MASK in _lib.lib().mval_last_error().decode()
+    assert red(P(per_map), N, N, K, P(metric), b, 4, j, 0, _lib._stream()) != 0
+    assert NULL_MASK in _lib.lib().mval_last_error().decode()
+    # (a mask_kind outside 0..2, or MVAL_MASK_NONE beside a mask: test_gpu_view_mask.py, for every entry and kind)
     assert peak(N, 0.5, P(gate), 4, 8, 8, _lib._stream()) != 0 and "NULL" in _lib.lib().mval_last_error().decode()
     assert peak(P(hm), 0.5, P(gate), 4, 0, 8, _lib._stream()) != 0 and "bad dims" in _lib.lib().mval_last_error().decode()
     torch.cuda.synchronize()
@@ -559,6 +561,99 @@ def test_entries_refuse_bad_arguments_and_launch_nothing(dev):
         assert (t == -7).all().item()
     assert (gate == 7).all().item()
     with pytest.raises(_lib.MvalError, match="view_joint_valid"):
-        _lib.triangulate_ransac_vj(kp[:, :4].contiguous(), proj[:, :4].contiguous(), None, mt, b, 4, j, 5.0)  # (B, 33, J) mask
+        _lib.triangulate_ransac(kp[:, :4].contiguous(), proj[:, :4].contiguous(), None, b, 4, j, 5.0, view_joint_valid=mt)  # (B, 33, J) mask
     with pytest.raises(_lib.MvalError, match="32"):
-        _lib.triangulate_ransac_pairs_vj(kp, proj, None, mt, pairs, b, v, j, 5.0)
+        _lib.triangulate_ransac_pairs(kp, proj, None, pairs, b, v, j, 5.0, view_joint_valid=mt)
+
+
+# ---- one (mask, mask_kind) argument for every kind ---------------------------------------------------------------------------------
+def _raw_triangulation(dev, entry, kp, pt, vt, mask_args, pairs, b, v, j):
+    """One raw call of a triangulation entry (unmasked: converted by hand, it carries no argtypes; ``_masked``: through its
+    argtypes) into sentinel-filled outputs; ``mask_args``: () or (mask pointer, mask_kind)."""
+    import ctypes as C
+
+    from multi_view_active_learning_amd import _lib
+
+    outs = [torch.full((b, j, 3), -7.0, dtype=torch.float64, device=dev), torch.full((b, j), -7.0, dtype=torch.float64, device=dev),
+            torch.full((b, j), -7, dtype=torch.int32, device=dev), torch.full((b,), -7.0, dtype=torch.float64, device=dev),
+            torch.full((b,), -7, dtype=torch.int32, device=dev)]
+    table = () if pairs is None else (_lib._p(pairs), C.c_int(pairs.shape[-2]), C.c_int(0))
+    f = _lib._views_entry(entry) if mask_args else getattr(_lib.lib(), entry)
+    rc = f(_lib._p(kp), C.c_int(int(kp.dtype == torch.float32)), _lib._p(pt), _lib._p(vt), *mask_args, *table, *(_lib._p(o) for o in outs),
+           C.c_int(b), C.c_int(v), C.c_int(j), C.c_double(vm.EPS), _lib._stream())
+    assert rc == 0, _lib.lib().mval_last_error().decode()
+    return outs
+
+
+@pytest.mark.parametrize("kp_dtype", [torch.int64, torch.float32], ids=["int64", "float32"])
+@pytest.mark.parametrize("name", ["m4", "m12_mixed", "degenerate"])
+def test_mask_kinds_agree(dev, name, kp_dtype):
+    """The existing missing-view inputs at V = 4 (one lane per pair; B = 3, J = 19: 57 problems in 8-lane groups, so the last block
+    has dead groups) and V = 12 (table kernel, one wave per problem), both key-point dtypes.
+    (a) Every ``_masked`` entry with MVAL_MASK_NONE / NULL has the bits of its unmasked sibling -- raw calls, the python wrappers
+    reach the ``_masked`` entries only.
+    (b) MVAL_MASK_VIEWS with view_valid has the bits of MVAL_MASK_VIEW_JOINT with view_valid broadcast over the joints --
+    triangulation, XE, score reduction in all four modes -- on every frame whose valid joints are all used.  On a frame with
+    fewer than two present views (case ``degenerate``) both write what the header documents: inlier_count -2 with a valid joint,
+    -1 without, metric NaN, no used joint (joint_inliers 0)."""
+    import ctypes as C
+
+    from multi_view_active_learning_amd import _lib
+    from multi_view_active_learning_amd.utils.triangulation import draw_view_pairs
+
+    c = vm.view_mask_cases()[name]
+    hm, proj, valid, vv = vm.build(c)
+    b, v, j, hh, wh = hm.shape
+    t, pt = torch.from_numpy(hm).to(dev), torch.from_numpy(proj).to(dev)
+    vt, vvt = torch.from_numpy(valid.astype(np.uint8)).to(dev), torch.from_numpy(vv.astype(np.uint8)).to(dev)
+    wide = vvt[:, :, None].expand(b, v, j).contiguous()
+    kp = _lib.argmax_decode(t, vt, b, v, j, hh, wh, c["stride"], hh).to(kp_dtype)
+    none = (_lib._p(None), _lib.MASK_NONE)
+    per_map = torch.from_numpy(np.random.default_rng(5).standard_normal(b * v * j).astype(np.float32)).to(dev)
+    sigma = 1.5
+
+    # (a) MVAL_MASK_NONE == the unmasked entry
+    drawn = torch.from_numpy(draw_view_pairs(valid, v, c["n_iters"], random.Random(1))).to(dev)  # (V = 12: 64 of 66 drawn per joint)
+    todo = [("mval_triangulate_ransac_pairs", drawn)] + ([("mval_triangulate_ransac", None)] if v <= 11 else [])
+    for entry, pairs in todo:
+        want = _raw_triangulation(dev, entry, kp, pt, vt, (), pairs, b, v, j)
+        got = _raw_triangulation(dev, entry + "_masked", kp, pt, vt, none, pairs, b, v, j)
+        for w, g in zip(want, got):
+            assert _same_bits(w, g), entry
+    kp3d = want[0]
+    xe = [torch.full((b,), -7.0, dtype=torch.float64, device=dev) for _ in range(2)]
+    ws = torch.empty((b * v * j,), dtype=torch.float64, device=dev)
+    assert _lib.lib().mval_reprojection_xe(_lib._p(kp3d), _lib._p(pt), _lib._p(t), _lib._p(xe[0]), _lib._p(ws), C.c_int(b), C.c_int(v), C.c_int(j),
+                                           C.c_int(hh), C.c_int(wh), C.c_double(sigma), _lib._stream()) == 0
+    assert _lib._views_entry("mval_reprojection_xe_masked")(_lib._p(kp3d), _lib._p(pt), _lib._p(t), *none, _lib._p(xe[1]), _lib._p(ws), b, v, j, hh, wh,
+                                                            sigma, _lib._stream()) == 0
+    assert _same_bits(xe[0], xe[1]) and not (xe[0] == -7).any().item()
+    for mode in (_lib.REDUCE_AVG_F64, _lib.REDUCE_AVG_F32, _lib.REDUCE_STD_F64, _lib.REDUCE_STD_F32):
+        red = [torch.full((b,), -7.0, dtype=torch.float64, device=dev) for _ in range(2)]
+        assert _lib.lib().mval_score_reduce(_lib._p(per_map), _lib._p(vt), _lib._p(red[0]), C.c_int(b), C.c_int(v), C.c_int(j), C.c_int(mode),
+                                            _lib._stream()) == 0
+        assert _lib._views_entry("mval_score_reduce_masked")(_lib._p(per_map), _lib._p(vt), *none, _lib._p(red[1]), b, v, j, mode, _lib._stream()) == 0
+        assert _same_bits(red[0], red[1]) and not (red[0] == -7).any().item(), mode
+
+    # (b) MVAL_MASK_VIEWS == MVAL_MASK_VIEW_JOINT with the mask broadcast over the joints
+    full = torch.from_numpy(vv.sum(axis=1) >= 2).to(dev)  # the frames whose valid joints are all used
+    by_frame, by_entry = dict(view_valid=vvt), dict(view_joint_valid=wide)
+    if v <= 11:
+        tri = [_lib.triangulate_ransac(kp, pt, vt, b, v, j, vm.EPS, **kw) for kw in (by_frame, by_entry)]
+    else:
+        tabs = [torch.from_numpy(draw_view_pairs(valid, v, c["n_iters"], random.Random(2), **kw)).to(dev)
+                for kw in (dict(view_valid=vv), dict(view_joint_valid=wide.cpu().numpy()))]
+        assert torch.equal(tabs[0], tabs[1])
+        tri = [_lib.triangulate_ransac_pairs(kp, pt, vt, tabs[0], b, v, j, vm.EPS, **kw) for kw in (by_frame, by_entry)]
+    for x, y in zip(*tri):
+        assert _same_bits(x[full], y[full])
+    any_valid = torch.from_numpy(valid.any(axis=1)).to(dev)
+    for kp3d_, jerr, jinl, metric, inl in tri:
+        assert not (jinl[~full] > 0).any().item() and torch.isnan(metric[~full]).all().item()  # no used joint
+        assert torch.equal(inl[~full], torch.where(any_valid[~full], -2, -1).to(torch.int32))
+    assert name != "degenerate" or (~full).sum().item() == 3
+    xes = [_lib.reprojection_xe(tri[0][0], pt, t, b, v, j, hh, wh, sigma, **kw) for kw in (by_frame, by_entry)]
+    assert _same_bits(xes[0][full], xes[1][full])
+    for mode in (_lib.REDUCE_AVG_F64, _lib.REDUCE_AVG_F32, _lib.REDUCE_STD_F64, _lib.REDUCE_STD_F32):
+        reds = [_lib.score_reduce(per_map, vt, b, v, j, mode, **kw) for kw in (by_frame, by_entry)]
+        assert _same_bits(reds[0][full], reds[1][full]), mode

@@ -1,5 +1,5 @@
-"""GPU tests of frames with missing views (``view_valid``): the masked triangulation entries, mval_score_reduce_views and
-mval_reprojection_xe_views, and the calls that carry the mask (triangulate_batch, the heat-map scorers, the scoring and
+"""GPU tests of frames with missing views (``view_valid``, MVAL_MASK_VIEWS): the `_masked` triangulation entries,
+mval_score_reduce_masked and mval_reprojection_xe_masked, and the calls that carry the mask (triangulate_batch, the heat-map scorers, the scoring and
 evaluation passes).
 
 Two oracles.  (1) The real reference handed each frame's present views alone (tests/golden/view_mask.npz and
@@ -178,7 +178,7 @@ def test_scores_equal_the_unmasked_scorer_on_each_frames_present_views(dev, name
 
 @pytest.mark.parametrize("name", list(vm.view_mask_cases()))
 def test_masked_hp_vs_reference_golden(dev, name):
-    """mval_score_reduce_views against the reference's _compute_hp on the sliced heat-maps, AVG and STD (tolerance of
+    """mval_score_reduce_masked (MVAL_MASK_VIEWS) against the reference's _compute_hp on the sliced heat-maps, AVG and STD (tolerance of
     test_scoring_vs_reference_golden)."""
     from multi_view_active_learning_amd.strategy import score_heatmaps_batch
 
@@ -252,7 +252,7 @@ def test_all_ones_mask_equals_no_mask(dev):
 
 @pytest.mark.parametrize("name", ["m4", "m11"])
 def test_masked_all_pairs_entry_equals_the_masked_table_entry(dev, name):
-    """V <= 11: mval_triangulate_ransac_views against mval_triangulate_ransac_pairs_views with one shared lexicographic
+    """V <= 11, MVAL_MASK_VIEWS: mval_triangulate_ransac_masked against mval_triangulate_ransac_pairs_masked with one shared lexicographic
     table of ALL C(V,2) pairs (the entries naming an absent view sit out) and against the padded per-problem tables of
     draw_view_pairs: bit for bit."""
     from multi_view_active_learning_amd import _lib
@@ -265,9 +265,9 @@ def test_masked_all_pairs_entry_equals_the_masked_table_entry(dev, name):
     kp, pt = torch.from_numpy(z["keypoints_2d"]).to(dev), torch.from_numpy(proj).to(dev)
     vt, vvt = torch.from_numpy(valid.astype(np.uint8)).to(dev), torch.from_numpy(vv.astype(np.uint8)).to(dev)
     lex = np.array([(a, k) for a in range(v) for k in range(a + 1, v)], np.uint8)
-    want = _lib.triangulate_ransac_views(kp, pt, vt, vvt, b, v, j, vm.EPS)
-    shared = _lib.triangulate_ransac_pairs_views(kp, pt, vt, vvt, torch.from_numpy(lex[None]).to(dev), b, v, j, vm.EPS)
-    own = _lib.triangulate_ransac_pairs_views(kp, pt, vt, vvt, torch.from_numpy(draw_view_pairs(valid, v, 64, None, vv)).to(dev), b, v, j, vm.EPS)
+    want = _lib.triangulate_ransac(kp, pt, vt, b, v, j, vm.EPS, view_valid=vvt)
+    shared = _lib.triangulate_ransac_pairs(kp, pt, vt, torch.from_numpy(lex[None]).to(dev), b, v, j, vm.EPS, view_valid=vvt)
+    own = _lib.triangulate_ransac_pairs(kp, pt, vt, torch.from_numpy(draw_view_pairs(valid, v, 64, None, vv)).to(dev), b, v, j, vm.EPS, view_valid=vvt)
     np.testing.assert_array_equal(want[2].cpu().numpy(), z["joint_inliers"])
     for w, s, o in zip(want, shared, own):
         assert _same_bits(w, s) and _same_bits(w, o)
@@ -438,8 +438,8 @@ def test_draw_reads_the_host_masks_of_a_staged_batch(dev):
 
 
 def test_entries_refuse_bad_arguments_and_launch_nothing(dev):
-    """V > 32 (V > 11 for the all-pairs entry), V < 2 and a NULL mask: the documented error, a message, and output buffers
-    that keep their sentinel values.  The wrappers raise; triangulate_batch names the limit."""
+    """V > 32 (V > 11 for the all-pairs entry), V < 2, a NULL mask and a mask_kind that is none or does not go with the mask
+    pointer: the documented error, a message, and output buffers that keep their sentinel values.  The wrappers raise; triangulate_batch names the limit."""
     from multi_view_active_learning_amd import _lib
     from multi_view_active_learning_amd.utils.triangulation import triangulate_batch
 
@@ -459,25 +459,36 @@ def test_entries_refuse_bad_arguments_and_launch_nothing(dev):
     ws = torch.full((b * v * j,), -7.0, dtype=torch.float64, device=dev)
     P, N = _lib._p, _lib._p(None)
     outs = (P(k3), P(jerr), P(jinl), P(metric), P(cnt))
-    views, table = _lib._views_entry("mval_triangulate_ransac_views"), _lib._views_entry("mval_triangulate_ransac_pairs_views")
-    xe, red = _lib._views_entry("mval_reprojection_xe_views"), _lib._views_entry("mval_score_reduce_views")
-    for vv_, mask, word in ((33, P(vvt), "32"), (1, P(vvt), "2 views"), (12, N, "view_valid is NULL")):
-        assert table(P(kp), 0, P(proj), N, mask, P(pairs), p, 0, *outs, b, vv_, j, 5.0, _lib._stream()) != 0
+    K, NULL_MASK = _lib.MASK_VIEWS, "a mask goes with mask_kind 1 or 2, NULL with 0"
+    views, table = _lib._views_entry("mval_triangulate_ransac_masked"), _lib._views_entry("mval_triangulate_ransac_pairs_masked")
+    xe, red = _lib._views_entry("mval_reprojection_xe_masked"), _lib._views_entry("mval_score_reduce_masked")
+    for vv_, mask, word in ((33, P(vvt), "32"), (1, P(vvt), "2 views"), (12, N, NULL_MASK)):
+        assert table(P(kp), 0, P(proj), N, mask, K, P(pairs), p, 0, *outs, b, vv_, j, 5.0, _lib._stream()) != 0
         assert word in _lib.lib().mval_last_error().decode(), (vv_, word)
-    for vv_, mask, word in ((33, P(vvt), "V > 11"), (12, P(vvt), "V > 11"), (1, P(vvt), "2 views"), (4, N, "view_valid is NULL")):
-        assert views(P(kp), 0, P(proj), N, mask, *outs, b, vv_, j, 5.0, _lib._stream()) != 0
+    for vv_, mask, word in ((33, P(vvt), "V > 11"), (12, P(vvt), "V > 11"), (1, P(vvt), "2 views"), (4, N, NULL_MASK)):
+        assert views(P(kp), 0, P(proj), N, mask, K, *outs, b, vv_, j, 5.0, _lib._stream()) != 0
         assert word in _lib.lib().mval_last_error().decode(), (vv_, word)
-    assert xe(P(k3), P(proj), P(hm), N, P(metric), P(ws), b, 4, j, 8, 8, 1.0, _lib._stream()) != 0
-    assert "view_valid is NULL" in _lib.lib().mval_last_error().decode()
-    assert red(P(per_map), N, N, P(metric), b, 4, j, 0, _lib._stream()) != 0
-    assert "view_valid is NULL" in _lib.lib().mval_last_error().decode()
+    assert xe(P(k3), P(proj), P(hm), N, K, P(metric), P(ws), b, 4, j, 8, 8, 1.0, _lib._stream()) != 0
+    assert NULL_MASK in _lib.lib().mval_last_error().decode()
+    assert red(P(per_map), N, N, K, P(metric), b, 4, j, 0, _lib._stream()) != 0
+    assert NULL_MASK in _lib.lib().mval_last_error().decode()
+    # the mask_kind contract of every `_masked` entry: a kind outside 0..2, MVAL_MASK_NONE with a mask, a mask kind with NULL
+    for mask, kind, word in ((P(vvt), 3, "mask_kind 3"), (P(vvt), _lib.MASK_NONE, NULL_MASK), (N, _lib.MASK_VIEWS, NULL_MASK),
+                             (N, _lib.MASK_VIEW_JOINT, NULL_MASK)):
+        for name, call in (("mval_triangulate_ransac_masked", lambda: views(P(kp), 0, P(proj), N, mask, kind, *outs, b, 4, j, 5.0, _lib._stream())),
+                           ("mval_triangulate_ransac_pairs_masked", lambda: table(P(kp), 0, P(proj), N, mask, kind, P(pairs), p, 0, *outs, b, 12, j, 5.0, _lib._stream())),
+                           ("mval_reprojection_xe_masked", lambda: xe(P(k3), P(proj), P(hm), mask, kind, P(metric), P(ws), b, 4, j, 8, 8, 1.0, _lib._stream())),
+                           ("mval_score_reduce_masked", lambda: red(P(per_map), N, mask, kind, P(metric), b, 4, j, 0, _lib._stream()))):
+            assert call() != 0, (name, kind)
+            msg = _lib.lib().mval_last_error().decode()
+            assert name in msg and word in msg, (name, kind, msg)
     torch.cuda.synchronize()
     for t in (k3, jerr, jinl, metric, cnt, ws):
         assert (t == -7).all().item()
     with pytest.raises(_lib.MvalError, match="32"):
-        _lib.triangulate_ransac_pairs_views(kp, proj, None, vvt, pairs, b, v, j, 5.0)
+        _lib.triangulate_ransac_pairs(kp, proj, None, pairs, b, v, j, 5.0, view_valid=vvt)
     with pytest.raises(_lib.MvalError, match="view_valid"):
-        _lib.triangulate_ransac_views(kp[:, :4].contiguous(), proj[:, :4].contiguous(), None, vvt, b, 4, j, 5.0)  # (B, 33) mask
+        _lib.triangulate_ransac(kp[:, :4].contiguous(), proj[:, :4].contiguous(), None, b, 4, j, 5.0, view_valid=vvt)  # (B, 33) mask
     for rng in (None, random):
         with pytest.raises(NotImplementedError, match="32"):
             triangulate_batch(torch.zeros((b, v, j, 8, 8), device=dev), proj, 4, torch.ones((b, j)), pair_rng=rng, view_valid=vvt)

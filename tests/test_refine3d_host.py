@@ -209,20 +209,14 @@ def _fake_post_stage(monkeypatch, calls):
         calls.append(("refine_keypoints", method))
         return torch.zeros((b, v, j, 2), dtype=torch.float32), torch.full((b, v, j), 0.5, dtype=torch.float32)
 
-    def triangulate_ransac(kp2d, proj, valid, b, v, j, eps):
-        calls.append(("triangulate_ransac", eps))
+    def which(view_valid, view_joint_valid):  # the mask a call got, as the tail of its record
+        return () if view_valid is None and view_joint_valid is None else ("views",) if view_joint_valid is None else ("view_joint",)
+
+    def triangulate_ransac(kp2d, proj, valid, b, v, j, eps, *, view_valid=None, view_joint_valid=None):
+        assert view_valid is None or view_joint_valid is None
+        calls.append(("triangulate_ransac", eps) + which(view_valid, view_joint_valid))
         return (torch.zeros((b, j, 3), dtype=torch.float64), torch.zeros((b, j), dtype=torch.float64), torch.full((b, j), 2, dtype=torch.int32),
                 torch.zeros((b,), dtype=torch.float64), torch.full((b,), 2, dtype=torch.int32))
-
-    def triangulate_ransac_views(kp2d, proj, valid, view_valid, b, v, j, eps):
-        out = triangulate_ransac(kp2d, proj, valid, b, v, j, eps)
-        calls[-1] = ("triangulate_ransac_views", eps)
-        return out
-
-    def triangulate_ransac_vj(kp2d, proj, valid, view_joint_valid, b, v, j, eps):
-        out = triangulate_ransac(kp2d, proj, valid, b, v, j, eps)
-        calls[-1] = ("triangulate_ransac_vj", eps)
-        return out
 
     def refine_points_3d(kp2d, proj, valid, kp3d, joint_err, joint_inliers, b, v, j, eps, view_valid=None, view_joint_valid=None, weights=None):
         calls.append(("refine_points_3d", eps, kp2d.dtype, "vv" if view_valid is not None else "vj" if view_joint_valid is not None else None,
@@ -230,11 +224,11 @@ def _fake_post_stage(monkeypatch, calls):
         return (torch.ones((b, j, 3), dtype=torch.float64), torch.ones((b, j), dtype=torch.float64), torch.full((b, j), v, dtype=torch.int32),
                 torch.full((b, j), 5, dtype=torch.int32), torch.ones((b,), dtype=torch.float64))
 
-    def reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, sigma):
-        calls.append(("reprojection_xe", float(kp3d.flatten()[0])))
+    def reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, sigma, *, view_valid=None, view_joint_valid=None):
+        calls.append(("reprojection_xe", float(kp3d.flatten()[0])) + which(view_valid, view_joint_valid))
         return torch.full((b,), 7.0, dtype=torch.float64)
 
-    for f in (argmax_decode, refine_keypoints, triangulate_ransac, triangulate_ransac_views, triangulate_ransac_vj, refine_points_3d, reprojection_xe):
+    for f in (argmax_decode, refine_keypoints, triangulate_ransac, refine_points_3d, reprojection_xe):
         monkeypatch.setattr(_lib, f.__name__, f)
 
 
@@ -269,8 +263,8 @@ def test_triangulate_batch_reaches_the_refinement_only_when_asked(monkeypatch):
     triangulation.triangulate_batch(hm, proj, 4, valid, refine_3d="lm", view_valid=torch.tensor([[1, 1, 0], [1, 1, 1]]))
     triangulation.triangulate_batch(hm, proj, 4, valid, refine_3d="lm", view_joint_valid=torch.ones(2, 3, 5), view_valid=torch.ones(2, 3),
                                     refine_3d_weights=torch.full((2, 3, 5), 2.0, dtype=torch.float64))
-    assert calls == [("argmax_decode",), ("triangulate_ransac_views", 5.0), ("refine_points_3d", 5.0, torch.int64, "vv", None),
-                     ("argmax_decode",), ("triangulate_ransac_vj", 5.0), ("refine_points_3d", 5.0, torch.int64, "vj", (torch.float32, (2, 3, 5), 2.0))]
+    assert calls == [("argmax_decode",), ("triangulate_ransac", 5.0, "views"), ("refine_points_3d", 5.0, torch.int64, "vv", None),
+                     ("argmax_decode",), ("triangulate_ransac", 5.0, "view_joint"), ("refine_points_3d", 5.0, torch.int64, "vj", (torch.float32, (2, 3, 5), 2.0))]
     del calls[:]
     r = triangulation.triangulate_batch(hm, proj, 4, valid, refine="taylor", refine_3d="lm", refine_3d_weights="conf")
     assert calls == [("argmax_decode",), ("refine_keypoints", "taylor"), ("triangulate_ransac", 5.0),

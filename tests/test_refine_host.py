@@ -181,21 +181,15 @@ def _fake_post_stage(monkeypatch, calls):
         calls.append(("refine_keypoints", method, kp2d.dtype))
         return torch.zeros((b, v, j, 2), dtype=torch.float32), torch.ones((b, v, j), dtype=torch.float32)
 
-    def triangulate_ransac(kp2d, proj, valid, b, v, j, eps):
-        calls.append(("triangulate_ransac", kp2d.dtype))
+    def triangulate_ransac(kp2d, proj, valid, b, v, j, eps, *, view_valid=None, view_joint_valid=None):
+        mask = () if view_valid is None and view_joint_valid is None else ("views",) if view_joint_valid is None else ("view_joint",)
+        calls.append(("triangulate_ransac", kp2d.dtype) + mask)
         return (torch.zeros((b, j, 3), dtype=torch.float64), torch.zeros((b, j), dtype=torch.float64), torch.zeros((b, j), dtype=torch.int32),
                 torch.zeros((b,), dtype=torch.float64), torch.zeros((b,), dtype=torch.int32))
 
     monkeypatch.setattr(_lib, "argmax_decode", argmax_decode)
     monkeypatch.setattr(_lib, "refine_keypoints", refine_keypoints)
     monkeypatch.setattr(_lib, "triangulate_ransac", triangulate_ransac)
-
-    def triangulate_ransac_views(kp2d, proj, valid, view_valid, b, v, j, eps):
-        out = triangulate_ransac(kp2d, proj, valid, b, v, j, eps)
-        calls[-1] = ("triangulate_ransac_views", kp2d.dtype)
-        return out
-
-    monkeypatch.setattr(_lib, "triangulate_ransac_views", triangulate_ransac_views)
     monkeypatch.setattr(_lib, "soft_argmax", lambda hm, n, hh, wh, scale: calls.append(("soft_argmax",)) or torch.zeros((n, 2)))
 
 
@@ -223,7 +217,7 @@ def test_triangulate_batch_reaches_the_refinement_only_when_asked(monkeypatch):
         del calls[:]
         r = triangulation.triangulate_batch(hm, proj, 4, valid, keypoints_2d=torch.zeros(2, 3, 5, 2, dtype=torch.int64), refine=method,
                                             view_valid=torch.tensor([[1, 1, 0], [1, 1, 1]]))
-        assert calls == [("refine_keypoints", method, torch.int64), ("triangulate_ransac_views", torch.float32)]
+        assert calls == [("refine_keypoints", method, torch.int64), ("triangulate_ransac", torch.float32, "views")]
         assert not r["keypoints_conf"][0, 2].any() and r["keypoints_conf"][0, :2].all() and r["keypoints_conf"][1].all()
 
 

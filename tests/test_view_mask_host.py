@@ -18,8 +18,8 @@ import view_mask_cases as vm
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(os.path.dirname(__file__), "golden")
 NPZ = os.path.join(G, "view_mask.npz")
-NEW_ENTRIES = ("mval_triangulate_ransac_views", "mval_triangulate_ransac_pairs_views", "mval_reprojection_xe_views",
-               "mval_score_reduce_views")
+NEW_ENTRIES = ("mval_triangulate_ransac_masked", "mval_triangulate_ransac_pairs_masked", "mval_reprojection_xe_masked",
+               "mval_score_reduce_masked", "mval_peak_mask")
 
 
 def _valid(c):

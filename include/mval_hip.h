@@ -134,8 +134,8 @@ int mval_triangulate_ransac_pairs(const void* kp2d, int kp_is_f32, const double*
 int mval_reprojection_xe(const double* kp3d, const double* proj, const float* heatmaps, double* out, double* ws,
                          int B, int V, int J, int hh, int wh, double sigma, void* stream);
 
-/* Presence masks.  The four `_masked` entries below -- and mval_refine_points_3d -- take `const uint8_t* mask, int mask_kind`
- * and compute what their unmasked sibling computes on the views that are present.  mask_kind must be one of the three values
+/* Presence masks.  The four `_masked` entries below -- and mval_refine_points_3d and mval_undistort_keypoints -- take
+ * `const uint8_t* mask, int mask_kind` and compute what their unmasked sibling computes on the views that are present.  mask_kind must be one of the three values
  * and (mask_kind == MVAL_MASK_NONE) == (mask == NULL); anything else is an error and nothing is launched.
  *
  * MVAL_MASK_NONE: no mask.  The entry runs what its unmasked sibling runs (which forwards here), bit for bit.
@@ -215,6 +215,47 @@ int mval_refine_points_3d(const void* kp2d, int kp_is_f32, const double* proj, c
                           const int32_t* joint_inliers, double* kp3d_out, double* joint_err_out, int32_t* joint_support,
                           int32_t* joint_status, double* metric, int32_t* inlier_count, int B, int V, int J, double eps,
                           void* stream);
+
+/* Undistortion of the decoded key-points (not in the reference, whose post stage takes the distorted peaks for pinhole
+ * observations; DESIGN.md 6.6 holds the definition).  One launch between the decode (with its refinement) and a triangulation
+ * entry: the inverse of the reference's forward model (utils/triangulation.py:433-456), per entry (frame, view, joint) in float64
+ *   d(x, y) = (xd, yd):  xd = x q + 2 p1 x y + p2 (r + 2 x^2),  yd = y q + 2 p2 xd y + p1 (r + 2 y^2),
+ *             r = x^2 + y^2,  q = 1 + k1 r + k2 r^2 + k3 r^3
+ *     (yd's cross term holds xd, not x: the reference overwrites x with its distorted value before it forms y, :444-453, and the
+ *      training targets sit where THAT model puts them; for p2 = 0 it is the Brown-Conrady polynomial of cv2.projectPoints),
+ *   pixel = K2 d(x, y) + c  with K2 = [K00 K01; K10 K11], c = (K02, K12): the six numbers of K the forward model reads.
+ *   kp2d [B,V,J,2] i64 | f32 (kp_is_f32), pixels (x, y) ; K [B,V,3,3] f64, the view's intrinsics after crop and resize ;
+ *   dist [B,V,5] f64 = k1, k2, p1, p2, k3 ; valid [B,J] u8 or NULL ; (mask, mask_kind) as under "Presence masks" above ;
+ *   out [B,V,J,2] f32 (x,y) ; status [B,V,J] i32.
+ * Not processed -- out (0, 0), status 0: an invalid joint, an absent view or entry.  Nothing of an absent entry is read, and
+ *   under MVAL_MASK_VIEWS the K and dist of an absent view may hold anything, NaN included.
+ * Handed through -- out = f32(kp2d) bit for bit:
+ *   status 0: all five coefficients are exactly 0 (K is not read);
+ *   status MVAL_UNDISTORT_FOLD: det J was not > 0, or not finite, at some iterate -- beyond the fold-over of a strong barrel
+ *     lens, a NaN or inf input, a singular K2;
+ *   status MVAL_UNDISTORT_NOCONV: MVAL_UNDISTORT_MAX_ITERS iterations did not converge.
+ * Otherwise status = k >= 1, the Newton iteration that converged, and out = f32(K00 x + K01 y + K02), f32(K10 x + K11 y + K12),
+ *   rounded once.  A handed-through entry still takes part in the triangulation, at its distorted position, as every entry does
+ *   without this stage; status is how a caller finds it.
+ * The arithmetic is part of the definition (the fold and convergence decisions of a host float64 evaluation are then the
+ * device's): a = px - K02, b = py - K12, D = K00 K11 - K01 K10, (tx, ty) = ((K11 a - K01 b) / D, (K00 b - K10 a) / D);
+ * (x, y) = (tx, ty); iteration k = 1 .. MVAL_UNDISTORT_MAX_ITERS: xx = x x, yy = y y, xy = x y, r = xx + yy, r2 = r r, r3 = r2 r,
+ *   q = 1 + k1 r + k2 r2 + k3 r3,  s = k1 + 2 k2 r + 3 k3 r2,
+ *   xd = x q + 2 p1 xy + p2 (r + 2 xx),  yd = y q + 2 p2 xd y + p1 (r + 2 yy),  fx = xd - tx,  fy = yd - ty,
+ *   jxx = q + 2 xx s + 2 p1 y + 6 p2 x,  jxy = 2 xy s + 2 p1 x + 2 p2 y,                      (d xd / dx, d xd / dy)
+ *   jyx = 2 xy s + 2 p1 x + 2 p2 y jxx,  jyy = q + 2 yy s + 6 p1 y + 2 p2 (xd + y jxy),       (d yd / dx, d yd / dy)
+ *   det J = jxx jyy - jxy jyx, tested BEFORE the step;  dx = (jyy fx - jxy fy) / det J,  dy = (jxx fy - jyx fx) / det J,
+ *   x -= dx, y -= dy;  converged iff max(|dx|, |dy|) <= 1e-13 (1 + max(|x|, |y|)) at the new (x, y).
+ * Sums and products left to right as written (2 p1 xy = (2 p1) xy), one IEEE float64 operation each, no FMA contraction
+ * (csrc/undistort.hip).
+ * One thread per entry; an entry's bits do not depend on the rest of the batch.  V outside 1..32, a mask_kind outside 0..2 or
+ * not matching `mask`, NULL or misaligned arrays return an error and launch nothing; B = 0 returns 0.  The launch runs on
+ * `stream` and adds no host synchronisation. */
+#define MVAL_UNDISTORT_MAX_ITERS 16
+#define MVAL_UNDISTORT_FOLD (-1)
+#define MVAL_UNDISTORT_NOCONV (-2)
+int mval_undistort_keypoints(const void* kp2d, int kp_is_f32, const double* K, const double* dist, const uint8_t* valid,
+                             const uint8_t* mask, int mask_kind, float* out, int32_t* status, int B, int V, int J, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Uncertainty scorers (strategy.py:1149-1215)

@@ -367,6 +367,35 @@ def refine_points_3d(kp2d, proj, valid, kp3d, joint_err, joint_inliers, b, v, j,
     return out, jerr, support, status, metric
 
 
+UNDISTORT_MAX_ITERS, UNDISTORT_FOLD, UNDISTORT_NOCONV = 16, -1, -2  # MVAL_UNDISTORT_*
+_VIEWS_ARGTYPES["mval_undistort_keypoints"] = [_VOIDP, _INT] + [_VOIDP] * 4 + [_INT] + [_VOIDP] * 2 + [_INT] * 3 + [_VOIDP]
+
+
+def undistort_keypoints(kp2d, K, dist, valid, b, v, j, view_valid=None, view_joint_valid=None):
+    """mval_undistort_keypoints: kp2d (b,v,j,2) int64|float32, K (b,v,3,3) f64, dist (b,v,5) f64 = k1, k2, p1, p2, k3, valid (b,j)
+    uint8 or None, at most one of view_valid (b,v) / view_joint_valid (b,v,j) uint8 -> (kp f32 (b,v,j,2), status i32 (b,v,j):
+    0 not processed or no distortion, k > 0 converged after k iterations, UNDISTORT_FOLD / UNDISTORT_NOCONV handed through)."""
+    mask, kind = _mask_arg(view_valid, view_joint_valid, b, v, j)
+    kp_is_f32 = 1 if kp2d.dtype == torch.float32 else 0
+    if not kp_is_f32:
+        _req(kp2d, torch.int64, "keypoints_2d")
+    if tuple(kp2d.shape) != (b, v, j, 2) or tuple(K.shape) != (b, v, 3, 3) or tuple(dist.shape) != (b, v, 5):
+        raise MvalError(f"undistort_keypoints: kp2d ({b}, {v}, {j}, 2), K ({b}, {v}, 3, 3) and dist ({b}, {v}, 5), got "
+                        f"{tuple(kp2d.shape)}, {tuple(K.shape)} and {tuple(dist.shape)}")
+    if valid is not None and tuple(_req(valid, torch.uint8, "valid").shape) != (b, j):
+        raise MvalError(f"undistort_keypoints: valid ({b}, {j}), got {tuple(valid.shape)}")
+    out = torch.empty((b, v, j, 2), dtype=torch.float32, device=kp2d.device)
+    status = torch.empty((b, v, j), dtype=torch.int32, device=kp2d.device)
+    _check(
+        _views_entry("mval_undistort_keypoints")(
+            _p(kp2d), kp_is_f32, _p(_req(K, torch.float64, "intrinsics")), _p(_req(dist, torch.float64, "distortion")), _p(valid),
+            _p(mask), kind, _p(out), _p(status), b, v, j, _stream(),
+        ),
+        "mval_undistort_keypoints",
+    )
+    return out, status
+
+
 def reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, sigma, *, view_valid=None, view_joint_valid=None):
     """mval_reprojection_xe_masked: (b,) float64; under a mask the sum over the present views / entries of each frame."""
     mask, kind = _mask_arg(view_valid, view_joint_valid, b, v, j)

@@ -66,6 +66,10 @@ def get_default_configs():
     # below, DESIGN.md 6.5
     c.AL.REFINE_3D = "none"
     c.AL.REFINE_3D_WEIGHTS = "none"
+    # not in the reference (whose post stage takes the distorted peaks for pinhole observations): the undistortion of the decoded
+    # key-points before the triangulation of the pool-scoring passes, "none" | "brown"; the batch then carries "intrinsics" and
+    # "distortion" (check_undistort below); not together with USE_REPROJECTION_XE
+    c.AL.UNDISTORT = "none"
     c.AL.CLUSTER = CN()  # EXPR_TYPE "CLUSTER" (strategy.py:137-191): what ActiveLearningStrategy.cluster writes
     c.AL.CLUSTER.TYPE = "LOSS"  # LOSS | POSE (cluster_type below)
     c.AL.CLUSTER.SAVE_PATH = ""
@@ -89,6 +93,7 @@ def get_default_configs():
     c.EVAL.DECODE_REFINE = "none"  # not in the reference: AL.DECODE_REFINE for evaluate_mkpe / evaluate_all
     c.EVAL.REFINE_3D = "none"  # not in the reference: AL.REFINE_3D / AL.REFINE_3D_WEIGHTS for evaluate_mkpe / evaluate_all
     c.EVAL.REFINE_3D_WEIGHTS = "none"
+    c.EVAL.UNDISTORT = "none"  # not in the reference: AL.UNDISTORT for evaluate_mkpe / evaluate_all
 
     c.POSE_ESTIMATOR = _pose_defaults()
     c.DATA = _data_defaults()
@@ -174,3 +179,20 @@ def check_refine_3d(value, weights="none", decode_refine="none"):
         raise ValueError("3-D refinement weights 'conf' need a decode refinement (DECODE_REFINE / refine = 'quarter' | 'taylor'): "
                          "the hard arg-max returns no confidences")
     return value, weights
+
+
+UNDISTORTS = ("none", "brown")  # "none": the decoded peaks as they are; "brown": the inverse of the k1, k2, p1, p2, k3 polynomial (mval_undistort_keypoints)
+UNDISTORT_KEYS = ("intrinsics", "distortion")  # what a batch carries under "brown": (B, V, 3, 3) and (B, V, 5) (prepare_views(with_cameras=True))
+
+
+def check_undistort(value, use_reprojection_xe=False):
+    """A valid (AL|EVAL).UNDISTORT / ``undistort=`` of utils.triangulation, or ValueError naming the accepted ones -- also for "brown"
+    together with the XE metric (AL.USE_REPROJECTION_XE, ``use_reprojection_xe``): that metric compares a map rendered at the
+    pinhole reprojection with the predicted map, whose peaks are at distorted pixels."""
+    if not isinstance(value, str) or value not in UNDISTORTS:
+        raise ValueError("undistortion %r: accepted are %s" % (value, ", ".join(repr(m) for m in UNDISTORTS)))
+    if value != "none" and use_reprojection_xe:
+        raise ValueError("undistortion %r together with the XE metric (AL.USE_REPROJECTION_XE / use_reprojection_xe): the rendered map "
+                         "sits at the pinhole reprojection and the predicted one at distorted pixels (accepted are %s)"
+                         % (value, ", ".join(repr(m) for m in UNDISTORTS)))
+    return value

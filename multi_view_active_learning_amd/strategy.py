@@ -185,7 +185,7 @@ def tables_to_sal_dict(per_rank, batch_sizes, sal_dict=None):
 _SMALL_KEYS = ("proj_matrices", "joint_valid", "3d_keypoints", "pose", "frame_id", "view_valid", "view_joint_valid")
 
 
-def _stage_batch(dp, mask_keys=()):
+def _stage_batch(dp, mask_keys=(), camera_keys=()):
     """The batch's SMALL tensors (cameras, validity, ground truth, ids) as device tensors, uploaded on the caller's stream BEFORE the
     network is launched, through pinned staging (torch's caching host allocator) with non_blocking copies.  Why: score_batch /
     evaluate_mkpe run inside the side-stream context (parallel.PostStream), and a pageable host -> device copy issued there blocks the
@@ -194,13 +194,14 @@ def _stage_batch(dp, mask_keys=()):
     view-pair draw of a rig with more than 11 views (utils.triangulation.draw_view_pairs) reads it, and copying the staged mask back
     would be such a blocking copy; a ``view_valid`` (frames with missing views) likewise stays as ``view_valid_host``, which that
     draw reads too, and so does a ``view_joint_valid`` (joints missing from single views) as ``view_joint_valid_host``.
-    ``mask_keys``: further batch keys to stage like ``view_joint_valid`` (the key AL.VIEW_JOINT_VALID_KEY names).  Returns a shallow
+    ``mask_keys``: further batch keys to stage like ``view_joint_valid`` (the key AL.VIEW_JOINT_VALID_KEY names).  ``camera_keys``:
+    further batch keys to stage like ``proj_matrices`` (``intrinsics`` and ``distortion`` under UNDISTORT "brown").  Returns a shallow
     copy of ``dp``; host-only runs (no HIP device) get ``dp`` back."""
     if not torch.cuda.is_available() or not isinstance(dp, dict):
         return dp
     dev = torch.device("cuda", torch.cuda.current_device())
     out = dict(dp)
-    for k in _SMALL_KEYS + tuple(k for k in mask_keys if k not in _SMALL_KEYS):
+    for k in _SMALL_KEYS + tuple(k for k in tuple(mask_keys) + tuple(camera_keys) if k not in _SMALL_KEYS):
         if k not in dp:
             continue
         t = torch.as_tensor(dp[k])
@@ -376,8 +377,27 @@ class ActiveLearningStrategy:
         return ("view_joint_valid",) + ((key,) if key not in ("", "view_joint_valid") else ())
 
     def _stage_masked(self, dp):
-        """``_stage_batch`` that also stages the key AL.VIEW_JOINT_VALID_KEY names (and keeps its host copy)."""
-        return _stage_batch(dp, self._mask_keys()[1:])
+        """``_stage_batch`` that also stages the key AL.VIEW_JOINT_VALID_KEY names (and keeps its host copy) and, under AL.UNDISTORT
+        or EVAL.UNDISTORT "brown", the batch's ``intrinsics`` and ``distortion`` where it has them (``_batch_cameras`` raises where
+        it has not)."""
+        from .config import UNDISTORT_KEYS
+
+        cfg = self.al_cfg
+        nodes = [cfg[n] for n in ("AL", "EVAL") if n in cfg]
+        brown = any("UNDISTORT" in n and n.UNDISTORT != "none" for n in nodes)
+        return _stage_batch(dp, self._mask_keys()[1:], UNDISTORT_KEYS if brown else ())
+
+    @staticmethod
+    def _batch_cameras(dp, b):
+        """The arguments ``triangulate_batch(undistort="brown")`` takes from a batch of ``b`` frames: its ``intrinsics`` (B, V, 3, 3) and
+        ``distortion`` (B, V, 5) -- what ``prepare_views(with_cameras=True)`` returns per frame --, or KeyError naming both keys."""
+        from .config import UNDISTORT_KEYS
+
+        if not all(k in dp for k in UNDISTORT_KEYS):
+            raise KeyError("UNDISTORT 'brown': the batch needs the keys %s (prepare_views(with_cameras=True))"
+                           % " and ".join(repr(k) for k in UNDISTORT_KEYS))
+        K, dist = (torch.as_tensor(dp[k]) for k in UNDISTORT_KEYS)
+        return {"intrinsics": K.reshape(b, -1, 3, 3), "distortion": dist.reshape(b, -1, 5)}
 
     def _view_joint_valid(self, hm, dp):
         """The ONE place where a batch's per-(view, joint) mask is resolved.  hm (B,V,J,h,w) on the device.  Sources, ANDed:
@@ -428,10 +448,14 @@ class ActiveLearningStrategy:
         the triangulation (``triangulate_batch(refine=...)``); "none" is the path above call for call.
         AL.REFINE_3D "lm" (with AL.REFINE_3D_WEIGHTS "none" | "conf"): every triangulated joint is refined by
         ``triangulate_batch(refine_3d=...)``, and sal_metric, the TRIANGULATION metric, the per-sample MKPE and
-        the key-point columns come from the refined points; "none" adds no launch."""
-        from .config import check_decode_refine, check_refine_3d
+        the key-point columns come from the refined points; "none" adds no launch.
+        AL.UNDISTORT "brown": the decoded key-points are undistorted with the batch's ``intrinsics`` and ``distortion`` before the
+        triangulation (``triangulate_batch(undistort=...)``; KeyError when the batch lacks them, ValueError together
+        with AL.USE_REPROJECTION_XE); "none" reads neither key and adds no launch."""
+        from .config import check_decode_refine, check_refine_3d, check_undistort
 
         cfg = self.al_cfg
+        undistort = check_undistort(cfg.AL.UNDISTORT if "UNDISTORT" in cfg.AL else "none", cfg.AL.USE_REPROJECTION_XE)
         refine = check_decode_refine(cfg.AL.DECODE_REFINE if "DECODE_REFINE" in cfg.AL else "none", cfg.AL.USE_SOFTARGMAX)
         refine_3d, weights_3d = check_refine_3d(cfg.AL.REFINE_3D if "REFINE_3D" in cfg.AL else "none",
                                                 cfg.AL.REFINE_3D_WEIGHTS if "REFINE_3D_WEIGHTS" in cfg.AL else "none", refine)
@@ -457,6 +481,8 @@ class ActiveLearningStrategy:
         refined = {} if refine == "none" else {"refine": refine}
         if refine_3d != "none":
             refined.update(refine_3d=refine_3d, refine_3d_weights=None if weights_3d == "none" else weights_3d)
+        if undistort != "none":
+            refined.update(undistort=undistort, **self._batch_cameras(dp, b))
         r = triangulation.triangulate_batch(
             hm, dp["proj_matrices"], cfg.POSE_ESTIMATOR.STRIDE, joint_valid,
             cfg.AL.USE_SOFTARGMAX, cfg.AL.USE_REPROJECTION_XE, cfg.AL.REPROJECTION_SIGMA,
@@ -770,10 +796,13 @@ class ActiveLearningStrategy:
         validity column it contributes is ``joint_valid & joint_used``: a joint nobody triangulated is left out.
         EVAL.DECODE_REFINE "quarter" | "taylor": the sub-pixel decode of ``triangulate_batch(refine=...)``.
         EVAL.REFINE_3D "lm" (with EVAL.REFINE_3D_WEIGHTS "none" | "conf"): the 3-D refinement of ``triangulate_batch(refine_3d=...)``
-        (DESIGN.md 6.5); MKPE and the 3-D PCK(h) figures of ``evaluate_all`` then come from the refined points."""
-        from .config import check_decode_refine, check_refine_3d
+        (DESIGN.md 6.5); MKPE and the 3-D PCK(h) figures of ``evaluate_all`` then come from the refined points.
+        EVAL.UNDISTORT "brown": the undistortion of ``triangulate_batch(undistort=...)`` with the batch's ``intrinsics`` and
+        ``distortion`` (KeyError when a batch lacks them)."""
+        from .config import check_decode_refine, check_refine_3d, check_undistort
 
         ev = self.al_cfg.EVAL
+        undistort = check_undistort(ev.UNDISTORT if "UNDISTORT" in ev else "none")
         refine = check_decode_refine(ev.DECODE_REFINE if "DECODE_REFINE" in ev else "none")
         refine_3d, weights_3d = check_refine_3d(ev.REFINE_3D if "REFINE_3D" in ev else "none",
                                                 ev.REFINE_3D_WEIGHTS if "REFINE_3D_WEIGHTS" in ev else "none", refine)
@@ -790,11 +819,12 @@ class ActiveLearningStrategy:
             (b, j), (hh, wh) = jv.shape, hm.shape[2:]
             hm5 = hm.reshape(b, -1, j, hh, wh)
             vj, vj_host = self._view_joint_valid(hm5, dp)
+            cameras = {} if undistort == "none" else dict(undistort=undistort, **self._batch_cameras(dp, b))
             r = triangulation.triangulate_batch(hm5, dp["proj_matrices"],
                                                 self.al_cfg.POSE_ESTIMATOR.STRIDE, jv, pair_rng=random,
                                                 valid_joints_host=dp.get("joint_valid_host"),
                                                 view_valid=dp.get("view_valid"), view_valid_host=dp.get("view_valid_host"),
-                                                view_joint_valid=vj, view_joint_valid_host=vj_host, **refined)
+                                                view_joint_valid=vj, view_joint_valid_host=vj_host, **refined, **cameras)
             scored = jv.to(hm.device, torch.float32)
             if vj is not None:
                 scored = ((scored != 0) & r["joint_used"].bool()).to(torch.float32)

@@ -166,7 +166,8 @@ def gt_heatmaps(pt, sigma, h, w):
     return out
 
 
-def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, gt_stride, sigma, augmentation=None, compact=False):
+def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, gt_stride, sigma, augmentation=None, compact=False,
+                  with_cameras=False):
     """Batch of views of one or more frames: images (list of uint8 HIP tensors (h0, w0, 3) RGB), boxes (list of
     (left, top, right, bottom)), cameras (list of dicts R, t, K, dist), kp_3d ((>=3, J) array, or one per
     view).  Returns the reference's per-view entries stacked over views: images (V,3,H,W) and gt_heatmap
@@ -183,13 +184,17 @@ def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, 
     compact: True returns the batch in its small form -- images as the resized (and, with an augmentation, augmented) uint8 views (V,H,W,3),
     what ``resize_views_u8`` gives, and gt_points (V,J,2) float64 on the device, the heat-map-pixel positions ``gt_heatmaps`` is handed
     otherwise, instead of gt_heatmap; the other keys are unchanged.  ``strategy.train_step`` and everything that goes through
-    ``_compute_batch_heatmap`` take such a batch: the views are normalised and the maps rendered on the device, to the same bits."""
+    ``_compute_batch_heatmap`` take such a batch: the views are normalised and the maps rendered on the device, to the same bits.
+    with_cameras: True adds two host float64 keys, what ``triangulate_batch(undistort="brown")`` and AL.UNDISTORT / EVAL.UNDISTORT need
+    beside proj_matrices = K [R|t]: intrinsics (V,3,3), the K after update_after_crop and update_after_resize, and distortion (V,5) =
+    k1, k2, p1, p2, k3 of the polynomial gt_heatmap / gt_points / 2d_keypoints were projected through (zeros for a camera without
+    ``dist``, which is projected without it).  False, the default, returns today's keys."""
     v = len(images)
     rotate_targets = "none" if augmentation is None else getattr(augmentation, "rotate_targets", "none")
     if rotate_targets == "maps" and compact:
         raise ValueError("prepare_views: rotate_targets='maps' rotates rendered heat-maps and a compact batch has none: use 'points'")
     kps = kp_3d if isinstance(kp_3d, (list, tuple)) else [kp_3d] * v
-    sq, proj, pts, pts_crop = [], [], [], []
+    sq, proj, pts, pts_crop, intrinsics, distortion = [], [], [], [], [], []
     for box, cam, kp in zip(boxes, cameras, kps):
         bbox = scale_bbox(get_square_bbox(tuple(int(b) for b in box)), scale_bbox_factor)
         K = np.array(cam["K"], dtype=np.float64).copy()
@@ -202,6 +207,8 @@ def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, 
         fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]                # Camera.update_after_resize
         K[0, 0], K[1, 1], K[0, 2], K[1, 2] = fx * (in_w / width), fy * (in_h / height), cx * (in_w / width), cy * (in_h / height)
         proj.append(K.dot(np.hstack([R, t])))
+        intrinsics.append(K)
+        distortion.append(np.zeros(5) if cam.get("dist") is None else np.asarray(cam["dist"], dtype=np.float64).flatten()[:5])
         pts.append(_project(K, R, t, cam.get("dist"), skel))
         sq.append(bbox)
     plan = None
@@ -226,9 +233,11 @@ def prepare_views(images, boxes, cameras, kp_3d, scale_bbox_factor, in_w, in_h, 
         target = {"gt_heatmap": gt_heatmaps(gt_points, sigma, in_h // gt_stride, in_w // gt_stride)}
         if rotate_targets == "maps":
             target["gt_heatmap"] = augmentation.rotate_maps(target["gt_heatmap"], plan, inplace=True)
+    cameras = {"intrinsics": np.stack(intrinsics), "distortion": np.stack(distortion)} if with_cameras else {}
     return {
         "images": out_images,
         **target,
+        **cameras,
         "proj_matrices": np.stack(proj),
         "2d_keypoints": pt.astype(np.float32),
         "2d_after_crop": np.stack(pts_crop).astype(np.float32),

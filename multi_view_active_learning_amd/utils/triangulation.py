@@ -27,6 +27,10 @@ DESIGN.md 6.4) and hands float32 key-points to the unchanged triangulation entri
 3-D refinement: ``refine_3d`` = "lm" moves every triangulated joint from the DLT point of its inlier views to the minimiser of the
 reprojection error over the views within eps of that point (``mval_refine_points_3d``, one launch after the triangulation,
 DESIGN.md 6.5).  It is a defined stand-in for the reference's ``direct_optimization``, which itself keeps raising.
+
+Lens distortion: ``undistort`` = "brown" inverts the reference's own forward model (k1, k2, p1, p2, k3) for every decoded key-point
+(``mval_undistort_keypoints``, one launch between the decode and the triangulation): the network's peaks sit at
+distorted pixels, the triangulation takes them for pinhole observations.  ``undistort_keypoints`` is the direct form.
 """
 from __future__ import annotations
 
@@ -36,7 +40,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..config import check_decode_refine, check_refine_3d
+from ..config import check_decode_refine, check_refine_3d, check_undistort
 
 
 def _device_of(heatmaps):
@@ -163,6 +167,9 @@ def triangulate_batch(
     refine_3d="none",
     refine_3d_weights=None,
     refine_3d_epsilon=None,
+    undistort="none",
+    intrinsics=None,
+    distortion=None,
 ):
     """heatmaps (B,V,J,Hh,Wh) f32 HIP tensor, proj (B,V,3,4), valid (B,J) ->
     dict of HIP tensors: keypoints_3d (B,J,3) f64, keypoints_2d (B,V,J,2) i64|f32,
@@ -219,13 +226,28 @@ def triangulate_batch(
     = the size of the support set and ``joint_status`` (B, J) int32 (0 not refined, k > 0 converged after k iterations, < 0
     the iteration cap was reached) are added; ``joint_inliers`` and ``inlier_count`` stay RANSAC's.  ``refine_3d_weights``:
     None | "conf" (``keypoints_conf``: needs ``refine`` != "none", else ValueError) | a (B, V, J) tensor; a view whose weight is
-    non-finite or <= 0 leaves the support set.  The launch runs on the current stream and adds no host sync."""
+    non-finite or <= 0 leaves the support set.  The launch runs on the current stream and adds no host sync.
+
+    ``undistort``: "none" (today's path call for call: no new launch, no new keys) | "brown": one more launch
+    (``mval_undistort_keypoints``) between the decode -- whichever it was: the int64 hard decode, ``keypoints_2d``
+    handed in, the soft-arg-max, a refined decode -- and the triangulation moves every key-point from its distorted pixel to the
+    pinhole pixel of the same ray, with ``intrinsics`` (B, V, 3, 3), the K of ``proj_matricies`` = K [R|t], and ``distortion``
+    (B, V, 5) = k1, k2, p1, p2, k3 (zeros: a view without distortion, handed through); both are needed, else ValueError.  The
+    result's ``keypoints_2d`` are then the undistorted float32 points -- what was triangulated --, ``keypoints_2d_distorted`` the
+    decode as it was, and ``undistort_status`` (B, V, J) int32: 0 not processed or no distortion, k > 0 converged after k
+    iterations, < 0 handed through at the distorted position (``_lib.UNDISTORT_FOLD``, ``_lib.UNDISTORT_NOCONV``).  Nothing of an
+    absent view is read (its K and distortion may hold NaN).  Not together with ``use_reprojection_xe``: ValueError."""
+    check_undistort(undistort, use_reprojection_xe)
+    if undistort != "none" and (intrinsics is None or distortion is None):
+        raise ValueError("undistort=%r needs intrinsics (B, V, 3, 3) and distortion (B, V, 5)" % (undistort,))
     dev = _device_of(heatmaps)
     check_decode_refine(refine, use_soft_argmax)
     check_refine_3d(refine_3d, refine_3d_weights, refine)
     if heatmaps.dim() != 5:
         raise ValueError("heatmaps must be (B, V, J, Hh, Wh)")
     b, v, j, hh, wh = heatmaps.shape
+    if undistort != "none":
+        intrinsics, distortion = _camera_tensors(intrinsics, distortion, b, v)
     if v < 2:
         raise AssertionError("need at least two views")  # reference: assert len(points) >= 2
     if v > _lib.PAIRS_MAX_VIEWS:
@@ -254,6 +276,12 @@ def triangulate_batch(
         kp2d = _lib.soft_argmax(hm, b * v * j, hh, wh, float(stride)).reshape(b, v, j, 2)
     else:
         kp2d = _lib.argmax_decode(hm, valid, b, v, j, hh, wh, int(stride), hh if mirror_nonsquare_quirk else wh)
+    undistorted = None
+    if undistort != "none":  # (the kernel reads the mask itself: K and distortion of an absent view may be NaN)
+        kp2d_distorted = kp2d
+        kp2d, undistort_status = _lib.undistort_keypoints(kp2d.contiguous(), intrinsics.to(dev), distortion.to(dev), valid, b, v, j,
+                                                          view_valid=None if per_joint else vv, view_joint_valid=vj if per_joint else None)
+        undistorted = {"keypoints_2d_distorted": kp2d_distorted, "undistort_status": undistort_status}
     if masked:
         # (the map kernels still decode the maps of absent views; a select, not a product: such a row may be NaN)
         present = vj.bool()[:, :, :, None] if per_joint else vv.bool()[:, :, None, None]
@@ -310,6 +338,8 @@ def triangulate_batch(
         out["keypoints_conf"] = conf
     if refined is not None:
         out.update(refined)
+    if undistorted is not None:
+        out.update(undistorted)
     if per_joint:
         out["joint_used"] = (jinl > 0).to(torch.uint8)  # a used joint's winning pair is in its own inlier set: >= 2
     return out
@@ -330,6 +360,37 @@ def decode_keypoints(heatmaps, stride, valid_joints=None, refine="none"):
         return _lib.argmax_decode(hm, valid, b, v, j, hh, wh, int(stride), hh), None
     kp2d = _lib.argmax_decode(hm, valid, b, v, j, hh, wh, int(stride), wh)
     return _lib.refine_keypoints(hm, kp2d, valid, b, v, j, hh, wh, int(stride), refine)
+
+
+def _camera_tensors(intrinsics, distortion, b, v):
+    """``intrinsics`` (B, V, 3, 3) and ``distortion`` (B, V, 5), anything ``torch.as_tensor`` takes, as contiguous float64 tensors
+    where they are; any other shape: ValueError (no device work yet)."""
+    K, dist = torch.as_tensor(intrinsics), torch.as_tensor(distortion)
+    if tuple(K.shape) != (b, v, 3, 3) or tuple(dist.shape) != (b, v, 5):
+        raise ValueError("intrinsics must be (%d, %d, 3, 3) and distortion (%d, %d, 5) = k1, k2, p1, p2, k3 per view, got %r and %r"
+                         % (b, v, b, v, tuple(K.shape), tuple(dist.shape)))
+    return K.to(torch.float64).contiguous(), dist.to(torch.float64).contiguous()
+
+
+def undistort_keypoints(keypoints_2d, intrinsics, distortion, valid_joints=None, view_valid=None, view_joint_valid=None):
+    """The undistortion alone (``mval_undistort_keypoints``): keypoints_2d (B, V, J, 2) int64 | float32 HIP tensor in
+    pixels of the network's input, intrinsics (B, V, 3, 3), distortion (B, V, 5) = k1, k2, p1, p2, k3 -> (keypoints float32
+    (B, V, J, 2), status int32 (B, V, J)) as ``triangulate_batch(undistort="brown")`` returns them.  valid_joints (B, J),
+    view_valid (B, V) and view_joint_valid (B, V, J) (ANDed with view_valid where both are given) say which entries exist:
+    the others come back (0, 0) with status 0, and nothing of them is read."""
+    if not torch.is_tensor(keypoints_2d) or keypoints_2d.dim() != 4 or keypoints_2d.shape[-1] != 2:
+        raise ValueError("keypoints_2d must be a (B, V, J, 2) tensor")
+    if keypoints_2d.dtype not in (torch.int64, torch.float32):
+        raise ValueError("keypoints_2d must be int64 (the hard decode) or float32, got %s" % (keypoints_2d.dtype,))
+    b, v, j = keypoints_2d.shape[:3]
+    K, dist = _camera_tensors(intrinsics, distortion, b, v)
+    dev = _device_of(keypoints_2d)
+    valid = _as_valid_u8(valid_joints, (b, j), dev)
+    vv = _as_valid_u8(view_valid, (b, v), dev)
+    vj = _as_valid_u8(view_joint_valid, (b, v, j), dev)
+    if vj is not None and vv is not None:
+        vj, vv = vj & vv[:, :, None], None
+    return _lib.undistort_keypoints(keypoints_2d.contiguous(), K.to(dev), dist.to(dev), valid, b, v, j, view_valid=vv, view_joint_valid=vj)
 
 
 _NEEDS_RNG = ("more view pairs than n_iters: the reference samples pairs from python's global RNG there "
@@ -378,6 +439,9 @@ def triangulation(
     refine="none",
     refine_3d="none",
     refine_3d_weights=None,
+    undistort="none",
+    intrinsics=None,
+    distortion=None,
 ):
     """One frame, reference signature and return types (utils/triangulation.py:168-233):
     heatmaps (V,J,Hh,Wh), proj (V,3,4), valid (J,) -> {"keypoints_3d": ndarray (J,3) f64,
@@ -387,7 +451,9 @@ def triangulation(
     but none with two such views raises the same AssertionError.  ``refine``: the sub-pixel decode of ``triangulate_batch``; the
     result then also holds "keypoints_conf": ndarray (V, J) f32.  ``refine_3d`` = "lm" (with ``refine_3d_weights`` None | "conf" |
     (V, J)): the 3-D refinement of ``triangulate_batch``; "keypoints_3d" are then the refined points and the result also holds
-    "keypoints_3d_dlt" (J, 3) f64, "joint_error" (J,) f64, "joint_support" and "joint_status" (J,) int32."""
+    "keypoints_3d_dlt" (J, 3) f64, "joint_error" (J,) f64, "joint_support" and "joint_status" (J,) int32.  ``undistort`` = "brown"
+    with ``intrinsics`` (V, 3, 3) and ``distortion`` (V, 5): the undistortion of ``triangulate_batch``; "keypoints_2d" are then the
+    undistorted float32 points and the result also holds "keypoints_2d_distorted" (V, J, 2) and "undistort_status" (V, J) int32."""
     if direct_optimization:
         raise NotImplementedError(
             "direct_optimization (scipy Huber least-squares, off in every reference call site): its result is where "
@@ -412,6 +478,9 @@ def triangulation(
             refine_3d=refine_3d,
             refine_3d_weights=refine_3d_weights if refine_3d_weights is None or isinstance(refine_3d_weights, str)
             else torch.as_tensor(refine_3d_weights).unsqueeze(0))),
+        **({} if undistort == "none" and intrinsics is None and distortion is None else dict(
+            undistort=undistort, intrinsics=None if intrinsics is None else torch.as_tensor(intrinsics).unsqueeze(0),
+            distortion=None if distortion is None else torch.as_tensor(distortion).unsqueeze(0))),
     )
     inl = int(r["inlier_count"][0].item())
     if inl == -2:
@@ -428,5 +497,8 @@ def triangulation(
         out["keypoints_conf"] = r["keypoints_conf"][0].cpu().numpy()
     if "joint_status" in r:
         for key in ("keypoints_3d_dlt", "joint_error", "joint_support", "joint_status"):
+            out[key] = r[key][0].cpu().numpy()
+    if "undistort_status" in r:
+        for key in ("keypoints_2d_distorted", "undistort_status"):
             out[key] = r[key][0].cpu().numpy()
     return out

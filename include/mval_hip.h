@@ -177,6 +177,33 @@ int mval_triangulate_ransac_pairs_masked(const void* kp2d, int kp_is_f32, const 
                                          double* kp3d, double* joint_err, int32_t* joint_inliers, double* metric,
                                          int32_t* inlier_count, int B, int V, int J, double eps, void* stream);
 
+/* Confidence-weighted triangulation and RANSAC's winning inlier set (not in the reference; DESIGN.md 6.7 holds the definition).
+ * One entry for both kernels: pairs == NULL walks all C(V,2) pairs as mval_triangulate_ransac_masked does (2 <= V <= 11),
+ * otherwise the table as mval_triangulate_ransac_pairs_masked does (2 <= V <= 32; P, pairs_shared as there).
+ *   joint_inlier_mask [B,J] i32 or NULL: bit v is set when view v is in the winning set the final DLT ran over; 0 for a joint
+ *       that is invalid or not used.  Its population count is joint_inliers.
+ *   weights [B,V,J] f32 or NULL.
+ * weights == NULL: every other output is bit for bit what the `_masked` entry of the same mask_kind and table writes.
+ * weights != NULL: an entry (b, v, j) is USABLE when its weight is finite and > 0, and its effective presence is "present under
+ *   (mask, mask_kind)" AND usable.  The call then has the semantics of MVAL_MASK_VIEW_JOINT with that effective mask, whichever
+ *   mask_kind came in: an unusable entry never votes, is never an inlier or part of a walked pair; "no usable pair: all views"
+ *   means all effectively present views; a valid joint with fewer than two of them is written like an invalid one; metric and
+ *   inlier_count run over the used joints (a valid joint but no used one: -2 and NaN; no valid joint: -1), which under
+ *   MVAL_MASK_VIEWS gives a frame with fewer than two present views its -2 / -1 as ever.  Nothing of an entry the mask calls
+ *   absent is read, its weight included.
+ *   Both DLT rows of view v -- in the pair solve of every hypothesis and in the final solve -- are multiplied by (double)w_v,
+ *   every element formed as without weights and then multiplied once: a weight of exactly 1.0f gives the unweighted bits.
+ *   The vote (error < eps) is unweighted, and joint_err stays the unweighted mean error of the inlier views, in pixels.
+ *   Ranking of hypotheses: more inliers; among equal counts the larger S = sum of w_v over the set (views ascending, float64);
+ *   among equal S the lower pair position.  With all weights equal this is the unweighted ranking.
+ * A problem's bits do not depend on its place in the batch.  Arguments are checked as the `_masked` entries check theirs; weights
+ * and joint_inlier_mask must be 4-byte aligned. */
+int mval_triangulate_ransac_weighted(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                     const uint8_t* mask, int mask_kind, const uint8_t* pairs, int P, int pairs_shared,
+                                     const float* weights, double* kp3d, double* joint_err, int32_t* joint_inliers,
+                                     int32_t* joint_inlier_mask, double* metric, int32_t* inlier_count, int B, int V, int J,
+                                     double eps, void* stream);
+
 /* mval_reprojection_xe under a mask: the maps of an absent view / entry are not read, their ws slots are not written, and the
  * serial view-major, joint-minor sum skips them.  A frame without a present view / entry gives 0. */
 int mval_reprojection_xe_masked(const double* kp3d, const double* proj, const float* heatmaps, const uint8_t* mask,

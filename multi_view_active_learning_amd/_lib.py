@@ -319,6 +319,48 @@ def triangulate_ransac(kp2d, proj, valid, b, v, j, eps, *, view_valid=None, view
     return _triangulate("mval_triangulate_ransac_masked", kp2d, proj, valid, mask, kind, b, v, j, eps)
 
 
+_VIEWS_ARGTYPES["mval_triangulate_ransac_weighted"] = ([_VOIDP, _INT] + [_VOIDP] * 3 + [_INT, _VOIDP] + [_INT] * 2 + [_VOIDP] * 7 + [_INT] * 3
+                                                       + [_DOUBLE, _VOIDP])
+
+
+def triangulate_ransac_weighted(kp2d, proj, valid, b, v, j, eps, *, pairs=None, view_valid=None, view_joint_valid=None, weights=None,
+                                want_inlier_mask=False):
+    """mval_triangulate_ransac_weighted: ``triangulate_ransac`` (pairs None, V <= 11) or ``triangulate_ransac_pairs`` with per-entry
+    ``weights`` (b, v, j) float32 inside the DLT and the ranking -- an entry whose weight is not finite and > 0 is absent -- and / or
+    the winning inlier set handed out -> (kp3d, joint_err, joint_inliers, metric, inlier_count, joint_inlier_mask (b, j) int32 with
+    bit v = view v is in the set, or None when not asked for)."""
+    mask, kind = _mask_arg(view_valid, view_joint_valid, b, v, j)
+    kp_is_f32 = 1 if kp2d.dtype == torch.float32 else 0
+    if not kp_is_f32:
+        _req(kp2d, torch.int64, "keypoints_2d")
+    if tuple(kp2d.shape) != (b, v, j, 2):
+        raise MvalError(f"triangulate_ransac_weighted: kp2d ({b}, {v}, {j}, 2), got {tuple(kp2d.shape)}")
+    if weights is not None and tuple(_req(weights, torch.float32, "weights").shape) != (b, v, j):
+        raise MvalError(f"triangulate_ransac_weighted: weights ({b}, {v}, {j}), got {tuple(weights.shape)}")
+    table = (_p(None), 0, 0)
+    if pairs is not None:
+        _req(pairs, torch.uint8, "pairs")
+        shared = pairs.dim() == 3
+        if pairs.shape[-1] != 2 or (tuple(pairs.shape[:-2]) != (1,) if shared else tuple(pairs.shape[:-2]) != (b, j)):
+            raise MvalError(f"pairs: expected (1, P, 2) or ({b}, {j}, P, 2), got {tuple(pairs.shape)}")
+        table = (_p(pairs), pairs.shape[-2], int(shared))
+    dev = proj.device
+    kp3d = torch.empty((b, j, 3), dtype=torch.float64, device=dev)
+    jerr = torch.empty((b, j), dtype=torch.float64, device=dev)
+    jinl = torch.empty((b, j), dtype=torch.int32, device=dev)
+    jmask = torch.empty((b, j), dtype=torch.int32, device=dev) if want_inlier_mask else None
+    metric = torch.empty((b,), dtype=torch.float64, device=dev)
+    inl = torch.empty((b,), dtype=torch.int32, device=dev)
+    _check(
+        _views_entry("mval_triangulate_ransac_weighted")(
+            _p(kp2d), kp_is_f32, _p(_req(proj, torch.float64, "proj_matricies")), _p(valid), _p(mask), kind, *table, _p(weights),
+            _p(kp3d), _p(jerr), _p(jinl), _p(jmask), _p(metric), _p(inl), b, v, j, float(eps), _stream(),
+        ),
+        "mval_triangulate_ransac_weighted",
+    )
+    return kp3d, jerr, jinl, metric, inl, jmask
+
+
 def peak_mask(hm, min_peak, n_maps, hh, wh):
     """mval_peak_mask: (n_maps,) uint8, 1 where some element of the map is >= min_peak."""
     out = torch.empty((n_maps,), dtype=torch.uint8, device=hm.device)

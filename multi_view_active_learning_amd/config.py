@@ -70,6 +70,9 @@ def get_default_configs():
     # key-points before the triangulation of the pool-scoring passes, "none" | "brown"; the batch then carries "intrinsics" and
     # "distortion" (check_undistort below); not together with USE_REPROJECTION_XE
     c.AL.UNDISTORT = "none"
+    # not in the reference (whose DLT takes every inlier view at the same weight): per-entry weights inside the triangulation of the
+    # pool-scoring passes, "none" | "conf" (the peak heights of DECODE_REFINE); check_triangulation_weights below, DESIGN.md 6.7
+    c.AL.TRIANGULATION_WEIGHTS = "none"
     c.AL.CLUSTER = CN()  # EXPR_TYPE "CLUSTER" (strategy.py:137-191): what ActiveLearningStrategy.cluster writes
     c.AL.CLUSTER.TYPE = "LOSS"  # LOSS | POSE (cluster_type below)
     c.AL.CLUSTER.SAVE_PATH = ""
@@ -94,6 +97,7 @@ def get_default_configs():
     c.EVAL.REFINE_3D = "none"  # not in the reference: AL.REFINE_3D / AL.REFINE_3D_WEIGHTS for evaluate_mkpe / evaluate_all
     c.EVAL.REFINE_3D_WEIGHTS = "none"
     c.EVAL.UNDISTORT = "none"  # not in the reference: AL.UNDISTORT for evaluate_mkpe / evaluate_all
+    c.EVAL.TRIANGULATION_WEIGHTS = "none"  # not in the reference: AL.TRIANGULATION_WEIGHTS for evaluate_mkpe / evaluate_all
 
     c.POSE_ESTIMATOR = _pose_defaults()
     c.DATA = _data_defaults()
@@ -179,6 +183,25 @@ def check_refine_3d(value, weights="none", decode_refine="none"):
         raise ValueError("3-D refinement weights 'conf' need a decode refinement (DECODE_REFINE / refine = 'quarter' | 'taylor'): "
                          "the hard arg-max returns no confidences")
     return value, weights
+
+
+TRIANGULATION_WEIGHTS = ("none", "conf")  # "none": every inlier view at the same weight; "conf": the peak heights a decode refinement returns
+
+
+def check_triangulation_weights(value, refine="none"):
+    """A valid (AL|EVAL).TRIANGULATION_WEIGHTS / ``weights=`` of utils.triangulation (None reads as "none"; a tensor is the caller's
+    own weights and is checked where it is used), or ValueError naming the accepted ones -- also for "conf" without a decode
+    refinement (``refine`` "none"): only a refined decode returns the confidences.  Returns the value."""
+    if value is None:
+        value = "none"
+    named = isinstance(value, str)
+    if (named and value not in TRIANGULATION_WEIGHTS) or not (named or hasattr(value, "shape")):
+        raise ValueError("triangulation weights %r: accepted are %s (or a (B, V, J) tensor handed to triangulate_batch)"
+                         % (value, ", ".join(repr(m) for m in TRIANGULATION_WEIGHTS)))
+    if named and value == "conf" and refine == "none":
+        raise ValueError("triangulation weights 'conf' need a decode refinement (DECODE_REFINE / refine = 'quarter' | 'taylor'): "
+                         "the hard arg-max returns no confidences")
+    return value
 
 
 UNDISTORTS = ("none", "brown")  # "none": the decoded peaks as they are; "brown": the inverse of the k1, k2, p1, p2, k3 polynomial (mval_undistort_keypoints)

@@ -38,6 +38,15 @@
 // everything a lane does with it is what it does with a frame's word.  A valid joint with fewer than two present views is
 // written like an invalid one, and frame_reduce_kernel runs over the USED joints (valid, two or more views) -- which are
 // the joints with joint_inliers > 0, a winning pair being part of its own inlier set.
+//
+// Confidence weights and the winning set (mval_triangulate_ransac_weighted): EXT, a second template parameter
+// beside MASK.  EXT_NONE is what the four entries above run: those instantiations compile to the code they were without it.
+// EXT_SET also writes the winning inlier set of every problem as a bit mask.  EXT_WEIGHTED multiplies the two DLT rows of view v
+// by its weight w_v, in the pair solve and in the final solve; an entry whose weight is not finite and > 0 is absent, so the
+// kernels then run masked over `present & usable` whatever MASK is (MASK only says how `present` is read); among hypotheses
+// with equally many inliers the larger sum of weights wins, then the lower pair position.  The vote and joint_err stay
+// unweighted.  Weights are read again where they are needed (V floats per problem, cached) instead of being kept in registers
+// beside finish_problem's error list.
 #include "mval_common.h"
 #include "numeric_order.h"  // np_pairwise_sum: np.mean's order
 
@@ -139,6 +148,12 @@ __device__ __forceinline__ void add_view_rows(R4& m, const double* __restrict__ 
   r4_add_row(m, py * P[8] - P[4], py * P[9] - P[5], py * P[10] - P[6], py * P[11] - P[7]);
 }
 
+// the same rows scaled by the view's weight: every element formed as above, then multiplied once (w = 1: the same bits)
+__device__ __forceinline__ void add_view_rows(R4& m, const double* __restrict__ P, double px, double py, double w) {
+  r4_add_row(m, (px * P[8] - P[0]) * w, (px * P[9] - P[1]) * w, (px * P[10] - P[2]) * w, (px * P[11] - P[3]) * w);
+  r4_add_row(m, (py * P[8] - P[4]) * w, (py * P[9] - P[5]) * w, (py * P[10] - P[6]) * w, (py * P[11] - P[7]) * w);
+}
+
 __device__ __forceinline__ void dehomogenise(const double h[4], double X[3]) {
   double w = (h[3] == 0.0) ? 1.0 : h[3];  // utils/triangulation.py:397-399
   X[0] = h[0] / w;
@@ -157,20 +172,26 @@ __device__ __forceinline__ double reproj_err(const double* __restrict__ P, const
 }
 
 // stage 1 of one lane: triangulate the view pair (a, c) and vote over all V views -> inlier mask (a and c always in it)
-// (MASK != MASK_NONE: over the views of `present` only)
-template <int MASK = MASK_NONE, typename KP>
+// (MASKED: over the views of `present` only; WT: the pair's rows weighted by wb[v * J])
+template <bool MASKED = false, bool WT = false, typename KP>
 __device__ __forceinline__ unsigned vote_pair(const double* __restrict__ Pb, const KP* __restrict__ kb, int V, int J,
-                                              int a, int c, double eps, unsigned present = 0u) {
+                                              int a, int c, double eps, unsigned present = 0u,
+                                              const float* __restrict__ wb = nullptr) {
   R4 m;
   r4_zero(m);
-  add_view_rows(m, Pb + a * 12, (double)kb[(int64_t)a * J * 2], (double)kb[(int64_t)a * J * 2 + 1]);
-  add_view_rows(m, Pb + c * 12, (double)kb[(int64_t)c * J * 2], (double)kb[(int64_t)c * J * 2 + 1]);
+  if (WT) {
+    add_view_rows(m, Pb + a * 12, (double)kb[(int64_t)a * J * 2], (double)kb[(int64_t)a * J * 2 + 1], (double)wb[(int64_t)a * J]);
+    add_view_rows(m, Pb + c * 12, (double)kb[(int64_t)c * J * 2], (double)kb[(int64_t)c * J * 2 + 1], (double)wb[(int64_t)c * J]);
+  } else {
+    add_view_rows(m, Pb + a * 12, (double)kb[(int64_t)a * J * 2], (double)kb[(int64_t)a * J * 2 + 1]);
+    add_view_rows(m, Pb + c * 12, (double)kb[(int64_t)c * J * 2], (double)kb[(int64_t)c * J * 2 + 1]);
+  }
   double h[4], X[3];
   r4_null_vector(m, h);
   dehomogenise(h, X);
   unsigned mask = (1u << a) | (1u << c);
   for (int v = 0; v < V; v++) {
-    if (MASK != MASK_NONE && !(present >> v & 1)) continue;
+    if (MASKED && !(present >> v & 1)) continue;
     double e = reproj_err(Pb + v * 12, X, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
     if (e < eps) mask |= 1u << v;
   }
@@ -178,11 +199,12 @@ __device__ __forceinline__ unsigned vote_pair(const double* __restrict__ Pb, con
 }
 
 // stage 2, one lane per problem: final DLT on the sorted inlier views `win`, its mean reprojection error and the count
-// (NMAX: the most views a caller's `win` can name)
-template <int NMAX, typename KP>
+// (NMAX: the most views a caller's `win` can name; WT: the rows weighted by wb[v * J], the errors and their mean are not)
+template <int NMAX, bool WT = false, typename KP>
 __device__ __forceinline__ void finish_problem(const double* __restrict__ Pb, const KP* __restrict__ kb, int V, int J,
                                                unsigned win, bool is_valid, double* __restrict__ X3,
-                                               double* __restrict__ err_out, int32_t* __restrict__ inl_out) {
+                                               double* __restrict__ err_out, int32_t* __restrict__ inl_out,
+                                               const float* __restrict__ wb = nullptr) {
   if (!is_valid) {
     X3[0] = X3[1] = X3[2] = 0.0;
     *err_out = 0.0;
@@ -191,8 +213,11 @@ __device__ __forceinline__ void finish_problem(const double* __restrict__ Pb, co
   }
   R4 m;
   r4_zero(m);
-  for (int v = 0; v < V; v++)
-    if (win >> v & 1) add_view_rows(m, Pb + v * 12, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
+  for (int v = 0; v < V; v++) {
+    if (!(win >> v & 1)) continue;
+    if (WT) add_view_rows(m, Pb + v * 12, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1], (double)wb[(int64_t)v * J]);
+    else add_view_rows(m, Pb + v * 12, (double)kb[(int64_t)v * J * 2], (double)kb[(int64_t)v * J * 2 + 1]);
+  }
   double h[4], X[3];
   r4_null_vector(m, h);
   dehomogenise(h, X);
@@ -228,18 +253,64 @@ __device__ __forceinline__ unsigned present_of(const uint8_t* __restrict__ mask,
   return m;
 }
 
+// What a kernel does beyond the four original entries, and the arguments that takes (the kernels' last parameter; none for
+// EXT_NONE).  inlier_mask [B*J] may be NULL under EXT_WEIGHTED.
+enum { EXT_NONE = 0, EXT_SET = 1, EXT_WEIGHTED = 2 };
+template <int EXT>
+struct TriExt {};
+template <>
+struct TriExt<EXT_SET> {
+  int32_t* inlier_mask;
+};
+template <>
+struct TriExt<EXT_WEIGHTED> {
+  int32_t* inlier_mask;
+  const float* weights;
+};
+
+__device__ __forceinline__ unsigned all_views(int V) { return (V >= 32) ? 0xffffffffu : ((1u << V) - 1u); }
+
+// the views of `present` whose weight is usable, finite and > 0 (wb: the problem's weights, + v * J); the weight of an absent
+// view is not read
+__device__ __forceinline__ unsigned usable_views(const float* __restrict__ wb, unsigned present, int V, int J) {
+  unsigned m = 0;
+  for (int v = 0; v < V; v++) {
+    if (!(present >> v & 1)) continue;
+    const float w = wb[(int64_t)v * J];
+    if (isfinite(w) && w > 0.f) m |= 1u << v;
+  }
+  return m;
+}
+
+// S of a hypothesis: the sum of its views' weights, views ascending, float64
+__device__ __forceinline__ double set_weight(const float* __restrict__ wb, unsigned set, int V, int J) {
+  double s = 0.0;
+  for (int v = 0; v < V; v++)
+    if (set >> v & 1) s += (double)wb[(int64_t)v * J];
+  return s;
+}
+
+// the weighted ranking of two hypotheses (key = count << SHIFT | (positions - 1 - position), S): more inliers, then the larger
+// S, then the lower position.  No set (key -1) loses to any.
+template <int SHIFT>
+__device__ __forceinline__ bool ranks_before(int ka, double sa, int kb, double sb) {
+  if ((ka >> SHIFT) != (kb >> SHIFT)) return ka > kb;
+  if (sa != sb) return sa > sb;
+  return ka > kb;
+}
+
 // All C(V,2) pairs in lexicographic order, pair p on lane p of the problem's group (V <= MAXV: n_pairs <= 64).
 // MASKED: lane p keeps its pair and sits out when one of its views is absent; the pairs that take part are the
 // lexicographic pairs of the present views in the same relative order, so the key picks the winner the unmasked
 // kernel picks on the frame's present views alone.  Fewer than two present views: the problem is written as an
 // invalid joint's (frame_reduce_kernel marks the frame).  MASK_VIEW_JOINT: the same with the problem's own `present`.
-template <int MASK, typename KP>
+template <int MASK, int EXT, typename KP>
 __global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ kp2d, const double* __restrict__ proj,
                                                          const uint8_t* __restrict__ valid,
                                                          const uint8_t* __restrict__ view_valid,
                                                          double* __restrict__ kp3d, double* __restrict__ joint_err,
                                                          int32_t* __restrict__ joint_inliers, int64_t n_prob, int V,
-                                                         int J, int n_pairs, int PG, double eps) {
+                                                         int J, int n_pairs, int PG, double eps, TriExt<EXT> ext) {
   const int lane = threadIdx.x;
   const int grp = lane / PG, p = lane % PG;
   const int64_t prob = (int64_t)blockIdx.x * (64 / PG) + grp;
@@ -251,8 +322,14 @@ __global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ k
   const double* Pb = proj + b * V * 12;
   const KP* kb = kp2d + (b * V * (int64_t)J + j) * 2;  // + v * J * 2
 
-  constexpr bool MASKED = MASK != MASK_NONE;
-  const unsigned present = present_of<MASK>(view_valid, b, j, V, J);
+  constexpr bool WT = EXT == EXT_WEIGHTED;
+  constexpr bool MASKED = MASK != MASK_NONE || WT;
+  unsigned present = present_of<MASK>(view_valid, b, j, V, J);
+  const float* wb = nullptr;  // + v * J
+  if constexpr (WT) {
+    wb = ext.weights + b * V * (int64_t)J + j;
+    present = usable_views(wb, MASK == MASK_NONE ? all_views(V) : present, V, J);
+  }
 
   unsigned mask = 0;
   bool voted = false;
@@ -261,19 +338,30 @@ __global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ k
     while (rem >= V - 1 - a) { rem -= V - 1 - a; a++; }
     const int c = a + 1 + rem;
     voted = !MASKED || ((present >> a & 1) && (present >> c & 1));
-    if (voted) mask = vote_pair<MASK>(Pb, kb, V, J, a, c, eps, present);
+    if (voted) mask = vote_pair<MASKED, WT>(Pb, kb, V, J, a, c, eps, present, wb);
   }
   // first pair with the strictly largest set: key = count * 64 + (63 - p), maximise
   int key = voted ? __popc(mask) * 64 + (63 - p) : -1;
   int best = key;
-  for (int o = PG >> 1; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
+  if constexpr (WT) {  // (count, S, position): the key travels with its S
+    double best_s = voted ? set_weight(wb, mask, V, J) : 0.0;
+    for (int o = PG >> 1; o > 0; o >>= 1) {
+      const int k = __shfl_xor(best, o, 64);
+      const double s = __shfl_xor(best_s, o, 64);
+      if (ranks_before<6>(k, s, best, best_s)) { best = k; best_s = s; }
+    }
+  } else {
+    for (int o = PG >> 1; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
+  }
   unsigned win = (key == best) ? mask : 0u;
   for (int o = PG >> 1; o > 0; o >>= 1) win |= __shfl_xor(win, o, 64);
 
   if (p != 0 || !live) return;
   // (MASKED, two or more present views: at least one pair voted, so `win` is never the unmasked kernel's empty set)
-  finish_problem<MAXV>(Pb, kb, V, J, win, is_valid && (!MASKED || __popc(present) >= 2), kp3d + pr * 3, joint_err + pr,
-                       joint_inliers + pr);
+  const bool used = is_valid && (!MASKED || __popc(present) >= 2);
+  finish_problem<MAXV, WT>(Pb, kb, V, J, win, used, kp3d + pr * 3, joint_err + pr, joint_inliers + pr, wb);
+  if constexpr (EXT != EXT_NONE)
+    if (ext.inlier_mask) ext.inlier_mask[pr] = used ? (int32_t)win : 0;
 }
 
 // The same two stages over an explicit pair table (pairs_stride = P * 2 per problem, 0 for one shared table).  A lane
@@ -281,14 +369,14 @@ __global__ __launch_bounds__(64) void ransac_dlt_kernel(const KP* __restrict__ k
 // lowest position among equal counts: the winner is the first position with the largest set (utils/triangulation.py
 // :299-300).  key = count * 512 + (511 - position) <= 32 * 512 + 511.  An entry that names a view >= V takes no part.
 // MASKED: neither does one that names an absent view, and the fallback is all PRESENT views.
-template <int MASK, typename KP>
+template <int MASK, int EXT, typename KP>
 __global__ __launch_bounds__(64) void ransac_pairs_kernel(const KP* __restrict__ kp2d, const double* __restrict__ proj,
                                                            const uint8_t* __restrict__ valid,
                                                            const uint8_t* __restrict__ view_valid,
                                                            const uint8_t* __restrict__ pairs, int64_t pairs_stride,
                                                            double* __restrict__ kp3d, double* __restrict__ joint_err,
                                                            int32_t* __restrict__ joint_inliers, int64_t n_prob, int V,
-                                                           int J, int P, int PG, double eps) {
+                                                           int J, int P, int PG, double eps, TriExt<EXT> ext) {
   const int lane = threadIdx.x;
   const int grp = lane / PG, p0 = lane % PG;
   const int64_t prob = (int64_t)blockIdx.x * (64 / PG) + grp;
@@ -300,29 +388,52 @@ __global__ __launch_bounds__(64) void ransac_pairs_kernel(const KP* __restrict__
   const double* Pb = proj + b * V * 12;
   const KP* kb = kp2d + (b * V * (int64_t)J + j) * 2;  // + v * J * 2
   const uint8_t* tab = pairs + pr * pairs_stride;
-  constexpr bool MASKED = MASK != MASK_NONE;
-  const unsigned present = present_of<MASK>(view_valid, b, j, V, J);
+  constexpr bool WT = EXT == EXT_WEIGHTED;
+  constexpr bool MASKED = MASK != MASK_NONE || WT;
+  unsigned present = present_of<MASK>(view_valid, b, j, V, J);
+  const float* wb = nullptr;  // + v * J
+  if constexpr (WT) {
+    wb = ext.weights + b * V * (int64_t)J + j;
+    present = usable_views(wb, MASK == MASK_NONE ? all_views(V) : present, V, J);
+  }
 
   int key = -1;
   unsigned mask = 0;
+  double key_s = 0.0;  // (WT) S of the lane's best set
   if (is_valid)  // (an invalid joint has no table: the reference skips it before the draw)
     for (int p = p0; p < P; p += 64) {  // PG < 64 means P <= PG: one trip
       int a = tab[p * 2], c = tab[p * 2 + 1];
       if (a >= V || c >= V) continue;
       if (MASKED && !((present >> a & 1) && (present >> c & 1))) continue;
-      unsigned m = vote_pair<MASK>(Pb, kb, V, J, a, c, eps, present);
+      unsigned m = vote_pair<MASKED, WT>(Pb, kb, V, J, a, c, eps, present, wb);
       int k = __popc(m) * 512 + (511 - p);
-      if ((k >> 9) > (key >> 9)) { key = k; mask = m; }  // key = -1 >> 9 = -1: any set beats none
+      if constexpr (WT) {  // (a later trip has the higher position: it wins on count or on S alone)
+        const double s = set_weight(wb, m, V, J);
+        if (ranks_before<9>(k, s, key, key_s)) { key = k; key_s = s; mask = m; }
+      } else {
+        if ((k >> 9) > (key >> 9)) { key = k; mask = m; }  // key = -1 >> 9 = -1: any set beats none
+      }
     }
   int best = key;
-  for (int o = PG >> 1; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
+  if constexpr (WT) {
+    double best_s = key_s;
+    for (int o = PG >> 1; o > 0; o >>= 1) {
+      const int k = __shfl_xor(best, o, 64);
+      const double s = __shfl_xor(best_s, o, 64);
+      if (ranks_before<9>(k, s, best, best_s)) { best = k; best_s = s; }
+    }
+  } else {
+    for (int o = PG >> 1; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
+  }
   unsigned win = (key == best) ? mask : 0u;
   for (int o = PG >> 1; o > 0; o >>= 1) win |= __shfl_xor(win, o, 64);
 
   if (p0 != 0 || !live) return;
-  if (best < 0) win = MASKED ? present : (V >= 32) ? 0xffffffffu : ((1u << V) - 1u);  // no usable pair: all views (:303-304)
-  finish_problem<MVAL_PAIRS_MAX_VIEWS>(Pb, kb, V, J, win, is_valid && (!MASKED || __popc(present) >= 2), kp3d + pr * 3,
-                                       joint_err + pr, joint_inliers + pr);
+  if (best < 0) win = MASKED ? present : all_views(V);  // no usable pair: all views (:303-304)
+  const bool used = is_valid && (!MASKED || __popc(present) >= 2);
+  finish_problem<MVAL_PAIRS_MAX_VIEWS, WT>(Pb, kb, V, J, win, used, kp3d + pr * 3, joint_err + pr, joint_inliers + pr, wb);
+  if constexpr (EXT != EXT_NONE)
+    if (ext.inlier_mask) ext.inlier_mask[pr] = used ? (int32_t)win : 0;
 }
 
 // per frame: metric = np.mean(errs of valid joints), inlier_count = min (utils/triangulation.py:226,231)
@@ -368,13 +479,23 @@ static void launch_frame_reduce(const double* joint_err, const int32_t* joint_in
   });
 }
 
-// The four triangulation entries: `name` is the one that was called, `pairs` its table or nullptr for the lexicographic
-// kernel.  Argument checks, the grid of PG-lane groups, the entry's kernel for the mask kind and the key-point type, and
-// frame_reduce_kernel.
+// The one place where the two optional arguments of mval_triangulate_ransac_weighted pick an instantiation: f gets EXT as a
+// std::integral_constant and the kernels' last argument (with_mask_kind's way).
+template <typename F>
+static inline void with_ext(const float* weights, int32_t* inlier_mask, F&& f) {
+  if (weights) f(std::integral_constant<int, EXT_WEIGHTED>{}, TriExt<EXT_WEIGHTED>{inlier_mask, weights});
+  else if (inlier_mask) f(std::integral_constant<int, EXT_SET>{}, TriExt<EXT_SET>{inlier_mask});
+  else f(std::integral_constant<int, EXT_NONE>{}, TriExt<EXT_NONE>{});
+}
+
+// The five triangulation entries: `name` is the one that was called, `pairs` its table or nullptr for the lexicographic
+// kernel, `weights` and `joint_inlier_mask` nullptr for the four entries that have neither.  Argument checks, the grid of PG-lane
+// groups, the entry's kernel for the mask kind, EXT and the key-point type, and frame_reduce_kernel -- in its used-joints form
+// under weights, whose unusable entries make presence a property of the problem whatever the mask kind.
 static int triangulate(const char* name, const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
                        const uint8_t* mask, int mask_kind, const uint8_t* pairs, int P, int pairs_shared, double* kp3d,
                        double* joint_err, int32_t* joint_inliers, double* metric, int32_t* inlier_count, int B, int V, int J,
-                       double eps, void* stream) {
+                       double eps, void* stream, const float* weights = nullptr, int32_t* joint_inlier_mask = nullptr) {
   MVAL_REQUIRE(V >= 2, "%s: need >= 2 views in the rig (the reference asserts len(points) >= 2)", name);
   if (pairs) {
     MVAL_REQUIRE(V <= MVAL_PAIRS_MAX_VIEWS, "%s: at most %d views (the inlier mask is 32 bits wide)", name, MVAL_PAIRS_MAX_VIEWS);
@@ -395,19 +516,22 @@ static int triangulate(const char* name, const void* kp2d, int kp_is_f32, const 
   const hipStream_t s = mval_stream(stream);
   with_mask_kind(mask_kind, [&](auto K) {
     constexpr int MASK = decltype(K)::value;
-    const auto launch = [&](auto* kp) {
-      if (pairs)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<MASK>), grid, dim3(64), 0, s, kp, proj, valid, mask, pairs, stride,
-                           kp3d, joint_err, joint_inliers, n_prob, V, J, P, PG, eps);
-      else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<MASK>), grid, dim3(64), 0, s, kp, proj, valid, mask, kp3d, joint_err,
-                           joint_inliers, n_prob, V, J, n_pairs, PG, eps);
-    };
-    if (kp_is_f32) launch((const float*)kp2d);
-    else launch((const int64_t*)kp2d);
+    with_ext(weights, joint_inlier_mask, [&](auto E, auto ext) {
+      constexpr int EXT = decltype(E)::value;
+      const auto launch = [&](auto* kp) {
+        if (pairs)
+          hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_pairs_kernel<MASK, EXT>), grid, dim3(64), 0, s, kp, proj, valid, mask, pairs,
+                             stride, kp3d, joint_err, joint_inliers, n_prob, V, J, P, PG, eps, ext);
+        else
+          hipLaunchKernelGGL(HIP_KERNEL_NAME(ransac_dlt_kernel<MASK, EXT>), grid, dim3(64), 0, s, kp, proj, valid, mask, kp3d,
+                             joint_err, joint_inliers, n_prob, V, J, n_pairs, PG, eps, ext);
+      };
+      if (kp_is_f32) launch((const float*)kp2d);
+      else launch((const int64_t*)kp2d);
+    });
   });
   MVAL_CHECK_LAUNCH(name);
-  launch_frame_reduce(joint_err, joint_inliers, valid, mask, mask_kind, metric, inlier_count, B, V, J, s);
+  launch_frame_reduce(joint_err, joint_inliers, valid, mask, weights ? MASK_VIEW_JOINT : mask_kind, metric, inlier_count, B, V, J, s);
   MVAL_CHECK_LAUNCH_STAGE(name, "/reduce");
   return 0;
 }
@@ -447,10 +571,24 @@ extern "C" int mval_triangulate_ransac_pairs_masked(const void* kp2d, int kp_is_
                      pairs_shared, kp3d, joint_err, joint_inliers, metric, inlier_count, B, V, J, eps, stream);
 }
 
+// Both kernels, any mask kind, with per-entry weights and / or the winning set handed out.  Neither given: the
+// `_masked` entry of the same table, call for call.
+extern "C" int mval_triangulate_ransac_weighted(const void* kp2d, int kp_is_f32, const double* proj, const uint8_t* valid,
+                                                const uint8_t* mask, int mask_kind, const uint8_t* pairs, int P,
+                                                int pairs_shared, const float* weights, double* kp3d, double* joint_err,
+                                                int32_t* joint_inliers, int32_t* joint_inlier_mask, double* metric,
+                                                int32_t* inlier_count, int B, int V, int J, double eps, void* stream) {
+  MVAL_REQUIRE(((uintptr_t)weights | (uintptr_t)joint_inlier_mask) % 4 == 0,
+               "mval_triangulate_ransac_weighted: weights or joint_inlier_mask is not 4-byte aligned");
+  return triangulate("mval_triangulate_ransac_weighted", kp2d, kp_is_f32, proj, valid, mask, mask_kind, pairs, P, pairs_shared,
+                     kp3d, joint_err, joint_inliers, metric, inlier_count, B, V, J, eps, stream, weights, joint_inlier_mask);
+}
+
 // ---- 3-D refinement (not in the reference) ---------------------------------------------------------------
 // Every triangulated joint is moved from its DLT point X0 to the minimiser of the reprojection error over its support set S:
 // the present views whose reproj_err at X0 is finite and < eps (with weights: and whose weight is finite and > 0) -- the
-// vote's test, taken again at the final point, since the RANSAC kernels do not hand their winning mask on.
+// vote's test, taken again at the final point (not the winning set mval_triangulate_ransac_weighted can hand out: the support
+// set is defined at the DLT point, whichever entry made it).
 //   E(X) = 1/2 sum_{v in S} w_v |p_v - pi(P_v [X; 1])|^2,  two smooth residuals per view.
 // One lane per problem, like mval_refine_keypoints: no LDS, no atomics, nothing indexed by a loaded value; the loops run over
 // v < V <= 32 in ascending order, so a problem's bits do not depend on its place in the batch.  Levenberg-Marquardt in float64

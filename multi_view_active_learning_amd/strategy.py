@@ -451,14 +451,18 @@ class ActiveLearningStrategy:
         the key-point columns come from the refined points; "none" adds no launch.
         AL.UNDISTORT "brown": the decoded key-points are undistorted with the batch's ``intrinsics`` and ``distortion`` before the
         triangulation (``triangulate_batch(undistort=...)``; KeyError when the batch lacks them, ValueError together
-        with AL.USE_REPROJECTION_XE); "none" reads neither key and adds no launch."""
-        from .config import check_decode_refine, check_refine_3d, check_undistort
+        with AL.USE_REPROJECTION_XE); "none" reads neither key and adds no launch.
+        AL.TRIANGULATION_WEIGHTS "conf" (needs AL.DECODE_REFINE): the triangulation weights every (view, joint) entry by its peak
+        height (``triangulate_batch(weights="conf")``), and the per-sample MKPE leaves out the joints without two
+        usable views (``joint_valid & joint_used``); "none" is the path above call for call."""
+        from .config import check_decode_refine, check_refine_3d, check_triangulation_weights, check_undistort
 
         cfg = self.al_cfg
         undistort = check_undistort(cfg.AL.UNDISTORT if "UNDISTORT" in cfg.AL else "none", cfg.AL.USE_REPROJECTION_XE)
         refine = check_decode_refine(cfg.AL.DECODE_REFINE if "DECODE_REFINE" in cfg.AL else "none", cfg.AL.USE_SOFTARGMAX)
         refine_3d, weights_3d = check_refine_3d(cfg.AL.REFINE_3D if "REFINE_3D" in cfg.AL else "none",
                                                 cfg.AL.REFINE_3D_WEIGHTS if "REFINE_3D_WEIGHTS" in cfg.AL else "none", refine)
+        tri_weights = check_triangulation_weights(cfg.AL.TRIANGULATION_WEIGHTS if "TRIANGULATION_WEIGHTS" in cfg.AL else "none", refine)
         dev = heatmaps.device
         pose = torch.as_tensor(dp["pose"]).reshape(-1)
         b = pose.shape[0]
@@ -483,6 +487,8 @@ class ActiveLearningStrategy:
             refined.update(refine_3d=refine_3d, refine_3d_weights=None if weights_3d == "none" else weights_3d)
         if undistort != "none":
             refined.update(undistort=undistort, **self._batch_cameras(dp, b))
+        if tri_weights != "none":
+            refined.update(weights=tri_weights)
         r = triangulation.triangulate_batch(
             hm, dp["proj_matrices"], cfg.POSE_ESTIMATOR.STRIDE, joint_valid,
             cfg.AL.USE_SOFTARGMAX, cfg.AL.USE_REPROJECTION_XE, cfg.AL.REPROJECTION_SIGMA,
@@ -518,7 +524,7 @@ class ActiveLearningStrategy:
             als.append(al[:, None])
         gt = torch.as_tensor(dp["3d_keypoints"]).to(dev)
         scored_joints = joint_valid.to(dev)
-        if vj is not None:  # a joint nobody triangulated is not scored as a prediction at the origin
+        if vj is not None or tri_weights != "none":  # a joint nobody triangulated is not scored as a prediction at the origin
             scored_joints = ((scored_joints != 0) & r["joint_used"].bool()).to(scored_joints.dtype)
         mk = evaluation.mkpe_per_sample(pred32, gt, scored_joints)
         self._pending_checks.append(("INLIER", r["inlier_count"], None))
@@ -798,8 +804,10 @@ class ActiveLearningStrategy:
         EVAL.REFINE_3D "lm" (with EVAL.REFINE_3D_WEIGHTS "none" | "conf"): the 3-D refinement of ``triangulate_batch(refine_3d=...)``
         (DESIGN.md 6.5); MKPE and the 3-D PCK(h) figures of ``evaluate_all`` then come from the refined points.
         EVAL.UNDISTORT "brown": the undistortion of ``triangulate_batch(undistort=...)`` with the batch's ``intrinsics`` and
-        ``distortion`` (KeyError when a batch lacks them)."""
-        from .config import check_decode_refine, check_refine_3d, check_undistort
+        ``distortion`` (KeyError when a batch lacks them).
+        EVAL.TRIANGULATION_WEIGHTS "conf" (needs EVAL.DECODE_REFINE): the confidence-weighted triangulation of
+        ``triangulate_batch(weights="conf")``; the validity column is then ``joint_valid & joint_used`` too."""
+        from .config import check_decode_refine, check_refine_3d, check_triangulation_weights, check_undistort
 
         ev = self.al_cfg.EVAL
         undistort = check_undistort(ev.UNDISTORT if "UNDISTORT" in ev else "none")
@@ -809,6 +817,9 @@ class ActiveLearningStrategy:
         refined = {} if refine == "none" else {"refine": refine}
         if refine_3d != "none":
             refined.update(refine_3d=refine_3d, refine_3d_weights=None if weights_3d == "none" else weights_3d)
+        tri_weights = check_triangulation_weights(ev.TRIANGULATION_WEIGHTS if "TRIANGULATION_WEIGHTS" in ev else "none", refine)
+        if tri_weights != "none":
+            refined.update(weights=tri_weights)
 
         def inputs(hm, dp):
             b = torch.as_tensor(dp["pose"]).reshape(-1).shape[0] if "pose" in dp else dp["images"].shape[0]
@@ -826,7 +837,7 @@ class ActiveLearningStrategy:
                                                 view_valid=dp.get("view_valid"), view_valid_host=dp.get("view_valid_host"),
                                                 view_joint_valid=vj, view_joint_valid_host=vj_host, **refined, **cameras)
             scored = jv.to(hm.device, torch.float32)
-            if vj is not None:
+            if vj is not None or tri_weights != "none":
                 scored = ((scored != 0) & r["joint_used"].bool()).to(torch.float32)
             return (r["keypoints_3d"].to(torch.float32), torch.as_tensor(dp["3d_keypoints"]).to(hm.device, torch.float32), scored)
 

@@ -31,6 +31,10 @@ DESIGN.md 6.5).  It is a defined stand-in for the reference's ``direct_optimizat
 Lens distortion: ``undistort`` = "brown" inverts the reference's own forward model (k1, k2, p1, p2, k3) for every decoded key-point
 (``mval_undistort_keypoints``, one launch between the decode and the triangulation): the network's peaks sit at
 distorted pixels, the triangulation takes them for pinhole observations.  ``undistort_keypoints`` is the direct form.
+
+Confidence weights: ``weights`` = "conf" | a (B, V, J) tensor multiplies the DLT rows of every (view, joint) entry by its weight, in
+RANSAC's pair solves and in the final solve, and breaks ties between equally large inlier sets by their summed weight
+(``mval_triangulate_ransac_weighted``, the same one launch); ``return_inlier_mask`` hands RANSAC's winning set out.
 """
 from __future__ import annotations
 
@@ -40,7 +44,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..config import check_decode_refine, check_refine_3d, check_undistort
+from ..config import check_decode_refine, check_refine_3d, check_triangulation_weights, check_undistort
 
 
 def _device_of(heatmaps):
@@ -170,6 +174,8 @@ def triangulate_batch(
     undistort="none",
     intrinsics=None,
     distortion=None,
+    weights=None,
+    return_inlier_mask=False,
 ):
     """heatmaps (B,V,J,Hh,Wh) f32 HIP tensor, proj (B,V,3,4), valid (B,J) ->
     dict of HIP tensors: keypoints_3d (B,J,3) f64, keypoints_2d (B,V,J,2) i64|f32,
@@ -236,8 +242,27 @@ def triangulate_batch(
     result's ``keypoints_2d`` are then the undistorted float32 points -- what was triangulated --, ``keypoints_2d_distorted`` the
     decode as it was, and ``undistort_status`` (B, V, J) int32: 0 not processed or no distortion, k > 0 converged after k
     iterations, < 0 handed through at the distorted position (``_lib.UNDISTORT_FOLD``, ``_lib.UNDISTORT_NOCONV``).  Nothing of an
-    absent view is read (its K and distortion may hold NaN).  Not together with ``use_reprojection_xe``: ValueError."""
+    absent view is read (its K and distortion may hold NaN).  Not together with ``use_reprojection_xe``: ValueError.
+
+    ``weights``: None (today's path call for call) | "conf" (``keypoints_conf``: needs ``refine`` != "none", else ValueError) | a
+    (B, V, J) tensor, with any decode: the triangulation goes through ``mval_triangulate_ransac_weighted``, still one
+    launch.  The two DLT rows of a (view, joint) entry are multiplied by its weight, in every pair solve and in the final solve;
+    the vote and ``joint_error`` stay unweighted (pixels); among equally large inlier sets the larger summed weight wins, then the
+    earlier pair.  An entry whose weight is not finite and > 0 is absent, as under ``view_joint_valid`` (its key-point may be NaN):
+    a valid joint with fewer than two usable views is written like an invalid one, ``metric`` and ``inlier_count`` run over the used
+    joints (-2 / NaN for a frame with a valid joint but no used one), and the result carries ``joint_used`` (B, J) uint8.  All-ones
+    weights give the unweighted bits.  Beyond 11 views the pair tables are drawn from the masks alone, as without weights: a table
+    entry naming a view with an unusable weight sits out on the device.  The launches after the triangulation take the same
+    effective presence (present AND usable) as their per-entry mask: ``refine_3d`` takes its own vote as ever, over the usable entries
+    -- an unused joint stays 0 with status 0, and the refined ``metric`` runs over the used joints --, and the XE metric sums the
+    usable entries' maps.
+
+    ``return_inlier_mask``: the result carries ``joint_inlier_mask`` (B, J) int32, bit v = view v is in RANSAC's winning set, the
+    views of the final DLT (0 for an invalid or unused joint; its population count is ``joint_inliers``); always there under
+    ``weights``.  Without ``weights`` every other key has the bits of the call without it."""
     check_undistort(undistort, use_reprojection_xe)
+    weights = check_triangulation_weights(weights, refine)
+    weighted = not (isinstance(weights, str) and weights == "none")
     if undistort != "none" and (intrinsics is None or distortion is None):
         raise ValueError("undistort=%r needs intrinsics (B, V, 3, 3) and distortion (B, V, 5)" % (undistort,))
     dev = _device_of(heatmaps)
@@ -306,7 +331,21 @@ def triangulate_batch(
         pairs = torch.from_numpy(draw_view_pairs(host_valid, v, n_iters, pair_rng)).pin_memory().to(dev, non_blocking=True)
     elif v > 11:  # all pairs, more than the 64 the one-lane-per-pair entry holds
         pairs = _lexicographic_pairs(v, dev)
-    if pairs is None:
+    jmask = None
+    post_mask = mask  # what the launches after the triangulation take for presence
+    if weighted or return_inlier_mask:
+        w = None
+        if weighted:  # "conf": the peak heights, absent entries already 0
+            w = conf if isinstance(weights, str) else torch.as_tensor(weights).to(device=dev, dtype=torch.float32).reshape(b, v, j).contiguous()
+            # the entry's effective presence, present AND usable, per entry: the 3-D refinement and the XE metric see the joints
+            # and views the triangulation saw (comparisons and selects only: an absent entry's weight may be NaN)
+            usable = torch.isfinite(w) & (w > 0)
+            if masked:
+                usable = usable & (vj.bool() if per_joint else vv.bool()[:, :, None])
+            post_mask = dict(view_valid=None, view_joint_valid=usable.to(torch.uint8).contiguous())
+        kp3d, jerr, jinl, metric, inl, jmask = _lib.triangulate_ransac_weighted(kp2d, proj, valid, b, v, j, eps, pairs=pairs, weights=w,
+                                                                                want_inlier_mask=True, **mask)
+    elif pairs is None:
         kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac(kp2d, proj, valid, b, v, j, eps, **mask)
     else:
         kp3d, jerr, jinl, metric, inl = _lib.triangulate_ransac_pairs(kp2d, proj, valid, pairs, b, v, j, eps, **mask)
@@ -320,12 +359,12 @@ def triangulate_batch(
         kp3d_dlt = kp3d
         kp3d, jerr, support, status, metric = _lib.refine_points_3d(
             kp2d, proj, valid, kp3d, jerr, jinl, b, v, j, eps if refine_3d_epsilon is None else float(refine_3d_epsilon),
-            view_valid=None if per_joint else vv, view_joint_valid=vj if per_joint else None, weights=weights)
+            weights=weights, **post_mask)
         refined = {"keypoints_3d_dlt": kp3d_dlt, "joint_support": support, "joint_status": status}
     if use_reprojection_xe:
-        xe = _lib.reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, float(sigma), **mask)
+        xe = _lib.reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, float(sigma), **post_mask)
         # (-2: fewer than two views / no used joint: NaN, the reference never reaches _compute_xe)
-        metric = torch.where(inl == -2, metric, xe) if masked else xe
+        metric = torch.where(inl == -2, metric, xe) if masked or weighted else xe
     out = {
         "keypoints_3d": kp3d,
         "keypoints_2d": kp2d,
@@ -340,7 +379,9 @@ def triangulate_batch(
         out.update(refined)
     if undistorted is not None:
         out.update(undistorted)
-    if per_joint:
+    if jmask is not None:
+        out["joint_inlier_mask"] = jmask
+    if per_joint or weighted:
         out["joint_used"] = (jinl > 0).to(torch.uint8)  # a used joint's winning pair is in its own inlier set: >= 2
     return out
 
@@ -442,6 +483,8 @@ def triangulation(
     undistort="none",
     intrinsics=None,
     distortion=None,
+    weights=None,
+    return_inlier_mask=False,
 ):
     """One frame, reference signature and return types (utils/triangulation.py:168-233):
     heatmaps (V,J,Hh,Wh), proj (V,3,4), valid (J,) -> {"keypoints_3d": ndarray (J,3) f64,
@@ -453,7 +496,10 @@ def triangulation(
     (V, J)): the 3-D refinement of ``triangulate_batch``; "keypoints_3d" are then the refined points and the result also holds
     "keypoints_3d_dlt" (J, 3) f64, "joint_error" (J,) f64, "joint_support" and "joint_status" (J,) int32.  ``undistort`` = "brown"
     with ``intrinsics`` (V, 3, 3) and ``distortion`` (V, 5): the undistortion of ``triangulate_batch``; "keypoints_2d" are then the
-    undistorted float32 points and the result also holds "keypoints_2d_distorted" (V, J, 2) and "undistort_status" (V, J) int32."""
+    undistorted float32 points and the result also holds "keypoints_2d_distorted" (V, J, 2) and "undistort_status" (V, J) int32.
+    ``weights`` None | "conf" | (V, J) and ``return_inlier_mask``: the confidence-weighted triangulation of ``triangulate_batch``; the
+    result then also holds "joint_inlier_mask" (J,) int32 and, under weights, "joint_used" (J,) uint8; a valid joint but none with
+    two usable views raises the AssertionError above."""
     if direct_optimization:
         raise NotImplementedError(
             "direct_optimization (scipy Huber least-squares, off in every reference call site): its result is where "
@@ -481,6 +527,9 @@ def triangulation(
         **({} if undistort == "none" and intrinsics is None and distortion is None else dict(
             undistort=undistort, intrinsics=None if intrinsics is None else torch.as_tensor(intrinsics).unsqueeze(0),
             distortion=None if distortion is None else torch.as_tensor(distortion).unsqueeze(0))),
+        **({} if weights is None and not return_inlier_mask else dict(
+            weights=weights if weights is None or isinstance(weights, str) else torch.as_tensor(weights).unsqueeze(0),
+            return_inlier_mask=return_inlier_mask)),
     )
     inl = int(r["inlier_count"][0].item())
     if inl == -2:
@@ -500,5 +549,8 @@ def triangulation(
             out[key] = r[key][0].cpu().numpy()
     if "undistort_status" in r:
         for key in ("keypoints_2d_distorted", "undistort_status"):
+            out[key] = r[key][0].cpu().numpy()
+    if "joint_inlier_mask" in r:
+        for key in ("joint_inlier_mask",) + (() if weights is None or (isinstance(weights, str) and weights == "none") else ("joint_used",)):
             out[key] = r[key][0].cpu().numpy()
     return out

@@ -91,6 +91,28 @@ int mval_refine_keypoints(int method, const float* heatmaps, const int64_t* kp2d
 int mval_peak_mask(const float* heatmaps, float min_peak, uint8_t* out, int64_t n_maps, int hh, int wh, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Flip test (not in the reference; HRNet's and Simple Baselines' TEST.FLIP_TEST / TEST.SHIFT_HEATMAP)
+ * ---------------------------------------------------------------------------------- */
+
+/* out[r][x] = in[r][W - 1 - x] for n_rows rows of W floats (an NCHW batch is N * 3 * H rows): a bit copy.  out must not
+ * overlap in.  n_rows = 0 returns 0. */
+int mval_mirror_images(const float* in, float* out, int64_t n_rows, int W, void* stream);
+/* The merge of a forward on the images (hm) with a forward on the mirrored images (hm_mirrored), both [N][J][hh][wh] f32:
+ * HRNet's flip_back, then its SHIFT_HEATMAP, then the average.  With p = pairs[j], the channel of joint j's mirror twin
+ * (pairs [J] i32 on the DEVICE, pairs[j] == j for a centre joint; an entry outside [0, J) is read as j),
+ *   merged[n][j][y][x] = (hm[n][j][y][x] + f) * 0.5f ,  f = hm_mirrored[n][p][y][wh - 1 - x]               (shift == 0)
+ *                                                        f = hm_mirrored[n][p][y][min(wh - x, wh - 1)]      (shift != 0:
+ * the flipped-back map moved one column to the right, column 0 keeping its own value) -- in float32, one add and then one
+ * multiply, each rounded on its own, so a host float32 evaluation in that order gives the same bits.
+ * argmax_keys: NULL, or [N][MVAL_ARGMAX_SLOTS][J] u64 that receives the keys of `merged` as mval_net_forward_keys documents
+ * them (every slot of every map is written here, the unused ones with 0: no clear needed beforehand), so
+ * mval_argmax_from_keys on them equals mval_argmax_decode on `merged`.
+ * merged must overlap neither input (the inputs may be one tensor).  N = 0 returns 0 before any pointer check; J >= 1 and
+ * hh * wh < 2^24.  One launch, two reads and one write per element. */
+int mval_flip_merge_heatmaps(const float* hm, const float* hm_mirrored, const int32_t* pairs, int shift, float* merged,
+                             uint64_t* argmax_keys, int64_t N, int J, int hh, int wh, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Triangulation
  * ---------------------------------------------------------------------------------- */
 

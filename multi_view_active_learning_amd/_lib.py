@@ -438,6 +438,62 @@ def undistort_keypoints(kp2d, K, dist, valid, b, v, j, view_valid=None, view_joi
     return out, status
 
 
+_VIEWS_ARGTYPES["mval_mirror_images"] = [_VOIDP, _VOIDP, C.c_longlong, _INT, _VOIDP]
+_VIEWS_ARGTYPES["mval_flip_merge_heatmaps"] = [_VOIDP] * 3 + [_INT] + [_VOIDP] * 2 + [C.c_longlong] + [_INT] * 3 + [_VOIDP]
+
+
+def mirror_images(x, out=None):
+    """mval_mirror_images: a float32 tensor whose last dimension is the image width (an NCHW batch) -> the same with every row
+    reversed, bit for bit.  ``out``: a tensor of x's shape to write to (it must not overlap x; arg-max keys remembered for it are
+    forgotten), else a new one."""
+    if x.dim() < 1:
+        raise MvalError("mirror_images: the last dimension is the row, got a 0-d tensor")
+    _req(x, torch.float32, "images")
+    if out is None:
+        out = torch.empty_like(x, memory_format=torch.contiguous_format)
+    elif out.shape != x.shape:
+        raise MvalError(f"mirror_images: out must be {tuple(x.shape)}, got {tuple(out.shape)}")
+    else:
+        forget_argmax_keys(out)
+    w = x.shape[-1]
+    if w == 0:  # (nothing to copy, and no row length the entry takes)
+        return out
+    _check(_views_entry("mval_mirror_images")(_p(x), _p(_req(out, torch.float32, "out")), x.numel() // w, w, _stream()), "mval_mirror_images")
+    return out
+
+
+def flip_merge_heatmaps(hm, hm_mirrored, pairs_dev, shift, keep_keys=True, out=None):
+    """mval_flip_merge_heatmaps: hm and hm_mirrored (N,J,hh,wh) f32 -- the network on a batch and on its mirror image --,
+    pairs_dev (J,) int32 on the device (the channel of each joint's mirror twin), shift: move the flipped-back map one column to
+    the right -> merged (N,J,hh,wh) f32 = (hm + flipped-back hm_mirrored) * 0.5.  With ``keep_keys`` the launch also writes the
+    arg-max keys of ``merged`` and they are remembered for it (``argmax_keys_of(merged)``), as a forward's are for its output.
+    ``out``: a tensor of hm's shape to write to, else a new one.  It must overlap neither input and must be a tensor of its own, not
+    a view of another: the keys are remembered per base tensor, and a view's would be found for nothing or for the wrong maps."""
+    if hm.dim() != 4 or hm_mirrored.shape != hm.shape:
+        raise MvalError(f"flip_merge_heatmaps: two heat-map tensors (N, J, hh, wh) of one shape, got {tuple(hm.shape)} and {tuple(hm_mirrored.shape)}")
+    n, j, hh, wh = hm.shape
+    if tuple(pairs_dev.shape) != (j,):
+        raise MvalError(f"flip_merge_heatmaps: pairs must be ({j},), got {tuple(pairs_dev.shape)}")
+    if out is None:
+        out = torch.empty_like(hm, memory_format=torch.contiguous_format)
+    elif out.shape != hm.shape or out._base is not None:
+        raise MvalError(f"flip_merge_heatmaps: out must be a tensor of its own (no view) of shape {tuple(hm.shape)}, got "
+                        f"{'a view of ' if out._base is not None else ''}{tuple(out.shape)}")
+    keys = torch.empty((n, ARGMAX_SLOTS, j), dtype=torch.int64, device=hm.device) if keep_keys else None
+    _check(
+        _views_entry("mval_flip_merge_heatmaps")(
+            _p(_req(hm, torch.float32, "heatmaps")), _p(_req(hm_mirrored, torch.float32, "mirrored heatmaps")),
+            _p(_req(pairs_dev, torch.int32, "pairs")), 1 if shift else 0, _p(_req(out, torch.float32, "out")), _p(keys), n, j, hh, wh, _stream(),
+        ),
+        "mval_flip_merge_heatmaps",
+    )
+    if keep_keys:
+        remember_argmax_keys(out, keys)
+    else:
+        forget_argmax_keys(out)
+    return out
+
+
 def reprojection_xe(kp3d, proj, hm, b, v, j, hh, wh, sigma, *, view_valid=None, view_joint_valid=None):
     """mval_reprojection_xe_masked: (b,) float64; under a mask the sum over the present views / entries of each frame."""
     mask, kind = _mask_arg(view_valid, view_joint_valid, b, v, j)

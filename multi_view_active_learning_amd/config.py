@@ -24,6 +24,9 @@ def _data_defaults():
     d.USE_IMAGE_AUG = True
     d.USE_CONST_AUG_MAGNITUDE = True
     d.ROTATE_TARGETS = "none"  # not in the reference (its Rotate drops the rotated heat-maps): utils.augmentation.ROTATE_TARGETS
+    # not in the reference (which has no flip test): the left/right joint pairs [[a, b], ...] of the skeleton for (AL|EVAL).FLIP_TEST;
+    # empty = the default of DATA.TYPE (utils.flip_test.flip_pairs)
+    d.FLIP_PAIRS = []
     return d
 
 
@@ -73,6 +76,10 @@ def get_default_configs():
     # not in the reference (whose DLT takes every inlier view at the same weight): per-entry weights inside the triangulation of the
     # pool-scoring passes, "none" | "conf" (the peak heights of DECODE_REFINE); check_triangulation_weights below, DESIGN.md 6.7
     c.AL.TRIANGULATION_WEIGHTS = "none"
+    # not in the reference (which runs the network once per image): the flip test of the pool-scoring passes, "none" | "mirror" |
+    # "mirror_shift" -- a second forward on the mirrored images, flipped back (and moved one column: HRNet's SHIFT_HEATMAP) and
+    # averaged with the first before anything decodes; check_flip_test below, DESIGN.md 6.8
+    c.AL.FLIP_TEST = "none"
     c.AL.CLUSTER = CN()  # EXPR_TYPE "CLUSTER" (strategy.py:137-191): what ActiveLearningStrategy.cluster writes
     c.AL.CLUSTER.TYPE = "LOSS"  # LOSS | POSE (cluster_type below)
     c.AL.CLUSTER.SAVE_PATH = ""
@@ -98,6 +105,7 @@ def get_default_configs():
     c.EVAL.REFINE_3D_WEIGHTS = "none"
     c.EVAL.UNDISTORT = "none"  # not in the reference: AL.UNDISTORT for evaluate_mkpe / evaluate_all
     c.EVAL.TRIANGULATION_WEIGHTS = "none"  # not in the reference: AL.TRIANGULATION_WEIGHTS for evaluate_mkpe / evaluate_all
+    c.EVAL.FLIP_TEST = "none"  # not in the reference: AL.FLIP_TEST for evaluate_mkpe / evaluate_all / evaluate_2d_pckh / evaluate
 
     c.POSE_ESTIMATOR = _pose_defaults()
     c.DATA = _data_defaults()
@@ -218,4 +226,14 @@ def check_undistort(value, use_reprojection_xe=False):
         raise ValueError("undistortion %r together with the XE metric (AL.USE_REPROJECTION_XE / use_reprojection_xe): the rendered map "
                          "sits at the pinhole reprojection and the predicted one at distorted pixels (accepted are %s)"
                          % (value, ", ".join(repr(m) for m in UNDISTORTS)))
+    return value
+
+
+FLIP_TESTS = ("none", "mirror", "mirror_shift")  # "mirror": HRNet's TEST.FLIP_TEST; "mirror_shift": with its TEST.SHIFT_HEATMAP (mval_flip_merge_heatmaps)
+
+
+def check_flip_test(value):
+    """A valid (AL|EVAL).FLIP_TEST / ``mode`` of utils.flip_test, or ValueError naming the accepted ones."""
+    if not isinstance(value, str) or value not in FLIP_TESTS:
+        raise ValueError("flip test %r: accepted are %s" % (value, ", ".join(repr(m) for m in FLIP_TESTS)))
     return value

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from .pose_estimators.loss import Pose2DMeanSquaredError
-from .utils import coreset, evaluation, preprocess, triangulation
+from .utils import coreset, evaluation, flip_test, preprocess, triangulation
 
 _KIND = {"HP": _lib.SCORE_HP, "MPE": _lib.SCORE_MPE, "BSB": _lib.SCORE_BSB}
 
@@ -274,18 +274,49 @@ class ActiveLearningStrategy:
 
     # ---- model glue ---------------------------------------------------------------
     @staticmethod
-    def _compute_batch_heatmap(pose_estimator, data):
-        """strategy.py:772-782: (B,V,C,H,W) -> (B*V,C,H,W), frame-major / view-minor.  A compact batch carries the resized views
-        as uint8 (B,V,H,W,3), a quarter of the bytes, and is normalised on the device (``mval_normalize_views_u8``) into the
-        float32 tensor the reference's loader would have uploaded, bit for bit."""
+    def _batch_images_nchw(data):
+        """The batch's images as the network takes them: (B,V,C,H,W) -> (B*V,C,H,W), frame-major / view-minor.  A compact batch
+        carries the resized views as uint8 (B,V,H,W,3), a quarter of the bytes, and is normalised on the device
+        (``mval_normalize_views_u8``) into the float32 tensor the reference's loader would have uploaded, bit for bit."""
         images = data["images"].cuda()
         if images.dtype == torch.uint8:
             if images.dim() != 5 or images.shape[4] != 3:
                 raise ValueError("uint8 images must be (B, V, H, W, 3), got %s" % (tuple(images.shape),))
             h, w = images.shape[2], images.shape[3]
-            return pose_estimator(preprocess.normalize_views_u8(images.reshape([-1, h, w, 3])))
+            return preprocess.normalize_views_u8(images.reshape([-1, h, w, 3]))
         c, h, w = images.shape[2], images.shape[3], images.shape[4]
-        return pose_estimator(images.reshape([-1, c, h, w]))
+        return images.reshape([-1, c, h, w])
+
+    @staticmethod
+    def _compute_batch_heatmap(pose_estimator, data):
+        """strategy.py:772-782: the network on ``_batch_images_nchw`` (float32 or uint8 compact batches)."""
+        return pose_estimator(ActiveLearningStrategy._batch_images_nchw(data))
+
+    def _compute_batch_heatmap_flip(self, pose_estimator, data, mode):
+        """``_compute_batch_heatmap`` under the flip test ``mode`` "mirror" | "mirror_shift" (DESIGN.md 6.8): the same batch
+        (``_batch_images_nchw``: a uint8 compact batch is normalised once and the float32 result is mirrored), then
+        ``flip_test_heatmaps`` -- the network, the mirrored batch, the network again, the merge, all on the caller's stream.  The
+        merged maps carry their arg-max keys."""
+        return flip_test.flip_test_heatmaps(pose_estimator, self._batch_images_nchw(data), self._flip_pairs(), mode)
+
+    def _flip_pairs(self):
+        """``flip_pairs`` of the config's DATA node, resolved on first use (a bad DATA.FLIP_PAIRS raises there)."""
+        if "_flip_pairs_table" not in self.__dict__:
+            self._flip_pairs_table = flip_test.flip_pairs(self.al_cfg.DATA)
+        return self._flip_pairs_table
+
+    def _flip_kwargs(self, node):
+        """What a pass hands to ``_pool_loop`` for the FLIP_TEST of the config node ``node`` ("AL" | "EVAL"), read and checked once
+        per pass: nothing under "none" or where the field is absent (the call is then the one it always was), else ``flip=mode`` --
+        and the pair table is resolved, so that a bad one raises before the pass starts."""
+        from .config import check_flip_test
+
+        cfg = getattr(self.al_cfg, node)
+        mode = check_flip_test(cfg.FLIP_TEST if "FLIP_TEST" in cfg else "none")
+        if mode == "none":
+            return {}
+        self._flip_pairs()
+        return {"flip": mode}
 
     @staticmethod
     def _compute_batch_loss(gt_heatmap, heatmaps, per_view_joint_valid, loss):
@@ -546,13 +577,19 @@ class ActiveLearningStrategy:
         ids, rest, als = self._score_columns(heatmaps, dp, strategies)
         return torch.cat(ids + [torch.zeros_like(als[0])] + rest + als, dim=1)
 
-    def _pool_loop(self, data_loader, pose_estimator, body, inputs=None, stage=_stage_batch):
+    def _pool_loop(self, data_loader, pose_estimator, body, inputs=None, stage=_stage_batch, flip="none"):
         """The loop of a pass over a pool: per batch ``stage(dp)`` (small tensors to the device BEFORE the network launch: no
         host-blocking copy on the side stream), the network, then ``body(*args)`` on the side stream (parallel.PostStream:
         beside the next batch's network), where ``args = inputs(heatmaps, dp)`` names every device tensor the body reads --
         by default the heat-maps, their arg-max keys where the network kept them, and the batch.  Nothing is copied to the
-        host; the caller's stream has joined the side stream when the list of the bodies' results is returned."""
+        host; the caller's stream has joined the side stream when the list of the bodies' results is returned.
+        ``flip`` "mirror" | "mirror_shift": the heat-maps of every batch are ``_compute_batch_heatmap_flip``'s -- two forwards and the
+        merge on the caller's stream, before the side stream takes over; the merged tensor has arg-max keys like a network output."""
         from .parallel import PostStream
+
+        heatmaps_of = self._compute_batch_heatmap
+        if flip != "none":  # (resolved once per pass: the default path runs the line it always ran)
+            heatmaps_of = lambda pe, dp: self._compute_batch_heatmap_flip(pe, dp, flip)  # noqa: E731
 
         if inputs is None:
             inputs = lambda hm, dp: (hm, _lib.argmax_keys_of(hm) if torch.is_tensor(hm) and hm.is_cuda else None, dp)  # noqa: E731
@@ -560,7 +597,7 @@ class ActiveLearningStrategy:
         with torch.no_grad():
             for dp in data_loader:
                 dp = stage(dp)
-                args = inputs(self._compute_batch_heatmap(pose_estimator, dp), dp)
+                args = inputs(heatmaps_of(pose_estimator, dp), dp)
                 with post.batch(*args):
                     results.append(body(*args))
         post.join()
@@ -595,7 +632,8 @@ class ActiveLearningStrategy:
         the reference's gather order (batch -> sample -> rank), but with one device->host
         copy and (when torch.distributed is initialised) one all_gather for the whole pass."""
         self._pending_checks = []
-        tables = self._pool_loop(data_loader, pose_estimator, lambda hm, _keys, dp: self.score_batch(hm, dp), stage=self._stage_masked)
+        tables = self._pool_loop(data_loader, pose_estimator, lambda hm, _keys, dp: self.score_batch(hm, dp), stage=self._stage_masked,
+                                 **self._flip_kwargs("AL"))
         gathered = self._gather_score_tables(tables, 6 + 3 * self.num_joints)
         return _empty_sal_dict() if gathered is None else tables_to_sal_dict(*gathered)
 
@@ -607,7 +645,7 @@ class ActiveLearningStrategy:
         strategies = check_strategies(strategies)
         self._pending_checks = []
         tables = self._pool_loop(data_loader, pose_estimator, lambda hm, _keys, dp: self.score_batch_all(hm, dp, strategies),
-                                 stage=self._stage_masked)
+                                 stage=self._stage_masked, **self._flip_kwargs("AL"))
         gathered = self._gather_score_tables(tables, 6 + 3 * self.num_joints + len(strategies))
         if gathered is None:
             return OrderedDict((s, _empty_sal_dict()) for s in strategies)
@@ -806,7 +844,8 @@ class ActiveLearningStrategy:
         EVAL.UNDISTORT "brown": the undistortion of ``triangulate_batch(undistort=...)`` with the batch's ``intrinsics`` and
         ``distortion`` (KeyError when a batch lacks them).
         EVAL.TRIANGULATION_WEIGHTS "conf" (needs EVAL.DECODE_REFINE): the confidence-weighted triangulation of
-        ``triangulate_batch(weights="conf")``; the validity column is then ``joint_valid & joint_used`` too."""
+        ``triangulate_batch(weights="conf")``; the validity column is then ``joint_valid & joint_used`` too.
+        EVAL.FLIP_TEST "mirror" | "mirror_shift": the heat-maps are the flip-test average of two forwards."""
         from .config import check_decode_refine, check_refine_3d, check_triangulation_weights, check_undistort
 
         ev = self.al_cfg.EVAL
@@ -841,7 +880,7 @@ class ActiveLearningStrategy:
                 scored = ((scored != 0) & r["joint_used"].bool()).to(torch.float32)
             return (r["keypoints_3d"].to(torch.float32), torch.as_tensor(dp["3d_keypoints"]).to(hm.device, torch.float32), scored)
 
-        rows = self._pool_loop(data_loader, pose_estimator, triangulate, inputs, stage=self._stage_masked)
+        rows = self._pool_loop(data_loader, pose_estimator, triangulate, inputs, stage=self._stage_masked, **self._flip_kwargs("EVAL"))
         preds, gts, valids = ([r[k] for r in rows] for k in range(3))
         sizes = [p.shape[0] for p in preds]
         from .parallel import all_gather_reference_order as gather
@@ -928,7 +967,7 @@ class ActiveLearningStrategy:
                 rows = rows.index_select(0, dp["view_rows"])
             return rows
 
-        rows = self._pool_loop(data_loader, pose_estimator, decode, stage=self._stage_pckh_targets)
+        rows = self._pool_loop(data_loader, pose_estimator, decode, stage=self._stage_pckh_targets, **self._flip_kwargs("EVAL"))
         from .parallel import all_gather_reference_order as gather
 
         if rows:

@@ -400,6 +400,42 @@ int mval_frame_loss(const float* heatmaps, const float* gt, const uint8_t* valid
 int mval_frame_loss_points(const float* heatmaps, const double* pt, double sigma, const uint8_t* valid, float* out,
                            double* per_map, int64_t n_frames, int maps_per_frame, int hh, int wh, void* stream);
 
+/* Workspace bytes of one mval_weighted_mse_fwd / _points_fwd call (0 for non-positive sizes). */
+size_t mval_weighted_mse_workspace_bytes(int64_t n_images, int n_joints);
+/* The training loss with per-joint weights and online hard key-point mining (no counterpart in the reference; HRNet's
+ * USE_TARGET_WEIGHT and JointsOHKMMSELoss).  lead = n_images * n_joints maps m = n * n_joints + j:
+ *   S[m]    = sum over the map's pixels of (h - g)^2: float32 difference and square, float64 sum, in mval_frame_loss's pixel ->
+ *             lane assignment and order (the same kernel), so S[m] has the bits of that entry's per_map[m]
+ *   l[m]    = (double)weight[m] * S[m], one rounding                                            -> per_map [lead] f64
+ *   per image its n_joints values l are ranked in torch.argmax's order (NaN first, ties to the lowest joint); the first topk are
+ *   selected, all of them for topk == 0: wsel[m] = selected ? weight[m] : 0.0f                  -> wsel [lead] f32
+ *   T[n]    = sum of the selected l[n][j], ascending j, sequential float64
+ *   out[0]  = (float)( (sum of T[n], ascending n, sequential float64) / (n_images * hh * wh) )  -> out [1] f32
+ * The divisor omits n_joints as mval_masked_mse_fwd's callers' does, and there is no division by topk: topk == n_joints is the
+ * weighted loss and a smaller topk only removes terms (HRNet divides by topk and carries a factor 0.5).  The weight multiplies
+ * the squared error: HRNet's target_weight t scales prediction and target, which is weight = t * t.
+ *   h, g [n_images][n_joints][hh][wh] f32 ; weight [lead] f32, finite and >= 0 (the caller's duty: a launcher does not synchronise) ;
+ *   0 <= topk <= n_joints ; ws >= mval_weighted_mse_workspace_bytes.
+ * A map with weight == 0 is not read, S = +0.0: NaNs under a zero weight do not reach the loss.  A NaN l ranks first and makes
+ * the loss NaN.  No atomics: T[n] does not depend on the other images.  n_images == 0: out = 0, nothing else is touched.
+ * Three launches. */
+int mval_weighted_mse_fwd(const float* h, const float* g, const float* weight, int topk, float* out, double* per_map,
+                          float* wsel, void* ws, int64_t n_images, int n_joints, int hh, int wh, void* stream);
+/* grad_h = ((2 (h - g)) * gs) * wsel[m] with gs = grad_out[0] / (float)(n_images * hh * wh), float32, every product rounded on
+ * its own; a map with wsel == 0 is not read and gets +0.0f.  With weights in {0, 1} and topk == 0 the bits of mval_masked_mse_bwd
+ * under that mask.  grad_out [1] f32 ; wsel [lead] f32 from the forward ; grad_h [lead][hh][wh] f32. */
+int mval_weighted_mse_bwd(const float* h, const float* g, const float* wsel, const float* grad_out, float* grad_h,
+                          int64_t n_images, int n_joints, int hh, int wh, void* stream);
+/* The same two against ground truth rendered per pixel: pt, sigma and sigma_per_map as in mval_masked_mse_points_fwd (a scalar
+ * sigma must be > 0, an array is its uploader's to check) -- bit-identical to the read form on the maps mval_gt_heatmaps writes.
+ * A map that does not count is not rendered (its point may be NaN).  hh * wh <= INT32_MAX - 1024. */
+int mval_weighted_mse_points_fwd(const float* h, const double* pt, double sigma, const double* sigma_per_map,
+                                 const float* weight, int topk, float* out, double* per_map, float* wsel, void* ws,
+                                 int64_t n_images, int n_joints, int hh, int wh, void* stream);
+int mval_weighted_mse_points_bwd(const float* h, const double* pt, double sigma, const double* sigma_per_map,
+                                 const float* wsel, const float* grad_out, float* grad_h, int64_t n_images, int n_joints, int hh,
+                                 int wh, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Per-view input pipeline (dataset/dataset.py:158-220 prepare_single_view, pixel work only)
  * ------------------------------------------------------------------------------------------- */

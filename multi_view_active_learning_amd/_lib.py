@@ -43,6 +43,7 @@ def lib() -> C.CDLL:
                 l.mval_last_error.restype = C.c_char_p
                 l.mval_kcenter_workspace_bytes.restype = C.c_size_t
                 l.mval_frame_loss_workspace_bytes.restype = C.c_size_t
+                l.mval_weighted_mse_workspace_bytes.restype = C.c_size_t
                 l.mval_kmeans_workspace_bytes.restype = C.c_size_t
                 l.mval_net_create.restype = C.c_void_p
                 l.mval_packed_weight_floats.restype = C.c_size_t
@@ -699,6 +700,105 @@ def frame_loss_points(h, pt, sigma, valid, n_frames, maps_per_frame, hh, wh):
         "mval_frame_loss_points",
     )
     return out, per_map
+
+
+def weighted_mse_workspace_bytes(n_images: int, n_joints: int) -> int:
+    return int(lib().mval_weighted_mse_workspace_bytes(C.c_longlong(n_images), C.c_int(n_joints)))
+
+
+def loss_weights(weight, lead, device, what):
+    """The (lead,) f32 per-map weights of the weighted loss on ``device``.  Like ``_points_sigma``: weights that arrive on the host are
+    checked there (finite and >= 0) and staged through pinned memory; a device tensor is taken as it is -- a NaN there makes the
+    loss NaN, a negative weight a loss that ranks and sums as the contract says but means nothing."""
+    t = torch.as_tensor(weight).to(torch.float32).reshape(-1)
+    if t.numel() != lead:
+        raise MvalError(f"{what}: {t.numel()} weights for {lead} maps")
+    if not t.is_cuda:
+        if lead and not bool((torch.isfinite(t) & (t >= 0)).all()):
+            raise MvalError(f"{what}: weights must be finite and >= 0")
+        t = t.contiguous()
+        t = (t if t.is_pinned() or not torch.cuda.is_available() else t.pin_memory()).to(device, non_blocking=True)
+    return t.contiguous()
+
+
+def _weighted_outputs(h, n_images, n_joints):
+    lead = n_images * n_joints
+    out = torch.zeros((), dtype=torch.float32, device=h.device)
+    per_map = torch.empty((lead,), dtype=torch.float64, device=h.device)
+    wsel = torch.empty((lead,), dtype=torch.float32, device=h.device)
+    ws = torch.empty((max(1, weighted_mse_workspace_bytes(n_images, n_joints) // 8),), dtype=torch.float64, device=h.device)
+    return out, per_map, wsel, ws
+
+
+def weighted_mse_fwd(h, g, weight, topk, n_images, n_joints, hh, wh):
+    """The weighted / hard-key-point-mining loss (mval_weighted_mse_fwd): h, g (n_images, n_joints, hh, wh) f32, weight
+    (n_images * n_joints,) f32 >= 0, topk in [0, n_joints] (0: every joint counts) -> (loss () f32, every map's weight * sum of
+    squared errors (lead,) f64, the weights of the selected maps and 0 elsewhere (lead,) f32: what the backward reads)."""
+    what = "mval_weighted_mse_fwd"
+    lead = n_images * n_joints
+    if h.numel() != lead * hh * wh or g.numel() != h.numel():
+        raise MvalError(f"{what}: heat-maps {tuple(h.shape)} / ground truth {tuple(g.shape)} are not {lead} maps of {hh} x {wh}")
+    w = loss_weights(weight, lead, h.device, what)
+    out, per_map, wsel, ws = _weighted_outputs(h, n_images, n_joints)
+    _check(
+        lib().mval_weighted_mse_fwd(
+            _p(_req(h, torch.float32, "heatmaps")), _p(_req(g, torch.float32, "gt")), _p(w), C.c_int(topk), _p(out), _p(per_map),
+            _p(wsel), _p(ws), C.c_longlong(n_images), C.c_int(n_joints), C.c_int(hh), C.c_int(wh), _stream(),
+        ),
+        what,
+    )
+    return out, per_map, wsel
+
+
+def weighted_mse_points_fwd(h, pt, sigma, weight, topk, n_images, n_joints, hh, wh):
+    """``weighted_mse_fwd`` against the maps mval_gt_heatmaps renders from pt (lead, 2) f64, without them.  sigma: a float, or one
+    per map ((lead,) array or tensor, host or device)."""
+    what = "mval_weighted_mse_points_fwd"
+    lead = n_images * n_joints
+    _points_args(h, pt, lead, hh, wh, what)
+    s, sm = _points_sigma(sigma, lead, h.device, what)
+    w = loss_weights(weight, lead, h.device, what)
+    out, per_map, wsel, ws = _weighted_outputs(h, n_images, n_joints)
+    _check(
+        lib().mval_weighted_mse_points_fwd(
+            _p(_req(h, torch.float32, "heatmaps")), _p(_req(pt, torch.float64, "points")), C.c_double(s), _p(sm), _p(w),
+            C.c_int(topk), _p(out), _p(per_map), _p(wsel), _p(ws), C.c_longlong(n_images), C.c_int(n_joints), C.c_int(hh),
+            C.c_int(wh), _stream(),
+        ),
+        what,
+    )
+    return out, per_map, wsel
+
+
+def weighted_mse_bwd(h, g, wsel, grad_out, n_images, n_joints, hh, wh):
+    """grad_h = ((2 (h - g)) * grad_out / (n_images * hh * wh)) * wsel[map], +0.0 on the maps with wsel == 0 (not read)."""
+    gh = torch.empty_like(h)
+    _check(
+        lib().mval_weighted_mse_bwd(
+            _p(_req(h, torch.float32, "heatmaps")), _p(_req(g, torch.float32, "gt")), _p(_req(wsel, torch.float32, "wsel")),
+            _p(_req(grad_out, torch.float32, "grad")), _p(gh), C.c_longlong(n_images), C.c_int(n_joints), C.c_int(hh), C.c_int(wh),
+            _stream(),
+        ),
+        "mval_weighted_mse_bwd",
+    )
+    return gh
+
+
+def weighted_mse_points_bwd(h, pt, sigma, wsel, grad_out, n_images, n_joints, hh, wh):
+    what = "mval_weighted_mse_points_bwd"
+    lead = n_images * n_joints
+    _points_args(h, pt, lead, hh, wh, what)
+    s, sm = _points_sigma(sigma, lead, h.device, what)
+    gh = torch.empty_like(h)
+    _check(
+        lib().mval_weighted_mse_points_bwd(
+            _p(_req(h, torch.float32, "heatmaps")), _p(_req(pt, torch.float64, "points")), C.c_double(s), _p(sm),
+            _p(_req(wsel, torch.float32, "wsel")), _p(_req(grad_out, torch.float32, "grad")), _p(gh), C.c_longlong(n_images),
+            C.c_int(n_joints), C.c_int(hh), C.c_int(wh), _stream(),
+        ),
+        what,
+    )
+    return gh
 
 
 def mkpe(pred, gt, valid, s, j, gt_rows):

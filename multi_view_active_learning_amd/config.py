@@ -97,6 +97,13 @@ def get_default_configs():
     c.TRAIN.OPTIM.TOTAL_STEPS = 5000
     c.TRAIN.OPTIM.LR = 0.001
     c.TRAIN.OPTIM.LR_DECAY_STEP_SIZE = 3000
+    # not in the reference (whose one loss is the masked MSE): per-joint weights and hard key-point mining of the training loss
+    # (check_train_loss, strategy.compose_joint_weights); at these defaults train_step is what it always was
+    c.TRAIN.LOSS = CN()
+    c.TRAIN.LOSS.JOINT_WEIGHTS = []  # DATA.NUM_JOINTS floats >= 0 (HRNet's USE_DIFFERENT_JOINTS_WEIGHT, squared), or empty: every joint 1
+    c.TRAIN.LOSS.OHKM_TOPK = 0  # per image only the OHKM_TOPK joints of the largest weighted loss count (JointsOHKMMSELoss); 0: all
+    c.TRAIN.LOSS.PSEUDO_LABEL_WEIGHT = 1.0  # factor on every joint of a frame whose batch entry pseudo_label is nonzero
+    c.TRAIN.LOSS.WEIGHT_KEY = ""  # name of a batch key holding (B, V, J) weights >= 0 ("" = none)
 
     c.EVAL = CN()
     c.EVAL.METRIC = "3DPCK"
@@ -237,3 +244,25 @@ def check_flip_test(value):
     if not isinstance(value, str) or value not in FLIP_TESTS:
         raise ValueError("flip test %r: accepted are %s" % (value, ", ".join(repr(m) for m in FLIP_TESTS)))
     return value
+
+
+def check_train_loss(loss_node, num_joints):
+    """A valid TRAIN.LOSS node for ``num_joints`` joints, or ValueError saying what is accepted.  Returns
+    (joint_weights: a tuple of num_joints floats or (), ohkm_topk, pseudo_label_weight, weight_key)."""
+    jw = loss_node.JOINT_WEIGHTS if "JOINT_WEIGHTS" in loss_node else []
+    topk = loss_node.OHKM_TOPK if "OHKM_TOPK" in loss_node else 0
+    pw = loss_node.PSEUDO_LABEL_WEIGHT if "PSEUDO_LABEL_WEIGHT" in loss_node else 1.0
+    key = loss_node.WEIGHT_KEY if "WEIGHT_KEY" in loss_node else ""
+
+    def weight(x):
+        return not isinstance(x, bool) and isinstance(x, (int, float)) and 0.0 <= float(x) < float("inf")
+
+    if not isinstance(jw, (list, tuple)) or len(jw) not in (0, num_joints) or not all(weight(x) for x in jw):
+        raise ValueError("TRAIN.LOSS.JOINT_WEIGHTS %r: accepted are %d finite numbers >= 0 (one per joint), or an empty list" % (jw, num_joints))
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 0 <= topk <= num_joints:
+        raise ValueError("TRAIN.LOSS.OHKM_TOPK %r: accepted is an integer in [0, %d] (0 = every joint counts)" % (topk, num_joints))
+    if not weight(pw):
+        raise ValueError("TRAIN.LOSS.PSEUDO_LABEL_WEIGHT %r: accepted is a finite number >= 0" % (pw,))
+    if not isinstance(key, str):
+        raise ValueError("TRAIN.LOSS.WEIGHT_KEY %r: accepted is a string, the name of a batch key (\"\" for none)" % (key,))
+    return tuple(float(x) for x in jw), topk, float(pw), key

@@ -28,7 +28,9 @@ __device__ T np_pairwise_sum(const T* a, int n) {
 }
 
 // order of torch.argmax: NaN is the maximum; ties -> lowest flat index.  True when (v, i) comes before (bv, bi).
-__device__ __forceinline__ bool argmax_better(float v, int i, float bv, int bi) {
+// (T: float for heat-map values, double for the per-map losses loss_weighted.hip ranks)
+template <typename T>
+__device__ __forceinline__ bool argmax_better(T v, int i, T bv, int bi) {
   const bool vn = v != v, bn = bv != bv;
   if (vn != bn) return vn;
   if (vn) return i < bi;

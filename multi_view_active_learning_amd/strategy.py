@@ -247,6 +247,50 @@ def _stage_small(t):
     return (t if t.is_pinned() else t.pin_memory()).to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
 
 
+def compose_joint_weights(per_view_joint_valid, loss_cfg, data):
+    """The per-map weights of the weighted training loss (``pose_2d_mse_weighted``) as a (B, V, J) float32 host
+    tensor, or None where nothing asks for them: every field of ``loss_cfg`` (TRAIN.LOSS, checked by ``check_train_loss``; None
+    reads as the defaults) at its default and neither ``data[WEIGHT_KEY]`` nor ``data["pseudo_label"]`` in the batch.  Otherwise
+      w[b, v, j] = (valid != 0 ? 1 : 0) * JOINT_WEIGHTS[j] * (pseudo_label[b] ? PSEUDO_LABEL_WEIGHT : 1) * data[WEIGHT_KEY][b, v, j]
+    in float32, the factors applied in that order (an empty JOINT_WEIGHTS, a missing ``pseudo_label`` and a missing key are 1).
+    ``pseudo_label`` is (B,), nonzero for a pseudo-labelled frame: the loader that sets ``gt_sigma`` per frame sets it too.  A
+    device tensor among the inputs keeps the result on the device; the loss checks weights only where they are on the host."""
+    from .config import check_train_loss
+
+    valid = torch.as_tensor(per_view_joint_valid)
+    if valid.dim() != 3:
+        raise ValueError("compose_joint_weights: per_view_joint_valid must be (B, V, J), got %s" % (tuple(valid.shape),))
+    b, v, j = valid.shape
+    joint_weights, topk, pseudo_weight, key = ((), 0, 1.0, "") if loss_cfg is None else check_train_loss(loss_cfg, j)
+    extra = data[key] if key and key in data else None
+    pseudo = data["pseudo_label"] if "pseudo_label" in data else None
+    if not joint_weights and topk == 0 and pseudo_weight == 1.0 and key == "" and extra is None and pseudo is None:
+        return None
+    w = (valid != 0).to(torch.float32)
+    if joint_weights:
+        w = w * torch.tensor(joint_weights, dtype=torch.float32, device=w.device).reshape(1, 1, j)
+    if pseudo is not None:
+        pseudo = torch.as_tensor(pseudo)
+        if tuple(pseudo.shape) != (b,):
+            raise ValueError("compose_joint_weights: pseudo_label must be (B,) = (%d,), got %s" % (b, tuple(pseudo.shape)))
+        factor = torch.where(pseudo != 0, torch.tensor(pseudo_weight, dtype=torch.float32, device=pseudo.device),
+                             torch.ones((), dtype=torch.float32, device=pseudo.device))
+        w = _times(w, factor.reshape(b, 1, 1))
+    if extra is not None:
+        extra = torch.as_tensor(extra).to(torch.float32)
+        if tuple(extra.shape) != (b, v, j):
+            raise ValueError("compose_joint_weights: data[%r] must be (B, V, J) = %s, got %s" % (key, (b, v, j), tuple(extra.shape)))
+        w = _times(w, extra)
+    return w
+
+
+def _times(w, factor):
+    """w * factor in float32; where one of the two is on the device, there."""
+    if factor.is_cuda != w.is_cuda:
+        w, factor = (w.to(factor.device), factor) if factor.is_cuda else (w, factor.to(w.device))
+    return w * factor
+
+
 class ActiveLearningStrategy:
     def __init__(self, al_cfg):
         self.al_cfg = al_cfg
@@ -353,19 +397,36 @@ class ActiveLearningStrategy:
         -> backward -> optimizer step -> scheduler step.  Returns (loss_value, stepped).
         The target is ``select_train_target``'s: ``gt_heatmap`` where the batch has it, else the maps of ``gt_points`` (or of
         ``2d_keypoints / STRIDE``, close to the reference's maps but not their bits) under ``gt_sigma`` / DATA.SIGMA, rendered
-        inside the loss kernels and never materialised; ``images`` may be uint8 (``_compute_batch_heatmap``)."""
+        inside the loss kernels and never materialised; ``images`` may be uint8 (``_compute_batch_heatmap``).
+        Where ``compose_joint_weights`` returns weights -- a TRAIN.LOSS field off its default, a ``pseudo_label`` or the
+        TRAIN.LOSS.WEIGHT_KEY tensor in the batch -- the loss is ``pose_2d_mse_weighted`` (``_from_points``) under them and
+        TRAIN.LOSS.OHKM_TOPK; otherwise the calls are the ones they always were."""
         optimizer.zero_grad()
         kind, target, sigma = select_train_target(data, self.al_cfg)
         if kind == "points":  # the small tensors go up before the network, like _stage_batch's
             target, sigma = self._stage_train_points(target, sigma)
+        loss_cfg = self.al_cfg.TRAIN.LOSS if "LOSS" in self.al_cfg.TRAIN else None
+        weights = compose_joint_weights(data["per_view_joint_valid"], loss_cfg, data)
+        if weights is not None:  # TRAIN.LOSS, pseudo_label or the WEIGHT_KEY tensor ask for the weighted loss: they go up here too
+            if not weights.is_cuda and not bool((torch.isfinite(weights) & (weights >= 0)).all()):  # (the loss checks host weights only)
+                raise ValueError("train_step: every loss weight must be finite and >= 0")
+            weights = _stage_small(weights)
+            topk = loss_cfg.OHKM_TOPK if loss_cfg is not None and "OHKM_TOPK" in loss_cfg else 0
         heatmaps = self._compute_batch_heatmap(pose_estimator, data)
         if kind == "gt_heatmap":
             gt = target.cuda()
-        pv = data["per_view_joint_valid"].to(torch.uint8).cuda()
-        if kind == "gt_heatmap":
-            batch_loss = self._compute_batch_loss(gt, heatmaps, pv, self.loss)
+        if weights is not None:
+            j = heatmaps.shape[1]
+            if kind == "gt_heatmap":
+                batch_loss = self.loss.pose_2d_mse_weighted(heatmaps, gt.reshape((-1, j) + tuple(gt.shape[-2:])), weights.reshape(-1, j), topk)
+            else:
+                batch_loss = self.loss.pose_2d_mse_weighted_from_points(heatmaps, target.reshape([-1, j, 2]), sigma, weights.reshape(-1, j), topk)
         else:
-            batch_loss = self._compute_batch_loss_points(target, sigma, heatmaps, pv, self.loss)
+            pv = data["per_view_joint_valid"].to(torch.uint8).cuda()
+            if kind == "gt_heatmap":
+                batch_loss = self._compute_batch_loss(gt, heatmaps, pv, self.loss)
+            else:
+                batch_loss = self._compute_batch_loss_points(target, sigma, heatmaps, pv, self.loss)
         value = batch_loss.data.item()
         ok = not (math.isnan(value) or math.isinf(value) or value > self.al_cfg.TRAIN.LOSS_CLIP_VALUE)
         if ok:

@@ -139,12 +139,18 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvArgs a) {
   float acc[DC_CO];
 #pragma unroll
   for (int q = 0; q < DC_CO; q++) acc[q] = 0.f;
+  // dil == 2: (dy, dx) index the zero-dilated input (the data gradient of a stride-2 conv); only even positions carry data
+  const int dsh = a.dil == 2 ? 1 : 0;
   for (int ky = 0; ky < a.k; ky++) {
-    const int iy = y * a.stride - a.pad + ky;
-    if (iy < 0 || iy >= a.Hin) continue;
+    const int dy = y * a.stride - a.pad + ky;
+    if (dy < 0 || (dy & dsh)) continue;
+    const int iy = dy >> dsh;
+    if (iy >= a.Hin) continue;
     for (int kx = 0; kx < a.k; kx++) {
-      const int ix = x * a.stride - a.pad + kx;
-      if (ix < 0 || ix >= a.Win) continue;
+      const int dx = x * a.stride - a.pad + kx;
+      if (dx < 0 || (dx & dsh)) continue;
+      const int ix = dx >> dsh;
+      if (ix >= a.Win) continue;
       const float* wp = a.w + ((int64_t)(ky * a.k + kx) * a.Cin) * a.Cout + c0;
       for (int ci = 0; ci < a.Cin; ci++) {
         const float v = a.in_nchw ? a.in[(((int64_t)n * a.Cin + ci) * a.Hin + iy) * a.Win + ix]

@@ -742,8 +742,8 @@ extern "C" int mval_conv_dgrad_scaled(const float* dz, const float* w_packed, co
                                       int accumulate, int N, int hin, int win, int cin, int hout, int wout, int cout, int k,
                                       int stride, int pad, int algo, const uint32_t* dz_amax_row, void* stream) {
   MVAL_REQUIRE(dz && w_packed && ones && zeros && dx && N > 0, "mval_conv_dgrad: bad arguments");
-  MVAL_REQUIRE(algo == MVAL_ALGO_MFMA || algo == MVAL_ALGO_MFMA_BF3 || stride == 1,
-               "mval_conv_dgrad: strided data gradient needs an MFMA kernel");
+  // (the direct kernel reads the zero-dilated dz as well: stride 2 with a cout that is no multiple of 16, which no MFMA kernel stages)
+  MVAL_REQUIRE(stride == 1 || (stride == 2 && algo != MVAL_ALGO_MFMA_H2), "mval_conv_dgrad: stride 1 or 2; the fp16-split form stride 1 only");
   MVAL_REQUIRE(algo != MVAL_ALGO_MFMA_H2 || (stride == 1 && dz_amax_row), "mval_conv_dgrad: fp16-split form: stride 1 with dz's magnitude row");
   ConvArgs a = {};
   dgrad_args(a, N, hin, win, cin, hout, wout, cout, k, stride, pad);

@@ -8,7 +8,10 @@ MADE to: start from the seeded Gaussian batch and, while any pre-activation lies
 gradient (float64, CPU) until it sits 1.5 x TAU away; the other pre-activations move an order of magnitude less, so a few rounds clear all
 of them.  Only the reference model is used (tests/tiny_graphs.py graph_forward); the parameters stay as the case's seed gives them.
 
-    python tests/golden/make_small_graph_inputs.py [case ...]"""
+    python tests/golden/make_small_graph_inputs.py [case ...]
+
+Only the cases named are made again (all of them without arguments); every other array of the file is written back as it was read, which the
+script asserts at its end.  The `linear` cases of the test have no ReLU and draw their inputs when they run: nothing of them is stored."""
 import os
 import sys
 
@@ -51,11 +54,16 @@ def widen(case):
 def main():
     todo = sys.argv[1:] or list(CASES)
     have = dict(np.load(INPUTS)) if os.path.exists(INPUTS) else {}
+    kept = {k: v.copy() for k, v in have.items() if k not in todo}
     for cid in todo:
         print(cid, flush=True)
         xf = widen(CASES[cid])
         have[cid] = xf.numpy()
         np.savez_compressed(INPUTS, **have)
+    # the arrays of the cases that were not asked for come out of the rewritten file as they went in, bit for bit
+    back = np.load(INPUTS)
+    assert set(back.files) == set(have) and all(back[k].dtype == v.dtype and np.array_equal(back[k], v) for k, v in kept.items())
+    print(f"{len(todo)} written, {len(kept)} unchanged")
 
 
 if __name__ == "__main__":

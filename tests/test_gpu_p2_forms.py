@@ -4,8 +4,9 @@ every inference form its dispatch picks, and on the later tiles of a workgroup's
 Which form a launch runs on is read from the library's own dispatch (mval_conv_p2_form: the launcher's dry run, host arithmetic, no GPU;
 tests/p2_forms.py names the forms -- kernel instance + runtime path -- and holds the sweep).  The host tests hold every row of the case table
 to the form it is in the table for, the table to every form a fixed sweep of shapes finds for mval_op_launch, and the forms of the two
-training uses to those the small training graphs reach plus a written-down remainder.  The GPU tests run each row against float64 and repeat
-the form assertion on the shape they ran.
+training uses to those the small training graphs reach (tests/test_train_small_graphs.py runs them against float64 autograd) plus the forms no
+training plan can reach, each with the plan rule that excludes it.  The GPU tests run each row against float64 and repeat the form assertion
+on the shape they ran.
 
 Rows were chosen from the sweep as the cheapest shape (device tensors + float64 reference) that reaches the form with, where the form's own
 conditions allow it, at least two images (three where that costs nothing: an odd batch), a ragged last tile in rows and in columns (odd-tile
@@ -182,23 +183,22 @@ LATE_CASES = [
 CUS_SIZED_FOR = 320  # the LATE_CASES batches exceed resident_cap with up to this many compute units (the MI355X has 256)
 OLDER_REACH = 25  # forms of mval_op_launch that the single-op cases of test_gpu_p2.py reach (test_forms_the_older_case_tables_reach)
 RMS_MIN_ELEMENTS = 12960  # the smallest row of test_gpu_p2.P2_CASES: below it the ratio of two small-sample rms values is noise
-# the forms of the two training uses that no case of tests/test_train_small_graphs.py reaches (test_training_forms_census): the written-down gap
-TRAIN_UNREACHED = [
-    "k1s1_g2_w2x2_nt1_ms2_tw16_e3", "k1s1_g2_w2x2_nt1_ms2_tw16_e3_flat", "k1s1_g2_w2x2_nt1_ms2_tw16_e3_sub", "k1s1_g2_w2x2_nt1_ms2_tw32_e3",
-    "k1s1_g2_w2x2_nt1_ms2_tw32_e3_flat", "k1s1_g2_w2x2_nt1_ms2_tw32_e3_sub", "k1s1_g2_w2x2_nt1_ms2_tw64_e3", "k1s1_g2_w2x2_nt1_ms2_tw64_e3_sub",
-    "k1s1_g2_w2x2_nt1_ms2_tw8_e3", "k1s1_g2_w2x2_nt1_ms2_tw8_e3_flat", "k1s1_g2_w2x2_nt1_ms2_tw8_e3_sub", "k1s1_g2_w4x1_nt1_ms4_tw16_e3",
-    "k1s1_g2_w4x1_nt1_ms4_tw32_e3", "k1s1_g2_w4x1_nt1_ms4_tw32_e3_flat", "k1s1_g2_w4x1_nt1_ms4_tw32_e3_sub", "k1s1_g2_w4x1_nt1_ms4_tw64_e3",
-    "k1s1_g2_w4x1_nt1_ms4_tw64_e3_sub", "k1s1_g2_w4x1_nt2_ms4_tw16_e3_flat", "k1s1_g2_w4x1_nt2_ms4_tw32_e3_flat", "k1s1_g2_w4x1_nt2_ms4_tw64_e3",
-    "k1s1_g2_w4x1_nt2_ms4_tw64_e3_flat", "k1s1_g2_w4x1_nt2_ms4_tw64_e3_sub", "k1s1_g2_w4x1_nt2_ms4_tw8_e3_flat", "k3s1_g1_w2x2_nt3_ms3_ow12_e3",
-    "k3s1_g1_w4x1_nt3_ms3_ow6_e3", "k3s2_g1_w4x1_nt1_ms3_ow6_e3",
-]
-DGRAD_UNREACHED = [
-    "k1s1_g2_w2x2_nt1_ms2_tw16_e3", "k1s1_g2_w2x2_nt1_ms2_tw16_e3_flat", "k1s1_g2_w2x2_nt1_ms2_tw32_e3", "k1s1_g2_w2x2_nt1_ms2_tw32_e3_flat",
-    "k1s1_g2_w2x2_nt1_ms2_tw64_e3", "k1s1_g2_w2x2_nt1_ms2_tw8_e3", "k1s1_g2_w2x2_nt1_ms2_tw8_e3_flat", "k1s1_g2_w4x1_nt1_ms4_tw16_e3",
-    "k1s1_g2_w4x1_nt1_ms4_tw32_e3", "k1s1_g2_w4x1_nt1_ms4_tw32_e3_flat", "k1s1_g2_w4x1_nt1_ms4_tw64_e3", "k1s1_g2_w4x1_nt1_ms4_tw8_e3",
-    "k1s1_g2_w4x1_nt2_ms4_tw16_e3_flat", "k1s1_g2_w4x1_nt2_ms4_tw32_e3_flat", "k1s1_g2_w4x1_nt2_ms4_tw64_e3", "k1s1_g2_w4x1_nt2_ms4_tw64_e3_flat",
-    "k1s1_g2_w4x1_nt2_ms4_tw8_e3_flat", "k3s1_g1_w2x2_nt3_ms3_ow12_e3", "k3s1_g1_w4x1_nt3_ms3_ow6_e3",
-]
+# the forms of the two training uses that no case of tests/test_train_small_graphs.py reaches (test_training_forms_census): those NO training
+# plan reaches (test_no_plan_reaches_the_forms_left_out), each with the plan rule of engine_train.py that excludes it.  Both are the 1x1 conv on
+# at most two cout sub-tiles (kernel couts 8, 24, 32) over a map that is not run as one flattened row -- one or two rows of under 64 pixels:
+# 2 x 16 and 1 x 48 on 16-wide tiles, 1 x 32 on 32-wide ones.  The dispatch of conv_p2.hip has the form, but a plan only puts a conv on the P2
+# kernels whose fp16-split kernel it chose first, and mval_op_algo_supported(MVAL_ALGO_MFMA_H2) has no 1x1 conv of 32 couts or fewer on such
+# a map (the plan runs it on the bf16x3 or the exact-fp32 kernel).
+_H2_FWD = ("TrainPlan._p2_forward_convs takes only ops whose forward algo is ALGO_MFMA_H2, and _choose_algorithms gives that algo only where "
+           "mval_op_algo_supported(ALGO_MFMA_H2) holds: not for this conv")
+_H2_DGRAD = ("TrainPlan._p2_dgrads takes only ops whose dgrad_algo is ALGO_MFMA_H2, and _choose_algorithms gives that algo only where "
+             "mval_op_algo_supported(ALGO_MFMA_H2) holds for the gradient's conv (cin' = cout, cout' = cin): not for this one")
+PLAN_UNREACHABLE = {
+    "train": {"k1s1_g2_w2x2_nt1_ms2_tw16_e3": _H2_FWD, "k1s1_g2_w2x2_nt1_ms2_tw32_e3": _H2_FWD},
+    "dgrad": {"k1s1_g2_w2x2_nt1_ms2_tw16_e3": _H2_DGRAD, "k1s1_g2_w2x2_nt1_ms2_tw32_e3": _H2_DGRAD},
+}
+TRAIN_UNREACHED = sorted(PLAN_UNREACHABLE["train"])
+DGRAD_UNREACHED = sorted(PLAN_UNREACHABLE["dgrad"])
 
 
 def _row_id(row):
@@ -352,14 +352,14 @@ def test_forms_the_older_case_tables_reach():
     assert not any("_nt2_" in k and k.startswith("k1") for k in reached), "no single-op case ran the 1x1 conv with two cout sub-tiles per wave"
 
 
-def _small_graph_forms():
-    """The forms of the training forward and of the data gradient that the default plans of tests/test_train_small_graphs.py's cases run,
-    read off each plan's ops."""
+def _small_graph_forms(cases=None):
+    """The forms of the training forward and of the data gradient that the default plans of tests/test_train_small_graphs.py's cases (all of
+    CASES and LINEAR_CASES, or `cases`) run, read off each plan's ops."""
     import test_train_small_graphs as tsg
     from multi_view_active_learning_amd import engine_train as et
 
     reached = {"train": set(), "dgrad": set()}
-    for case in tsg.CASES.values():
+    for case in (list(tsg.CASES.values()) + list(tsg.LINEAR_CASES.values()) if cases is None else cases):
         plan = tsg._host_plan(case, "default")
         for i, (op, t) in enumerate(zip(plan.graph.ops, plan.ops)):
             hin, win = plan.geo[i][:2]
@@ -372,16 +372,102 @@ def _small_graph_forms():
 
 def test_training_forms_census():
     """The two training uses: the forms the sweep finds for mval_train_forward's convs (48, 3 of them the in_z instances) and for the data
-    gradients mval_train_backward runs on these kernels (32), against those the small training graphs reach (22 and 13, six and three of them by the
-    single-conv cases added with this suite).  The rest is held
-    equal to TRAIN_UNREACHED / DGRAD_UNREACHED: the gap is written down and cannot grow silently -- 1x1 convs at all but a few tile widths and
-    every flattened or stride-2 1x1, the odd-tile 3x3 forms, 3x3 stride 2 at 32 couts or fewer.  (Whole-network training tests run some of them.)"""
+    gradients mval_train_backward runs on these kernels (32), against those the small training graphs reach: 46 and 30 -- 22 and 13 by the
+    graphs of blocks and by the first single-conv cases, 18 and 12 more by the single-conv cases chosen per form, 6 and 5 (the `nt2` forms of
+    the 1x1 conv) by the ReLU-free cases of 16 images.  The rest is held equal to TRAIN_UNREACHED / DGRAD_UNREACHED, which are the forms no
+    training plan reaches (PLAN_UNREACHABLE, two per use): a form that appears without a case, or a case that stops reaching its form, fails here."""
     reached = _small_graph_forms()
     for use, gap in (("train", TRAIN_UNREACHED), ("dgrad", DGRAD_UNREACHED)):
         found = set(pf.sweep(use))
         print(f"[p2 forms] {use}: {len(found)} forms, the small graphs reach {len(reached[use])}")
         assert reached[use] <= found, (use, sorted(reached[use] - found))
         assert sorted(found - reached[use]) == sorted(gap), (use, sorted(found - reached[use] - set(gap)), sorted(set(gap) - (found - reached[use])))
+        assert sorted(gap) == sorted(PLAN_UNREACHABLE[use]) and len(gap) == 2
+    assert (len(pf.sweep("train")), len(pf.sweep("dgrad"))) == (48, 32) and (len(reached["train"]), len(reached["dgrad"])) == (46, 30)
+
+
+def _single_plan_forms(shape):
+    """(training forward, data gradient) form names of conv "c" in the default plan of tiny_graphs.single at a sweep shape (None: no P2 launch)."""
+    import test_train_small_graphs as tsg
+
+    n, cin, cout, h, w, k, s = shape
+    case = dict(graph="single", args=(cin, cout, k, s), n=n, hw=(h, w), seed=1)
+    return tuple(f and pf.name(f) for f in tsg._c_forms(case, tsg._host_plan(case, "default")))
+
+
+def test_no_plan_reaches_the_forms_left_out():
+    """PLAN_UNREACHABLE: EVERY shape of the sweep that the dispatch answers with one of these forms, put behind the head as the conv of
+    tiny_graphs.single, gets a default plan that runs conv c (for `dgrad`: its data gradient) on another kernel family -- and for the reason written
+    down: the library's P2 query accepts the conv, its fp16-split query (what _choose_algorithms asks before a P2 pass may take the op) does not."""
+    from multi_view_active_learning_amd import _lib
+    from multi_view_active_learning_amd.engine import _query_op
+
+    lib = _lib.lib()
+    for use, forms in PLAN_UNREACHABLE.items():
+        for form in forms:
+            cands = pf.sweep(use)[form]
+            assert len(cands) >= 40 and {c[0] for c in cands} == {"conv"}
+            for kind, shape, o, _ in cands:
+                n, cin, cout, h, w, k, s = shape
+                assert (k, s) == (1, 1) and h <= 2 and h * w < 64 and (cin if use == "dgrad" else cout) <= 32, shape
+                got = _single_plan_forms(shape)[use == "dgrad"]
+                assert got is None, (use, form, shape, got)
+                d = _query_op(0, 1, 1, 0, cin, cout, h, w, h, w) if use == "train" else _query_op(0, 1, 1, 0, cout, cin, h, w, h, w)
+                ok = lambda algo: bool(lib.mval_op_algo_supported(C.byref(d), C.c_int(n), C.c_int(algo)))
+                assert ok(pf.ALGO_P2) and not ok(3), (use, form, shape)  # (3: MVAL_ALGO_MFMA_H2)
+
+
+def _train_rows():
+    """(use, form, shape, case) of the single-conv cases chosen per form: for every form that the graphs of blocks and the first single-conv
+    cases (those without `forms`) do not reach, the first case of the table that names it."""
+    import test_train_small_graphs as tsg
+
+    seen = _small_graph_forms([c for c in tsg.CASES.values() if "forms" not in c])
+    rows = []
+    for cid, c in tsg.CASES.items():
+        for use, form in zip(("train", "dgrad"), c.get("forms", (None, None))):
+            if form is not None and form not in seen[use]:
+                seen[use].add(form)
+                rows.append((use, form, (c["n"],) + c["args"][:2] + c["hw"] + c["args"][2:], cid))
+    return rows
+
+
+def test_training_rows_carry_their_edges():
+    """The single-conv cases chosen per form (tests/test_train_small_graphs.py, the cases with `forms`) as rows of the sweeps of the two
+    training uses: each is a shape of its form's sweep whose plan takes the form, and it has, in this order, a ragged last tile in rows, in
+    columns, a partly empty last cout sub-tile (the kernel's couts: the conv's cins for a data gradient), a tile count that is no multiple of 8
+    -- unless no shape of the form's sweep WHOSE PLAN TAKES THE FORM (two or three images, the row's cin) has it together with the ones before.
+    Over every family (1x1, flattened, over every second pixel, 3x3 stride 1 and 2) and use, each of the four edges occurs in some row unless
+    no such shape of any of the family's rows has it."""
+    rows = _train_rows()
+    new = set(pf.sweep("train")) | set(pf.sweep("dgrad"))
+    assert (sum(r[0] == "train" for r in rows), sum(r[0] == "dgrad" for r in rows)) == (18, 12) and all(form in new for _, form, _, _ in rows)
+    kcout = lambda use, shape: shape[1] if use == "dgrad" else shape[2]
+    edge = lambda use, shape: (lambda f: pf.ragged(use, "conv", shape, f) + (kcout(use, shape) % 16 == 8, f.tiles_total % 8 != 0))(pf.query(use, *shape))
+    bad, have, could = [], {}, {}
+    for use, form, shape, cid in rows:
+        sweep = [c[1] for c in pf.sweep(use)[form] if c[0] == "conv" and "inz" not in c[2]]
+        if shape not in sweep:
+            bad.append((cid, use, "not a shape of the sweep"))
+        cands = [c for c in sweep if c[0] >= 2 and c[1] == shape[1] and _single_plan_forms(c)[use == "dgrad"] == form]
+        assert shape in cands, (cid, use)
+        fam = (use, _family(form))
+        me = edge(use, shape)
+        for i in range(4):
+            have.setdefault(fam, [False] * 4)[i] |= me[i]
+            could.setdefault(fam, [False] * 4)[i] |= any(edge(use, c)[i] for c in cands)
+        for i in range(4):  # (each edge in turn, among the shapes that have the ones before it)
+            keep = [c for c in cands if edge(use, c)[i]]
+            if keep:
+                cands = keep
+                if not me[i]:
+                    bad.append((cid, use, form, "edge", i))
+    assert not bad, bad
+    assert {f for _, f in have} == {"k1s1", "k1s1_flat", "k1s1_sub", "k3s1", "k3s2"} and {u for u, _ in have} == {"train", "dgrad"}
+    for fam in have:
+        assert have[fam] == could[fam], (fam, have[fam], could[fam])
+    print("[p2 forms] training rows, edges (rows, columns, cout sub-tile, tiles % 8) per family: " + "; ".join(f"{u} {f}: {''.join('x' if v else '-' for v in have[(u, f)])}"
+                                                                                                               for u, f in sorted(have)))
 
 
 def test_later_tile_rows_exceed_what_the_device_holds():

@@ -20,9 +20,9 @@ OUT_CHANNELS = 5
 
 
 # ---- graph builders: every graph starts with a 3-channel NCHW 3x3 stride-2 conv + BN + ReLU and ends with a biased 1x1 conv to 5 NCHW maps ----
-def _head(g, c):
+def _head(g, c, relu=True):
     g.input = g.act(3, 1, "nchw")
-    return g.conv(g.input, c, 3, 2, "head", "head_bn", relu=True)
+    return g.conv(g.input, c, 3, 2, "head", "head_bn", relu=relu)
 
 
 def _tail(g, x):
@@ -121,7 +121,18 @@ def single(cin, cout, k, stride):
     return _tail(g, y)
 
 
-BUILDERS = {"blocks": blocks, "bneck": bneck, "fuse": fuse, "deconv": deconv, "branches": branches, "shared": shared, "single": single}
+def linear(cin, cout, k, stride):
+    """``single`` without a ReLU on the head or on "c": no mask exists that could flip, so the batch needs no margin and may be as large as the
+    form asks for (the two-sub-tile 1x1 forms start at 32 768 pixels x 256 channels, a workgroup's second tile at hundreds of images)."""
+    g = _graph.Graph()
+    x = _head(g, cin, relu=False)
+    g.new_phase()
+    y = g.conv(x, cout, k, stride, "c", "c_bn", relu=False)
+    return _tail(g, y)
+
+
+BUILDERS = {"blocks": blocks, "bneck": bneck, "fuse": fuse, "deconv": deconv, "branches": branches, "shared": shared, "single": single,
+            "linear": linear}
 
 
 # ---- the model on the HIP engine ----
